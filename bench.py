@@ -3,7 +3,7 @@
 features -> DeepSpeech forward -> greedy CTC decode -> strings -- on synthetic 10 s clips, batch 32 per GPU
 (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One process per GPU.  ``--gpus N`` with N > 1 starts the N rank processes itself (fresh children with RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set; the parent never touches a GPU), or runs as one rank
@@ -16,13 +16,25 @@ recognize(), reference danspeech/audio/resources.py:640) and returns strings on 
 Inputs are resident before the timed region: at N > 1 rank 0 synthesises all clips and scatters the shards over RCCL as
 int16 (widened on the device before the timed region); the per-step gather of the transcripts to rank 0 (fixed-size
 payload) is inside the timed region.  Weights are seeded random tensors of the DanSpeech shapes (no network for
-checkpoints): data = "synthetic"; they are scaled so that a 10 s clip decodes to 100+ tokens (synthetic.TALKATIVE), and
-the timed batch is CHECKED against the CPU oracle -- a failed check makes the process exit non-zero.
+checkpoints): data = "synthetic"; they are scaled so that a 10 s clip decodes to 100+ tokens (synthetic.TALKATIVE).
 
-Rank 0 prints ONE JSON line (see the driver contract), including
+Rank 0 prints ONE JSON line: `metric`, `value` (audio-s/s of the timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step`,
+`steps`, `warmup`, `config`, and
   roofline       -- the kernel with the largest total time in the timed region: algorithmic FLOPs per
                     launch / its mean dispatch duration (per-dispatch begin/end timestamps sampled live
                     through hipExtLaunchKernelGGL events) vs the MFMA peak of the instruction it runs on
+  rccl           -- N > 1: RCCL's version and the world size the process group reports (a rank count other than --gpus exits 4)
+A plain run does only that: set-up, warm-up, the timed steps, the line.
+
+``--dump-outputs DIR`` writes what the timed path returned in its last step, after the timed region, on rank 0:
+  transcripts.npy  -- float32 [clips, max transcript length]: each clip's string as Unicode code points, -1 past its end
+  probs.npy        -- float32 [clips per GPU, output frames, labels]: rank 0's softmax output of that step's batch (0 past a clip's
+                      output length), from which its transcripts were decoded
+At most 64 MB in all: a file that would hold more is a fixed, seeded sample of its rows, listed in <name>_rows.npy.  The inputs
+(seeded clips, seeded weights) are the same in every run with the same arguments.
+
+``--full`` adds what takes runs of its own, each after the timed region and never `value` (the timed batch is then also
+CHECKED against the CPU oracle -- a failed check makes the process exit non-zero):
   cpu_baseline   -- oracle/torch_port.py (the reference's own CPU operators: oneDNN conv, aten::gru, ...;
                     kind "port") on this host's physical cores, same batch
   parity         -- max |probs - oracle| and transcript equality of the GPU's batch vs that oracle run
@@ -30,7 +42,7 @@ Rank 0 prints ONE JSON line (see the driver contract), including
   abi_path       -- the same work as bare C-ABI calls (dsmi_features / dsmi_forward / dsmi_greedy), N = 1 only
   steady_state   -- the timed entry again over --steady-steps (>= 96) steps after the timed region, with `energy` (mean board
                     power and joules per batch over those steps), N = 1 only; never `value`
-  rccl           -- N > 1: RCCL's version and the world size the process group reports (a rank count other than --gpus exits 4)
+  f32_strict, other_configs -- the strict-fp32 arithmetic and BASELINE.json configs 3-5, each in a process of its own
 
 ``--dry-run`` (CPU, no GPU work, backend gloo, a stand-in engine) exercises the launch, scatter, per-step gather and
 the JSON line; its numbers mean nothing and the line says so.
@@ -255,6 +267,9 @@ def main(argv=None):
     ap.add_argument("--lanes", type=int, default=None, help="experiments: forwards in flight (default: the engine's own choice; the line says what ran)")
     ap.add_argument("--steady-steps", type=int, default=384, help="steps of the steady_state side run (at least 96)")
     ap.add_argument("--dry-run", action="store_true", help="CPU only: launch, scatter, gather and the JSON line with a stand-in engine")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="also the side figures: CPU baseline and parity, steady state and energy, "
+                                                        "device_resident, abi_path, f32_strict, other_configs")
     args = ap.parse_args(argv)
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -408,6 +423,8 @@ def main(argv=None):
     out = run(args.steps) or out
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # before any side run replaces the engine's last output
+        dump_outputs(args.dump_outputs, out, eng.last_output if eng is not None else None, B, cap)
     stats = {}
     if sampled:
         for h in sampled:                        # merge the sampled handles' figures
@@ -425,7 +442,7 @@ def main(argv=None):
     # ---- side measurement, after the timed region: the same entry over enough steps that the pipeline's fill and drain (four forwards
     # of two batches) are a few per cent of it, with the board power sampled beside it.  Never `value`.
     steady = None
-    if world == 1 and not dry and not args.no_side_paths and not args.strict_f32_child:
+    if args.full and world == 1 and not dry and not args.no_side_paths and not args.strict_f32_child:
         ss_steps = max(args.steady_steps, 96)
         with PowerSampler(local) as pw:
             sync()
@@ -484,6 +501,7 @@ def main(argv=None):
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32 (two-term fp16 split operands, 3 MFMA products, fp32 accumulate)",
             "data": "synthetic" if not dry else "dry-run (CPU stand-in engine: NOT a measurement)",
+            "full": args.full,
             "config": {"workload": "BASELINE.json configs[1]: 2conv + 5xBiGRU%d (DanSpeechPrimary per BASELINE), greedy CTC, "
                                    "batch=%d x %.0f s 16 kHz clips per GPU, STFT+forward+decode" % (c["rnn_hidden_size"], B, c["seconds"]),
                        "entry": ("Recognizer.recognize_batches: float64 HOST arrays -> strings on the host (pinned staging and the PCIe "
@@ -515,7 +533,7 @@ def main(argv=None):
         }
         if rccl:
             result["rccl"] = rccl
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             probs, sizes = eng.last_output          # the last forward: consecutive batches merged, this batch's clips first
             base, parity = cpu_baseline_and_parity(cfg, sd, B, n_samples, labels, {"probs": probs[:B], "out_lens": np.asarray(sizes)[:B]}, out)
             result["cpu_baseline"] = base
@@ -524,10 +542,10 @@ def main(argv=None):
         else:
             result["cpu_baseline"] = None
             result["parity_checked"] = False
-        if world == 1 and not args.no_side_paths and not dry:
+        if args.full and world == 1 and not args.no_side_paths and not dry:
             result["device_resident"] = device_resident(rec, clips, host_clips, B, n_samples, args.steps, out)
             failed = failed or not result["device_resident"]["same_strings_as_timed_path"]
-    if rank == 0 and world == 1 and not args.no_side_paths and not dry:
+    if args.full and rank == 0 and world == 1 and not args.no_side_paths and not dry:
         del rec, eng
         result["abi_path"] = abi_path_child(args, out)
         failed = failed or not result["abi_path"]["same_strings_as_timed_path"]
@@ -546,6 +564,36 @@ def main(argv=None):
     if failed:
         sys.exit(2)           # a throughput line from a computation that failed its own check must not read as a result
     return result
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, strings, last_output, B, cap):
+    """--dump-outputs: the timed path's last step as float32 .npy files (module docstring).  `strings`: the step's transcripts
+    (every rank's at N > 1); `last_output`: the engine's (probs, out_lens) of its last forward, whose first B clips are one
+    batch (every step hands over the same clips).  2.2 MB at the default size; a file that would take more than its share of
+    DUMP_BYTES holds a fixed, seeded sample of its rows instead, and <name>_rows.npy says which."""
+    def save(name, a, share):
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(share // (a.nbytes // len(a)), 1), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float32))
+        np.save(os.path.join(path, name + ".npy"), a)
+        return a.nbytes
+
+    os.makedirs(path, exist_ok=True)
+    strings = list(strings or [])
+    codes = np.full((len(strings), max([cap] + [len(s) for s in strings])), -1.0, dtype=np.float32)
+    for i, s in enumerate(strings):
+        codes[i, :len(s)] = [ord(ch) for ch in s]
+    used = save("transcripts", codes, DUMP_BYTES // 4)
+    if last_output is not None:
+        probs, sizes = last_output
+        p = probs[:B].float().cpu().numpy()
+        for b, n in enumerate(np.asarray(sizes)[:B]):
+            p[b, int(n):] = 0.0
+        save("probs", p, DUMP_BYTES - used - (1 << 20))     # (1 MB for the row lists)
 
 
 def cpu_baseline_and_parity(cfg, sd, B, n_samples, labels, last, gpu_strings):
@@ -689,7 +737,7 @@ def f32_strict_child(args):
     import subprocess
     env = dict(os.environ, DSMI_DENSE_MODE="f32", DSMI_RNN_MODE="steps")
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(max(args.steps // 4, 4)), "--warmup", "2", "--config", args.config,
-           "--no-kernel-sampling", "--strict-f32-child", "--no-side-paths"]
+           "--no-kernel-sampling", "--strict-f32-child", "--no-side-paths", "--full"]      # --full: its CPU baseline and parity check
     if args.batch:
         cmd += ["--batch", str(args.batch)]
     try:

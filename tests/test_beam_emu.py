@@ -6,7 +6,6 @@ host threads for inputs of a few dozen frames.  (What it cannot see: memory orde
 import os
 import shutil
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -41,8 +40,8 @@ def test_kernel_source_on_the_emulation_revivals_and_walks(emu):
         assert emu.compare(probs, None, "_abc", beam, 192)
 
 
-def test_kernel_source_on_the_emulation_scorer_and_pruning(emu):
-    path = os.path.join(tempfile.gettempdir(), "emu_test3.arpa")
+def test_kernel_source_on_the_emulation_scorer_and_pruning(emu, tmp_path):
+    path = str(tmp_path / "emu_test3.arpa")
     syn.make_arpa(path, order=3, n_words=120, seed=5, ngrams_per_order=300)
     probs = emu.peaky(np.random.default_rng(2), 1, 24, 33, 2.0)
     assert emu.compare(probs, np.array([24]), syn.DANSPEECH_LABELS, 12, 192, lm_path=path, alpha=1.3, beta=0.2)

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -48,6 +51,55 @@ def test_bench_single_rank_dry_run_has_the_same_line_shape():
     assert line["n_gpus"] == 1 and line["transcripts_gathered"] == line["config"]["clips_per_gpu"]
     for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line
+
+
+def _transcript(row):
+    return "".join(chr(int(c)) for c in row if c >= 0)
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_dump_outputs_dry_run(tmp_path, gpus):
+    """--dump-outputs DIR: the last timed step's transcripts (every rank's, gathered on rank 0) as float32 code points, the
+    same in two runs with the same arguments; --steps is the number of timed steps; a plain run carries no side figures."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        r = _run(["--gpus", str(gpus), "--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["full"] is False
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["steady_state"] is None
+        assert sorted(os.listdir(d)) == ["transcripts.npy"]
+        dumps.append(np.load(d / "transcripts.npy"))
+    t = dumps[0]
+    assert t.dtype == np.float32 and t.shape[0] == gpus * line["config"]["clips_per_gpu"]
+    assert np.array_equal(dumps[0], dumps[1])
+    assert all(_transcript(row).startswith("dry ") for row in t)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_what_its_last_step_returned(tmp_path):
+    """The plain GPU run: the dumped probabilities of the last step's batch decode (greedy CTC, oracle/decoder.py) to the dumped
+    transcripts, and the line holds the headline fields and none of --full's side runs."""
+    from danspeech_amd import synthetic as syn
+    from oracle import decoder as od
+    r = _run(["--steps", "8", "--warmup", "4", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 8 and line["value"] > 0 and line["full"] is False
+    assert line["cpu_baseline"] is None and line["parity_checked"] is False and line["steady_state"] is None
+    assert "abi_path" not in line and "f32_strict" not in line and "other_configs" not in line
+    t, p = np.load(tmp_path / "transcripts.npy"), np.load(tmp_path / "probs.npy")
+    B = line["config"]["clips_per_gpu"]
+    assert t.dtype == np.float32 and p.dtype == np.float32 and t.shape[0] == B and p.shape[0] == B
+    assert p.shape[2] == len(syn.DANSPEECH_LABELS)
+    lens = np.array([int((row.sum(axis=1) > 0).sum()) for row in p])
+    assert np.all(lens > 0) and np.allclose(p.sum(axis=2)[:, :lens.min()], 1.0, atol=1e-4)
+    strings, _ = od.greedy_decode(p, lens, syn.DANSPEECH_LABELS, 0)
+    assert [s[0] for s in strings] == [_transcript(row) for row in t]
+    assert min(len(s[0]) for s in strings) > 0
 
 
 def test_a_dying_rank_fails_the_whole_launch():

@@ -71,8 +71,8 @@ def test_bench_with_its_process_group_forced_on_one_rank():
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, DSMI_BENCH_FORCE_GROUP="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "4", "--no-side-paths",
-                        "--no-other-configs"], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "4", "--full",
+                        "--no-side-paths", "--no-other-configs"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["rccl"]["world_size_seen"] == 1 and line["rccl"]["backend"] == "nccl"

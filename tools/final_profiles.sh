@@ -13,9 +13,9 @@ mkdir -p $O
 hdr() { echo "# commit $COMMIT, $(date -u +%Y-%m-%dT%H:%MZ), MI355X (gfx950), tools/final_profiles.sh"; }
 
 # 1. the bench line: the defaults (96 timed steps), and the driver's own command
-python3 bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 tail -c 600 $O/${TAG}_bench.json | head -c 300; echo
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_command.json 2> $O/${TAG}_bench_driver_command.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_command.json 2> $O/${TAG}_bench_driver_command.err
 
 # 2. kernel stats + trace of the same timed command (without the CPU baseline and the side paths: their kernels are not the timed ones)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace -- python3 bench.py --no-cpu-baseline --no-side-paths > $O/${TAG}_trace_bench.json 2> $O/${TAG}_trace.log
