@@ -58,6 +58,21 @@ class _StreamingSession(object):
         return piece
 
 
+class StreamingSessionHandle(object):
+    """One utterance of ``DanSpeechRecognizer.streaming_transcribe_many``: its streaming parser, its ``dsmi_stream`` handle
+    (conv contexts, recurrent state, lookahead buffer on the GPU) and its running text / outputs / spectrograms."""
+
+    def __init__(self, parser, stream, state):
+        self.parser = parser
+        self.stream = stream
+        self.state = state
+
+    text = property(lambda self: self.state.text)
+
+    def close(self):
+        self.stream.close()
+
+
 class _UnmergedDeviceClips(object):
     """Device-resident batches on their way into one forward: merged on the stream that runs it."""
 
@@ -662,6 +677,55 @@ class DanSpeechRecognizer(object):
             text = ses.text
         ses.clear()
         return text
+
+    def new_streaming_session(self):
+        """A session of its own for ``streaming_transcribe_many``: its parser, its ``dsmi_stream`` handle on the streaming
+        model and its running text, outputs and spectrograms; the secondary model and string-parts setting are those of
+        ``enable_streaming``."""
+        from . import _native
+        if self._session is None or not isinstance(self.audio_parser, InferenceSpectrogramAudioParser):
+            raise RuntimeError("call enable_streaming first")
+        native = getattr(self.model, "_native", None)
+        if native is None:
+            raise RuntimeError("the streaming model runs only on an MI355X: call model.to('cuda') first (no CPU path)")
+        return StreamingSessionHandle(InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index()),
+                                      _native.NativeStream(native),
+                                      _StreamingSession(self._session.secondary_model, self._session.string_parts))
+
+    def streaming_transcribe_many(self, sessions, recordings, is_last, is_first):
+        """``streaming_transcribe`` for several sessions (``new_streaming_session``) at once, each on its next part of its own
+        utterance; the parts' spectrograms and the model pass run batched over all sessions.  -> one string per session, each
+        what ``streaming_transcribe`` returns for that session alone."""
+        from . import _native
+        n = len(sessions)
+        if not (len(recordings) == len(is_last) == len(is_first) == n):
+            raise ValueError("sessions, recordings, is_last and is_first must have one entry per session")
+        if len(set(id(s) for s in sessions)) != n:
+            raise ValueError("a session appears twice in one call")
+        spects = InferenceSpectrogramAudioParser.parse_audio_many([s.parser for s in sessions], recordings, is_last)
+        run = [k for k in range(n) if len(spects[k]) != 0]
+        for k in run:
+            if sessions[k].state.secondary_model:
+                sessions[k].state.spectrograms.append(spects[k])
+        probs = _native.NativeStream.forward_many([sessions[k].stream for k in run], [spects[k] for k in run],
+                                                  [is_first[k] for k in run], [is_last[k] for k in run])
+        probs = dict(zip(run, probs))
+        said = []
+        for k in range(n):
+            ses = sessions[k].state
+            piece = ""
+            if k in probs:
+                if is_first[k]:
+                    said.append("")
+                    continue
+                ses.outputs.append(probs[k])
+                piece = ses.extend_text(self.greedy_decoder.decode(probs[k])[0][0][0])
+                piece = piece if ses.string_parts else ses.text
+            if not is_last[k]:
+                said.append(piece)
+            else:
+                said.append(self._final_text(ses) if len(ses.text) > 1 else "")
+        return said
 
     def streaming_transcribe(self, recording, is_last, is_first):
         """One part of an utterance through the streaming model.  Returns this part's text (or the whole text so far

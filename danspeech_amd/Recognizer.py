@@ -11,6 +11,7 @@ import numpy as np
 
 from .errors.recognizer_errors import ModelNotInitialized
 from .DanSpeechRecognizer import DanSpeechRecognizer
+from .stream_plan import stream_cut_plan, stream_rounds
 
 
 class Recognizer(object):
@@ -81,35 +82,42 @@ class Recognizer(object):
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
-        lookahead_context = rec.model.context
-        required_spec_frames = (lookahead_context - 1) * 2
-        samples_pr_10ms = int(rec.audio_parser.sampling_rate / 100)
-        general_sample_requirement = samples_pr_10ms * 2 + (samples_pr_10ms * (required_spec_frames - 1))
-        first_sample_requirement = general_sample_requirement + (samples_pr_10ms * 15)
         audio_data = np.asarray(audio_data, dtype=np.float64)
-        step = int(chunk_samples) if chunk_samples else 1024
-        pos, n = 0, len(audio_data)
-        is_first_pass = True
-        data_array = audio_data[:0]
-        while pos < n:
-            part = audio_data[pos:pos + step]
-            pos += len(part)
-            is_last = pos >= n
-            data_array = np.concatenate((data_array, part))
-            output = None
-            if is_first_pass:
-                if is_last:
-                    output = None                      # too short for a first pass: discarded (:666-667)
-                elif len(data_array) >= first_sample_requirement:
-                    output = rec.streaming_transcribe(data_array, is_last=False, is_first=True)
-                    is_first_pass = False
-                    data_array = audio_data[:0]
-            else:
-                if is_last or len(data_array) >= general_sample_requirement:
-                    output = rec.streaming_transcribe(data_array, is_last=is_last, is_first=False)
-                    data_array = audio_data[:0]
+        for lo, hi, is_first, is_last in self._cut_plan(len(audio_data), chunk_samples):
+            output = rec.streaming_transcribe(audio_data[lo:hi], is_last=is_last, is_first=is_first)
             if output:
                 yield is_last, output
+
+    def stream_recordings(self, audio_list, chunk_samples=None):
+        """``stream_recording`` for many recordings at once, one streaming session each: every recording is cut as
+        ``stream_recording`` cuts it, and in each round every session that has a part due advances in ONE batched pass
+        (``DanSpeechRecognizer.streaming_transcribe_many``).  Yields ``(index, is_last, text)``; for every index the
+        subsequence it yields equals ``list(stream_recording(audio_list[index], chunk_samples))`` as the first recording
+        after ``enable_real_time_streaming`` (every session starts with a fresh parser).  Requires
+        ``enable_real_time_streaming``."""
+        if not getattr(self, "stream", False):
+            raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
+        rec = self.danspeech_recognizer
+        audio = [np.asarray(a, dtype=np.float64) for a in audio_list]
+        plans = [self._cut_plan(len(a), chunk_samples) for a in audio]
+        sessions = {}
+        try:
+            for due in stream_rounds(plans):
+                for k, _ in due:
+                    if k not in sessions:
+                        sessions[k] = rec.new_streaming_session()
+                texts = rec.streaming_transcribe_many([sessions[k] for k, _ in due], [audio[k][c[0]:c[1]] for k, c in due],
+                                                      [c[3] for _, c in due], [c[2] for _, c in due])
+                for (k, c), text in zip(due, texts):
+                    if text:
+                        yield k, c[3], text
+        finally:
+            for ses in sessions.values():
+                ses.close()
+
+    def _cut_plan(self, n_samples, chunk_samples=None):
+        rec = self.danspeech_recognizer
+        return stream_cut_plan(n_samples, chunk_samples, rec.model.context, int(rec.audio_parser.sampling_rate / 100))
 
     def recognize_long(self, audio_data, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
                        max_batch=32, show_all=False):
@@ -131,3 +139,4 @@ class Recognizer(object):
     def update_decoder(self, lm=None, alpha=None, beta=None, beam_width=None):
         self.danspeech_recognizer.update_decoder(lm=lm, alpha=alpha, beta=beta, beam_width=beam_width)
         print("DanSpeech decoder updated ")  # ToDO: Include model name
+

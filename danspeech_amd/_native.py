@@ -81,6 +81,8 @@ _PROTOS = {
     "dsmi_stream_last_error": (C.c_char_p, [_vp]),
     "dsmi_stream_reset": (C.c_int, [_vp]),
     "dsmi_stream_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "dsmi_stream_forward_many": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "dsmi_features_stream_many": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_segment": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, C.c_int,
                                C.POINTER(C.c_int), _vp, _vp]),
     "dsmi_decoder_create": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_vp)]),
@@ -493,6 +495,37 @@ def _features_stream(self, pcm_dev, state):
 NativeFrontend.features_stream = _features_stream
 
 
+def _features_stream_many(self, pcms, states):
+    """dsmi_features_stream_many: the next chunk of several streaming parsers in one pass.  ``pcms``: CUDA tensors of one
+    dtype (one chunk per parser, each at least one window long), ``states``: their float64[3] running statistics, updated in
+    place.  -> [feat [n_freq, frames_i] float32 CUDA] (views of one batch buffer), equal to ``features_stream`` one by one."""
+    import torch
+    n = len(pcms)
+    if n == 0:
+        return []
+    dt = {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcms[0].dtype]
+    ns = np.array([p.numel() for p in pcms], dtype=np.int64)
+    n_fft = 2 * (self.n_freq - 1)
+    nfr = [1 + (int(k) - n_fft) // self.hop if k >= n_fft else 0 for k in ns]
+    pcm = torch.cat([p.reshape(-1) for p in pcms]).contiguous()
+    t_stride = max(max(nfr), 1)
+    feat = torch.empty((n, self.n_freq, t_stride), dtype=torch.float32, device=pcm.device)
+    st = np.ascontiguousarray(np.stack([np.asarray(s, dtype=np.float64).reshape(3) for s in states]))
+    fr = np.zeros(n, dtype=np.int32)
+    rc = lib().dsmi_features_stream_many(self._h, pcm.data_ptr(), dt, _np_ptr(ns), n, _np_ptr(st), feat.data_ptr(), t_stride,
+                                         _np_ptr(fr), _stream(self.device))
+    if rc != 0:
+        raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
+    for s_, row in zip(states, st):
+        s_[:] = row
+    return [feat[i, :, :int(fr[i])] for i in range(n)]
+
+
+NativeFrontend.features_stream_many = _features_stream_many
+
+STREAM_MANY_MAX = 256       # DSMI_STREAM_MANY_MAX: sessions of one dsmi_stream_forward_many call
+
+
 class NativeStream:
     """Owns one dsmi_stream handle: the carried state of one utterance streamed through a unidirectional model."""
 
@@ -528,6 +561,47 @@ class NativeStream:
             break
         n = int(tout[0])
         return probs[:n].unsqueeze(0) if n > 0 else None
+
+    @staticmethod
+    def forward_many(streams, feats, is_first, is_last):
+        """dsmi_stream_forward_many: advance several sessions (distinct ``NativeStream`` of one model) by one chunk each in
+        one batched pass.  ``feats[i]``: CUDA float32 [F,T_i] (or [1,1,F,T_i]); ``is_first`` / ``is_last``: one flag per
+        session.  -> a list of probs [1,T_out,C] CUDA, or None for a session whose lookahead is still buffering, each equal to
+        what ``forward`` returns for that session alone.  Longer lists than STREAM_MANY_MAX run as several passes."""
+        import torch
+        n = len(streams)
+        if not (len(feats) == len(is_first) == len(is_last) == n):
+            raise ValueError("streams, feats, is_first and is_last must have one entry per session")
+        if n > STREAM_MANY_MAX:
+            out = []
+            for k in range(0, n, STREAM_MANY_MAX):
+                sl = slice(k, k + STREAM_MANY_MAX)
+                out += NativeStream.forward_many(streams[sl], feats[sl], is_first[sl], is_last[sl])
+            return out
+        if n == 0:
+            return []
+        model = streams[0].model
+        fs = [f.reshape(f.shape[-2], f.shape[-1]).contiguous() for f in feats]
+        for f in fs:
+            assert f.is_cuda and f.dtype == torch.float32
+        T = np.array([f.shape[1] for f in fs], dtype=np.int32)
+        hs = (C.c_void_p * n)(*[s._h for s in streams])
+        fp = (C.c_void_p * n)(*[f.data_ptr() for f in fs])
+        first = np.array([int(bool(v)) for v in is_first], dtype=np.int32)
+        last = np.array([int(bool(v)) for v in is_last], dtype=np.int32)
+        cap = int(T.max()) + 4 * int(model.desc.context) + 2048
+        while True:
+            probs = torch.empty((n, cap, model.n_labels), dtype=torch.float32, device=fs[0].device)
+            tout = np.zeros(n, dtype=np.int32)
+            rc = lib().dsmi_stream_forward_many(hs, n, fp, _np_ptr(T), _np_ptr(first), _np_ptr(last), probs.data_ptr(), cap,
+                                                _np_ptr(tout), _stream(model.device))
+            if rc == DSMI_ERR_CAPACITY and cap < (1 << 24):
+                cap *= 4               # refused before any state changed
+                continue
+            if rc != 0:
+                raise DsmiError(rc, (lib().dsmi_stream_last_error(None) or b"").decode())
+            break
+        return [probs[i, :int(tout[i])].unsqueeze(0) if tout[i] > 0 else None for i in range(n)]
 
     def reset(self):
         self._check(lib().dsmi_stream_reset(self._h))

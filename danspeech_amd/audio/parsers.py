@@ -332,6 +332,37 @@ class InferenceSpectrogramAudioParser(AudioParser):
         pcm = torch.from_numpy(np.ascontiguousarray(samples[:usable])).to("cuda:%d" % self.device)
         return self._frontend().features_stream(pcm, self._state)
 
+    @staticmethod
+    def parse_audio_many(parsers, parts, is_last):
+        """``[p.parse_audio(part, last) for p, part, last in zip(parsers, parts, is_last)]`` in one batched pass
+        (``dsmi_features_stream_many``): every parser keeps its own carry buffer and statistics, and a closing part shorter
+        than one window still ends that parser's utterance with nothing.  The parsers share one configuration; the first
+        one's frontend runs the pass."""
+        import torch
+        out = [[] for _ in parsers]
+        todo, pcms = [], []
+        for k, (p, part, last) in enumerate(zip(parsers, parts, is_last)):
+            if last and len(part) < p.n_fft:
+                p.reset()
+                continue
+            samples = np.asarray(part, dtype=np.float64).reshape(-1)
+            if p.has_buffer:
+                samples = np.concatenate((p.buffer, samples))
+            usable = len(samples) - len(samples) % p.hop_length
+            p.buffer = samples[max(usable - p.hop_length, 0):].copy()
+            p.has_buffer = True
+            todo.append(k)
+            pcms.append(samples[:usable])
+        if todo:
+            lead = parsers[todo[0]]
+            pcm = torch.from_numpy(np.ascontiguousarray(np.concatenate(pcms))).to("cuda:%d" % lead.device)
+            cuts = np.cumsum([0] + [len(x) for x in pcms])
+            feats = lead._frontend().features_stream_many([pcm[cuts[j]:cuts[j + 1]] for j in range(len(todo))],
+                                                          [parsers[k]._state for k in todo])
+            for k, f in zip(todo, feats):
+                out[k] = f
+        return out
+
     def reset(self):
         self.buffer = None
         self.has_buffer = False

@@ -620,6 +620,7 @@ extern "C" void dsmi_model_destroy(dsmi_model* m) {
     if (m->lens_stage) (void)hipHostFree(m->lens_stage);
     for (hipEvent_t e : m->stage_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : m->kt.free_events) (void)hipEventDestroy(e);
+    stream_batch_free(m);
     delete m;
 }
 
@@ -1120,6 +1121,20 @@ extern "C" int dsmi_rnn_layer(dsmi_model* m, int layer, const float* x, const in
         m->recomputed += 1;
     }
     return DSMI_OK;
+}
+
+// stream.hip's batched pass (dsmi_stream_forward_many): one carried-state launch of the first-generation persistent layer.  Sized
+// for the whole device like the offline first-generation launch, so it takes every gate slot and never shares the chip with another
+// persistent kernel of the process; the same test hooks apply.
+bool stream_persist_layer(dsmi_model* m, int l, RnnPersistLaunch& pl, hipStream_t s) {
+    pl.spin_limit = m->spin_limit;
+    if (m->drop_layer == l) { pl.drop_wg = m->drop_wg; pl.drop_step = m->drop_step; }
+    PersistGate* gate = persist_gate(m->device);
+    std::lock_guard<std::mutex> lk(gate->mu);
+    gate_wait(gate, s, 0, kMaxLanes);
+    const bool ok = launch_rnn_persist(pl, s);
+    gate_record(gate, s, 0, kMaxLanes);
+    return ok;
 }
 
 extern "C" int dsmi_recompute_count(const dsmi_model* m) { return m ? m->recomputed : DSMI_ERR_INVALID; }

@@ -162,6 +162,10 @@ struct RnnPersistLaunch {
     int drop_wg = -1, drop_step = -1;    // test hook: see DSMI_DEBUG_DROP_SIGNAL in api.hip
     EvPair ev;
     unsigned long long* dbg = nullptr;   // diagnostics: accumulated per-wave phase times
+    // carried-state variant (D = 1): h0 [B][Hs] seeds the chains; counters are then [D * ceil(B/32)][1 + T] words (each chain's seed
+    // counter in front of its step counters); cst [B][Hs] LSTM c in and out (see rnn_persist.hip)
+    const float* h0 = nullptr;
+    float* cst = nullptr;
 };
 bool rnn_persist_eligible(const RnnGeom& g, int B, int n_cus);
 std::vector<uint16_t> pack_whh_split(const RnnGeom& g, const float* w_hh);

@@ -344,6 +344,32 @@ __global__ __launch_bounds__(1024) void chunk_stats_kernel(const float* feat, in
     if (tid == 0) { out2[0] = mean; out2[1] = sqrt(var); }
 }
 
+// the same statistics for n chunks at once (blockIdx.x = chunk; per-chunk frame counts from the sample counts, no centre padding)
+__global__ __launch_bounds__(1024) void chunk_stats_many_kernel(const float* feat, const int64_t* nsamp, int n_fft, int hop, int n_freq,
+                                                                int t_stride, double* out2) {
+    __shared__ double sh[16];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nfr = 1 + (int)((nsamp[b] - n_fft) / hop), total = n_freq * nfr;
+    const float* fb = feat + (size_t)b * n_freq * t_stride;
+    double s = 0.0;
+    for (int i = tid; i < total; i += 1024) s += (double)fb[(size_t)(i / nfr) * t_stride + i % nfr];
+    const double mean = block_sum(s, sh) / (double)total;
+    double q = 0.0;
+    for (int i = tid; i < total; i += 1024) { const double d = (double)fb[(size_t)(i / nfr) * t_stride + i % nfr] - mean; q += d * d; }
+    const double var = block_sum(q, sh) / (double)total;
+    if (tid == 0) { out2[2 * b] = mean; out2[2 * b + 1] = sqrt(var); }
+}
+
+// grid (blocks, n): chunk b normalised with ms[2b], ms[2b+1] (float mean, std), frames past its own count zeroed
+__global__ void chunk_normalize_many_kernel(float* feat, const int64_t* nsamp, int n_fft, int hop, int n_freq, int t_stride, const float* ms) {
+    const int b = blockIdx.y;
+    const int nfr = 1 + (int)((nsamp[b] - n_fft) / hop), total = n_freq * t_stride;
+    const float mean = ms[2 * b], stdv = ms[2 * b + 1];
+    float* fb = feat + (size_t)b * n_freq * t_stride;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+        fb[i] = (i % t_stride < nfr) ? (fb[i] - mean) / stdv : 0.f;
+}
+
 __global__ void chunk_normalize_kernel(float* feat, int n_freq, int nfr, int t_stride, float mean, float stdv) {
     const int total = n_freq * t_stride;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
@@ -410,6 +436,23 @@ void launch_stft_mfma(dim3 grid, hipStream_t s, const void* pcm, int dtype, cons
 
 }  // namespace
 
+// parsers.py:146-158: the parser's running statistics after a chunk whose own mean / population std are st[0] / st[1]
+// (np.mean / np.std of a float32 array are float32 values) -> state3 updated, and the mean / std that normalise the chunk
+static void stream_norm_update(const double* st, double* state3, double* mean_out, double* std_out) {
+    const double dataset_mean = 5.492418704733003, dataset_std = 1.7552755216970917, alpha_increment = 0.1;
+    double input_mean = state3[0], input_std = state3[1], alpha = state3[2];
+    alpha += alpha_increment;
+    input_mean = (input_mean + (double)(float)st[0]) / 2;
+    input_std = (input_std + (double)(float)st[1]) / 2;
+    double mean = input_mean, stdv = input_std;
+    if (alpha < 1.0) {
+        mean = input_mean * alpha + (1 - alpha) * dataset_mean;
+        stdv = input_std * alpha + (1 - alpha) * dataset_std;
+    }
+    state3[0] = input_mean; state3[1] = input_std; state3[2] = alpha;
+    *mean_out = mean; *std_out = stdv;
+}
+
 extern "C" int dsmi_features_stream(dsmi_frontend* f, const void* pcm, int dtype, int64_t n_samples, double* state3, float* feat,
                                     int t_stride, int32_t* frames, void* stream) {
     if (!f) return DSMI_ERR_INVALID;
@@ -446,18 +489,8 @@ extern "C" int dsmi_features_stream(dsmi_frontend* f, const void* pcm, int dtype
     const bool ok = hipMemcpyAsync(st, stats_dev, sizeof(st), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     (void)hipFree(stats_dev);
     if (!ok) return bad(DSMI_ERR_HIP, "streaming feature kernels failed");
-    // parsers.py:146-158 (np.mean / np.std of a float32 array are float32 values)
-    const double dataset_mean = 5.492418704733003, dataset_std = 1.7552755216970917, alpha_increment = 0.1;
-    double input_mean = state3[0], input_std = state3[1], alpha = state3[2];
-    alpha += alpha_increment;
-    input_mean = (input_mean + (double)(float)st[0]) / 2;
-    input_std = (input_std + (double)(float)st[1]) / 2;
-    double mean = input_mean, stdv = input_std;
-    if (alpha < 1.0) {
-        mean = input_mean * alpha + (1 - alpha) * dataset_mean;
-        stdv = input_std * alpha + (1 - alpha) * dataset_std;
-    }
-    state3[0] = input_mean; state3[1] = input_std; state3[2] = alpha;
+    double mean = 0, stdv = 1;
+    stream_norm_update(st, state3, &mean, &stdv);
     hipLaunchKernelGGL(chunk_normalize_kernel, dim3(64), dim3(256), 0, s, feat, f->n_freq, nfr, t_stride, (float)mean, (float)stdv);
     if (hipGetLastError() != hipSuccess) return bad(DSMI_ERR_HIP, "streaming feature kernels failed to launch");
     *frames = nfr;
@@ -601,5 +634,65 @@ extern "C" int dsmi_features(dsmi_frontend* m, const void* pcm, int dtype, const
     }
     hipLaunchKernelGGL(normalize_kernel, dim3(NSL, B), dim3(1024), 0, s, feat, f->offs + f->cap, m->hop, m->n_freq, t_stride, m->desc.normalize, stats);
     if (hipGetLastError() != hipSuccess) return bad(DSMI_ERR_HIP, "feature kernels failed to launch");
+    return DSMI_OK;
+}
+
+// The streaming parser for n sessions in one pass: their chunks back to back in `pcm` (n_samples[i] each), features [n][n_freq][t_stride].
+// One STFT launch, one statistics launch, ONE host synchronisation (the running statistics are host state, as in
+// dsmi_features_stream), one normalise launch.  Session i's features and state3[3i..3i+2] equal a dsmi_features_stream call of its own.
+extern "C" int dsmi_features_stream_many(dsmi_frontend* f, const void* pcm, int dtype, const int64_t* n_samples, int n, double* state3,
+                                         float* feat, int t_stride, int32_t* frames, void* stream) {
+    if (!f) return DSMI_ERR_INVALID;
+    auto bad = [&](int code, const std::string& msg) { f->err = msg; return code; };
+    const int base = dtype & 15;
+    const bool stereo_ok = base == DSMI_PCM_I16 || base == DSMI_PCM_I24 || base == DSMI_PCM_I32;
+    if (!pcm || !n_samples || !state3 || !feat || !frames || n < 1 || dtype < 0 || base > DSMI_PCM_I32 || (dtype & ~(15 | DSMI_PCM_STEREO)) ||
+        ((dtype & DSMI_PCM_STEREO) && !stereo_ok))
+        return bad(DSMI_ERR_INVALID, "bad streaming features arguments");
+    std::vector<int64_t> host(2 * (size_t)n);
+    int64_t off = 0;
+    int maxfr = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < f->n_fft) return bad(DSMI_ERR_INVALID, "session " + std::to_string(i) + ": fewer samples than one STFT window");
+        const int nfr = 1 + (int)((n_samples[i] - f->n_fft) / f->hop);
+        if (nfr > t_stride) return bad(DSMI_ERR_INVALID, "t_stride smaller than a chunk's frame count");
+        host[i] = off; host[n + i] = n_samples[i]; off += n_samples[i];
+        maxfr = std::max(maxfr, nfr);
+    }
+    if (hipSetDevice(f->device) != hipSuccess) return bad(DSMI_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    if (n > f->cap) {       // offs: [cap] offsets, [cap] sample counts, then [cap][NSL][2] doubles (here: the n mean / std pairs)
+        if (f->offs) { (void)hipStreamSynchronize(s); (void)hipFree(f->offs); f->offs = nullptr; }
+        if (hipMalloc((void**)&f->offs, sizeof(int64_t) * (2 + 2 * NSL) * n) != hipSuccess) return bad(DSMI_ERR_NOMEM, "hipMalloc failed");
+        f->cap = n;
+    }
+    if (!fe_stage_copy(f, f->offs, host.data(), n, s) || !fe_stage_copy(f, f->offs + f->cap, host.data() + n, n, s))
+        return bad(DSMI_ERR_HIP, "staging the chunks' offsets / lengths failed");
+    if (stft_on_mfma(f->n_fft, dtype)) {
+        launch_stft_mfma(dim3(ceil_div(maxfr, MF), n), s, pcm, dtype, f->offs, f->offs + f->cap, f->tw, f->win, f->hop, PAD_NONE, feat, t_stride);
+    } else {
+        const size_t lds = sizeof(double) * ((size_t)2 * f->n_fft + (size_t)f->n_fft * FT);
+        hipLaunchKernelGGL(stft_logmag_kernel, dim3(ceil_div(maxfr, FT), n), dim3(256), lds, s, pcm, dtype, f->offs, f->offs + f->cap,
+                           f->tw, f->win, f->n_fft, f->hop, f->n_freq, PAD_NONE, feat, t_stride);
+    }
+    double* stats = reinterpret_cast<double*>(f->offs + 2 * (size_t)f->cap);
+    hipLaunchKernelGGL(chunk_stats_many_kernel, dim3(n), dim3(1024), 0, s, feat, f->offs + f->cap, f->n_fft, f->hop, f->n_freq, t_stride, stats);
+    std::vector<double> st(2 * (size_t)n);
+    if (hipMemcpyAsync(st.data(), stats, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return bad(DSMI_ERR_HIP, "streaming feature kernels failed");
+    // the normalising mean / std as float pairs, staged through the pinned ring as int64 words (2 floats each)
+    std::vector<int64_t> ms(n);
+    for (int i = 0; i < n; ++i) {
+        double mean = 0, stdv = 1;
+        stream_norm_update(&st[2 * (size_t)i], state3 + 3 * (size_t)i, &mean, &stdv);
+        const float pr[2] = {(float)mean, (float)stdv};
+        std::memcpy(&ms[i], pr, sizeof(pr));
+        frames[i] = 1 + (int)((n_samples[i] - f->n_fft) / f->hop);
+    }
+    if (!fe_stage_copy(f, reinterpret_cast<int64_t*>(stats), ms.data(), n, s)) return bad(DSMI_ERR_HIP, "staging the chunks' statistics failed");
+    const int blocks = std::max(1, std::min(64, ceil_div(f->n_freq * t_stride, 256)));
+    hipLaunchKernelGGL(chunk_normalize_many_kernel, dim3(blocks, n), dim3(256), 0, s, feat, f->offs + f->cap, f->n_fft, f->hop, f->n_freq,
+                       t_stride, reinterpret_cast<const float*>(stats));
+    if (hipGetLastError() != hipSuccess) return bad(DSMI_ERR_HIP, "streaming feature kernels failed to launch");
     return DSMI_OK;
 }

@@ -107,6 +107,9 @@ struct dsmi_model {
     std::vector<int32_t> host_out_lens;   // output lengths of the batch being processed
     int32_t *lens_dev = nullptr, *sizes_dev = nullptr, *raw_ids = nullptr, *ids = nullptr, *offs = nullptr, *nout = nullptr;
 
+    // dsmi_stream_forward_many: the batched pass's workspaces (stream.hip), grown on demand
+    struct StreamBatch* sbatch = nullptr;
+
     // profiling
     int profiling = 0;        // 0 off, 1 stage events, 2 + sampled per-kernel dispatch timestamps
     KernelTimer kt;
@@ -117,3 +120,7 @@ struct dsmi_model {
 };
 
 dsmi::EvPair timer_arm(dsmi_model* m, int kind, bool sample, double flops, double bytes);
+
+// stream.hip / api.hip: the batched streaming pass
+void stream_batch_free(dsmi_model* m);
+bool stream_persist_layer(dsmi_model* m, int l, dsmi::RnnPersistLaunch& pl, hipStream_t s);

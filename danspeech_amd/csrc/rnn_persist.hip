@@ -29,6 +29,11 @@
 //     co-resident run one launch per direction;
 //   * every spin is bounded: on timeout the workgroup raises an error word and stops waiting,
 //     so a lost workgroup can never hang the GPU (the host then reports DSMI_ERR_HIP).
+//   * CARRY (the batched streaming pass of stream.hip, unidirectional): every chain starts from a carried h (and c) instead of
+//     zero.  The prologue publishes the split h0 as the state of "step -1" with the same stores, drain, barrier and counter
+//     as a step (a seed counter in front of each chain's step counters), step 0 waits for it like any step waits for its predecessor, and
+//     LSTM's c leaves the kernel as it stood at each clip's own last live step (the cell holds c past a clip's length; h at
+//     that step is row lens[b] - 1 of the output).  The other instantiations are unchanged.
 // Requires all workgroups co-resident: the launcher checks grid <= number of CUs (the kernel
 // requests > 80 KiB of LDS so that at most one workgroup fits a CU) and otherwise falls back
 // to the per-step path.
@@ -62,6 +67,10 @@ struct PersistArgs {
     int drop_wg, drop_step;    // test hook (DSMI_DEBUG_DROP_SIGNAL): this workgroup of direction 0 never signals that step (-1: off)
     unsigned long long* dbg;   // diagnostics build only: per-wave accumulated phase times [wg][wave][8]
 };
+// CARRY (the batched streaming pass of stream.hip) is unidirectional: it passes its carried state in the reverse direction's
+// slots, so that the argument block -- and with it every other instantiation's code -- stays as it was
+//   bhh[1] -> h0  [B][Hs] h of each clip's previous chunk (zeros for a clip on its first chunk)
+//   out[1] -> cst [B][Hs] LSTM c of the previous chunk in, c at each clip's own last live step out
 
 // Cell non-linearities on the hardware exp2 / reciprocal (v_exp_f32, v_rcp_f32: ~1 ulp each) instead of libm's
 // branchy expf / tanhf: the cell sits on the critical path of every step (-0.3 us of 4.56 per step).  Absolute
@@ -80,7 +89,7 @@ struct PersistArgs {
 
 constexpr int PMAXZ = 8;               // batch tiles per launch (B <= 256)
 
-template <int KIND, int NPW, bool MULTI, bool STAMP = false>
+template <int KIND, int NPW, bool MULTI, bool STAMP = false, bool CARRY = false>
 __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
     unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long tlast = STAMP ? __builtin_amdgcn_s_memrealtime() : 0;
@@ -137,6 +146,34 @@ __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
             st_len[z * PU * 32 + tid] = (eunit_ok && eb < p.B) ? p.lens[eb] : 0;
         }
     }
+    if (CARRY) {
+        const float* h0 = p.bhh[1];
+        const float* c0 = p.out[1];
+        // seed: each cell thread takes its (unit, clip) of the carried h (and c) and publishes the split h as the state of
+        // "step -1" (parity 1) of every tile with the same write-through stores as a step; then one signal per chain on its
+        // seed counter (counters [chain][1 + T]: the seed's, then the steps').  Step 0 waits for them like any later step waits for s - 1.
+        if (tid < PU * 32) {
+            for (int z = 0; z < nz; ++z) {
+                const int eb = z * 32 + ebl;
+                const bool ok = eunit_ok && eb < p.B;
+                const float h = ok ? h0[(size_t)eb * p.Hs + eunit] : 0.f;
+                const float c = (ok && KIND == DSMI_RNN_LSTM) ? c0[(size_t)eb * p.Hs + eunit] : 0.f;
+                if (MULTI) { st_h[z * PU * 32 + tid] = h; st_c[z * PU * 32 + tid] = c; }
+                else { hprev_own = h; cprev_own = c; }
+                const _Float16 h1 = (_Float16)h;
+                const _Float16 h2 = (_Float16)((h - (float)h1) * kLoScale);
+                const unsigned off = (unsigned)hp_par + (unsigned)((size_t)(d * p.nz + z) * p.npair * 2048) + (unsigned)(w >> 1) * 2048u +
+                                     (unsigned)(w & 1) * 512u + (unsigned)tid * 2u;
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h1), hrs, off, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h2), hrs, off + 1024u, 0, 16);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0)
+            for (int z = 0; z < nz; ++z)
+                __hip_atomic_fetch_add(p.cnt + (size_t)(d * p.nz + z) * (p.T + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __syncthreads();
 
     unsigned* pend = nullptr;      // MULTI: counter of the tile just published, not yet signalled
@@ -148,7 +185,7 @@ __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
         const int eb = b0 + ebl;
         const bool eact = eunit_ok && ebl < nb;
         const int chain = d * p.nz + z;
-        unsigned* cnt = p.cnt + (size_t)chain * p.T;
+        unsigned* cnt = p.cnt + (size_t)chain * (p.T + CARRY) + CARRY;   // CARRY: the chain's seed counter is cnt[-1]
         const unsigned hchain = (unsigned)((size_t)chain * p.npair * 2048);
         if (MULTI && tid < PU * 32) { mylen = st_len[z * PU * 32 + tid]; hprev_own = st_h[z * PU * 32 + tid]; cprev_own = st_c[z * PU * 32 + tid]; }
         // x-projection operands of this step do not depend on other workgroups: request them first
@@ -164,7 +201,7 @@ __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acl[r] = 0.f; }
         PSTAMP(0);   // loop head + x-projection request
-        if (s > 0) {
+        if (s > 0 || CARRY) {
             // ---- wait until every workgroup of this chain has published h_{s-1}
             // (bounded: after a timeout here or anywhere else on the chip nobody waits any more)
             if (v == 0 && !s_dead) {
@@ -250,6 +287,13 @@ __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
         PSTAMP(5);   // publish + drain + signal
       }
     }
+    if (CARRY && KIND == DSMI_RNN_LSTM && tid < PU * 32) {
+        // c at each clip's own last live step: the cell holds c past the clip's length
+        for (int z = 0; z < nz; ++z) {
+            const int eb = z * 32 + ebl;
+            if (eunit_ok && eb < p.B) p.out[1][(size_t)eb * p.Hs + eunit] = MULTI ? st_c[z * PU * 32 + tid] : cprev_own;
+        }
+    }
     if (STAMP && lane == 0) {
         unsigned long long* o = p.dbg + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * PNW + v) * 8;
         for (int k = 0; k < 6; ++k) o[k] = tacc[k];
@@ -257,7 +301,7 @@ __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
 }
 
 template <int KIND>
-bool launch_kind(const PersistArgs& a, int ny, hipStream_t s, const EvPair& ev) {
+bool launch_kind(const PersistArgs& a, int ny, hipStream_t s, const EvPair& ev, bool carry) {
     const int npw = ceil_div(a.npair, PNW);
     const dim3 grid(a.nwg, ny, 1), block(PNT);
 #define LAUNCH_P(N, MU, ST)                                                                                          \
@@ -267,6 +311,22 @@ bool launch_kind(const PersistArgs& a, int ny, hipStream_t s, const EvPair& ev) 
         DSMI_LAUNCH((rnn_persist_kernel<KIND, N, MU, ST>), grid, block, PERSIST_LDS, s, ev, a);                       \
     } while (0)
     if (a.dbg) { if (npw > 7 || a.nz > 1) return false; LAUNCH_P(7, false, true); return true; }
+    if (carry) {
+#define LAUNCH_C(N, MU)                                                                                              \
+    do {                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_kernel<KIND, N, MU, false, true>),        \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)PERSIST_LDS);                      \
+        DSMI_LAUNCH((rnn_persist_kernel<KIND, N, MU, false, true>), grid, block, PERSIST_LDS, s, ev, a);              \
+    } while (0)
+        const bool mu = a.nz > 1;
+        if (npw <= 2) { if (mu) LAUNCH_C(2, true); else LAUNCH_C(2, false); }
+        else if (npw <= 4) { if (mu) LAUNCH_C(4, true); else LAUNCH_C(4, false); }
+        else if (npw <= 7) { if (mu) LAUNCH_C(7, true); else LAUNCH_C(7, false); }
+        else if (npw <= 10) { if (mu) LAUNCH_C(10, true); else LAUNCH_C(10, false); }
+        else return false;
+#undef LAUNCH_C
+        return true;
+    }
     if (a.nz > 1) {
         if (npw <= 4) LAUNCH_P(4, true, false);
         else if (npw <= 7) LAUNCH_P(7, true, false);
@@ -332,10 +392,15 @@ bool launch_rnn_persist(const RnnPersistLaunch& p, hipStream_t s) {
     a.B = p.B; a.T = p.T; a.G = p.g.G; a.H = p.g.H; a.Hs = p.g.Kp; a.npair = ceil_div(p.g.nq, 2); a.Np = p.g.Np; a.nwg = p.g.nwg;
     a.nz = ceil_div(p.B, 32); a.d0 = p.d0; a.nd = p.g.D;
     a.spin_limit = p.spin_limit; a.drop_wg = p.drop_wg; a.drop_step = p.drop_step;
+    const bool carry = p.h0 != nullptr;
+    if (carry) {
+        if (p.g.D != 1 || p.ny != 1 || p.d0 != 0 || p.dbg) return false;
+        a.bhh[1] = p.h0; a.out[1] = p.cst;
+    }
     switch (p.g.kind) {
-        case DSMI_RNN_GRU: return launch_kind<DSMI_RNN_GRU>(a, p.ny, s, p.ev);
-        case DSMI_RNN_LSTM: return launch_kind<DSMI_RNN_LSTM>(a, p.ny, s, p.ev);
-        default: return launch_kind<DSMI_RNN_TANH>(a, p.ny, s, p.ev);
+        case DSMI_RNN_GRU: return launch_kind<DSMI_RNN_GRU>(a, p.ny, s, p.ev, carry);
+        case DSMI_RNN_LSTM: return launch_kind<DSMI_RNN_LSTM>(a, p.ny, s, p.ev, carry);
+        default: return launch_kind<DSMI_RNN_TANH>(a, p.ny, s, p.ev, carry);
     }
 }
 

@@ -148,6 +148,12 @@ int dsmi_pack_pcm_i16(const double* src, int64_t n, int16_t* dst);
 int dsmi_upload(int device, void* dst_dev, const void* src_pinned, int64_t bytes, void* stream);
 int dsmi_features_stream(dsmi_frontend* f, const void* pcm_dev, int pcm_dtype, int64_t n_samples, double* state3,
                          float* feat_dev, int t_stride, int32_t* frames_host, void* stream);
+/* The streaming parser for n sessions in one pass: their chunks back to back in pcm_dev (n_samples[i] samples each),
+ * features to feat_dev [n][n_freq][t_stride], frames_host[i] = session i's frame count, and session i's running
+ * statistics state3[3*i .. 3*i+2] updated.  One STFT launch, one statistics launch, one host synchronisation, one
+ * normalise launch; session i's result equals its own dsmi_features_stream call. */
+int dsmi_features_stream_many(dsmi_frontend* f, const void* pcm_dev, int pcm_dtype, const int64_t* n_samples, int n,
+                              double* state3, float* feat_dev, int t_stride, int32_t* frames_host, void* stream);
 
 /* ---- Chunked unidirectional inference: DeepSpeech(streaming_inference_model=True).streaming_forward
  * (model.py:517-537) with the state MaskConvStream (:156-201), BatchRNNStream (:204-238) and LookaheadStream
@@ -164,6 +170,18 @@ const char* dsmi_stream_last_error(const dsmi_stream* s);
 int dsmi_stream_reset(dsmi_stream* s);
 int dsmi_stream_forward(dsmi_stream* s, const float* feat_dev, int T, int is_first, int is_last, float* probs_dev,
                         int T_out_cap, int32_t* T_out, void* stream);
+/* Advances n sessions of ONE model by one chunk each in one batched pass whose launch count does not depend on n
+ * (1 <= n <= DSMI_STREAM_MANY_MAX).  streams[i] are distinct handles of the same dsmi_model; feat_dev[i] is session i's
+ * chunk [n_freq][T[i]] float32 on the device; is_first[i] / is_last[i] as for dsmi_stream_forward.  Session i's
+ * probabilities go to probs_dev + i * T_out_cap * n_labels (frames past T_out[i] of its slot are scratch), and T_out[i]
+ * receives its frame count (0 while its lookahead is still buffering).  Each handle is left exactly as the same chunk
+ * through dsmi_stream_forward would leave it, so a session may alternate freely between the two calls.  Either every
+ * session advances or the call is refused with no session's state changed; the error text (dsmi_stream_last_error(NULL))
+ * names the session index.  Returns when the pass is complete (the caller's stream is synchronised). */
+#define DSMI_STREAM_MANY_MAX 256
+int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, const float* const* feat_dev, const int* T,
+                             const int* is_first, const int* is_last, float* probs_dev, int T_out_cap, int32_t* T_out,
+                             void* stream);
 
 /* ---- Offline long-form segmentation: the energy gate of
  * example_scripts/video_transcribe_simulation.py:68-143 over one recording.
