@@ -37,17 +37,29 @@ _DECODER_SETTINGS = ("lm", "alpha", "beta", "labels", "beam_width")
 class _StreamingSession(object):
     """Running state of one utterance that arrives in parts (reference DanSpeechRecognizer.py:97-216): the text so
     far, the model outputs of every part (for a final pass of the language-model decoder) and, when a secondary
-    model gives the final text, the spectrograms of every part."""
+    model gives the final text, the spectrograms of every part.  With ``lm_partials`` also the utterance's beam search,
+    carried from part to part (a ``NativeBeamStream`` of ``beam_decoder``), and its best text after the last part."""
 
-    def __init__(self, secondary_model, string_parts):
+    def __init__(self, secondary_model, string_parts, lm_partials=False):
         self.secondary_model = secondary_model
         self.string_parts = string_parts
+        self.lm_partials = lm_partials
+        self.beam = None
+        self.beam_decoder = None
         self.clear()
 
     def clear(self):
         self.text = ""
         self.outputs = []
         self.spectrograms = []
+        self.beam_text = None
+        if self.beam is not None:
+            self.beam.reset()
+
+    def close(self):
+        if self.beam is not None:
+            self.beam.close()
+            self.beam = None
 
     def extend_text(self, piece):
         """Append a part's greedy text; a part that starts with the character the text ends with continues that
@@ -71,6 +83,7 @@ class StreamingSessionHandle(object):
 
     def close(self):
         self.stream.close()
+        self.state.close()
 
 
 class _UnmergedDeviceClips(object):
@@ -637,11 +650,20 @@ class DanSpeechRecognizer(object):
         return res
 
     # ---- utterances that arrive in parts ----------------------------------------------------------------------------
-    def enable_streaming(self, secondary_model=None, return_string_parts=True):
+    def enable_streaming(self, secondary_model=None, return_string_parts=True, lm_partials=False):
+        """Streaming mode.  ``lm_partials=True`` (needs a language-model decoder, else ``ValueError``) carries the beam search
+        from part to part: every middle part then returns the best beam's text of the WHOLE utterance so far -- language-model
+        hypotheses revise earlier words, so ``return_string_parts`` does not apply to them -- and the final text, when no
+        secondary model gives it, comes from the carried search (equal to the full decode it replaces).  The running greedy
+        text and the final-text rules are those of ``lm_partials=False``, which is the reference's behaviour."""
+        if lm_partials and not isinstance(self.decoder, BeamCTCDecoder):
+            raise ValueError("lm_partials needs a language-model decoder (update_decoder(lm=...)); this recogniser decodes greedily")
         if secondary_model:
             secondary_model = secondary_model.to(self.device)
             secondary_model.eval()
-        self._session = _StreamingSession(secondary_model or None, bool(return_string_parts))
+        if self._session:
+            self._session.close()
+        self._session = _StreamingSession(secondary_model or None, bool(return_string_parts), bool(lm_partials))
         self.greedy_decoder = GreedyDecoder(labels=self.labels, blank_index=self.labels.index('_'))
         self.audio_parser = InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index())
 
@@ -649,6 +671,8 @@ class DanSpeechRecognizer(object):
         self.audio_parser = SpectrogramAudioParser(self.audio_config, device=self._device_index())
         self.greedy_decoder = None
         kept = self._session.secondary_model if (self._session and keep_secondary_model) else None
+        if self._session:
+            self._session.close()
         self._session = _StreamingSession(kept, False)
 
     def reset_streaming_params(self):
@@ -672,7 +696,10 @@ class DanSpeechRecognizer(object):
             probs, _ = ses.secondary_model(spect, torch.IntTensor([spect.size(3)]).int())
             text = self.decoder.decode(probs)[0][0][0]
         elif self.lm != "greedy":
-            text = self.decoder.decode(torch.cat(ses.outputs, dim=1))[0][0][0]
+            if ses.beam_text is not None and ses.beam_decoder is self.decoder:
+                text = ses.beam_text          # the carried search, advanced by the last part
+            else:
+                text = self.decoder.decode(torch.cat(ses.outputs, dim=1))[0][0][0]
         else:
             text = ses.text
         ses.clear()
@@ -690,7 +717,33 @@ class DanSpeechRecognizer(object):
             raise RuntimeError("the streaming model runs only on an MI355X: call model.to('cuda') first (no CPU path)")
         return StreamingSessionHandle(InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index()),
                                       _native.NativeStream(native),
-                                      _StreamingSession(self._session.secondary_model, self._session.string_parts))
+                                      _StreamingSession(self._session.secondary_model, self._session.string_parts,
+                                                        self._session.lm_partials))
+
+    def _advance_lm_partials(self, items):
+        """lm_partials: advance the carried beam searches of several sessions in ONE launch, [(session state, this part's
+        probabilities or None)], and keep each one's best text in ``beam_text``.  A session without a search yet, or whose
+        search belongs to a decoder that ``update_decoder`` has since replaced, gets a fresh one that replays all its kept
+        outputs in this same launch."""
+        import torch
+        dec = self.decoder
+        if not items or not isinstance(dec, BeamCTCDecoder):
+            for ses, _ in items:
+                ses.beam_text = None
+            return
+        streams, chunks = [], []
+        for ses, probs in items:
+            if ses.beam is None or ses.beam_decoder is not dec:
+                if ses.beam is not None:
+                    ses.beam.close()
+                ses.beam, ses.beam_decoder = dec.new_stream(self._device_index()), dec
+                kept = [o for o in ses.outputs if o is not None]
+                probs = torch.cat(kept, dim=1) if kept else None
+            streams.append(ses.beam)
+            chunks.append(probs)
+        strings, _ = dec.advance_streams(streams, chunks, 1)
+        for (ses, _), s in zip(items, strings):
+            ses.beam_text = s[0]
 
     def streaming_transcribe_many(self, sessions, recordings, is_last, is_first):
         """``streaming_transcribe`` for several sessions (``new_streaming_session``) at once, each on its next part of its own
@@ -710,19 +763,27 @@ class DanSpeechRecognizer(object):
         probs = _native.NativeStream.forward_many([sessions[k].stream for k in run], [spects[k] for k in run],
                                                   [is_first[k] for k in run], [is_last[k] for k in run])
         probs = dict(zip(run, probs))
-        said = []
+        pieces, lm_items = [None] * n, []
         for k in range(n):
             ses = sessions[k].state
             piece = ""
             if k in probs:
                 if is_first[k]:
-                    said.append("")
                     continue
                 ses.outputs.append(probs[k])
                 piece = ses.extend_text(self.greedy_decoder.decode(probs[k])[0][0][0])
                 piece = piece if ses.string_parts else ses.text
-            if not is_last[k]:
-                said.append(piece)
+            pieces[k] = piece
+            if ses.lm_partials and (k in probs or is_last[k]):
+                lm_items.append((ses, probs.get(k)))
+        self._advance_lm_partials(lm_items)          # every due session's search in one launch, last parts included
+        said = []
+        for k in range(n):
+            ses = sessions[k].state
+            if pieces[k] is None:
+                said.append("")
+            elif not is_last[k]:
+                said.append(ses.beam_text if ses.lm_partials and k in probs and ses.beam_text is not None else pieces[k])
             else:
                 said.append(self._final_text(ses) if len(ses.text) > 1 else "")
         return said
@@ -734,6 +795,7 @@ class DanSpeechRecognizer(object):
         ses = self._session
         spect = self.audio_parser.parse_audio(recording, is_last)
         said = ""
+        probs = None
         if len(spect) != 0:
             if ses.secondary_model:
                 ses.spectrograms.append(spect)
@@ -744,6 +806,10 @@ class DanSpeechRecognizer(object):
             ses.outputs.append(probs)
             piece = ses.extend_text(self.greedy_decoder.decode(probs)[0][0][0])
             said = piece if ses.string_parts else ses.text
+        if ses.lm_partials and (len(spect) != 0 or is_last):
+            self._advance_lm_partials([(ses, probs)])
+            if len(spect) != 0 and ses.beam_text is not None:
+                said = ses.beam_text
         if not is_last:
             return said
         return self._final_text(ses) if len(ses.text) > 1 else ""

@@ -57,11 +57,13 @@ class Recognizer(object):
         return parallel.recognize_sharded(eng, audio_list, dist.get_rank(), dist.get_world_size(), dev)
 
     # ---- real-time streaming (Recognizer.py:499-720) without the microphone -----------------------------
-    def enable_real_time_streaming(self, streaming_model, secondary_model=None, string_parts=True):
+    def enable_real_time_streaming(self, streaming_model, secondary_model=None, string_parts=True, lm_partials=False):
         """Recognizer.py:499-533: switch to a unidirectional streaming model (e.g.
-        ``pretrained_models.GPUStreamingRNN``), optionally with a secondary model for the final text."""
+        ``pretrained_models.GPUStreamingRNN``), optionally with a secondary model for the final text.  ``lm_partials``
+        (needs a language model): every middle output is the language-model decoder's best text of the whole utterance so
+        far, from a beam search carried from part to part (``DanSpeechRecognizer.enable_streaming``)."""
         self.update_model(streaming_model)
-        self.danspeech_recognizer.enable_streaming(secondary_model, string_parts)
+        self.danspeech_recognizer.enable_streaming(secondary_model, string_parts, lm_partials)
         self.stream = True
 
     def disable_real_time_streaming(self, keep_secondary_model_loaded=False):

@@ -121,6 +121,13 @@ _PROTOS = {
     "dsmi_beam_collect": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "dsmi_decoder_beam_stats": (C.c_int, [_vp, _vp]),
     "dsmi_debug_beam_stamps": (C.c_int, [_vp, _vp, C.c_int64]),
+    "dsmi_beam_stream_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(_vp)]),
+    "dsmi_beam_stream_destroy": (None, [_vp]),
+    "dsmi_beam_stream_last_error": (C.c_char_p, [_vp]),
+    "dsmi_beam_stream_reset": (C.c_int, [_vp]),
+    "dsmi_beam_stream_frames": (C.c_int, [_vp, _i64p]),
+    "dsmi_beam_stream_advance_many": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "dsmi_beam_stream_collect_many": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -712,6 +719,96 @@ class NativeDecoder:
         c = np.zeros(4, dtype=np.int32)
         self._check(lib().dsmi_decoder_beam_stats(self._h, _np_ptr(c)))
         return dict(zip(("revivals", "walk_hops", "list_rankings", "full_rankings"), (int(v) for v in c)))
+
+
+BEAM_STREAM_MANY_MAX = 4096     # DSMI_BEAM_STREAM_MANY_MAX: streams of one dsmi_beam_stream_advance_many launch
+
+
+class NativeBeamStream:
+    """Owns one dsmi_beam_stream handle: one utterance's beam search carried from chunk to chunk, with the language model,
+    alpha and beta of ``decoder`` (a ``NativeDecoder``, kept alive by the stream)."""
+
+    def __init__(self, decoder, beam_width=64, cutoff_top_n=40, cutoff_prob=1.0):
+        self.decoder = decoder
+        self.beam_width = int(beam_width)
+        h = _vp()
+        rc = lib().dsmi_beam_stream_create(decoder._h, self.beam_width, int(cutoff_top_n), float(cutoff_prob), C.byref(h))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_beam_stream_last_error(None) or b"").decode())
+        self._h = h
+
+    @property
+    def frames(self):
+        f = C.c_int64()
+        if lib().dsmi_beam_stream_frames(self._h, C.byref(f)) != 0:
+            raise DsmiError(DSMI_ERR_INVALID, "closed beam stream")
+        return int(f.value)
+
+    @staticmethod
+    def advance_many(streams, probs_list, n_best=0):
+        """dsmi_beam_stream_advance_many: advance distinct ``NativeBeamStream`` of one decoder in one launch, stream i by the
+        frames of ``probs_list[i]`` (CUDA float32 [T,C] or [1,T,C]; None or T = 0: no frames).  n_best = 0 -> None; else a
+        list with, per stream, (tokens [n_best,T], timesteps [n_best,T], lens [n_best], scores [n_best]) over all its frames so
+        far, T = its frame count: what ``NativeDecoder.beam`` returns first for the concatenated probabilities.  Longer lists
+        than BEAM_STREAM_MANY_MAX run as several launches."""
+        import torch
+        n = len(streams)
+        if len(probs_list) != n:
+            raise ValueError("streams and probs_list must have one entry per stream")
+        if n > BEAM_STREAM_MANY_MAX:
+            out = []
+            for k in range(0, n, BEAM_STREAM_MANY_MAX):
+                r = NativeBeamStream.advance_many(streams[k:k + BEAM_STREAM_MANY_MAX], probs_list[k:k + BEAM_STREAM_MANY_MAX], n_best)
+                out = None if r is None else out + r
+            return out
+        if n == 0:
+            return None if not n_best else []
+        ps = []
+        for p in probs_list:
+            if p is None:
+                ps.append(None)
+                continue
+            p = p.reshape(p.shape[-2], p.shape[-1]).contiguous()
+            assert p.is_cuda and p.dtype == torch.float32
+            ps.append(p if p.shape[0] > 0 else None)
+        hs = (C.c_void_p * n)(*[s._h for s in streams])
+        fp = (C.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in ps])
+        fr = np.array([0 if p is None else p.shape[0] for p in ps], dtype=np.int32)
+        dev = streams[0].decoder.device
+        rc = lib().dsmi_beam_stream_advance_many(hs, n, fp, _np_ptr(fr), int(n_best), _stream(dev))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_beam_stream_last_error(None) or b"").decode())
+        if not n_best:
+            return None
+        T = max(1, max(s.frames for s in streams))
+        tok = np.zeros((n, n_best, T), dtype=np.int32)
+        ts = np.zeros((n, n_best, T), dtype=np.int32)
+        ln = np.zeros((n, n_best), dtype=np.int32)
+        sc = np.zeros((n, n_best), dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.int32)
+        rc = lib().dsmi_beam_stream_collect_many(hs, n, int(n_best), T, _np_ptr(tok), _np_ptr(ts), _np_ptr(ln), _np_ptr(sc), _np_ptr(cnt))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_beam_stream_last_error(None) or b"").decode())
+        return [(tok[i, :, :max(1, s.frames)], ts[i, :, :max(1, s.frames)], ln[i], sc[i]) for i, s in enumerate(streams)]
+
+    def advance(self, probs, n_best=0):
+        r = NativeBeamStream.advance_many([self], [probs], n_best)
+        return None if r is None else r[0]
+
+    def reset(self):
+        if lib().dsmi_beam_stream_reset(self._h) != 0:
+            raise DsmiError(DSMI_ERR_INVALID, "closed beam stream")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dsmi_beam_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class NativeLM:

@@ -25,7 +25,38 @@ struct BeamArgs {
     unsigned long long* stamps;  // optional [64 frames][8]: 100 MHz timestamps of utterance 0's phase boundaries, from the middle of the clip
     // outputs
     int32_t *out_tok, *out_step, *out_len, *out_n; double* out_score;
+    const struct BeamStreamDesc* desc;   // RESUME: [gridDim.x] one session each (the batch fields above are unused)
 };
+
+// One session of a resumable launch (beam_kernel<..., RESUME = true>): this chunk's rows, the search carried from the frames
+// before it, the session's node pool, and where its best hypotheses go.
+struct BeamStreamDesc {
+    const float* probs;          // [T][C] this chunk's probabilities (T = 0 allowed)
+    unsigned char* state;        // the carried search, laid out by stream_state()
+    NodeRec* nodes;              // the session's node pool (capacity >= 2 + (t0 + T) * beam, kept by the host)
+    int32_t *out_tok, *out_step; // [n_best][out_T] hypotheses over frames 0 .. t0 + T, best first
+    int32_t *out_len, *out_n;    // [n_best], [1]: beams written (min(beams in the search, n_best))
+    double* out_score;           // [n_best] totals with the trailing-word term, as the offline search reports them
+    int T, t0, n_best, out_T;    // n_best = 0: advance only
+};
+
+// The carried search of one session in HBM: every value a frame reads that an earlier frame wrote.  That is the current buffer's
+// entry arrays and child table, the beam size, the scorer's min_cutoff key, the score bound and the node count; everything else
+// in the carve is written in the frame that reads it (the hist bins are cleared as they are read, the other buffer's child table
+// in F2, the probability row one frame ahead -- the entry makes the chunk's first).
+struct StreamHdr { int nb, nn; uint64_t kmin; double bound; double pad; };
+struct StreamState { size_t hdr, bprev, nbprev, score, uplpc, ownlpc, node, ch, ds, depth, up, upch, upnode, memo, ctx, cell, bytes; };
+__host__ __device__ inline StreamState stream_state(int BW, int C) {
+    StreamState k; size_t o = 0;
+    auto take = [&](size_t n, size_t sz) { const size_t at = o; o += ((n * sz + 15) & ~(size_t)15); return at; };
+    k.hdr = take(1, sizeof(StreamHdr));
+    k.bprev = take(BW, 8); k.nbprev = take(BW, 8); k.score = take(BW, 8); k.uplpc = take(BW, 8); k.ownlpc = take(BW, 8);
+    k.node = take(BW, 4); k.ch = take(BW, 4); k.ds = take(BW, 4); k.depth = take(BW, 4); k.up = take(BW, 4);
+    k.upch = take(BW, 4); k.upnode = take(BW, 4); k.memo = take(BW, 4); k.ctx = take((size_t)BW * MAXCTX, 4);
+    k.cell = take(((size_t)BW * C + 1) & ~(size_t)1, 2);
+    k.bytes = o;
+    return k;
+}
 
 // On-chip layout of one utterance's search, shared by the kernel and the launcher's size check.
 struct Carve {
@@ -122,7 +153,10 @@ __device__ __noinline__ float lm_word_log10(const LmView* v, const int32_t* ctx,
 // CBW / CC: beam width and label count as compile-time constants (0: read from the arguments).  With them every LDS array's
 // offset is an immediate of its instruction instead of a register the frame loop keeps live: the generic build holds ~30 such
 // bases and spills 60 dwords per lane at 1024 threads.
-template <int BT, int KMAX, int CBW = 0, int CC = 0>
+// RESUME: one workgroup per session of a.desc, resuming that session's carried search at frame t0 for its chunk's T frames,
+// saving the search back, and -- n_best > 0 -- writing the best n_best hypotheses over all t0 + T frames (the final section on
+// the saved copy: the carried scores never receive the trailing-word term).  Node timesteps are absolute (t0 + t).
+template <int BT, int KMAX, int CBW = 0, int CC = 0, bool RESUME = false>
 __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
     constexpr int NWAVE = BT / 64, NBINS = BT, BPL = NBINS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -179,9 +213,12 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
 #define s_nrev si[5]
 #define s_kmin su[0]
 
-    NodeRec* nodes = a.nodes + (size_t)b * a.ncap;
-    const int T = a.sizes ? min(a.sizes[b], a.T) : a.T;
-    const float* pb = a.probs + (size_t)b * a.T * C;
+    const BeamStreamDesc* sdsc = RESUME ? a.desc + b : nullptr;
+    NodeRec* nodes = RESUME ? sdsc->nodes : a.nodes + (size_t)b * a.ncap;
+    const int T = RESUME ? sdsc->T : a.sizes ? min(a.sizes[b], a.T) : a.T;
+    const float* pb = RESUME ? sdsc->probs : a.probs + (size_t)b * a.T * C;
+    const int t0 = RESUME ? sdsc->t0 : 0;
+    const bool fresh = !RESUME || t0 == 0;
     const int NCTX = a.order - 1;
     const double betap = fmax(0.0, a.beta);
     const bool prune = a.cutoff_prob < 1.0f || a.cutoff_top_n < C;
@@ -240,7 +277,9 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
     };
 
     // ---- start: the root is the whole beam
+    int nn0 = 1;
     for (int q = tid; q < NBINS; q += BT) hist[q] = 0;
+    if (fresh) {
     for (int q = tid; q < CELLS; q += BT) reinterpret_cast<int*>(cell)[q] = -1;       // both buffers (2 * CELLS shorts)
     if (tid == 0) {
         NodeRec r; r.parent = -1; r.ch = -1; r.tstep = 0; r.depth = 0; r.lpc = -INFINITY; r.pad = 0.0;
@@ -251,10 +290,29 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
         s_nb = 1; s_kmin = okey(0.0); sd[4] = 0.0; s_nlist = 0; s_nrev = 0;
         *s_lm = a.lm;
     }
+    } else if constexpr (RESUME) {
+        // ---- resume: the carried search into buffer 0 (buffer 1's child table is cleared in F2 before anything uses it)
+        const StreamState ks = stream_state(BW, C);
+        const unsigned char* st = sdsc->state;
+        const StreamHdr h = *reinterpret_cast<const StreamHdr*>(st + ks.hdr);
+        nn0 = h.nn;
+        for (int j = tid; j < h.nb; j += BT) {
+            e_bprev[j] = reinterpret_cast<const double*>(st + ks.bprev)[j]; e_nbprev[j] = reinterpret_cast<const double*>(st + ks.nbprev)[j];
+            e_score[j] = reinterpret_cast<const double*>(st + ks.score)[j]; e_uplpc[j] = reinterpret_cast<const double*>(st + ks.uplpc)[j];
+            e_ownlpc[j] = reinterpret_cast<const double*>(st + ks.ownlpc)[j];
+            e_node[j] = reinterpret_cast<const int*>(st + ks.node)[j]; e_ch[j] = reinterpret_cast<const int*>(st + ks.ch)[j];
+            e_ds[j] = reinterpret_cast<const int*>(st + ks.ds)[j]; e_depth[j] = reinterpret_cast<const int*>(st + ks.depth)[j];
+            e_up[j] = reinterpret_cast<const int*>(st + ks.up)[j]; e_upch[j] = reinterpret_cast<const int*>(st + ks.upch)[j];
+            e_upnode[j] = reinterpret_cast<const int*>(st + ks.upnode)[j]; e_memo[j] = reinterpret_cast<const int*>(st + ks.memo)[j];
+            for (int k = 0; k < MAXCTX; ++k) e_ctx[(size_t)j * MAXCTX + k] = reinterpret_cast<const int*>(st + ks.ctx)[(size_t)j * MAXCTX + k];
+        }
+        for (int q = tid; q < CELLS / 2; q += BT) reinterpret_cast<int*>(cell)[q] = reinterpret_cast<const int*>(st + ks.cell)[q];
+        if (tid == 0) { s_nb = h.nb; s_kmin = h.kmin; sd[4] = h.bound; s_nlist = 0; s_nrev = 0; *s_lm = a.lm; }
+    }
     if (wid == NWAVE - 1 && T > 0)
         make_row(0, lane < C ? pb[lane] : 0.f, lane + 64 < C ? pb[lane + 64] : 0.f, pb[a.blank]);
     __syncthreads();
-    int cur = 0, nn = 1;
+    int cur = 0, nn = nn0;
     const int stamp_t0 = T / 2;
     auto stamp = [&](int t, int phase) {
         if (a.stamps && b == 0 && tid == 0 && t >= stamp_t0 && t < stamp_t0 + 64) a.stamps[(t - stamp_t0) * 8 + phase] = wall_clock64();
@@ -331,7 +389,7 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
                         if (uplpc[j] < lpv[c]) {            // get_path_trie: a better emission frame for the edge's top node
                             uplpc[j] = lpv[c];
                             NodeRec* tn = nodes + upnode[j];
-                            tn->lpc = lpv[c]; tn->tstep = t;
+                            tn->lpc = lpv[c]; tn->tstep = t0 + t;
                         }
                         if (upnode[j] == node[j]) {
                             int arcw = -1;
@@ -569,7 +627,7 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
             if (mk == 1) {                                  // a new node
                 id = nn + f_fr[sl];
                 lpc = lpv[c];
-                NodeRec r; r.parent = node[i]; r.ch = c; r.tstep = t; r.depth = depth[i] + 1; r.lpc = lpc; r.pad = 0.0;
+                NodeRec r; r.parent = node[i]; r.ch = c; r.tstep = t0 + t; r.depth = depth[i] + 1; r.lpc = lpc; r.pad = 0.0;
                 nodes[id] = r;
             } else {                                             // a dormant prefix is back: same node, its log_prob_c kept
                 const int rep = mk - 2;
@@ -605,7 +663,28 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
     // ---- final: trailing partial word, order, write out
     DSMI_WAIT_STORES();
     __syncthreads();
-    {
+    if constexpr (RESUME) {
+        // ---- save the carried search (the final section below then works on the LDS copy)
+        const StreamState ks = stream_state(BW, C);
+        unsigned char* st = sdsc->state;
+        const int nb = s_nb;
+        const size_t o = (size_t)cur * BW;
+        for (int j = tid; j < nb; j += BT) {
+            reinterpret_cast<double*>(st + ks.bprev)[j] = e_bprev[o + j]; reinterpret_cast<double*>(st + ks.nbprev)[j] = e_nbprev[o + j];
+            reinterpret_cast<double*>(st + ks.score)[j] = e_score[o + j]; reinterpret_cast<double*>(st + ks.uplpc)[j] = e_uplpc[o + j];
+            reinterpret_cast<double*>(st + ks.ownlpc)[j] = e_ownlpc[o + j];
+            reinterpret_cast<int*>(st + ks.node)[j] = e_node[o + j]; reinterpret_cast<int*>(st + ks.ch)[j] = e_ch[o + j];
+            reinterpret_cast<int*>(st + ks.ds)[j] = e_ds[o + j]; reinterpret_cast<int*>(st + ks.depth)[j] = e_depth[o + j];
+            reinterpret_cast<int*>(st + ks.up)[j] = e_up[o + j]; reinterpret_cast<int*>(st + ks.upch)[j] = e_upch[o + j];
+            reinterpret_cast<int*>(st + ks.upnode)[j] = e_upnode[o + j]; reinterpret_cast<int*>(st + ks.memo)[j] = e_memo[o + j];
+            for (int k = 0; k < MAXCTX; ++k) reinterpret_cast<int*>(st + ks.ctx)[(size_t)j * MAXCTX + k] = e_ctx[(o + j) * MAXCTX + k];
+        }
+        const int* cellv = reinterpret_cast<const int*>(cell + (size_t)cur * CELLS);
+        for (int q = tid; q < CELLS / 2; q += BT) reinterpret_cast<int*>(st + ks.cell)[q] = cellv[q];
+        if (tid == 0) { StreamHdr h; h.nb = nb; h.nn = nn; h.kmin = s_kmin; h.bound = sd[4]; h.pad = 0.0; *reinterpret_cast<StreamHdr*>(st + ks.hdr) = h; }
+        __syncthreads();
+    }
+    if (!RESUME || sdsc->n_best > 0) {
         const int nb = s_nb;
         double* score = e_score + cur * BW; const int* node = e_node + cur * BW; const int* ech = e_ch + cur * BW;
         const int* eds = e_ds + cur * BW; const int* depth = e_depth + cur * BW; const int* ctx = e_ctx + (size_t)cur * BW * MAXCTX;
@@ -629,13 +708,22 @@ __global__ __launch_bounds__(BT) void beam_kernel(BeamArgs a) {
                 rank += score[j] > score[i] || (score[j] == score[i] && (ech[j] < ech[i] || (ech[j] == ech[i] && j < i)));
             }
             const int len = depth[i];
+            if constexpr (RESUME) {
+                if (rank >= sdsc->n_best) continue;
+                const size_t o = (size_t)rank * sdsc->out_T;
+                int n = node[i];
+                for (int k = len - 1; k >= 0; --k) { const NodeRec r = nodes[n]; sdsc->out_tok[o + k] = r.ch; sdsc->out_step[o + k] = r.tstep; n = r.parent; }
+                sdsc->out_len[rank] = len;
+                sdsc->out_score[rank] = score[i];
+                continue;
+            }
             const size_t o = ((size_t)b * BW + rank) * a.T;
             int n = node[i];
             for (int k = len - 1; k >= 0; --k) { const NodeRec r = nodes[n]; a.out_tok[o + k] = r.ch; a.out_step[o + k] = r.tstep; n = r.parent; }
             a.out_len[(size_t)b * BW + rank] = len;
             a.out_score[(size_t)b * BW + rank] = score[i];
         }
-        if (tid == 0) a.out_n[b] = nb;
+        if (tid == 0) { if constexpr (RESUME) *sdsc->out_n = min(nb, sdsc->n_best); else a.out_n[b] = nb; }
     }
     if (a.dbg) {
         dbg_rev = wave_sum(dbg_rev); dbg_hops = wave_sum(dbg_hops); dbg_list = wave_sum(dbg_list); dbg_full = wave_sum(dbg_full);

@@ -54,6 +54,11 @@ struct dsmi_decoder {
     unsigned char* pin = nullptr; size_t pin_bytes = 0;
     hipEvent_t beam_done = nullptr;
     hipStream_t copy_stream = nullptr;      // the collect's device-to-host copies: the device's collect stream (collect_stream)
+    // resumable searches (dsmi_beam_stream): bumped by every dsmi_decoder_set_lm, so that a stream can tell that the scorer it was
+    // created with is gone; the launch table and result staging of dsmi_beam_stream_advance_many (not the offline workspace above)
+    uint64_t lm_gen = 0;
+    std::mutex bs_mu;
+    unsigned char *bs_dev = nullptr, *bs_pin = nullptr; size_t bs_dev_cap = 0, bs_pin_cap = 0;
 };
 
 // ONE stream per device for the device-to-host copies of every decoder handle's collect, made at the first collect and kept for
@@ -120,6 +125,8 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     (void)hipDeviceSynchronize();
     for (void* p : {(void*)d->g_raw, (void*)d->g_ids, (void*)d->g_offs, (void*)d->g_nout, (void*)d->g_sizes, (void*)d->ws}) if (p) (void)hipFree(p);
     free_lm(d);
+    if (d->bs_dev) (void)hipFree(d->bs_dev);
+    if (d->bs_pin) (void)hipHostFree(d->bs_pin);
     delete d;
 }
 
@@ -139,6 +146,7 @@ extern "C" const char* dsmi_decoder_label(const dsmi_decoder* d, int index) {
 
 extern "C" int dsmi_decoder_set_lm(dsmi_decoder* d, const char* path, double alpha, double beta) {
     if (!d) return DSMI_ERR_INVALID;
+    ++d->lm_gen;
     DEC_HIP(d, hipSetDevice(d->device));
     DEC_HIP(d, hipDeviceSynchronize());
     free_lm(d);
@@ -348,6 +356,26 @@ extern "C" int dsmi_beam_enqueue(dsmi_decoder* d, const float* probs, const int3
     return DSMI_OK;
 }
 
+// ctcdecode's reported score of one beam: its total with the word bonus and the LM weight stripped, negated ("-approx_ctc")
+static float beam_score_out(const dsmi_decoder* d, const int32_t* tk, int len, double total) {
+    double approx = total;
+    if (d->has_lm) {
+        std::vector<int32_t> words;
+        std::string cur;
+        auto flush = [&]() {
+            if (cur.empty()) return;
+            auto it = d->lm.word2id.find(cur);
+            words.push_back(it == d->lm.word2id.end() ? -1 : it->second);
+            cur.clear();
+        };
+        for (int k = 0; k < len; ++k) { if (tk[k] == d->space) flush(); else cur += d->labels[tk[k]]; }
+        flush();
+        approx -= (double)len * d->beta;
+        approx -= d->lm.sent_ln(words) * d->alpha;
+    }
+    return (float)-approx;
+}
+
 // Waits for the enqueued beam search and hands its results over (layouts of dsmi_beam).
 extern "C" int dsmi_beam_collect(dsmi_decoder* d, int32_t* tokens, int32_t* tsteps, int32_t* lens, float* scores) {
     if (!d) return DSMI_ERR_INVALID;
@@ -394,23 +422,7 @@ extern "C" int dsmi_beam_collect(dsmi_decoder* d, int32_t* tokens, int32_t* tste
             const size_t q = (size_t)b * beam + p;
             if (p >= h_n[b]) { lens[q] = 0; scores[q] = 0.f; continue; }
             lens[q] = h_len[q];
-            double approx = h_score[q];
-            if (d->has_lm) {
-                std::vector<int32_t> words;
-                std::string cur;
-                auto flush = [&]() {
-                    if (cur.empty()) return;
-                    auto it = d->lm.word2id.find(cur);
-                    words.push_back(it == d->lm.word2id.end() ? -1 : it->second);
-                    cur.clear();
-                };
-                const int32_t* tk = p_tok + q * To;
-                for (int k = 0; k < h_len[q]; ++k) { if (tk[k] == d->space) flush(); else cur += d->labels[tk[k]]; }
-                flush();
-                approx -= (double)h_len[q] * d->beta;
-                approx -= d->lm.sent_ln(words) * d->alpha;
-            }
-            scores[q] = (float)-approx;
+            scores[q] = beam_score_out(d, p_tok + q * To, h_len[q], h_score[q]);
         }
     return DSMI_OK;
 }
@@ -436,6 +448,268 @@ extern "C" int dsmi_beam(dsmi_decoder* d, const float* probs, const int32_t* siz
     return dsmi_beam_collect(d, tokens, tsteps, lens, scores);
 }
 
+
+// ---- resumable search: one utterance's CTC prefix beam search carried across chunks (beam_kernel<..., RESUME = true>)
+struct dsmi_beam_stream {
+    dsmi_decoder* d = nullptr;
+    int device = 0, C = 0, beam = 0, cutoff_top_n = 0;
+    double cutoff_prob = 1.0;
+    uint64_t gen = 0;                  // the decoder's lm_gen at creation
+    int64_t frames = 0;                // frames decoded so far
+    unsigned char* state = nullptr;    // stream_state(beam, C) bytes
+    NodeRec* nodes = nullptr; int64_t ncap = 0;
+    std::string err;
+    // the hypotheses of the last advance with n_best > 0, until dsmi_beam_stream_collect_many
+    bool pending = false; int pend_best = 0, pend_n = 0, pend_len = 0;
+    std::vector<int32_t> h_tok, h_step, h_len; std::vector<double> h_score;
+};
+
+static thread_local std::string g_bs_error;
+static constexpr int64_t kStreamPoolFrames = 8;     // the first pool holds 8 frames' nodes; it doubles as the utterance grows
+
+static int64_t pool_need(int beam, int64_t frames) { return 2 + frames * beam; }     // = dsmi_beam_enqueue's ncap for To = frames
+
+extern "C" int dsmi_beam_stream_create(dsmi_decoder* d, int beam_width, int cutoff_top_n, double cutoff_prob, dsmi_beam_stream** out) {
+    if (!d || !out || beam_width < 1) { g_bs_error = "bad beam stream arguments"; return DSMI_ERR_INVALID; }
+    const int C = (int)d->labels.size();
+    constexpr int BT = 1024;
+    const int EW = (beam_width + 63) / 64, RW = d->has_lm ? 2 * EW : EW;
+    const size_t per = BT > 64 * RW ? ((size_t)beam_width * C + (BT - 64 * RW) - 1) / (BT - 64 * RW) : ~(size_t)0;
+    if (carve(beam_width, C, BT).bytes > 160 * 1024 - 256 || per > 24 || C > MAXC) {
+        g_bs_error = "beam_width * (n_labels + 1) exceeds the on-chip candidate buffer"; return DSMI_ERR_CAPACITY;
+    }
+    if (hipSetDevice(d->device) != hipSuccess) { g_bs_error = "hipSetDevice failed"; return DSMI_ERR_HIP; }
+    dsmi_beam_stream* s = new dsmi_beam_stream();
+    s->d = d; s->device = d->device; s->C = C; s->beam = beam_width; s->cutoff_top_n = cutoff_top_n; s->cutoff_prob = cutoff_prob;
+    s->gen = d->lm_gen;
+    s->ncap = pool_need(beam_width, kStreamPoolFrames);
+    if (hipMalloc((void**)&s->state, stream_state(beam_width, C).bytes) != hipSuccess ||
+        hipMalloc((void**)&s->nodes, sizeof(NodeRec) * (size_t)s->ncap) != hipSuccess) {
+        dsmi_beam_stream_destroy(s);
+        g_bs_error = "beam stream: HIP allocation failed"; return DSMI_ERR_NOMEM;
+    }
+    *out = s;
+    return DSMI_OK;
+}
+
+extern "C" void dsmi_beam_stream_destroy(dsmi_beam_stream* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipDeviceSynchronize();
+    if (s->state) (void)hipFree(s->state);
+    if (s->nodes) (void)hipFree(s->nodes);
+    delete s;
+}
+
+extern "C" const char* dsmi_beam_stream_last_error(const dsmi_beam_stream* s) { return s ? s->err.c_str() : g_bs_error.c_str(); }
+
+extern "C" int dsmi_beam_stream_reset(dsmi_beam_stream* s) {
+    if (!s) return DSMI_ERR_INVALID;
+    s->frames = 0; s->pending = false;     // the next advance starts at the root (t0 = 0): nothing of the state is read
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_beam_stream_frames(const dsmi_beam_stream* s, int64_t* frames) {
+    if (!s || !frames) return DSMI_ERR_INVALID;
+    *frames = s->frames;
+    return DSMI_OK;
+}
+
+static int bs_fail(int code, int i, const std::string& msg) {
+    g_bs_error = i >= 0 ? "beam stream " + std::to_string(i) + ": " + msg : msg;
+    return code;
+}
+
+#define BS_HIP(expr)                                                                                      \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) { g_bs_error = std::string(#expr) + ": " + hipGetErrorString(e_); return DSMI_ERR_HIP; } \
+    } while (0)
+
+extern "C" int dsmi_beam_stream_advance_many(dsmi_beam_stream* const* ss, int n, const float* const* probs_dev, const int32_t* frames,
+                                             int n_best, void* stream) {
+    // ---- refusals, before any state changes
+    if (!ss || !frames || n < 1 || n > DSMI_BEAM_STREAM_MANY_MAX) return bs_fail(DSMI_ERR_INVALID, -1, "bad beam stream arguments");
+    for (int i = 0; i < n; ++i) if (!ss[i]) return bs_fail(DSMI_ERR_INVALID, i, "null handle");
+    {
+        std::vector<const dsmi_beam_stream*> sorted(ss, ss + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return bs_fail(DSMI_ERR_INVALID, -1, "the same handle appears twice in one call");
+    }
+    dsmi_beam_stream* s0 = ss[0];
+    dsmi_decoder* d = s0->d;
+    if (n_best < 0 || n_best > s0->beam) return bs_fail(DSMI_ERR_INVALID, -1, "n_best must lie in 0 .. beam_width");
+    int64_t tmax = 1;
+    for (int i = 0; i < n; ++i) {
+        const dsmi_beam_stream* s = ss[i];
+        if (s->d != d || s->device != s0->device) return bs_fail(DSMI_ERR_INVALID, i, "the streams of one call must belong to one decoder");
+        if (s->beam != s0->beam || s->cutoff_top_n != s0->cutoff_top_n || s->cutoff_prob != s0->cutoff_prob)
+            return bs_fail(DSMI_ERR_INVALID, i, "the streams of one call must share beam_width, cutoff_top_n and cutoff_prob");
+        if (s->gen != d->lm_gen) return bs_fail(DSMI_ERR_INVALID, i, "the decoder's language model or alpha / beta changed since the stream was created");
+        if (s->pending) return bs_fail(DSMI_ERR_INVALID, i, "the hypotheses of the previous advance have not been collected");
+        if (frames[i] < 0 || (frames[i] > 0 && (!probs_dev || !probs_dev[i]))) return bs_fail(DSMI_ERR_INVALID, i, "bad frame count or probabilities");
+        if (s->frames + frames[i] > (int64_t)INT32_MAX / 2 / s->beam) return bs_fail(DSMI_ERR_CAPACITY, i, "utterance too long for one node pool");
+        tmax = std::max(tmax, s->frames + frames[i]);
+    }
+    std::lock_guard<std::mutex> lock(d->bs_mu);
+    BS_HIP(hipSetDevice(d->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int beam = s0->beam, C = s0->C;
+    // ---- node pools: grown before the launch that could overflow them (doubled, stream-ordered device-to-device copy); every
+    // allocation is made before any handle changes, and a failure frees what was made
+    std::vector<NodeRec*> grown(n, nullptr);
+    std::vector<int64_t> grown_cap(n, 0);
+    for (int i = 0; i < n; ++i) {
+        const int64_t need = pool_need(beam, ss[i]->frames + frames[i]);
+        if (need <= ss[i]->ncap) continue;
+        int64_t cap = ss[i]->ncap;
+        while (cap < need) cap *= 2;
+        if (hipMalloc((void**)&grown[i], sizeof(NodeRec) * (size_t)cap) != hipSuccess) {
+            for (NodeRec* p : grown) if (p) (void)hipFree(p);
+            return bs_fail(DSMI_ERR_NOMEM, i, "node pool allocation failed");
+        }
+        grown_cap[i] = cap;
+    }
+    // ---- launch workspace: [n] descriptors, then the outputs [n][n_best][tmax] tokens, steps, [n][n_best] lens, [n] counts,
+    // [n][n_best] scores
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nb = (size_t)std::max(n_best, 1);
+    const size_t o_tab = 0, o_tok = al(sizeof(BeamStreamDesc) * n), o_step = o_tok + al((size_t)n * nb * tmax * 4);
+    const size_t o_len = o_step + al((size_t)n * nb * tmax * 4), o_cnt = o_len + al((size_t)n * nb * 4), o_score = o_cnt + al((size_t)n * 4);
+    const size_t bytes = o_score + al((size_t)n * nb * 8);
+    if (bytes > d->bs_dev_cap || o_tok > d->bs_pin_cap) {
+        (void)hipDeviceSynchronize();
+        bool ok = true;
+        if (bytes > d->bs_dev_cap) {
+            if (d->bs_dev) (void)hipFree(d->bs_dev);
+            d->bs_dev = nullptr; d->bs_dev_cap = 0;
+            ok = hipMalloc((void**)&d->bs_dev, bytes) == hipSuccess;
+            if (ok) d->bs_dev_cap = bytes;
+        }
+        if (ok && o_tok > d->bs_pin_cap) {
+            if (d->bs_pin) (void)hipHostFree(d->bs_pin);
+            d->bs_pin = nullptr; d->bs_pin_cap = 0;
+            ok = hipHostMalloc((void**)&d->bs_pin, o_tok, hipHostMallocDefault) == hipSuccess;
+            if (ok) d->bs_pin_cap = o_tok;
+        }
+        if (!ok) {
+            for (NodeRec* p : grown) if (p) (void)hipFree(p);
+            return bs_fail(DSMI_ERR_NOMEM, -1, "beam stream launch workspace allocation failed");
+        }
+    }
+    // ---- from here on the handles change
+    for (int i = 0; i < n; ++i) {
+        if (!grown[i]) continue;
+        dsmi_beam_stream* s = ss[i];
+        if (s->frames > 0) BS_HIP(hipMemcpyAsync(grown[i], s->nodes, sizeof(NodeRec) * (size_t)pool_need(beam, s->frames), hipMemcpyDeviceToDevice, st));
+    }
+    unsigned char* w = d->bs_dev;
+    BeamStreamDesc* tab = reinterpret_cast<BeamStreamDesc*>(d->bs_pin);
+    for (int i = 0; i < n; ++i) {
+        dsmi_beam_stream* s = ss[i];
+        BeamStreamDesc& q = tab[i];
+        q.probs = frames[i] > 0 ? probs_dev[i] : nullptr; q.state = s->state; q.nodes = grown[i] ? grown[i] : s->nodes;
+        q.out_tok = (int32_t*)(w + o_tok) + (size_t)i * nb * tmax; q.out_step = (int32_t*)(w + o_step) + (size_t)i * nb * tmax;
+        q.out_len = (int32_t*)(w + o_len) + (size_t)i * nb; q.out_n = (int32_t*)(w + o_cnt) + i; q.out_score = (double*)(w + o_score) + (size_t)i * nb;
+        q.T = frames[i]; q.t0 = (int)s->frames; q.n_best = n_best; q.out_T = (int)tmax;
+    }
+    BS_HIP(hipMemcpyAsync(w + o_tab, tab, sizeof(BeamStreamDesc) * n, hipMemcpyHostToDevice, st));
+    BeamArgs a{};
+    a.C = C; a.blank = d->blank; a.space = d->space; a.beam = beam;
+    a.cutoff_top_n = s0->cutoff_top_n; a.cutoff_prob = (float)s0->cutoff_prob;
+    a.has_lm = d->has_lm ? 1 : 0; a.order = d->has_lm ? d->lm.order : 1; a.alpha = d->alpha; a.beta = d->beta;
+    a.lm = d->lm.view(); a.lm.tab = d->d_tab; a.lm.klm.base = d->d_klm; a.trie_next = d->d_next; a.trie_word = d->d_word; a.unk = d->lm.unk; a.bos = d->lm.bos;
+    a.desc = reinterpret_cast<const BeamStreamDesc*>(w + o_tab);
+    constexpr int BT = 1024;
+    const size_t lds = carve(beam, C, BT).bytes;
+    const int EW = (beam + 63) / 64, RW = d->has_lm ? 2 * EW : EW;
+    const size_t per = ((size_t)beam * C + (BT - 64 * RW) - 1) / (BT - 64 * RW);
+    auto launch = [&](auto kern) -> hipError_t {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(n), dim3(BT), lds, st, a);
+        return hipSuccess;
+    };
+    // the instantiations of dsmi_beam_enqueue, resumable
+    if (C == 33 && beam == 64) BS_HIP(launch(beam_kernel<1024, 3, 64, 33, true>));
+    else if (C == 33 && beam == 128) BS_HIP(launch(beam_kernel<1024, 6, 128, 33, true>));
+    else if (per <= 3) BS_HIP(launch(beam_kernel<1024, 3, 0, 0, true>));
+    else if (per <= 6) BS_HIP(launch(beam_kernel<1024, 6, 0, 0, true>));
+    else if (per <= 12) BS_HIP(launch(beam_kernel<1024, 12, 0, 0, true>));
+    else BS_HIP(launch(beam_kernel<1024, 24, 0, 0, true>));
+    BS_HIP(hipGetLastError());
+    std::vector<NodeRec*> old(n, nullptr);
+    for (int i = 0; i < n; ++i) {
+        dsmi_beam_stream* s = ss[i];
+        if (grown[i]) { old[i] = s->nodes; s->nodes = grown[i]; s->ncap = grown_cap[i]; }
+        s->frames += frames[i];
+    }
+    // the pass is complete when this returns: the old pools can go, the table can be refilled
+    const hipError_t sync = hipStreamSynchronize(st);
+    for (NodeRec* p : old) if (p) (void)hipFree(p);
+    if (sync != hipSuccess) { g_bs_error = std::string("beam stream launch: ") + hipGetErrorString(sync); return DSMI_ERR_HIP; }
+    if (n_best == 0) return DSMI_OK;
+    // ---- the hypotheses: lengths, counts and scores, then the token columns that hold tokens
+    std::vector<int32_t> h_len((size_t)n * nb), h_cnt(n); std::vector<double> h_score((size_t)n * nb);
+    BS_HIP(hipMemcpy(h_len.data(), w + o_len, h_len.size() * 4, hipMemcpyDeviceToHost));
+    BS_HIP(hipMemcpy(h_cnt.data(), w + o_cnt, h_cnt.size() * 4, hipMemcpyDeviceToHost));
+    BS_HIP(hipMemcpy(h_score.data(), w + o_score, h_score.size() * 8, hipMemcpyDeviceToHost));
+    int maxlen = 0;
+    for (int i = 0; i < n; ++i) for (int p = 0; p < h_cnt[i]; ++p) maxlen = std::max(maxlen, (int)h_len[(size_t)i * nb + p]);
+    std::vector<int32_t> h_tok((size_t)n * nb * std::max(maxlen, 1)), h_step(h_tok.size());
+    if (maxlen > 0) {
+        BS_HIP(hipMemcpy2D(h_tok.data(), (size_t)maxlen * 4, w + o_tok, (size_t)tmax * 4, (size_t)maxlen * 4, (size_t)n * nb, hipMemcpyDeviceToHost));
+        BS_HIP(hipMemcpy2D(h_step.data(), (size_t)maxlen * 4, w + o_step, (size_t)tmax * 4, (size_t)maxlen * 4, (size_t)n * nb, hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < n; ++i) {
+        dsmi_beam_stream* s = ss[i];
+        const int cnt = h_cnt[i];
+        s->pend_best = n_best; s->pend_n = cnt; s->pend_len = maxlen;
+        s->h_len.assign(h_len.begin() + (size_t)i * nb, h_len.begin() + (size_t)i * nb + n_best);
+        s->h_score.assign(h_score.begin() + (size_t)i * nb, h_score.begin() + (size_t)i * nb + n_best);
+        const size_t per_s = (size_t)n_best * std::max(maxlen, 1);
+        s->h_tok.assign(h_tok.begin() + (size_t)i * nb * std::max(maxlen, 1), h_tok.begin() + (size_t)i * nb * std::max(maxlen, 1) + per_s);
+        s->h_step.assign(h_step.begin() + (size_t)i * nb * std::max(maxlen, 1), h_step.begin() + (size_t)i * nb * std::max(maxlen, 1) + per_s);
+        s->pending = true;
+    }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_beam_stream_collect_many(dsmi_beam_stream* const* ss, int n, int n_best, int T_stride, int32_t* tokens,
+                                             int32_t* tsteps, int32_t* lens, float* scores, int32_t* counts) {
+    if (!ss || n < 1 || n_best < 1 || T_stride < 1 || !tokens || !tsteps || !lens || !scores || !counts)
+        return bs_fail(DSMI_ERR_INVALID, -1, "bad beam stream arguments");
+    for (int i = 0; i < n; ++i) if (!ss[i]) return bs_fail(DSMI_ERR_INVALID, i, "null handle");
+    {
+        std::vector<const dsmi_beam_stream*> sorted(ss, ss + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return bs_fail(DSMI_ERR_INVALID, -1, "the same handle appears twice in one call");
+    }
+    for (int i = 0; i < n; ++i) {
+        const dsmi_beam_stream* s = ss[i];
+        if (!s->pending) return bs_fail(DSMI_ERR_INVALID, i, "no hypotheses to collect");
+        if (s->pend_best != n_best) return bs_fail(DSMI_ERR_INVALID, i, "n_best differs from the advance's");
+        if (s->gen != s->d->lm_gen) return bs_fail(DSMI_ERR_INVALID, i, "the decoder's language model or alpha / beta changed since the stream was created");
+        for (int p = 0; p < s->pend_n; ++p) if (s->h_len[p] > T_stride) return bs_fail(DSMI_ERR_CAPACITY, i, "T_stride is shorter than a hypothesis");
+    }
+    for (int i = 0; i < n; ++i) {
+        dsmi_beam_stream* s = ss[i];
+        const int L = std::max(s->pend_len, 1);
+        for (int p = 0; p < n_best; ++p) {
+            const size_t q = (size_t)i * n_best + p;
+            int32_t* tk = tokens + q * T_stride; int32_t* tp = tsteps + q * T_stride;
+            if (p >= s->pend_n) { lens[q] = 0; scores[q] = 0.f; continue; }
+            const int len = s->h_len[p];
+            std::memcpy(tk, s->h_tok.data() + (size_t)p * L, (size_t)len * 4);
+            std::memcpy(tp, s->h_step.data() + (size_t)p * L, (size_t)len * 4);
+            lens[q] = len;
+            scores[q] = beam_score_out(s->d, tk, len, s->h_score[p]);
+        }
+        counts[i] = s->pend_n;
+        s->pending = false;
+    }
+    return DSMI_OK;
+}
 
 // ---- host-only view of a language model file (no GPU needed): lets callers and the CPU tests inspect what
 // dsmi_decoder_set_lm would load.  See include/dsmi.h.

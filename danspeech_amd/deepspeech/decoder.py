@@ -157,6 +157,24 @@ class BeamCTCDecoder(Decoder):
         dec.beam_enqueue(probs, sz, beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n, cutoff_prob=self.cutoff_prob)
         return dec
 
+    def new_stream(self, device_index=0):
+        """A resumable search of one utterance (``NativeBeamStream``) on the native decoder ``decode`` uses on that device:
+        the same language-model tables, alpha and beta, and this decoder's beam_width / cutoff_top_n / cutoff_prob.  It is
+        tied to this decoder's settings: a decoder with other settings needs streams of its own."""
+        from .. import _native
+        return _native.NativeBeamStream(self._dec(device_index), self.beam_width, self.cutoff_top_n, self.cutoff_prob)
+
+    def advance_streams(self, streams, probs_list, n_best=1):
+        """Advance streams of ``new_stream`` by one chunk of probabilities each (CUDA [1,T,C] / [T,C], or None) in one launch
+        and return ``(strings[N][n_best], offsets[N][n_best])`` over each stream's whole utterance so far: what ``decode``
+        returns first for the concatenated chunks."""
+        import torch
+        from .. import _native
+        res = _native.NativeBeamStream.advance_many(streams, probs_list, n_best)
+        strings = [[self._to_string(tok[p, :ln[p]]) for p in range(n_best)] for tok, _, ln, _ in res]
+        offsets = [[torch.from_numpy(ts[p, :ln[p]].astype(np.int32)) for p in range(n_best)] for _, ts, ln, _ in res]
+        return strings, offsets
+
     def decode_collect(self, ticket):
         import torch
         tok, ts, ln, sc = ticket.beam_collect()

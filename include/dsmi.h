@@ -321,6 +321,40 @@ int dsmi_decoder_beam_stats(const dsmi_decoder* d, int32_t* counts4);
  * (100 MHz ticks; 0 = frame start, 1..6 = after the frame's six barriers); tools/beam_stamps.py prints the anatomy. */
 int dsmi_debug_beam_stamps(const dsmi_decoder* d, uint64_t* stamps_host, int64_t n_words);
 
+/* ---- Resumable beam search: one utterance's CTC prefix beam search carried from one chunk of probabilities to the next, so
+ * that a streaming caller pays for each chunk's frames once and can read the best hypotheses of the whole utterance so far
+ * after every chunk.  A dsmi_beam_stream is bound to one dsmi_decoder and searches with that decoder's language model, alpha
+ * and beta and the beam_width / cutoff_top_n / cutoff_prob given here.  Its state and node pool are device buffers of its own;
+ * it never touches the decoder's offline-search workspace nor a pending dsmi_beam_enqueue.  A decoder serves any number of
+ * streams; destroy every stream of a decoder before the decoder.  dsmi_decoder_set_lm on the decoder retires its streams:
+ * their later advances and collects are refused (create new ones).  dsmi_beam_stream_reset starts a new utterance.
+ *
+ * dsmi_beam_stream_advance_many advances n distinct streams of one decoder, with equal beam settings, in ONE launch on
+ * `stream` (1 <= n <= DSMI_BEAM_STREAM_MANY_MAX): stream i by frames[i] >= 0 rows of probs_dev[i] (device, [frames[i]][n_labels]
+ * float32, the softmax output; may be NULL when frames[i] = 0).  With n_best > 0 (<= beam_width) it also produces each
+ * stream's n_best best hypotheses over ALL its frames so far, exactly those dsmi_beam returns first for the concatenated
+ * probabilities (timesteps count from the utterance's first frame); they wait in the handle for
+ * dsmi_beam_stream_collect_many, and until then the stream refuses to advance.  Either every stream advances or the call is
+ * refused with no stream's state changed (bad arguments, a handle listed twice, handles of different decoders or beam
+ * settings, a collect pending, a retired stream); the error text (dsmi_beam_stream_last_error(NULL)) names the stream index.
+ * Returns when the launch is complete (`stream` is synchronised).
+ *
+ * dsmi_beam_stream_collect_many hands the pending hypotheses of n streams over in dsmi_beam's layouts cut to n_best:
+ * tokens / tsteps [n][n_best][T_stride], lens [n][n_best], scores [n][n_best] (ctcdecode's -approx_ctc), counts [n] (beams
+ * present: min(beams in the search, n_best); rows past it have length 0).  Refused with nothing written when a stream has none
+ * pending, was advanced with another n_best, or holds a hypothesis longer than T_stride. */
+typedef struct dsmi_beam_stream dsmi_beam_stream;
+#define DSMI_BEAM_STREAM_MANY_MAX 4096
+int dsmi_beam_stream_create(dsmi_decoder* d, int beam_width, int cutoff_top_n, double cutoff_prob, dsmi_beam_stream** out);
+void dsmi_beam_stream_destroy(dsmi_beam_stream* s);
+const char* dsmi_beam_stream_last_error(const dsmi_beam_stream* s);
+int dsmi_beam_stream_reset(dsmi_beam_stream* s);
+int dsmi_beam_stream_frames(const dsmi_beam_stream* s, int64_t* frames);
+int dsmi_beam_stream_advance_many(dsmi_beam_stream* const* streams, int n, const float* const* probs_dev, const int32_t* frames,
+                                  int n_best, void* stream);
+int dsmi_beam_stream_collect_many(dsmi_beam_stream* const* streams, int n, int n_best, int T_stride, int32_t* tokens_host,
+                                  int32_t* tsteps_host, int32_t* lens_host, float* scores_host, int32_t* counts_host);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off
