@@ -113,6 +113,22 @@ class _BatchJob(object):
         return self.recomputed
 
 
+def _words(text, spans, token_probs, frame_s):
+    """Characters of ``text`` with their frame spans and mean probabilities -> ``[(word, start_s, end_s, confidence)]``, a
+    word being a maximal run of non-space characters."""
+    words, k = [], 0
+    while k < len(text):
+        if text[k] == " ":
+            k += 1
+            continue
+        j = k
+        while j < len(text) and text[j] != " ":
+            j += 1
+        words.append((text[k:j], int(spans[k][0]) * frame_s, int(spans[j - 1][1]) * frame_s, float(np.mean(token_probs[k:j]))))
+        k = j
+    return words
+
+
 _SIDE_STREAMS = {}        # (name, device index) -> torch.cuda.Stream, shared by every engine of the process: see _side_stream
 
 
@@ -595,6 +611,43 @@ class DanSpeechRecognizer(object):
     def transcribe(self, recording, show_all=False):
         beams = self._finish_batch(self._enqueue_batch([recording]), True, warn=show_all)[0]
         return beams if show_all else beams[0]
+
+    # ---- word timings of known transcripts (CTC forced alignment) ----------------------------------------------------
+    def frame_seconds(self):
+        """Seconds per output frame: the parser's hop times the time strides of the model's convolutions."""
+        from .synthetic import CONV_SPECS
+        stride = 1
+        for spec in CONV_SPECS[:self.model.conv_layers]:
+            stride *= spec[5]
+        return float(self.audio_config["window_stride"]) * stride
+
+    def align_batch(self, recordings, transcripts):
+        """Word timings of ``transcripts[i]`` in ``recordings[i]``, as one batch: per recording ``None`` when the transcript
+        cannot fit the recording's frames, else ``[(word, start_s, end_s, confidence), ...]`` for the words of the normalised
+        transcript (``Decoder.normalise_transcript``).  A word's start is its first character's first frame, its end the end
+        of its last character's last frame, its confidence the mean of its characters' mean probabilities.  Every transcript
+        is checked before any GPU work (``ValueError`` for characters that are not labels)."""
+        if self.model is None:
+            raise ModelNotInitialized("Trying to align without a DanSpeech model.")
+        if len(recordings) != len(transcripts):
+            raise ValueError("align_batch: %d recordings and %d transcripts" % (len(recordings), len(transcripts)))
+        texts = [self.decoder.normalise_transcript(t) for t in transcripts]
+        ids = [self.decoder.transcript_ids(t) for t in texts]
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        aligned = self.decoder.align_ids(job.probs, [ids[i] for i in job.order], job.sizes)
+        frame_s = self.frame_seconds()
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            if aligned[pos] is not None:
+                results[i] = _words(texts[i], aligned[pos][0], aligned[pos][1], frame_s)
+        return results
+
+    def align(self, recording, transcript):
+        """``align_batch`` of one recording."""
+        return self.align_batch([recording], [transcript])[0]
 
     # ---- long recordings and files ----------------------------------------------------------------------------------
     def transcribe_long(self, recording, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,

@@ -39,6 +39,16 @@ class Recognizer(object):
         """``recognize`` for a list of clips in one batched pass over the GPU."""
         return self.danspeech_recognizer.transcribe_batch(audio_list, show_all=show_all)
 
+    def align(self, audio_data, transcript):
+        """Word timings of a transcript the caller already has (an edited subtitle, a correction, or ``recognize(audio_data)``)
+        in ``audio_data``: ``[(word, start_s, end_s, confidence), ...]``, or ``None`` when the transcript cannot fit the
+        audio (``DanSpeechRecognizer.align_batch``)."""
+        return self.danspeech_recognizer.align(audio_data, transcript)
+
+    def align_batch(self, audio_list, transcripts):
+        """``align`` for a list of clips in one batched pass over the GPU; results in the caller's order."""
+        return self.danspeech_recognizer.align_batch(audio_list, transcripts)
+
     def recognize_batches(self, batches, show_all=False):
         """Generator: ``recognize_batch`` over a sequence of batches, with the upload of the next batch and the
         decoding of the previous one overlapped with the GPU's work on the current one."""

@@ -128,6 +128,7 @@ _PROTOS = {
     "dsmi_beam_stream_frames": (C.c_int, [_vp, _i64p]),
     "dsmi_beam_stream_advance_many": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "dsmi_beam_stream_collect_many": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_align": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -719,6 +720,37 @@ class NativeDecoder:
         c = np.zeros(4, dtype=np.int32)
         self._check(lib().dsmi_decoder_beam_stats(self._h, _np_ptr(c)))
         return dict(zip(("revivals", "walk_hops", "list_rankings", "full_rankings"), (int(v) for v in c)))
+
+    def align(self, probs, sizes, targets, target_lens=None):
+        """CTC forced alignment (``dsmi_align``).  probs: CUDA [B,T,C]; sizes: [B] frames or None (= T); targets: [B, L_stride]
+        int array with ``target_lens`` [B], or a list of B id sequences (``target_lens`` None).  Returns numpy arrays
+        (spans int32 [B,L_stride,2], token_probs float32 [B,L_stride], path_logp float32 [B], status int32 [B]: 1 = infeasible)."""
+        B, T = probs.shape[0], probs.shape[1]
+        if target_lens is None:
+            seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+            if len(seqs) != B:
+                raise ValueError("align: %d target sequences for a batch of %d" % (len(seqs), B))
+            target_lens = np.array([len(t) for t in seqs], dtype=np.int32)
+            tg = np.zeros((B, int(target_lens.max()) if B else 0), dtype=np.int32)
+            for b, t in enumerate(seqs):
+                tg[b, :len(t)] = t
+        else:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(B, -1)
+            target_lens = np.ascontiguousarray(target_lens, dtype=np.int32)
+        Ls = tg.shape[1]
+        tg = np.ascontiguousarray(tg)
+        sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.int32)
+        spans = np.zeros((B, Ls, 2), dtype=np.int32)
+        tp = np.zeros((B, Ls), dtype=np.float32)
+        lp = np.zeros(B, dtype=np.float32)
+        st = np.zeros(B, dtype=np.int32)
+        self._check(lib().dsmi_align(self._h, probs.data_ptr(), None if sz is None else _np_ptr(sz), B, T, _np_ptr(tg),
+                                     _np_ptr(target_lens), Ls, _np_ptr(spans), _np_ptr(tp), _np_ptr(lp), _np_ptr(st),
+                                     _stream(self.device)))
+        return spans, tp, lp, st
+
+
+ALIGN_MAX_TOKENS = 4096         # DSMI_ALIGN_MAX_TOKENS: the longest transcript dsmi_align takes (L_stride)
 
 
 BEAM_STREAM_MANY_MAX = 4096     # DSMI_BEAM_STREAM_MANY_MAX: streams of one dsmi_beam_stream_advance_many launch

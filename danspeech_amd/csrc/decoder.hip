@@ -9,6 +9,7 @@
 // algorithm, oracle/beam_flat.py the kernel's own formulation of it (implicit prefix trie held on chip, edge tuples, one-pass
 // histogram selection); the parity tests compare with both.  DESIGN.md 4 "Beam search" describes the frame's six phases.
 #include "common.h"
+#include "align.h"
 #include <cstring>
 #include <mutex>
 #include "lm.h"
@@ -59,6 +60,9 @@ struct dsmi_decoder {
     uint64_t lm_gen = 0;
     std::mutex bs_mu;
     unsigned char *bs_dev = nullptr, *bs_pin = nullptr; size_t bs_dev_cap = 0, bs_pin_cap = 0;
+    // dsmi_align: inputs and outputs of the launch (int32 words), backpointers [B][T_out][S_stride] bytes
+    int32_t* al_io = nullptr; size_t al_io_cap = 0;
+    unsigned char* al_bp = nullptr; size_t al_bp_cap = 0;
 };
 
 // ONE stream per device for the device-to-host copies of every decoder handle's collect, made at the first collect and kept for
@@ -127,6 +131,8 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     free_lm(d);
     if (d->bs_dev) (void)hipFree(d->bs_dev);
     if (d->bs_pin) (void)hipHostFree(d->bs_pin);
+    if (d->al_io) (void)hipFree(d->al_io);
+    if (d->al_bp) (void)hipFree(d->al_bp);
     delete d;
 }
 
@@ -446,6 +452,87 @@ extern "C" int dsmi_beam(dsmi_decoder* d, const float* probs, const int32_t* siz
     const int rc = dsmi_beam_enqueue(d, probs, sizes, B, To, beam, cutoff_top_n, cutoff_prob, stream);
     if (rc) return rc;
     return dsmi_beam_collect(d, tokens, tsteps, lens, scores);
+}
+
+// ---- CTC forced alignment of known transcripts (the kernel: align.hip).  Every refusal comes before any launch or output write;
+// a clip whose transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
+extern "C" int dsmi_align(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* targets,
+                          const int32_t* target_lens, int L_stride, int32_t* spans, float* token_probs, float* path_logp,
+                          int32_t* status, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !target_lens || !path_logp || !status || (L_stride > 0 && (!targets || !spans || !token_probs))) {
+        d->err = "bad align arguments"; return DSMI_ERR_INVALID;
+    }
+    if (B <= 0 || To <= 0) { d->err = "align: B and T_out must be positive"; return DSMI_ERR_INVALID; }
+    if (L_stride < 0) { d->err = "align: negative L_stride"; return DSMI_ERR_INVALID; }
+    if (L_stride > DSMI_ALIGN_MAX_TOKENS) {
+        d->err = "align: L_stride " + std::to_string(L_stride) + " exceeds DSMI_ALIGN_MAX_TOKENS (" + std::to_string(DSMI_ALIGN_MAX_TOKENS) + ")";
+        return DSMI_ERR_CAPACITY;
+    }
+    std::vector<int32_t> sz(B), tl(B);
+    int L_max = 0;
+    for (int b = 0; b < B; ++b) {
+        sz[b] = sizes ? sizes[b] : To;
+        if (sz[b] < 0 || sz[b] > To) { d->err = "align: clip " + std::to_string(b) + ": size outside 0 .. T_out"; return DSMI_ERR_INVALID; }
+        const int L = target_lens[b];
+        if (L < 0 || L > L_stride) { d->err = "align: clip " + std::to_string(b) + ": target length outside 0 .. L_stride"; return DSMI_ERR_INVALID; }
+        const int32_t* tg = targets + (size_t)b * L_stride;
+        int repeats = 0;
+        for (int k = 0; k < L; ++k) {
+            if (tg[k] < 0 || tg[k] >= C || tg[k] == d->blank) {
+                d->err = "align: clip " + std::to_string(b) + ": target id " + std::to_string(tg[k]) + " is the blank or not a label";
+                return DSMI_ERR_INVALID;
+            }
+            if (k > 0 && tg[k] == tg[k - 1]) ++repeats;
+        }
+        tl[b] = L + repeats > sz[b] ? -1 : L;        // -1: infeasible, the kernel skips the clip
+        if (tl[b] > L_max) L_max = tl[b];
+    }
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces, grown on demand: io = sizes [B], lens [B], targets [B][L], spans [B][L][2], token probs [B][L], logp [B]
+    const int S_max = 2 * L_max + 1, S_stride = round_up(S_max, 4);
+    const size_t BL = (size_t)B * L_stride, io_words = 3 * (size_t)B + 4 * BL;
+    const size_t bp_bytes = (size_t)B * To * S_stride + kAlignBpSlack;
+    if (io_words > d->al_io_cap || bp_bytes > d->al_bp_cap) {
+        DEC_HIP(d, hipDeviceSynchronize());
+        if (io_words > d->al_io_cap) {
+            if (d->al_io) (void)hipFree(d->al_io);
+            d->al_io = nullptr; d->al_io_cap = 0;
+            DEC_HIP(d, hipMalloc((void**)&d->al_io, sizeof(int32_t) * io_words));
+            d->al_io_cap = io_words;
+        }
+        if (bp_bytes > d->al_bp_cap) {
+            if (d->al_bp) (void)hipFree(d->al_bp);
+            d->al_bp = nullptr; d->al_bp_cap = 0;
+            DEC_HIP(d, hipMalloc((void**)&d->al_bp, bp_bytes));
+            d->al_bp_cap = bp_bytes;
+        }
+    }
+    int32_t* w_sz = d->al_io; int32_t* w_tl = w_sz + B; int32_t* w_tg = w_tl + B;
+    int32_t* w_sp = w_tg + BL; float* w_tp = reinterpret_cast<float*>(w_sp + 2 * BL); float* w_lp = w_tp + BL;
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    if (BL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * BL, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_sp, 0, sizeof(int32_t) * (3 * BL + B), s));
+    AlignArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w_sz; a.tlen = w_tl; a.targets = w_tg; a.L_stride = L_stride; a.S_max = S_max;
+    a.bp = d->al_bp; a.S_stride = S_stride;
+    a.spans = w_sp; a.token_probs = w_tp; a.path_logp = w_lp;
+    DEC_HIP(d, launch_align(a, B, s));
+    if (BL) {
+        DEC_HIP(d, hipMemcpyAsync(spans, w_sp, sizeof(int32_t) * 2 * BL, hipMemcpyDeviceToHost, s));
+        DEC_HIP(d, hipMemcpyAsync(token_probs, w_tp, sizeof(float) * BL, hipMemcpyDeviceToHost, s));
+    }
+    DEC_HIP(d, hipMemcpyAsync(path_logp, w_lp, sizeof(float) * B, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+        status[b] = tl[b] < 0 ? 1 : 0;
+        if (tl[b] < 0) path_logp[b] = -INFINITY;
+    }
+    return DSMI_OK;
 }
 
 

@@ -85,6 +85,45 @@ class Decoder(object):
     def decode(self, probs, sizes=None):
         raise NotImplementedError
 
+    # ---- CTC forced alignment of known transcripts (dsmi_align); the same on every decoder, a language model plays no part
+    @staticmethod
+    def normalise_transcript(text):
+        """What ``align`` aligns: lower case, runs of whitespace collapsed to one space, stripped."""
+        return " ".join(str(text).lower().split())
+
+    def transcript_ids(self, text):
+        """Label ids of an already normalised transcript; ``ValueError`` naming every character that is not a label (the
+        blank's character included): nothing is dropped."""
+        table = getattr(self, "_char_ids", None)
+        if table is None:
+            table = {c: i for i, c in enumerate(self.labels) if i != self.blank_index and len(c) == 1}
+            self._char_ids = table
+        bad = sorted(set(c for c in text if c not in table))
+        if bad:
+            raise ValueError("transcript holds characters that are not labels of this model: %s" % ", ".join(repr(c) for c in bad))
+        return np.array([table[c] for c in text], dtype=np.int32)
+
+    def align(self, probs, transcripts, sizes=None):
+        """Forced alignment of ``transcripts[b]`` (normalised with ``normalise_transcript``) to the probabilities of clip b
+        (``probs`` [B,T,C], ``sizes`` frames per clip).  Per clip ``None`` when the transcript cannot fit the clip's frames,
+        else ``(spans int32 [L,2], token_probs float32 [L], path_logp)``: the frames [start, end) of each character of the
+        normalised transcript, the mean probability of the character over them, and the path's natural-log probability."""
+        ids = [self.transcript_ids(self.normalise_transcript(t)) for t in transcripts]      # every check before any GPU work
+        return self.align_ids(probs, ids, sizes)
+
+    def align_ids(self, probs, ids, sizes=None):
+        """``align`` for label-id sequences as they are (no normalisation)."""
+        import torch
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        spans, tp, lp, status = dec.align(probs, sz, ids)
+        out = []
+        for b, t in enumerate(ids):
+            L = len(t)
+            out.append(None if status[b] else (spans[b, :L].copy(), tp[b, :L].copy(), float(lp[b])))
+        return out
+
 
 class GreedyDecoder(Decoder):
     """decoder.py:147-198: argmax per frame, collapse repeats, drop blanks; one path per utterance."""

@@ -355,6 +355,29 @@ int dsmi_beam_stream_advance_many(dsmi_beam_stream* const* streams, int n, const
 int dsmi_beam_stream_collect_many(dsmi_beam_stream* const* streams, int n, int n_best, int T_stride, int32_t* tokens_host,
                                   int32_t* tsteps_host, int32_t* lens_host, float* scores_host, int32_t* counts_host);
 
+/* ---- CTC forced alignment (no reference counterpart): the most probable frame-level CTC path of a transcript the caller
+ * already has, through the probabilities dsmi_forward wrote.  The decoder's language model plays no part.
+ * probs_dev [B][T_out][n_labels]; sizes_host[B] frames per clip (NULL = T_out for all); targets_host [B][L_stride] label ids,
+ * clip b's first target_lens_host[b] valid (never the blank; 0 tokens is legal: the path is all blanks).
+ * Clip b with L tokens has S = 2L + 1 states: blank, t_1, blank, t_2, ..., blank.  With lp(t, c) = logf(fmaxf(p, FLT_MIN))
+ * accumulated in float32 over frames in order,
+ *     alpha_t(s) = max(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2) [only if s is a token state and
+ *                  label(s) != label(s-2)]) + lp(t, label(s)),   alpha_0 = {lp(0, blank), lp(0, t_1), -inf, ...}.
+ * Tie rule (part of the contract): a state's predecessor on equal alpha is s, then s-1, then s-2; the path ends in the
+ * trailing blank S-1 unless alpha(S-2) (the last token) is strictly larger.
+ * Outputs: spans_host [B][L_stride][2] = frames [start, end) the path spends in token k's state; token_probs_host
+ * [B][L_stride] = the float32 mean of p(t, label_k) over those frames (summed in frame order); path_logp_host [B] = the
+ * path's sum of lp (natural log); status_host [B] = 0 aligned, 1 infeasible (L + #{k : t_k == t_{k+1}} > frames: path_logp
+ * = -inf).  Rows past target_lens[b] and the rows of infeasible clips are 0.
+ * Refused with nothing written (DSMI_ERR_INVALID; DSMI_ERR_CAPACITY for L_stride above the limit): B <= 0, T_out <= 0,
+ * sizes[b] outside 0 .. T_out, target_lens[b] outside 0 .. L_stride, L_stride > DSMI_ALIGN_MAX_TOKENS, a target id that is
+ * the blank or >= n_labels.  The limit comes from LDS: two alpha rows of S floats per clip.  Synchronises `stream`. */
+#define DSMI_ALIGN_MAX_TOKENS 4096
+int dsmi_align(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+               const int32_t* targets_host, const int32_t* target_lens_host, int L_stride,
+               int32_t* spans_host, float* token_probs_host, float* path_logp_host, int32_t* status_host,
+               void* stream);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off
