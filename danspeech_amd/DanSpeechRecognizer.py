@@ -278,10 +278,17 @@ class DanSpeechRecognizer(object):
             results[i] = decoded[pos] if show_all else decoded[pos][0]
         return results
 
-    def transcribe_batch(self, recordings, show_all=False):
-        """``[transcribe(r) for r in recordings]`` as one batch; results in the caller's order."""
+    def transcribe_batch(self, recordings, show_all=False, sample_rate=None, resample="polyphase"):
+        """``[transcribe(r) for r in recordings]`` as one batch; results in the caller's order.  ``sample_rate``: the rate of the
+        recordings when it is not the model's; they are then converted on the device first (``dsmi_resample``, method
+        ``resample``: "polyphase" or "ratecv") and never come back to the host in between."""
         if len(recordings) == 0:
             return []
+        if sample_rate is not None and int(sample_rate) != int(self.audio_parser.sampling_rate) and not isinstance(recordings, DeviceClips):
+            order = np.argsort([-len(r) for r in recordings], kind="stable")
+            clips = self.audio_parser.resample_batch([recordings[i] for i in order], int(sample_rate), resample)
+            clips.order = order
+            return self._finish_batch(self._enqueue_batch(clips), show_all)
         return self._finish_batch(self._enqueue_batch(recordings), show_all)
 
     # how `transcribe_batches` fills the GPU: forwards in flight (each on a model handle, stream and persistent-kernel gate slot of
@@ -651,15 +658,21 @@ class DanSpeechRecognizer(object):
 
     # ---- long recordings and files ----------------------------------------------------------------------------------
     def transcribe_long(self, recording, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
-                        max_batch=32, show_all=False):
+                        max_batch=32, show_all=False, sample_rate=None, resample="polyphase"):
         """Long-form transcription: the energy gate of the reference's
         example_scripts/video_transcribe_simulation.py:68-143 cuts the recording into phrases (``dsmi_segment``: hop
         energies on the GPU), the phrases are transcribed in batches of at most ``max_batch`` (longest first), and
         ``[(start_sample, end_sample, transcription), ...]`` comes back in time order.  The recording is uploaded
-        once; phrases are sliced on the device."""
+        once; phrases are sliced on the device.  ``sample_rate``: the recording's rate when it is not the model's (a video
+        sound track): the whole recording is then converted once on the device (``resample``: "polyphase" or "ratecv"), the
+        energy gate and the slicing run on the converted signal, and the returned sample ranges count samples at the MODEL's
+        rate (16 kHz), not the recording's."""
         import torch
         parser = self.audio_parser
-        pcm = torch.from_numpy(np.ascontiguousarray(recording, dtype=np.float64)).to("cuda:%d" % parser.device)
+        if sample_rate is not None and int(sample_rate) != int(parser.sampling_rate):
+            pcm = parser.resample_batch([recording], int(sample_rate), resample).pcm
+        else:
+            pcm = torch.from_numpy(np.ascontiguousarray(recording, dtype=np.float64)).to("cuda:%d" % parser.device)
         hop_seconds = step / float(parser.sampling_rate)
         segs = parser._frontend().segment(pcm, energy_threshold=energy_threshold, step=step,
                                           pause_hops=int(np.ceil(pause_threshold / hop_seconds)),
@@ -677,23 +690,33 @@ class DanSpeechRecognizer(object):
                 res[i] = (int(segs[i][0]), int(segs[i][1]), decoded_output[pos] if show_all else decoded_output[pos][0])
         return res
 
-    def transcribe_files(self, paths, show_all=False):
+    def transcribe_files(self, paths, show_all=False, resample=None):
         """``transcribe_batch([load_audio(p) for p in paths])`` without decoding the files on the host:
         the WAV frames go to the GPU as bytes and ``dsmi_features`` applies ``load_audio``'s sample-width
         conversion and saturating stereo fold (resources.py:302-303).  Files are grouped by
-        (sample width, channels); every group is one batch."""
+        (sample width, channels); every group is one batch.
+        ``resample=None`` takes every file's samples as 16 kHz whatever its header says, as ``load_audio`` does.  With
+        "polyphase" or "ratecv" the header's frame rate counts: files are grouped by (sample width, channels, rate) and the
+        groups whose rate is not the model's are converted on the device (``dsmi_resample``) in front of the spectrograms."""
         import torch
-        from .audio.resources import read_wav_frames
+        from .audio.resources import read_wav_frames, read_wav_frames_rate
         if len(paths) == 0:
             return []
-        loaded = [read_wav_frames(p) for p in paths]
+        if resample is None:
+            loaded = [read_wav_frames(p) + (None,) for p in paths]
+        else:
+            if resample not in ("polyphase", "ratecv"):
+                raise ValueError("resample must be None, 'polyphase' or 'ratecv'")
+            loaded = [read_wav_frames_rate(p) for p in paths]
+            loaded = [(raw, width, nch, None if rate == int(self.audio_parser.sampling_rate) else rate) for raw, width, nch, rate in loaded]
         groups = {}
-        for i, (raw, width, nch) in enumerate(loaded):
-            groups.setdefault((width, nch), []).append(i)
+        for i, (raw, width, nch, rate) in enumerate(loaded):
+            groups.setdefault((width, nch, rate), []).append(i)
         res = [None] * len(paths)
-        for (width, nch), idxs in groups.items():
+        for (width, nch, rate), idxs in groups.items():
             idxs = sorted(idxs, key=lambda i: -len(loaded[i][0]))       # stable: longest first
-            feats, frames = self.audio_parser.parse_wav_frames([loaded[i][0] for i in idxs], width, nch)
+            feats, frames = self.audio_parser.parse_wav_frames([loaded[i][0] for i in idxs], width, nch, rate=rate,
+                                                               resample=resample or "polyphase")
             out, output_sizes = self.model(feats, torch.from_numpy(frames.astype(np.int32)))
             decoded_output, _ = self.decoder.decode(out, output_sizes)
             for pos, i in enumerate(idxs):

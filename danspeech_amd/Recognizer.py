@@ -35,9 +35,11 @@ class Recognizer(object):
         all beams when ``show_all`` and a language model is set."""
         return self.danspeech_recognizer.transcribe(audio_data, show_all=show_all)
 
-    def recognize_batch(self, audio_list, show_all=False):
-        """``recognize`` for a list of clips in one batched pass over the GPU."""
-        return self.danspeech_recognizer.transcribe_batch(audio_list, show_all=show_all)
+    def recognize_batch(self, audio_list, show_all=False, sample_rate=None, resample="polyphase"):
+        """``recognize`` for a list of clips in one batched pass over the GPU.  ``sample_rate``: the clips' rate when it is not
+        the model's 16 kHz; they are converted on the GPU first (``resample``: "polyphase", or "ratecv" for the reference's
+        ``audioop.ratecv``)."""
+        return self.danspeech_recognizer.transcribe_batch(audio_list, show_all=show_all, sample_rate=sample_rate, resample=resample)
 
     def align(self, audio_data, transcript):
         """Word timings of a transcript the caller already has (an edited subtitle, a correction, or ``recognize(audio_data)``)
@@ -132,17 +134,22 @@ class Recognizer(object):
         return stream_cut_plan(n_samples, chunk_samples, rec.model.context, int(rec.audio_parser.sampling_rate / 100))
 
     def recognize_long(self, audio_data, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
-                       max_batch=32, show_all=False):
+                       max_batch=32, show_all=False, sample_rate=None, resample="polyphase"):
         """Segment a long recording with the reference example's energy gate
         (example_scripts/video_transcribe_simulation.py:68-143) and transcribe the phrases in batches:
-        ``[(start_sample, end_sample, transcription), ...]`` in time order."""
+        ``[(start_sample, end_sample, transcription), ...]`` in time order.  ``sample_rate``: the recording's rate when it is
+        not the model's 16 kHz (a video sound track); it is converted once on the GPU (``resample``), the gate runs on the
+        converted signal, and ``start_sample`` / ``end_sample`` count 16 kHz samples."""
         return self.danspeech_recognizer.transcribe_long(audio_data, energy_threshold=energy_threshold, step=step,
                                                          pause_threshold=pause_threshold, phrase_threshold=phrase_threshold,
-                                                         max_batch=max_batch, show_all=show_all)
+                                                         max_batch=max_batch, show_all=show_all, sample_rate=sample_rate,
+                                                         resample=resample)
 
-    def recognize_files(self, paths, show_all=False):
-        """``[recognize(load_audio(p)) for p in paths]`` in batched passes, WAV decoding on the GPU."""
-        return self.danspeech_recognizer.transcribe_files(paths, show_all=show_all)
+    def recognize_files(self, paths, show_all=False, resample=None):
+        """``[recognize(load_audio(p)) for p in paths]`` in batched passes, WAV decoding on the GPU.  ``resample``: None takes
+        every file as 16 kHz audio (``load_audio``'s contract); "polyphase" or "ratecv" reads each file's frame rate and
+        converts the files of another rate to 16 kHz on the GPU."""
+        return self.danspeech_recognizer.transcribe_files(paths, show_all=show_all, resample=resample)
 
     def update_model(self, model):
         self.danspeech_recognizer.update_model(model)

@@ -19,6 +19,7 @@ RNN_TYPES = {"gru": 0, "lstm": 1, "rnn": 2}
 WINDOWS = {"hamming": 0, "hann": 1, "blackman": 2, "bartlett": 3}
 PCM_DTYPES = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
 PAD_MODES = {"reflect": 0, "constant": 1}
+RESAMPLE_METHODS = {"polyphase": 0, "ratecv": 1}      # DSMI_RESAMPLE_*
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -76,6 +77,9 @@ _PROTOS = {
     "dsmi_frontend_last_error": (C.c_char_p, [_vp]),
     "dsmi_features": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "dsmi_features_stream": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp]),
+    "dsmi_resample": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp]),
+    "dsmi_resample_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "dsmi_resample_taps": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_stream_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dsmi_stream_destroy": (None, [_vp]),
     "dsmi_stream_last_error": (C.c_char_p, [_vp]),
@@ -453,6 +457,70 @@ class NativeFrontend:
         if rc != 0:
             raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
         return feat, fr
+
+
+def _pcm_dtype(self, pcm_dev, n_samples, wav_format):
+    """DSMI_PCM_* of a device buffer: a sample tensor, or (``wav_format=(sample_width, channels)``) a file's raw frames."""
+    import torch
+    if wav_format is None:
+        return {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcm_dev.dtype]
+    width, channels = wav_format
+    if pcm_dev.dtype != torch.uint8 or width not in self.WAV_WIDTH_DTYPE or channels not in (1, 2):
+        raise ValueError("raw WAV frames: uint8 tensor, sample width 1..4, one or two channels")
+    if int(n_samples.sum()) * width * channels != pcm_dev.numel():
+        raise ValueError("frame counts do not add up to the size of the byte buffer")
+    return self.WAV_WIDTH_DTYPE[width] | (self.PCM_STEREO if channels == 2 else 0)
+
+
+def _resample_count(self, n_samples, rate_in, method="polyphase"):
+    """dsmi_resample_count: the lengths clips of ``n_samples`` samples at ``rate_in`` have at the frontend's rate (int64 array)."""
+    if method not in RESAMPLE_METHODS:
+        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
+    out = np.array([lib().dsmi_resample_count(RESAMPLE_METHODS[method], int(rate_in), int(self.desc.sample_rate), int(n))
+                    for n in np.atleast_1d(n_samples)], dtype=np.int64)
+    if (out < 0).any():
+        raise DsmiError(DSMI_ERR_INVALID, "bad resample arguments (rate_in %r)" % (rate_in,))
+    return out
+
+
+def _resample(self, pcm_dev, n_samples, rate_in, method="polyphase", wav_format=None):
+    """dsmi_resample: clips of ``rate_in`` Hz back to back in ``pcm_dev`` (a sample tensor, or raw WAV frames with
+    ``wav_format=(sample_width, channels)``, as for ``features``) -> (float64 CUDA tensor with the clips at the frontend's
+    rate back to back, their lengths int64[B]).  One launch on the current stream; nothing is synchronised."""
+    import torch
+    if method not in RESAMPLE_METHODS:
+        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
+    n_samples = np.ascontiguousarray(n_samples, dtype=np.int64)
+    dt = _pcm_dtype(self, pcm_dev, n_samples, wav_format)
+    if wav_format is None and int(n_samples.sum()) != pcm_dev.numel():
+        raise ValueError("sample counts do not add up to the size of the buffer")
+    counts = self.resample_count(n_samples, rate_in, method)
+    total = int(counts.sum())
+    if pcm_dev.numel() == 0:            # nothing but empty clips: nothing to launch
+        return torch.empty(0, dtype=torch.float64, device=pcm_dev.device), counts
+    out = torch.empty(max(total, 1), dtype=torch.float64, device=pcm_dev.device)
+    n_out = np.zeros(len(n_samples), dtype=np.int64)
+    rc = lib().dsmi_resample(self._h, pcm_dev.data_ptr(), dt, _np_ptr(n_samples), len(n_samples), int(rate_in), RESAMPLE_METHODS[method],
+                             out.data_ptr(), total, _np_ptr(n_out), _stream(self.device))
+    if rc != 0:
+        raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
+    return out[:total], n_out
+
+
+NativeFrontend.resample_count = _resample_count
+NativeFrontend.resample = _resample
+
+
+def resample_taps(rate_in, rate_out=16000):
+    """dsmi_resample_taps (host only): (h[-half .. half] float64, up, down) of the polyphase filter for this rate pair."""
+    up, down = C.c_int(0), C.c_int(0)
+    rc = lib().dsmi_resample_taps(int(rate_in), int(rate_out), None, 0, C.byref(up), C.byref(down))
+    if rc == 0:
+        h = np.empty(20 * max(up.value, down.value) + 1, dtype=np.float64)
+        rc = lib().dsmi_resample_taps(int(rate_in), int(rate_out), _np_ptr(h), len(h), C.byref(up), C.byref(down))
+    if rc != 0:
+        raise DsmiError(rc, (lib().dsmi_frontend_last_error(None) or b"").decode())
+    return h, up.value, down.value
 
 
 def _segment(self, pcm_dev, energy_threshold=600, step=1024, pause_hops=9, phrase_hops=4, wav_format=None,

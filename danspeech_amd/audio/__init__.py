@@ -1,1 +1,1 @@
-from .resources import load_audio, load_audio_wavPCM  # noqa: F401
+from .resources import load_audio, load_audio_wavPCM, resample  # noqa: F401

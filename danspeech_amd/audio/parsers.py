@@ -265,14 +265,39 @@ class SpectrogramAudioParser(AudioParser):
             staged.pcm.record_stream(main)
         return out
 
-    def parse_wav_frames(self, raws, width, channels):
+    def parse_wav_frames(self, raws, width, channels, rate=None, resample="polyphase"):
         """Raw PCM WAV frames (``read_wav_frames``; one common sample width / channel count) ->
-        same result as ``parse_batch([load_audio(f) for f in files])`` with the decoding on the GPU."""
+        same result as ``parse_batch([load_audio(f) for f in files])`` with the decoding on the GPU.
+        With ``rate`` (the files' frame rate, ``read_wav_frames_rate``) the frames are first converted to the parser's
+        sampling rate by ``resample`` ("polyphase" or "ratecv"): upload -> ``dsmi_resample`` -> ``dsmi_features`` on the
+        current stream, no host round trip in between.  ``rate=None``: the samples are taken as they are."""
         import torch
         n = np.array([len(r) // (width * channels) for r in raws], dtype=np.int64)
         buf = np.frombuffer(b"".join(raws), dtype=np.uint8)
         pcm = torch.from_numpy(buf.copy()).to("cuda:%d" % self.device)
-        return self._frontend().features(pcm, n, wav_format=(width, channels))
+        if rate is None:
+            return self._frontend().features(pcm, n, wav_format=(width, channels))
+        pcm, n = self._frontend().resample(pcm, n, rate, method=resample, wav_format=(width, channels))
+        return self._frontend().features(pcm, n)
+
+    def resample_batch(self, recordings, rate, resample="polyphase"):
+        """list of 1-D arrays sampled at ``rate`` Hz -> ``DeviceClips`` at the parser's rate, in the given order (the caller
+        orders them longest first): one upload and one ``dsmi_resample`` launch on the current stream."""
+        import torch
+        recordings = [np.asarray(r).reshape(-1) for r in recordings]
+        kinds = {r.dtype for r in recordings}
+        dtype = kinds.pop() if len(kinds) == 1 and next(iter(kinds)) in self._NATIVE_PCM else np.dtype(np.float64)
+        if resample == "ratecv" and dtype != np.int16:
+            # ratecv is defined on integers of a sample width: float arrays as load_audio returns them for 16-bit files
+            # (integers in int16's range) go as int16, anything else has no width to convert at
+            if not all(np.array_equal(r, np.clip(np.round(r), -32768, 32767)) for r in recordings):
+                raise ValueError("resample='ratecv' needs int16 samples (or float arrays holding int16 integers, as load_audio "
+                                 "returns them for 16-bit files)")
+            dtype = np.dtype(np.int16)
+        n = np.array([len(r) for r in recordings], dtype=np.int64)
+        pcm = torch.from_numpy(np.concatenate([r.astype(dtype, copy=False) for r in recordings])).to("cuda:%d" % self.device)
+        out, n_out = self._frontend().resample(pcm, n, rate, method=resample)
+        return DeviceClips(out, n_out)
 
     def parse_audio(self, recording):
         feat, frames = self.parse_batch([recording])

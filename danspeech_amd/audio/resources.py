@@ -62,6 +62,50 @@ def read_wav_frames(path, duration=None, offset=None):
     return b"".join(parts), width, nch
 
 
+def read_wav_frames_rate(path, duration=None, offset=None):
+    """(raw frames, sample width, channels, frame rate) of a PCM WAV file: what ``read_wav_frames`` returns together with the
+    rate the file's header states, for callers that resample (``Recognizer.recognize_files(..., resample=...)``).  ``offset``
+    and ``duration`` are seconds of the file's OWN rate, cut to whole frames -- not ``read_wav_frames``' 4096-frame chunks
+    at the pinned 16 kHz, which are the reference's bookkeeping and stay as they are."""
+    try:
+        reader = wave.open(path, "rb")
+    except (wave.Error, EOFError):
+        raise ValueError("Audio file could not be read as PCM WAV; AIFF/FLAC decoding is outside this package's scope")
+    with reader:
+        nch, width, rate = reader.getnchannels(), reader.getsampwidth(), reader.getframerate()
+        assert 1 <= nch <= 2, "Audio must be mono or stereo"
+        if nch == 2 and width == 1:
+            raise ValueError("8-bit stereo WAV is not supported")
+        if offset:
+            reader.setpos(min(int(round(offset * rate)), reader.getnframes()))
+        left = reader.getnframes() - reader.tell()
+        raw = reader.readframes(min(int(round(duration * rate)), left) if duration else left)
+    return raw, width, nch, rate
+
+
+def resample(audio, rate_in, rate_out=16000, method="polyphase", device=0):
+    """Samples at ``rate_in`` Hz -> float64 samples at ``rate_out`` Hz, converted on the GPU (``dsmi_resample``).  A numpy array
+    (int16 / float32 / float64; anything else is taken as float64) comes back as a numpy array, a 1-D CUDA tensor as a CUDA
+    tensor.  ``method``: "polyphase" (Kaiser-windowed sinc, ``scipy.signal.resample_poly``'s default design) or "ratecv"
+    (``audioop.ratecv``, what the reference's ``AudioData.get_array_data(convert_rate=...)`` applies; int16 samples only here)."""
+    import torch
+    from .. import _native
+    key = (int(rate_out), int(device) if not torch.is_tensor(audio) else int(audio.device.index))
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = _native.NativeFrontend(dict(sampling_rate=int(rate_out)), device=key[1])
+    if torch.is_tensor(audio):
+        out, _ = _RESAMPLERS[key].resample(audio.reshape(-1), [audio.numel()], rate_in, method)
+        return out
+    a = np.ascontiguousarray(audio).reshape(-1)
+    if a.dtype not in (np.dtype(np.int16), np.dtype(np.float32), np.dtype(np.float64)):
+        a = a.astype(np.float64)
+    out, _ = _RESAMPLERS[key].resample(torch.from_numpy(a).to("cuda:%d" % key[1]), [len(a)], rate_in, method)
+    return out.cpu().numpy()
+
+
+_RESAMPLERS = {}      # (rate_out, device) -> the frontend handle that keeps the filters of `resample`
+
+
 def load_audio(path, duration=None, offset=None):
     """PCM WAV -> float64 numpy array ready for ``Recognizer.recognize``."""
     raw, width, nch = read_wav_frames(path, duration=duration, offset=offset)

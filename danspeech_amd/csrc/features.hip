@@ -12,6 +12,7 @@
 // the frame folded twice); the direct kernel serves every other window length and the WAV-frame sample types.
 // Mean and unbiased std are accumulated in float64 per clip (two passes, fixed order).
 #include "common.h"
+#include "frontend.h"
 #include "host_logic.h"
 
 #include <cmath>
@@ -20,25 +21,8 @@
 
 using namespace dsmi;
 
-// The handle behind dsmi_frontend* : one SpectrogramAudioParser on one GPU.
-struct dsmi_frontend {
-    dsmi_frontend_desc desc{};
-    int device = 0;
-    int n_fft = 0, hop = 0, n_freq = 0;
-    std::string err;
-    double* tw = nullptr;    // [n_fft][2] cos, sin
-    double* win = nullptr;   // [n_fft]
-    int64_t* offs = nullptr; // device: per-clip sample offset, n_samples [2][cap], then float64 partial statistics [cap][NSL][2]
-    int cap = 0;
-    // pinned staging of the per-batch offsets / lengths (an async copy must not read pageable memory that is gone or
-    // overwritten when the copy engine gets to it): a ring of slots, each reused only after its copy has completed
-    static constexpr int kStage = 4;
-    int64_t* stage = nullptr; int stage_cap = 0, stage_next = 0;
-    hipEvent_t stage_ev[kStage] = {nullptr, nullptr, nullptr, nullptr}; bool stage_used[kStage] = {false, false, false, false};
-};
-
 // host[0..n) -> dev[0..n) on stream s through the frontend's pinned ring
-static bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, int n, hipStream_t s) {
+bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, int n, hipStream_t s) {
     if (n > f->stage_cap) {
         if (hipDeviceSynchronize() != hipSuccess) return false;
         if (f->stage) (void)hipHostFree(f->stage);
@@ -62,37 +46,12 @@ static bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, i
 }
 
 static thread_local std::string g_fe_error;
+void fe_set_thread_error(const char* msg) { g_fe_error = msg; }
 
 namespace {
 
 constexpr int FT = 8;   // frames per workgroup
 constexpr int PAD_NONE = 2;   // internal third pad mode: no centre padding
-
-// One integer sample of a WAV frame stream (resources.py:551-554 for the 8-bit bias).
-__device__ __forceinline__ int64_t ld_int(const void* p, int base, int64_t i) {
-    switch (base) {
-        case DSMI_PCM_I16: return ((const int16_t*)p)[i];
-        case DSMI_PCM_U8: return (int64_t)((const uint8_t*)p)[i] - 128;
-        case DSMI_PCM_I32: return ((const int32_t*)p)[i];
-        default: {
-            const uint8_t* q = (const uint8_t*)p + 3 * i;
-            const int32_t v = (int32_t)q[0] | ((int32_t)q[1] << 8) | ((int32_t)q[2] << 16);
-            return v >= (1 << 23) ? v - (1 << 24) : v;
-        }
-    }
-}
-
-// Sample i of a clip at its integer scale as float64 (load_audio, resources.py:630-640); two channels fold
-// into the saturating sum of audioop.tomono(buf, width, 1, 1) (resources.py:302-303).
-__device__ __forceinline__ double ld_sample(const void* p, int dtype, int64_t i) {
-    if (dtype == DSMI_PCM_F64) return ((const double*)p)[i];
-    if (dtype == DSMI_PCM_F32) return (double)((const float*)p)[i];
-    const int base = dtype & 15;
-    if (!(dtype & DSMI_PCM_STEREO)) return (double)ld_int(p, base, i);
-    const int64_t lim = base == DSMI_PCM_I16 ? (1ll << 15) : (base == DSMI_PCM_I24 ? (1ll << 23) : (1ll << 31));
-    const int64_t v = ld_int(p, base, 2 * i) + ld_int(p, base, 2 * i + 1);
-    return (double)(v < -lim ? -lim : (v > lim - 1 ? lim - 1 : v));
-}
 
 __global__ __launch_bounds__(256) void stft_logmag_kernel(const void* pcm, int dtype, const int64_t* offs, const int64_t* nsamp,
                                                           const double* tw, const double* win, int n_fft, int hop, int n_freq,
@@ -574,6 +533,7 @@ extern "C" void dsmi_frontend_destroy(dsmi_frontend* f) {
     if (f->win) (void)hipFree(f->win);
     if (f->offs) (void)hipFree(f->offs);
     if (f->stage) (void)hipHostFree(f->stage);
+    fe_resample_release(f);
     for (hipEvent_t e : f->stage_ev) if (e) (void)hipEventDestroy(e);
     delete f;
 }

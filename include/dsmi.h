@@ -126,6 +126,38 @@ const char* dsmi_frontend_last_error(const dsmi_frontend* f);
 int dsmi_features(dsmi_frontend* f, const void* pcm_dev, int pcm_dtype, const int64_t* n_samples_host,
                   int B, float* feat_dev, int t_stride, int32_t* frames_host, void* stream);
 
+/* ---- Sample-rate conversion in front of dsmi_features: AudioData.get_raw_data / get_array_data(convert_rate=...)
+ * (resources.py:568-570), batched.  pcm_dev / pcm_dtype / n_samples_host[B] as for dsmi_features (every DSMI_PCM_* type,
+ * DSMI_PCM_STEREO included: a WAV file's bytes are resampled as they are); rate_in is the clips' rate, the frontend's
+ * sample_rate the rate they are converted to.  out_dev: float64, the resampled clips back to back (clip b at offset
+ * sum(n_out_host[:b])), at their integer scale -- what dsmi_features(..., DSMI_PCM_F64, n_out_host, ...) and
+ * dsmi_recognize_enqueue_device take; out_capacity is its size in samples, n_out_host[B] receives the clips' new lengths
+ * (= dsmi_resample_count).  One launch per call however many clips, asynchronous on `stream`; a clip of 0 samples gives 0.
+ *   DSMI_RESAMPLE_POLYPHASE  rational polyphase FIR, the design of scipy.signal.resample_poly's default: with
+ *                            up = rate_out / g, down = rate_in / g, half = 10 max(up, down),
+ *                                h[m] = sinc(m / max(up, down)) / max(up, down) * kaiser(beta = 5)(m), m = -half .. half, h *= up / sum(h)
+ *                                y[j] = sum_k x[k] h[j down - k up]   (x zero outside the clip),   ceil(n up / down) outputs
+ *                            float64 taps (made on the host once per rate_in, kept on the handle), float64 sums.
+ *   DSMI_RESAMPLE_RATECV     audioop.ratecv(data, width, 1, rate_in, rate_out, None) bit for bit (linear interpolation, no
+ *                            low-pass: the reference's own conversion), applied as the reference applies it: after the 8-bit
+ *                            bias and the saturating stereo fold, at the file's sample width.  (n - 1) o / i + 1 outputs
+ *                            (integer division).  Integer sample types only.
+ * rate_in equal to the frontend's rate is no error: both methods then copy the decoded samples.
+ * Refused before any launch, with nothing written to out_dev or n_out_host: rate_in <= 0, an unknown method, float PCM with
+ * RATECV (DSMI_ERR_INVALID); out_capacity below the sum of the new lengths, a filter of more than DSMI_RESAMPLE_MAX_TAPS taps
+ * (16001 -> 16000 has 320 021: admitted; 2.7 MB on the device), rate_in above DSMI_RESAMPLE_MAX_DECIMATION times the
+ * frontend's rate (DSMI_ERR_CAPACITY).
+ * dsmi_resample_count (host only): the length n samples have after the conversion, < 0 for bad arguments.
+ * dsmi_resample_taps (host only): up, down and, when taps_out is not NULL (capacity >= 20 max(up, down) + 1 doubles), the filter
+ * h[-half .. half] the polyphase kernel uses; failures are reported by dsmi_frontend_last_error(NULL). */
+enum { DSMI_RESAMPLE_POLYPHASE = 0, DSMI_RESAMPLE_RATECV = 1 };
+#define DSMI_RESAMPLE_MAX_TAPS (1 << 19)
+#define DSMI_RESAMPLE_MAX_DECIMATION 24
+int dsmi_resample(dsmi_frontend* f, const void* pcm_dev, int pcm_dtype, const int64_t* n_samples_host, int B, int rate_in,
+                  int method, double* out_dev, int64_t out_capacity, int64_t* n_out_host, void* stream);
+int64_t dsmi_resample_count(int method, int rate_in, int rate_out, int64_t n);
+int dsmi_resample_taps(int rate_in, int rate_out, double* taps_out, int64_t capacity, int* up, int* down);
+
 /* ---- InferenceSpectrogramAudioParser.parse_audio (parsers.py:102-164), the arithmetic half: STFT of the
  * samples WITHOUT centre padding (librosa.stft(center=False), :137-138: 1 + (n - n_fft)/hop frames), log1p|.|,
  * then the adaptive normalisation of :146-161.  state3 = {input_mean, input_std, alpha} is read and updated
