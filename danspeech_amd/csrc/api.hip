@@ -82,7 +82,7 @@ static void timer_resolve(dsmi_model* m) {
 //  * The device is four gate slots of a quarter of the CUs each (DSMI_PERSIST_LANES=1: one).  A persistent kernel whose grid
 //    fits a quarter takes ONE slot (handle-affine: four batches in flight on four handles and streams run their recurrent
 //    layers side by side), one that fits half takes a PAIR of slots (two batches in flight), anything else all four.
-constexpr int kMaxLanes = 4;
+//    (kMaxLanes: rnn_plan.h, which also says which launch takes which slots)
 //  * Launches that take the WHOLE device (the tile-walking kernel of H > 896, the paired-tile windows, the first generation) of
 //    several handles take turns through a lock word IN DEVICE MEMORY, not through the events: an event wait orders a launch behind
 //    whatever was recorded when the wait was ENQUEUED, and a forward is enqueued whole -- forward B's first recurrent layer then
@@ -97,7 +97,7 @@ constexpr int kMaxLanes = 4;
 // The ring kernel's windows (rnn_persist_ring.hip: H / 32 workgroups per direction, 50 CUs for cfgA) have slots of their own: as many as
 // fit the device side by side, at most kRingSlots; a ring launch is ordered behind every launch of the other kernels and vice versa
 // (the two families never share the device: the other kernels' grids are sized for halves and quarters of it).
-constexpr int kRingSlots = 5;
+// (kRingSlots: rnn_plan.h)
 struct PersistGate { std::mutex mu; hipEvent_t ev[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t ring_ev[kRingSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr};
                      hipEvent_t full_ev = nullptr;      // the whole-device launch recorded last (the slot-sized launches wait for it)
                      unsigned* turn = nullptr;           // device word: 0 free, 1 a whole-device persistent launch is running
@@ -157,11 +157,9 @@ static int dense_scope() {
     return k;
 }
 
-// slots a launch of `width` (1, 2 or kMaxLanes) takes for a handle whose home slot is `lane`: [first, first + width)
-static int gate_first(int lane, int width) { return width >= kMaxLanes ? 0 : (width == 2 ? 2 * (lane & 1) : (lane % kMaxLanes)); }
-// Under g->mu: make stream `s` wait for the slots this launch needs ...
-static void gate_wait(PersistGate* g, hipStream_t s, int lane, int width) {
-    for (int i = gate_first(lane, width); i < gate_first(lane, width) + width && i < kMaxLanes; ++i)
+// Under g->mu: make stream `s` wait for the lane slots [first, first + width) this launch needs (rnn_plan.h: gate_first) ...
+static void gate_wait(PersistGate* g, hipStream_t s, int first, int width) {
+    for (int i = first; i < first + width && i < kMaxLanes; ++i)
         if (g->ev[i]) (void)hipStreamWaitEvent(s, g->ev[i], 0);
     for (int i = 0; i < kRingSlots; ++i)
         if (g->ring_ev[i]) (void)hipStreamWaitEvent(s, g->ring_ev[i], 0);
@@ -199,13 +197,13 @@ static void ring_gate_record(PersistGate* g, hipStream_t s, int first, int n, in
     }
 }
 // ... and publish the launch on them.
-static void gate_record(PersistGate* g, hipStream_t s, int lane, int width) {
+static void gate_record(PersistGate* g, hipStream_t s, int first, int width) {
     if (width >= kMaxLanes && g->turn) {
         hipLaunchKernelGGL(turn_release_kernel, dim3(1), dim3(64), 0, s, g->turn);
         if (g->full_ev) (void)hipEventRecord(g->full_ev, s);
         return;
     }
-    for (int i = gate_first(lane, width); i < gate_first(lane, width) + width && i < kMaxLanes; ++i)
+    for (int i = first; i < first + width && i < kMaxLanes; ++i)
         if (g->ev[i]) (void)hipEventRecord(g->ev[i], s);
 }
 static PersistGate* persist_gate(int device) {
@@ -677,64 +675,135 @@ static int run_conv(dsmi_model* m, const float* feat, int B, int T, int To, int 
     return DSMI_OK;
 }
 
-// One BatchRNN layer on the internal buffers: x-projection GEMM + To recurrent step launches.
+// The launch descriptions of layer l's recurrent kernels on the internal buffers (output to hbuf[dst]); which window of the layer a
+// launch carries is the caller's to fill in (rnn_plan.h).  The spin-limit and drop-signal test hooks of every persistent launch are
+// set here and nowhere else.
+RnnPersist16Launch persist16_launch(const dsmi_model* m, int l, int B, int To, int dst) {
+    RnnPersist16Launch pl;
+    pl.g = m->geom16;
+    for (int dd = 0; dd < 2; ++dd) { pl.whh16[dd] = m->rnn[l].whh16_sp[dd]; pl.bhh[dd] = m->rnn[l].bhh[dd]; pl.out[dd] = m->hbuf[dst][dd]; }
+    pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack16 = m->hpack16; pl.counters = m->pcnt; pl.err = m->perr;
+    pl.B = B; pl.T = To; pl.pgroups = 0;
+    pl.spin_limit = m->spin_limit;
+    if (m->drop_layer == l) { pl.drop_wg = m->drop_wg; pl.drop_step = m->drop_step; }
+    return pl;
+}
+RnnPersistLaunch persist_launch(const dsmi_model* m, int l, int B, int To, int dst) {
+    RnnPersistLaunch pl;
+    pl.g = m->geom;
+    for (int dd = 0; dd < 2; ++dd) { pl.whh_sp[dd] = m->rnn[l].whh_sp[dd]; pl.bhh[dd] = m->rnn[l].bhh[dd]; pl.out[dd] = m->hbuf[dst][dd]; }
+    pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack_sp = m->hpack_sp; pl.counters = m->pcnt; pl.err = m->perr; pl.B = B; pl.T = To;
+    pl.spin_limit = m->spin_limit;
+    if (m->drop_layer == l) { pl.drop_wg = m->drop_wg; pl.drop_step = m->drop_step; }
+    return pl;
+}
+static RnnStepLaunch rnn_step_launch(const dsmi_model* m, int l, int B, int To, int dst) {
+    RnnStepLaunch st;
+    st.g = m->geom;
+    for (int dd = 0; dd < 2; ++dd) {
+        st.whh_packed[dd] = m->rnn[l].whh[dd]; st.bhh[dd] = m->rnn[l].bhh[dd];
+        st.out[dd] = m->hbuf[dst][dd]; st.cstate[dd] = m->cst[dd];
+    }
+    st.xp = m->xp; st.lens_dev = m->lens_dev; st.B = B; st.T = To; st.hpack = m->hpack;
+    return st;
+}
+
+// What the ring kernels' predicates and plan take from the environment (rnn_plan.h keeps them pure).  DSMI_RNN_KERNEL=ring4 also
+// lifts the fence around the four-wave form's small shapes (rnn_persist_ring4_tiles) -- and THAT is read once per process, here,
+// not per handle like dsmi_model::ring4 (dsmi_model_create): a handle created under the variable in a process started without it
+// runs the four-wave form on every window of the shapes it takes anyway, and the fenced shapes on the eight-wave form.  An oddity
+// kept from when the predicate read the variable itself -- with ONE difference: the predicate read it at its first call (the first
+// layer that reached the ring kernels without ring8, or the ring stamps), this is read when the first recurrent layer of any kind
+// is planned.  A process whose first layers are lone batches of up to 32 clips and which only THEN sets the variable used to get the
+// fence lifted and no longer does.  A process started with the variable, or one that never sets it, sees no difference.  The other
+// two inputs exist in the experiments build only.
+struct RingEnv { bool small_shapes; int most, slot_cap; };
+static const RingEnv& ring_env() {
+    static const RingEnv env = [] {
+        const char *k = std::getenv("DSMI_RNN_KERNEL"), *t = exp_env("DSMI_RING_TILES"), *c = exp_env("DSMI_DEBUG_RING_SLOTS");
+        return RingEnv{k && std::string(k) == "ring4", t ? std::atoi(t) : 4, c ? std::atoi(c) : 0};
+    }();
+    return env;
+}
+
+static RnnPlanInput rnn_plan_input(const dsmi_model* m, int B, bool split16) {
+    RnnPlanInput in;
+    in.geom = m->geom; in.geom16 = m->geom16; in.have16 = m->have16; in.split16 = split16;
+    in.B = B; in.n_cus = m->n_cus; in.inflight = m->inflight; in.ring_windows = m->ring_windows; in.lane = m->lane;
+    in.rnn_mode = m->rnn_mode; in.persist_gen = m->persist_gen; in.rnn_kernel = m->rnn_kernel; in.ring8 = m->ring8; in.ring4 = m->ring4;
+    in.ring4_small_shapes = ring_env().small_shapes; in.ring4_most = ring_env().most; in.ring_slot_cap = ring_env().slot_cap;
+    return in;
+}
+
+// Launch a layer's plan on the internal buffers.  Per launch: arm the timer, take the gate slots, launch, record -- wait -> launch
+// -> record under the gate's mutex, atomic against other host threads (two persistent kernels must never share CUs: see
+// persist_gate).  false: a launcher refused its shape and the layer has not run.
+static bool run_rnn_plan(dsmi_model* m, const RnnPlan& plan, int l, int B, int To, int dst, double sumlen, hipStream_t s) {
+    const double H = m->desc.rnn_hidden_size, GH = (double)m->geom.G * m->desc.rnn_hidden_size, Dd = m->geom.D;
+    if (plan.launches[0].kernel == RNN_STEPS) {
+        RnnStepLaunch st = rnn_step_launch(m, l, B, To, dst);
+        for (int step = 0; step < To; ++step) {
+            st.step = step;
+            // algorithmic FLOPs of this launch: clips still running at this step (both directions)
+            int act = 0;
+            for (int i = 0; i < B; ++i) act += step < m->host_out_lens[i] ? 1 : 0;
+            st.ev = timer_arm(m, KK_STEP, (step & 7) == 3, 2.0 * Dd * GH * H * act, 4.0 * Dd * (GH * H + (double)B * (GH + 2.0 * H)));
+            launch_rnn_step(st, s);
+        }
+        return true;
+    }
+    RnnPersist16Launch p16;      // a plan's launches are of one family: the 16-unit kernels or the first generation
+    RnnPersistLaunch p8;
+    if (plan.x16) p16 = persist16_launch(m, l, B, To, dst);
+    else p8 = persist_launch(m, l, B, To, dst);
+    // counters are single-use per step, zeroed right before (the 16-unit kernels': with the ring kernels' direction tickets behind
+    // them, two words per window)
+    const size_t cnt_words = (size_t)m->geom.D * ceil_div(B, 16) * To * kPersist16CntWords;
+    if (plan.x16) (void)hipMemsetAsync(m->pcnt, 0, sizeof(unsigned) * (cnt_words + 2 * ceil_div(B, 16) + 2), s);
+    else (void)hipMemsetAsync(m->pcnt, 0, sizeof(unsigned) * (size_t)m->geom.D * ceil_div(B, 32) * To, s);
+    // the four-wave ring kernel's directions by XCD half (its prologue; profiles/r06_ring_experiments.txt: 2.29 -> 1.56 GB fetched per
+    // launch); DSMI_DEBUG_RING_XCD=0 in the experiments build: by blockIdx
+    static const bool ring_xcd = [] { const char* e = exp_env("DSMI_DEBUG_RING_XCD"); return !(e && e[0] == '0'); }();
+    PersistGate* gate = persist_gate(m->device);
+    std::unique_lock<std::mutex> turn(gate->mu, std::defer_lock);
+    bool ok = true;
+    for (int i = 0; i < plan.launches.size() && ok; ++i) {
+        const RnnLaunch& L = plan.launches[i];
+        const EvPair ev = timer_arm(m, KK_PERSIST, true, L.part * 2.0 * Dd * GH * H * sumlen, L.part * 4.0 * Dd * (GH * H + (double)To * B * (GH + 2.0 * H)));
+        if (!L.join) {
+            turn.lock();
+            if (L.gate == GATE_RING) ring_gate_wait(gate, s, L.slot0, L.nslots, L.cus, m->n_cus);
+            else gate_wait(gate, s, L.slot0, L.nslots);
+        }
+        p16.ev = ev;
+        switch (L.kernel) {
+            case RNN_PERSIST8: p8.ev = ev; p8.d0 = L.at; p8.ny = L.n; ok = launch_rnn_persist(p8, s); break;
+            case RNN_PERSIST16: p16.pgroups = L.n; p16.waves = 8; ok = launch_rnn_persist16(p16, s); break;
+            case RNN_PERSIST16_HALF: p16.pgroups = L.n; p16.waves = 4; ok = launch_rnn_persist16(p16, s); break;
+            case RNN_DUO: p16.pair0 = L.at; p16.npairs = L.n; ok = launch_rnn_persist_duo(p16, s); break;
+            default:
+                p16.tile0 = L.at; p16.ntw = L.n; p16.nwin = L.nwin;
+                p16.tickets = ring_xcd ? m->pcnt + cnt_words + L.ticket : nullptr;
+                ok = L.kernel == RNN_RING8 ? launch_rnn_persist_ring(p16, s) : launch_rnn_persist_ring4(p16, s);
+        }
+        if (!ok || i + 1 == plan.launches.size() || !plan.launches[i + 1].join) {
+            if (L.gate == GATE_RING) ring_gate_record(gate, s, L.slot0, L.nslots, L.cus);
+            else gate_record(gate, s, L.slot0, L.nslots);
+            turn.unlock();
+        }
+    }
+    return ok;
+}
+
+// One BatchRNN layer on the internal buffers: plan it (rnn_plan.h), x-projection GEMM in the column order the plan's kernels read,
+// launch the plan.
 static void run_rnn_layer(dsmi_model* m, int l, GemmLaunch gl, int B, int To, int dst, hipStream_t s) {
     double sumlen = 0;
     for (int i = 0; i < B; ++i) sumlen += m->host_out_lens[i];
     const double GH = (double)m->geom.G * m->desc.rnn_hidden_size, Dd = m->geom.D;
-    int pgroups = 0, waves = 8;
-    bool use16 = m->rnn_mode == 1 && m->persist_gen == 2 && m->gemm_mode == 1 && m->have16 && gl.w_sp;
-    // Which 16-unit kernel.  The caller says how many batches it keeps in flight (dsmi_model_set_inflight):
-    //   1 -> whole-CU workgroups on the whole device: the shortest step for a lone batch (2.7 us for cfgA at B = 32);
-    //   2 -> the paired-tile pipeline on ONE gate lane's CUs when the batch fits there (B = 17..32 for cfgA: 100 CUs), so that
-    //        the second batch's recurrent layer runs on the other half of the chip; failing that, half-CU workgroups (one lane,
-    //        the two batches share every CU); failing that, whole-CU workgroups (both lanes: the two batches take turns).
-    bool duo = false, duo_lane = false;
-    if (use16 && m->inflight >= 2) {
-        duo_lane = rnn_persist_duo_eligible(m->geom16, B, m->n_cus / 2);
-        duo = duo_lane || rnn_persist_duo_eligible(m->geom16, B, m->n_cus);
-    }
-    // Batches of more than one tile pair (B > 32): the paired-tile kernel in WINDOWS of as many tile pairs as the device holds,
-    // one launch after the other (batches in flight take turns): 3.8 us per step and window against 2.3-2.9 us per 32 clips for
-    // the kernel that walks the tiles.  (One pair per launch on the handle's own lane, the other batch's windows beside it, was
-    // measured and is worse -- config 5: 169 against 128 ms per batch: four times as many persistent launches, each of which
-    // waits for whole free CUs behind the other batch's small dense workgroups.)
-    int duo_window = 0;
-    if (use16 && !duo_lane && B > 32) {
-        duo_window = rnn_persist_duo_pairs(m->geom16, B, m->n_cus);
-        duo = duo_window >= 1;
-    }
-    // The ring kernel (rnn_persist_ring.hip): a window = every tile of up to 4..8 on H / 32 workgroups per direction (cfgA: 50 CUs,
-    // ONE gate slot).  With batches in flight a handle's layer is one window on its own slot -- the other slots and the rest of
-    // the chip belong to the other batches; a lone batch of more than 32 clips spreads its tiles over as many windows side by
-    // side as the device holds.  (A lone batch of up to 32 clips keeps the whole-device kernel: the shortest step.)
-    int ring_ntw = 0, ring_nwin = 0, ring_slots = 0;
-    bool ring_only8 = m->ring8;      // the eight-wave form on every window: asked for, or a shape the four-wave form does not take
-    if (use16 && m->rnn_kernel != 1 && (m->inflight >= 2 || B > 32 || m->rnn_kernel == 2)) {
-        const int rcus = rnn_persist_ring_cus(m->geom16);
-        ring_slots = rcus > 0 ? std::min(kRingSlots, m->n_cus / rcus) : 0;        // windows the device holds side by side
-        static const int slot_cap = [] { const char* e = exp_env("DSMI_DEBUG_RING_SLOTS"); return e ? std::atoi(e) : 0; }();      // (experiments)
-        if (slot_cap >= 2 && ring_slots > slot_cap) ring_slots = slot_cap;
-        const int cap4 = m->ring8 ? 0 : rnn_persist_ring4_tiles(m->geom16, B, rcus);
-        ring_only8 = ring_only8 || cap4 == 0;
-        const int cap = ring_slots >= 2 ? (ring_only8 ? rnn_persist_ring_tiles(m->geom16, B, rcus) : cap4) : 0;
-        if (cap > 0) {
-            const int ntiles = ceil_div(B, 16);
-            // windows side by side: one with batches in flight, up to four for a lone batch -- or what the caller said
-            // (dsmi_model_set_ring_windows: two where only two forwards will share the chip)
-            const int slots = m->ring_windows > 0 ? std::min(std::min(m->ring_windows, ring_slots), kMaxLanes)
-                                                  : (m->inflight >= 2 ? 1 : std::min(ring_slots, kMaxLanes));
-            ring_ntw = std::min(std::max(ceil_div(ntiles, slots), 1), cap);
-            if (m->inflight < 2 && m->ring_windows <= 0) ring_ntw = std::max(ring_ntw, std::min(ntiles, 2));
-            ring_nwin = std::min(ceil_div(ntiles, ring_ntw), slots);
-            duo = false;
-        }
-    }
-    if (use16 && !duo && !ring_ntw) {
-        if (m->inflight >= 2 && rnn_persist16_half_eligible(m->geom16, B, m->n_cus, &pgroups)) waves = 4;
-        else use16 = rnn_persist16_eligible(m->geom16, B, m->n_cus, &pgroups);
-    }
-    if (use16) {      // the second-generation kernel reads the x-projection in its own column order
+    RnnPlanInput in = rnn_plan_input(m, B, m->gemm_mode == 1 && gl.w_sp);
+    RnnPlan plan = plan_rnn_layer(in);
+    if (plan.x16) {      // the second-generation kernels read the x-projection in their own column order
         gl.w_sp = m->rnn[l].wih16_sp; gl.bias = m->rnn[l].bih16; gl.N = m->geom16.Np; gl.ldc = m->geom16.Np;
     }
     gl.ev = timer_arm(m, gl.mode == GEMM_A_CONV ? KK_GEMM0 : KK_GEMM, true, 2.0 * Dd * GH * gl.K * sumlen,
@@ -743,111 +812,19 @@ static void run_rnn_layer(dsmi_model* m, int l, GemmLaunch gl, int B, int To, in
     if (sem) hipLaunchKernelGGL(dense_enter_kernel, dim3(1), dim3(64), 0, s, sem, (unsigned)dense_tokens());
     launch_gemm(gl, s);
     if (sem) hipLaunchKernelGGL(dense_leave_kernel, dim3(1), dim3(64), 0, s, sem);
-    if (use16) {
-        RnnPersist16Launch pl;
-        pl.g = m->geom16;
-        for (int dd = 0; dd < 2; ++dd) {
-            pl.whh16[dd] = m->rnn[l].whh16_sp[dd];
-            pl.bhh[dd] = m->rnn[l].bhh[dd]; pl.out[dd] = m->hbuf[dst][dd];
-        }
-        pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack16 = m->hpack16; pl.counters = m->pcnt; pl.err = m->perr;
-        pl.B = B; pl.T = To; pl.pgroups = pgroups; pl.waves = waves;
-        pl.spin_limit = m->spin_limit;
-        if (m->drop_layer == l) { pl.drop_wg = m->drop_wg; pl.drop_step = m->drop_step; }
-        const size_t cnt_words = (size_t)m->geom.D * ceil_div(B, 16) * To * kPersist16CntWords;
-        (void)hipMemsetAsync(m->pcnt, 0, sizeof(unsigned) * (cnt_words + 2 * ceil_div(B, 16) + 2), s);
-        // the four-wave ring kernel's directions by XCD half (its prologue; profiles/r06_ring_experiments.txt: 2.29 -> 1.56 GB fetched per
-        // launch); DSMI_DEBUG_RING_XCD=0 in the experiments build: by blockIdx
-        static const bool ring_xcd = [] { const char* e = exp_env("DSMI_DEBUG_RING_XCD"); return !(e && e[0] == '0'); }();
-        const int total_pairs = (ceil_div(B, 16) + 1) / 2;
-        const int window = duo && duo_window > 0 ? duo_window : total_pairs;
-        bool ok = true;
-        const int ntiles = ceil_div(B, 16);
-        for (int t0 = 0; ring_ntw && t0 < ntiles && ok; t0 += ring_ntw * ring_nwin) {
-            const int nw = std::min(ring_nwin, ceil_div(ntiles - t0, ring_ntw));
-            const double part = (double)std::min(ring_ntw * nw, ntiles - t0) / ntiles;
-            pl.tile0 = t0; pl.ntw = ring_ntw; pl.nwin = nw;
-            pl.tickets = ring_xcd ? m->pcnt + cnt_words + 2 * (t0 / ring_ntw) : nullptr;
-            pl.ev = timer_arm(m, KK_PERSIST, true, part * 2.0 * Dd * GH * m->desc.rnn_hidden_size * sumlen,
-                              part * 4.0 * Dd * (GH * m->desc.rnn_hidden_size + (double)To * B * (GH + 2.0 * m->desc.rnn_hidden_size)));
-            PersistGate* gate = persist_gate(m->device);
-            std::lock_guard<std::mutex> lk(gate->mu);
-            // a handle's own slot; a PAIR of windows with batches in flight: the handle's own pair of slots (consecutive forwards run on
-            // consecutive handles: their pairs differ); a lone batch's windows: from slot 0
-            const int first = nw == 1 ? m->lane % ring_slots : ((nw == 2 && m->inflight >= 2 && ring_slots >= 4) ? 2 * (m->lane & 1) : 0);
-            const int rcus = rnn_persist_ring_cus(m->geom16);
-            ring_gate_wait(gate, s, first, nw, rcus, m->n_cus);
-            // Which form of the ring kernel.  Four waves (one per SIMD, the cell in the MFMAs' shadows) where a window walks three
-            // tiles or more: 6.4 against 7.2 us per step of four tiles (cfgA, alone on the chip).  The four-wave form multiplies
-            // phantom tiles like real ones (its phase has no branch), the eight-wave form skips them: a window of one or two tiles
-            // -- a lone 32-clip batch at the end of a stream -- is 4.3 / 5.4 us per step there against 5.8 / 6.0 (round 5,
-            // tools/exp/ring_layer_time.py).  DSMI_RNN_KERNEL=ring8 / ring4: one form everywhere (A/B runs, the forms' own tests).
-            const bool eight = ring_only8 || (!m->ring4 && std::min(ring_ntw, ntiles - t0) <= 2 && rnn_persist_ring_tiles(m->geom16, B, rcus) > 0);
-            if (eight) pl.ntw = std::min(ring_ntw, rnn_persist_ring_tiles(m->geom16, B, rcus));      // (its own cap: at most two real tiles are left)
-            ok = eight ? launch_rnn_persist_ring(pl, s) : launch_rnn_persist_ring4(pl, s);
-            ring_gate_record(gate, s, first, nw, rcus);
-        }
-        if (ring_ntw && ok) return;
-        for (int p0 = 0; !ring_ntw && p0 < (duo ? total_pairs : 1) && ok; p0 += window) {
-            const double part = duo ? (double)std::min(window, total_pairs - p0) / total_pairs : 1.0;
-            if (duo) { pl.pair0 = p0; pl.npairs = std::min(window, total_pairs - p0); }
-            pl.ev = timer_arm(m, KK_PERSIST, true, part * 2.0 * Dd * GH * m->desc.rnn_hidden_size * sumlen,
-                              part * 4.0 * Dd * (GH * m->desc.rnn_hidden_size + (double)To * B * (GH + 2.0 * m->desc.rnn_hidden_size)));
-            PersistGate* gate = persist_gate(m->device);
-            std::lock_guard<std::mutex> lk(gate->mu);       // wait -> launch -> record is atomic against other host threads
-            // a half-CU / half-chip kernel takes one lane (a pair of gate slots), anything else the device
-            const int width = ((waves == 4 && !duo) || duo_lane) ? 2 : kMaxLanes;
-            gate_wait(gate, s, m->lane, width);
-            ok = duo ? launch_rnn_persist_duo(pl, s) : launch_rnn_persist16(pl, s);
-            gate_record(gate, s, m->lane, width);
-        }
-        if (ok) return;
-        // (not reachable for eligible shapes; the x-projection is in the other column order, so redo it)
+    if (run_rnn_plan(m, plan, l, B, To, dst, sumlen, s)) return;
+    // Launchers refuse what the predicates let through only by mistake; the layer still runs.
+    if (plan.x16) {
+        // first: the x-projection is in the 16-unit column order, so redo it in the other, and plan without the 16-unit kernels
+        // (the first-generation kernel if eligible)
         gl.w_sp = m->rnn[l].wih_sp; gl.bias = m->rnn[l].bih; gl.N = m->geom.Np; gl.ldc = m->geom.Np; gl.ev = EvPair{};
         launch_gemm(gl, s);
+        in.have16 = false;
+        plan = plan_rnn_layer(in);
+        if (run_rnn_plan(m, plan, l, B, To, dst, sumlen, s)) return;
     }
-    if (m->rnn_mode == 1 && rnn_persist_eligible(m->geom, B, m->n_cus)) {
-        // whole layer in one launch; counters are single-use per step, zeroed right before
-        RnnPersistLaunch pl;
-        pl.g = m->geom;
-        for (int dd = 0; dd < 2; ++dd) { pl.whh_sp[dd] = m->rnn[l].whh_sp[dd]; pl.bhh[dd] = m->rnn[l].bhh[dd]; pl.out[dd] = m->hbuf[dst][dd]; }
-        pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack_sp = m->hpack_sp; pl.counters = m->pcnt; pl.err = m->perr; pl.B = B; pl.T = To;
-        pl.spin_limit = m->spin_limit;
-        if (m->drop_layer == l) { pl.drop_wg = m->drop_wg; pl.drop_step = m->drop_step; }
-        (void)hipMemsetAsync(m->pcnt, 0, sizeof(unsigned) * (size_t)m->geom.D * ceil_div(B, 32) * To, s);
-        // Two persistent kernels must never share the device (see persist_gate): chain them through the per-device
-        // event.  A layer too wide for both directions at once runs them one after the other.
-        const int ny = m->geom.nwg * m->geom.D <= m->n_cus ? m->geom.D : 1;
-        PersistGate* gate = persist_gate(m->device);
-        std::lock_guard<std::mutex> lk(gate->mu);
-        gate_wait(gate, s, 0, kMaxLanes);              // the first-generation kernel is sized for the whole device
-        bool ok = true;
-        for (int d0 = 0; d0 < m->geom.D && ok; d0 += ny) {
-            const double part = (double)ny;
-            pl.d0 = d0; pl.ny = ny;
-            pl.ev = timer_arm(m, KK_PERSIST, true, 2.0 * part * GH * m->desc.rnn_hidden_size * sumlen,
-                              4.0 * part * (GH * m->desc.rnn_hidden_size + (double)To * B * (GH + 2.0 * m->desc.rnn_hidden_size)));
-            ok = launch_rnn_persist(pl, s);
-        }
-        gate_record(gate, s, 0, kMaxLanes);
-        if (ok) return;
-    }
-    RnnStepLaunch st;
-    st.g = m->geom;
-    for (int dd = 0; dd < 2; ++dd) {
-        st.whh_packed[dd] = m->rnn[l].whh[dd]; st.bhh[dd] = m->rnn[l].bhh[dd];
-        st.out[dd] = m->hbuf[dst][dd]; st.cstate[dd] = m->cst[dd];
-    }
-    st.xp = m->xp; st.lens_dev = m->lens_dev; st.B = B; st.T = To; st.hpack = m->hpack;
-    for (int step = 0; step < To; ++step) {
-        st.step = step;
-        // algorithmic FLOPs of this launch: clips still running at this step (both directions)
-        int act = 0;
-        for (int i = 0; i < B; ++i) act += step < m->host_out_lens[i] ? 1 : 0;
-        st.ev = timer_arm(m, KK_STEP, (step & 7) == 3, 2.0 * Dd * GH * m->desc.rnn_hidden_size * act,
-                          4.0 * Dd * (GH * m->desc.rnn_hidden_size + (double)B * (GH + 2.0 * m->desc.rnn_hidden_size)));
-        launch_rnn_step(st, s);
-    }
+    in.rnn_mode = 0;      // then: per step
+    (void)run_rnn_plan(m, plan_rnn_layer(in), l, B, To, dst, sumlen, s);
 }
 
 static GemmLaunch xproj_gemm(dsmi_model* m, int l, int B, int To) {
@@ -1125,10 +1102,8 @@ extern "C" int dsmi_rnn_layer(dsmi_model* m, int layer, const float* x, const in
 
 // stream.hip's batched pass (dsmi_stream_forward_many): one carried-state launch of the first-generation persistent layer.  Sized
 // for the whole device like the offline first-generation launch, so it takes every gate slot and never shares the chip with another
-// persistent kernel of the process; the same test hooks apply.
-bool stream_persist_layer(dsmi_model* m, int l, RnnPersistLaunch& pl, hipStream_t s) {
-    pl.spin_limit = m->spin_limit;
-    if (m->drop_layer == l) { pl.drop_wg = m->drop_wg; pl.drop_step = m->drop_step; }
+// persistent kernel of the process; the launch description comes from persist_launch: the same test hooks apply.
+bool stream_persist_layer(dsmi_model* m, const RnnPersistLaunch& pl, hipStream_t s) {
     PersistGate* gate = persist_gate(m->device);
     std::lock_guard<std::mutex> lk(gate->mu);
     gate_wait(gate, s, 0, kMaxLanes);
@@ -1199,40 +1174,53 @@ extern "C" int dsmi_last_forward_stats(const dsmi_model* m, int64_t* n_step, dou
     return DSMI_OK;
 }
 
-// ---- diagnostics: per-wave phase timestamps (s_memrealtime, 100 MHz) of ONE recurrent step launch.
-// Runs steps 0..step of `layer` on whatever the workspaces hold (timing only) and returns
-// stamps[D*nwg][8 waves][8] for the last one.  GRU, B <= 32.
-extern "C" int dsmi_debug_step_stamps(dsmi_model* m, int layer, int B, int To, int step, uint64_t* stamps_host, int64_t n_words) {
-    if (!m || !m->finalized || m->desc.rnn_type != DSMI_RNN_GRU || B > 32 || layer < 0 || layer >= m->desc.rnn_layers) return DSMI_ERR_INVALID;
+// The stamp entry points' common beginning: workspaces for (B, To); for a persistent kernel the same rules as the product path --
+// one process per GPU, and the per-device gate held to the end of the call on a drained device (every launch is followed by a
+// device synchronise before the lock is released); then a zeroed stamp buffer of `need` words, full-length clips and a zero
+// x-projection.  The buffer is freed and the gate released when the StampRun goes out of scope, on every return path.
+struct StampRun {
+    std::unique_lock<std::mutex> gate;
+    unsigned long long* dbg = nullptr;
+    ~StampRun() { if (dbg) (void)hipFree(dbg); }
+};
+static int stamp_begin(dsmi_model* m, int B, int To, bool persistent, int64_t need, int64_t n_words, StampRun& r) {
     int Tin = To;
     while (seq_len(m, Tin) < To) Tin += 1;
     int rc;
     if ((rc = dsmi_reserve(m, B, Tin))) return rc;
     HIP_OK(m, hipSetDevice(m->device));
-    const int64_t need = (int64_t)m->geom.D * m->geom.nwg * 8 * 8;
+    if (persistent) {
+        if (!persist_process_lock(m->device)) return fail(m, DSMI_ERR_INVALID, "another process holds this GPU's persistent-kernel lock");
+        r.gate = std::unique_lock<std::mutex>(persist_gate(m->device)->mu);      // (no other launch of this process can start)
+        HIP_OK(m, hipDeviceSynchronize());
+    }
     if (n_words < need) return fail(m, DSMI_ERR_INVALID, "stamp buffer too small");
-    unsigned long long* dbg;
-    HIP_OK(m, hipMalloc((void**)&dbg, sizeof(unsigned long long) * need));
-    HIP_OK(m, hipMemset(dbg, 0, sizeof(unsigned long long) * need));
+    HIP_OK(m, hipMalloc((void**)&r.dbg, sizeof(unsigned long long) * need));
+    HIP_OK(m, hipMemset(r.dbg, 0, sizeof(unsigned long long) * need));
     std::vector<int32_t> lens(B, To);
     HIP_OK(m, hipMemcpy(m->lens_dev, lens.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
-    HIP_OK(m, hipMemset(m->xp, 0, sizeof(float) * (size_t)To * B * m->geom.Np));
+    HIP_OK(m, hipMemset(m->xp, 0, sizeof(float) * (size_t)To * B * std::max(m->geom.Np, m->have16 ? m->geom16.Np : 0)));
+    return DSMI_OK;
+}
+
+// ---- diagnostics: per-wave phase timestamps (s_memrealtime, 100 MHz) of ONE recurrent step launch.
+// Runs steps 0..step of `layer` on whatever the workspaces hold (timing only) and returns
+// stamps[D*nwg][8 waves][8] for the last one.  GRU, B <= 32.
+extern "C" int dsmi_debug_step_stamps(dsmi_model* m, int layer, int B, int To, int step, uint64_t* stamps_host, int64_t n_words) {
+    if (!m || !m->finalized || m->desc.rnn_type != DSMI_RNN_GRU || B > 32 || layer < 0 || layer >= m->desc.rnn_layers) return DSMI_ERR_INVALID;
+    const int64_t need = (int64_t)m->geom.D * m->geom.nwg * 8 * 8;
+    StampRun run;
+    int rc;
+    if ((rc = stamp_begin(m, B, To, false, need, n_words, run))) return rc;
     for (int dd = 0; dd < m->geom.D; ++dd) HIP_OK(m, hipMemset(m->hbuf[0][dd], 0, sizeof(float) * (size_t)To * B * m->Hs));
-    RnnStepLaunch st;
-    st.g = m->geom;
-    for (int dd = 0; dd < 2; ++dd) {
-        st.whh_packed[dd] = m->rnn[layer].whh[dd]; st.bhh[dd] = m->rnn[layer].bhh[dd];
-        st.out[dd] = m->hbuf[0][dd]; st.cstate[dd] = m->cst[dd];
-    }
-    st.xp = m->xp; st.lens_dev = m->lens_dev; st.B = B; st.T = To; st.hpack = m->hpack;
+    RnnStepLaunch st = rnn_step_launch(m, layer, B, To, 0);
     for (int s2 = 0; s2 <= step; ++s2) {
         st.step = s2;
-        st.dbg = s2 == step ? dbg : nullptr;
+        st.dbg = s2 == step ? run.dbg : nullptr;
         launch_rnn_step(st, nullptr);
     }
     HIP_OK(m, hipDeviceSynchronize());
-    HIP_OK(m, hipMemcpy(stamps_host, dbg, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
-    (void)hipFree(dbg);
+    HIP_OK(m, hipMemcpy(stamps_host, run.dbg, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
     return DSMI_OK;
 }
 
@@ -1248,119 +1236,52 @@ extern "C" int dsmi_debug_persist_stamps(dsmi_model* m, int layer, int B, int To
     if (m && m->finalized && std::getenv("DSMI_STAMP_RING")) return ring_stamps(m, layer, B, To, stamps_host, n_words);
     if (!m || !m->finalized || B > 32 || layer < 0 || layer >= m->desc.rnn_layers || !rnn_persist_eligible(m->geom, B, m->n_cus) ||
         m->geom.nwg * m->geom.D > m->n_cus) return DSMI_ERR_INVALID;
-    int Tin = To;
-    while (seq_len(m, Tin) < To) Tin += 1;
-    int rc;
-    if ((rc = dsmi_reserve(m, B, Tin))) return rc;
-    HIP_OK(m, hipSetDevice(m->device));
-    // diagnostics launch persistent kernels too: same rules as the product path -- one process per GPU, and the per-device gate
-    // held from here to the end (every launch below is followed by a device synchronise before the lock is released)
-    if (!persist_process_lock(m->device)) return fail(m, DSMI_ERR_INVALID, "another process holds this GPU's persistent-kernel lock");
-    PersistGate* stamp_gate = persist_gate(m->device);
-    std::lock_guard<std::mutex> stamp_lk(stamp_gate->mu);
-    HIP_OK(m, hipDeviceSynchronize());
+    // which kernel: DSMI_STAMP_DUO: the paired-tile kernel, stamps[workgroup][8 waves][8] = time in slots 0..3 and at the barrier
+    // behind each; else the 16-unit kernel with one tile per workgroup (the plain single-tile path is what is stamped); else the
+    // first generation
     int pgroups = 0;
     const bool duo = std::getenv("DSMI_STAMP_DUO") && m->have16 && rnn_persist_duo_eligible(m->geom16, B, m->n_cus);
-    if (duo) {          // the paired-tile kernel: stamps[workgroup][8 waves][8] = time in slots 0..3 and at the barrier behind each
-        const int64_t needd = (int64_t)m->geom16.D * ceil_div(ceil_div(B, 16), 2) * m->geom16.nwg * 8 * 8;
-        if (n_words < needd) return fail(m, DSMI_ERR_INVALID, "stamp buffer too small");
-        unsigned long long* dbg;
-        HIP_OK(m, hipMalloc((void**)&dbg, sizeof(unsigned long long) * needd));
-        HIP_OK(m, hipMemset(dbg, 0, sizeof(unsigned long long) * needd));
-        std::vector<int32_t> lens(B, To);
-        HIP_OK(m, hipMemcpy(m->lens_dev, lens.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
-        HIP_OK(m, hipMemset(m->xp, 0, sizeof(float) * (size_t)To * B * m->geom16.Np));
-        RnnPersist16Launch pl;
-        pl.g = m->geom16;
-        for (int dd = 0; dd < 2; ++dd) { pl.whh16[dd] = m->rnn[layer].whh16_sp[dd]; pl.bhh[dd] = m->rnn[layer].bhh[dd]; pl.out[dd] = m->hbuf[0][dd]; }
-        pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack16 = m->hpack16; pl.counters = m->pcnt; pl.err = m->perr;
-        pl.B = B; pl.T = To;
-        for (int rep = 0; rep < 2; ++rep) {
-            HIP_OK(m, hipMemset(m->pcnt, 0, sizeof(unsigned) * (size_t)m->geom.D * ceil_div(B, 16) * To * kPersist16CntWords));
-            pl.dbg = rep ? dbg : nullptr;
-            launch_rnn_persist_duo(pl, nullptr);
-            HIP_OK(m, hipDeviceSynchronize());
-        }
-        HIP_OK(m, hipMemcpy(stamps_host, dbg, sizeof(unsigned long long) * needd, hipMemcpyDeviceToHost));
-        (void)hipFree(dbg);
-        return (int)(needd / 64);
-    }
-    const bool use16 = m->persist_gen == 2 && m->have16 && rnn_persist16_eligible(m->geom16, B, m->n_cus, &pgroups) &&
-                       ceil_div(B, 16) <= pgroups;        // one tile per workgroup: the plain single-tile path is what is stamped
-    const int64_t need = use16 ? (int64_t)m->geom16.D * pgroups * m->geom16.nwg * 8 * 8 : (int64_t)m->geom.D * m->geom.nwg * 8 * 8;
-    if (n_words < need) return fail(m, DSMI_ERR_INVALID, "stamp buffer too small");
-    unsigned long long* dbg;
-    HIP_OK(m, hipMalloc((void**)&dbg, sizeof(unsigned long long) * need));
-    HIP_OK(m, hipMemset(dbg, 0, sizeof(unsigned long long) * need));
-    std::vector<int32_t> lens(B, To);
-    HIP_OK(m, hipMemcpy(m->lens_dev, lens.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
-    HIP_OK(m, hipMemset(m->xp, 0, sizeof(float) * (size_t)To * B * std::max(m->geom.Np, m->have16 ? m->geom16.Np : 0)));
-    if (use16) {
-        RnnPersist16Launch pl;
-        pl.g = m->geom16;
-        for (int dd = 0; dd < 2; ++dd) { pl.whh16[dd] = m->rnn[layer].whh16_sp[dd]; pl.bhh[dd] = m->rnn[layer].bhh[dd]; pl.out[dd] = m->hbuf[0][dd]; }
-        pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack16 = m->hpack16; pl.counters = m->pcnt; pl.err = m->perr;
-        pl.B = B; pl.T = To; pl.pgroups = pgroups;
-        for (int rep = 0; rep < 2; ++rep) {     // first pass warms up, second is stamped
-            HIP_OK(m, hipMemset(m->pcnt, 0, sizeof(unsigned) * (size_t)m->geom.D * ceil_div(B, 16) * To * kPersist16CntWords));
-            pl.dbg = rep ? dbg : nullptr;
-            launch_rnn_persist16(pl, nullptr);
-            HIP_OK(m, hipDeviceSynchronize());
-        }
-        HIP_OK(m, hipMemcpy(stamps_host, dbg, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
-        (void)hipFree(dbg);
-        return (int)(need / 64);      // number of workgroups stamped
-    }
-    RnnPersistLaunch pl;
-    pl.g = m->geom;
-    for (int dd = 0; dd < 2; ++dd) { pl.whh_sp[dd] = m->rnn[layer].whh_sp[dd]; pl.bhh[dd] = m->rnn[layer].bhh[dd]; pl.out[dd] = m->hbuf[0][dd]; }
-    pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack_sp = m->hpack_sp; pl.counters = m->pcnt; pl.err = m->perr; pl.B = B; pl.T = To;
-    pl.d0 = 0; pl.ny = m->geom.D;
+    const bool use16 = duo || (m->persist_gen == 2 && m->have16 && rnn_persist16_eligible(m->geom16, B, m->n_cus, &pgroups) && ceil_div(B, 16) <= pgroups);
+    const int64_t need = duo ? (int64_t)m->geom16.D * ceil_div(ceil_div(B, 16), 2) * m->geom16.nwg * 8 * 8
+                             : (use16 ? (int64_t)m->geom16.D * pgroups * m->geom16.nwg * 8 * 8 : (int64_t)m->geom.D * m->geom.nwg * 8 * 8);
+    StampRun run;
+    int rc;
+    if ((rc = stamp_begin(m, B, To, true, need, n_words, run))) return rc;
+    RnnPersist16Launch p16 = persist16_launch(m, layer, B, To, 0);
+    p16.pgroups = pgroups;
+    RnnPersistLaunch p8 = persist_launch(m, layer, B, To, 0);
+    p8.d0 = 0; p8.ny = m->geom.D;
     for (int rep = 0; rep < 2; ++rep) {     // first pass warms up, second is stamped
-        HIP_OK(m, hipMemset(m->pcnt, 0, sizeof(unsigned) * (size_t)m->geom.D * To));
-        pl.dbg = rep ? dbg : nullptr;
-        launch_rnn_persist(pl, nullptr);
+        HIP_OK(m, hipMemset(m->pcnt, 0, sizeof(unsigned) * (use16 ? (size_t)m->geom.D * ceil_div(B, 16) * To * kPersist16CntWords : (size_t)m->geom.D * To)));
+        p16.dbg = p8.dbg = rep ? run.dbg : nullptr;
+        if (duo) launch_rnn_persist_duo(p16, nullptr);
+        else if (use16) launch_rnn_persist16(p16, nullptr);
+        else launch_rnn_persist(p8, nullptr);
         HIP_OK(m, hipDeviceSynchronize());
     }
-    HIP_OK(m, hipMemcpy(stamps_host, dbg, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
-    (void)hipFree(dbg);
+    HIP_OK(m, hipMemcpy(stamps_host, run.dbg, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
     return (int)(need / 64);          // number of workgroups stamped
 }
 
 static int ring_stamps(dsmi_model* m, int layer, int B, int To, uint64_t* stamps_host, int64_t n_words) {
     if (B < 1 || B > 128 || layer < 0 || layer >= m->desc.rnn_layers || !m->have16) return DSMI_ERR_INVALID;
-    const int cap = m->ring8 ? rnn_persist_ring_tiles(m->geom16, B, m->n_cus) : rnn_persist_ring4_tiles(m->geom16, B, m->n_cus);
+    const int cap = m->ring8 ? rnn_persist_ring_tiles(m->geom16, B, m->n_cus)
+                             : rnn_persist_ring4_tiles(m->geom16, B, m->n_cus, ring_env().small_shapes, ring_env().most);
     if (cap < ceil_div(B, 16)) return DSMI_ERR_INVALID;
-    int Tin = To;
-    while (seq_len(m, Tin) < To) Tin += 1;
-    int rc;
-    if ((rc = dsmi_reserve(m, B, Tin))) return rc;
-    HIP_OK(m, hipSetDevice(m->device));
-    if (!persist_process_lock(m->device)) return fail(m, DSMI_ERR_INVALID, "another process holds this GPU's persistent-kernel lock");
-    PersistGate* stamp_gate = persist_gate(m->device);
-    std::lock_guard<std::mutex> stamp_lk(stamp_gate->mu);      // (no other launch of this process can start; the device is drained below)
-    HIP_OK(m, hipDeviceSynchronize());
     // per workgroup: the eight-wave form 8 waves x 16 words, the four-wave form 4 waves x 8 words (in the first 32 of the 128)
     const int64_t need = (int64_t)rnn_persist_ring_cus(m->geom16) * 8 * 16;
-    if (n_words < need) return fail(m, DSMI_ERR_INVALID, "stamp buffer too small");
-    struct DevBuf { unsigned long long* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } } dbg;      // freed on every return
-    HIP_OK(m, hipMalloc((void**)&dbg.p, sizeof(unsigned long long) * need));
-    HIP_OK(m, hipMemset(dbg.p, 0, sizeof(unsigned long long) * need));
-    std::vector<int32_t> lens(B, To);
-    HIP_OK(m, hipMemcpy(m->lens_dev, lens.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
-    HIP_OK(m, hipMemset(m->xp, 0, sizeof(float) * (size_t)To * B * m->geom16.Np));
-    RnnPersist16Launch pl;
-    pl.g = m->geom16;
-    for (int dd = 0; dd < 2; ++dd) { pl.whh16[dd] = m->rnn[layer].whh16_sp[dd]; pl.bhh[dd] = m->rnn[layer].bhh[dd]; pl.out[dd] = m->hbuf[0][dd]; }
-    pl.xp = m->xp; pl.lens_dev = m->lens_dev; pl.hpack16 = m->hpack16; pl.counters = m->pcnt; pl.err = m->perr;
-    pl.B = B; pl.T = To; pl.tile0 = 0; pl.ntw = ceil_div(B, 16); pl.nwin = 1;
+    StampRun run;
+    int rc;
+    if ((rc = stamp_begin(m, B, To, true, need, n_words, run))) return rc;
+    RnnPersist16Launch pl = persist16_launch(m, layer, B, To, 0);
+    pl.tile0 = 0; pl.ntw = ceil_div(B, 16); pl.nwin = 1;
     bool ok = true;
     for (int rep = 0; rep < 2 && ok; ++rep) {
         HIP_OK(m, hipMemset(m->pcnt, 0, sizeof(unsigned) * (size_t)m->geom.D * ceil_div(B, 16) * To * kPersist16CntWords));
-        pl.dbg = rep ? dbg.p : nullptr;
+        pl.dbg = rep ? run.dbg : nullptr;
         ok = m->ring8 ? launch_rnn_persist_ring(pl, nullptr) : launch_rnn_persist_ring4(pl, nullptr);
         HIP_OK(m, hipDeviceSynchronize());
     }
-    HIP_OK(m, hipMemcpy(stamps_host, dbg.p, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
+    HIP_OK(m, hipMemcpy(stamps_host, run.dbg, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost));
     return ok ? (int)(need / 128) : DSMI_ERR_INVALID;
 }

@@ -10,6 +10,7 @@
 #include <map>
 
 #include "../../include/dsmi.h"
+#include "rnn_plan.h"      // RnnGeom, ceil_div / round_up, the recurrent kernels' shape predicates and the layer plan (host-only)
 
 namespace dsmi {
 
@@ -40,9 +41,6 @@ inline const char* exp_env(const char* name) {
     return nullptr;
 #endif
 }
-
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 
 // ---- conv geometry: reference model.py:359,372,389 ------------------------------
 struct ConvSpec { int ci, co, kf, kt, sf, st, pf, pt; };
@@ -109,18 +107,7 @@ void launch_gemm(const GemmLaunch& p, hipStream_t s);
 std::vector<uint16_t> pack_gemm_w_split(const float* w, int N, int K, int ldw);
 
 // rnn_step.hip: one time step of both directions of one recurrent layer.
-struct RnnGeom {
-    int kind;      // DSMI_RNN_*
-    int G;         // gates per unit: 3 / 4 / 1
-    int H;
-    int U;         // hidden units per workgroup (8: its h granules are whole 16-byte groups of the packed state)
-    int nwg;       // ceil(H / U) workgroups per direction
-    int Kp;        // H rounded up to 8
-    int nq;        // Kp / 8 k-blocks
-    int D;         // directions
-    int Np;        // D * nwg * G * U : permuted + padded gate columns of the x-projection
-};
-RnnGeom make_rnn_geom(int kind, int H, int D);
+// (RnnGeom, make_rnn_geom: rnn_plan.h)
 // Row r of the packed x-projection weight / bias  <->  (dir, gate, unit) of torch's [G*H][I].
 // returns -1 for padding rows.
 int rnn_src_row(const RnnGeom& g, int packed_col, int* dir_out);
@@ -167,13 +154,11 @@ struct RnnPersistLaunch {
     const float* h0 = nullptr;
     float* cst = nullptr;
 };
-bool rnn_persist_eligible(const RnnGeom& g, int B, int n_cus);
 std::vector<uint16_t> pack_whh_split(const RnnGeom& g, const float* w_hh);
 bool launch_rnn_persist(const RnnPersistLaunch& p, hipStream_t s);
 
 // rnn_persist16.hip: second-generation persistent layer (16 units per workgroup, 16-clip batch tiles as separate
 // chains side by side); needs the x-projection in the U = 16 geometry.
-RnnGeom make_rnn_geom_u(int kind, int H, int D, int U);
 struct RnnPersist16Launch {
     RnnGeom g;                   // make_rnn_geom_u(kind, H, D, 16)
     const uint16_t* whh16[2];    // pack_whh16 output per direction
@@ -181,7 +166,7 @@ struct RnnPersist16Launch {
     const int32_t* lens_dev; uint16_t* hpack16;     // rnn_persist16_state_halfs(g, B) fp16 values
     unsigned* counters;          // [D * ceil(B/16)][T][kPersist16CntWords], zeroed before the launch
     unsigned* err;
-    int B, T, pgroups;           // pgroups from rnn_persist16_eligible / rnn_persist16_half_eligible
+    int B, T, pgroups;           // pgroups from rnn_persist16_eligible / rnn_persist16_half_eligible (rnn_plan.h)
     int waves = 8;               // 8: one workgroup per CU; 4: the half-CU variant (two batches in flight share every CU)
     int pair0 = 0, npairs = 0;   // paired-tile kernel: the window of tile pairs this launch carries (npairs 0: all of them)
     int tile0 = 0, ntw = 0, nwin = 1;   // ring kernel: nwin windows of ntw tiles each, from tile0, side by side (ntw 0: all tiles in one window)
@@ -193,27 +178,20 @@ struct RnnPersist16Launch {
 };
 constexpr int kPersist16Shards = 4;                        // shards of the hand-off counter of a (chain, step) ...
 constexpr int kPersist16CntWords = kPersist16Shards * 64;   // ... each on its own 256-byte line
-bool rnn_persist16_eligible(const RnnGeom& g16, int B, int n_cus, int* pgroups_out);
-bool rnn_persist16_half_eligible(const RnnGeom& g16, int B, int n_cus, int* pgroups_out);
 std::vector<uint16_t> pack_whh16(const RnnGeom& g16, const float* w_hh);
 size_t rnn_persist16_state_halfs(const RnnGeom& g16, int B);
 bool launch_rnn_persist16(const RnnPersist16Launch& p, hipStream_t s);
 
 // rnn_persist_duo.hip: one workgroup carries the two 16-clip tiles of a batch in a fixed four-slot pipeline (a 32-clip
 // batch of cfgA on 100 CUs); same packed weights, x-projection order and state layout as rnn_persist16.hip.
-bool rnn_persist_duo_eligible(const RnnGeom& g16, int B, int n_cus);
-int rnn_persist_duo_pairs(const RnnGeom& g16, int B, int n_cus);     // tile pairs one launch can carry on n_cus CUs (0: not this shape)
 bool launch_rnn_persist_duo(const RnnPersist16Launch& p, hipStream_t s);
 
 // rnn_persist_ring.hip: a workgroup = 32 units of one direction (two adjacent 16-unit groups), walking every tile of its
 // window with the tiles' states staged through an LDS ring (a 64-clip layer of cfgA on 50 CUs); same packed weights,
 // x-projection order, state layout and counters as rnn_persist16.hip.
-int rnn_persist_ring_tiles(const RnnGeom& g16, int B, int n_cus);    // tiles one window can walk (0: not this shape)
-int rnn_persist_ring_cus(const RnnGeom& g16);                        // CUs one window occupies
 bool launch_rnn_persist_ring(const RnnPersist16Launch& p, hipStream_t s);
 // rnn_persist_ring4.hip: the same window on FOUR waves, one per SIMD on the whole register file (W_hh of a 16-unit group's K half
 // per wave, in AccVGPRs), the cell of an item in the shadows of the next item's MFMAs.  Same CUs per window as the eight-wave form.
-int rnn_persist_ring4_tiles(const RnnGeom& g16, int B, int n_cus);   // tiles one window can walk (0: not this shape)
 bool launch_rnn_persist_ring4(const RnnPersist16Launch& p, hipStream_t s);
 
 // head.hip

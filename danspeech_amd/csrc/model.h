@@ -123,4 +123,7 @@ dsmi::EvPair timer_arm(dsmi_model* m, int kind, bool sample, double flops, doubl
 
 // stream.hip / api.hip: the batched streaming pass
 void stream_batch_free(dsmi_model* m);
-bool stream_persist_layer(dsmi_model* m, int l, dsmi::RnnPersistLaunch& pl, hipStream_t s);
+bool stream_persist_layer(dsmi_model* m, const dsmi::RnnPersistLaunch& pl, hipStream_t s);
+// api.hip: the launch descriptions of layer l's persistent kernels on the model's own buffers, test hooks included
+dsmi::RnnPersist16Launch persist16_launch(const dsmi_model* m, int l, int B, int To, int dst);
+dsmi::RnnPersistLaunch persist_launch(const dsmi_model* m, int l, int B, int To, int dst);

@@ -45,9 +45,9 @@ namespace dsmi {
 
 namespace {
 
-constexpr int PNW = 8;                 // waves per workgroup
+constexpr int PNW = kPersistWaves;     // waves per workgroup
 constexpr int PNT = PNW * 64;
-constexpr int PU = 8;                  // hidden units per workgroup (rnn geometry U)
+constexpr int PU = kPersistUnits;      // hidden units per workgroup (rnn geometry U)
 constexpr int RP = 40;                 // row pitch of the reduce buffer in words
 constexpr size_t PERSIST_LDS = 82 * 1024;   // > half of the CU's 160 KiB: at most one workgroup per CU
 
@@ -87,7 +87,7 @@ struct PersistArgs {
         }                                                                                 \
     } while (0)
 
-constexpr int PMAXZ = 8;               // batch tiles per launch (B <= 256)
+constexpr int PMAXZ = kPersistMaxTiles;   // batch tiles per launch (B <= 256)
 
 template <int KIND, int NPW, bool MULTI, bool STAMP = false, bool CARRY = false>
 __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
@@ -343,15 +343,6 @@ bool launch_kind(const PersistArgs& a, int ny, hipStream_t s, const EvPair& ev, 
 }
 
 }  // namespace
-
-// H up to 1280 (10 pairs of 16 k per wave: 80 + 80 operand VGPRs); every workgroup of a launch must own a CU, so a layer whose
-// two directions do not fit together (H > 1024 on 256 CUs) runs them as two launches, one after the other.
-bool rnn_persist_eligible(const RnnGeom& g, int B, int n_cus) {
-    if (g.U != PU || (g.H % 8) != 0) return false;
-    if (ceil_div(ceil_div(g.nq, 2), PNW) > 10) return false;
-    if (ceil_div(B, 32) > PMAXZ) return false;
-    return g.nwg <= n_cus;
-}
 
 static inline uint16_t f16_bits(_Float16 h) {
     uint16_t u;

@@ -28,13 +28,13 @@ namespace dsmi {
 
 namespace {
 
-constexpr int QNW = 8;                 // waves per workgroup (K-split) of the full-CU variants
+constexpr int QNW = kPersist16Waves;   // waves per workgroup (K-split) of the full-CU variants
 constexpr int QNT = QNW * 64;
 constexpr int QNKR4 = 6;               // four-wave variant: k-blocks of W_hh a wave keeps in registers; a seventh sits in LDS
-constexpr int QU = 16;                 // hidden units per workgroup
-constexpr int QB = 16;                 // clips per batch tile
+constexpr int QU = kTileUnits;         // hidden units per workgroup
+constexpr int QB = kTileClips;         // clips per batch tile
 constexpr int QRP = 20;                // row pitch (words) of the reduce buffer: conflict-free for the MFMA-layout writes
-constexpr int QMAXZ = 8;               // batch tiles one workgroup can walk
+constexpr int QMAXZ = kPersist16MaxTiles;   // batch tiles one workgroup can walk
 constexpr size_t Q_LDS = 82 * 1024;    // > half of the CU's LDS: one workgroup per CU
 constexpr size_t Q_LDS_HALF = 78 * 1024;   // four-wave variant: at most two workgroups per CU (its 256 registers per wave allow no third)
 
@@ -649,42 +649,6 @@ bool launch16(const P16Args& a, hipStream_t s, const EvPair& ev, int waves) {
 }
 
 }  // namespace
-
-RnnGeom make_rnn_geom_u(int kind, int H, int D, int U) {
-    RnnGeom g = make_rnn_geom(kind, H, D);
-    g.U = U;
-    g.nwg = ceil_div(H, U);
-    g.Np = D * g.nwg * g.G * U;
-    return g;
-}
-
-// H a multiple of 16, at most 4 k-blocks per wave (H <= 1024; 5 for GRU / RNN: H <= 1280), both directions of a
-// tile group co-resident, no more tiles per workgroup than the carried-state arrays hold.
-bool rnn_persist16_eligible(const RnnGeom& g16, int B, int n_cus, int* pgroups_out) {
-    if (g16.U != QU || (g16.H % QU) != 0) return false;
-    const int nkb = ceil_div(g16.H, 32), nkw = ceil_div(nkb, QNW);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 5)) return false;
-    if (g16.nwg * g16.D > n_cus) return false;
-    const int ntiles = ceil_div(B, QB);
-    const int pg = std::min(ntiles, n_cus / (g16.nwg * g16.D));
-    if (ceil_div(ntiles, pg) > QMAXZ) return false;
-    if (pgroups_out) *pgroups_out = pg;
-    return true;
-}
-
-// The half-CU (four-wave) variant: its register budget holds 6 + 1 k-blocks per wave for three gates (H <= 896), 4 for an
-// LSTM (H <= 512); at most two tiles per workgroup; one workgroup slot per CU and lane.
-bool rnn_persist16_half_eligible(const RnnGeom& g16, int B, int n_cus, int* pgroups_out) {
-    if (g16.U != QU || (g16.H % QU) != 0) return false;
-    const int nkw = ceil_div(ceil_div(g16.H, 32), 4);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 7)) return false;
-    if (g16.nwg * g16.D > n_cus) return false;
-    const int ntiles = ceil_div(B, QB);
-    const int pg = std::min(ntiles, n_cus / (g16.nwg * g16.D));
-    if (ceil_div(ntiles, pg) > 2) return false;
-    if (pgroups_out) *pgroups_out = pg;
-    return true;
-}
 
 // w_hh [G*H][H] (torch layout) of one direction -> [workgroup][kb][gate][plane][lane][8] fp16 terms (hi, lo * 2^11);
 // lane (u = lane & 15, kg = lane >> 4) element e holds W[gate * H + 16 * wg + u][32 * kb + 8 * kg + e].

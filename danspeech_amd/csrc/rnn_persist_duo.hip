@@ -35,8 +35,8 @@ namespace {
 
 constexpr int DNW = 8;                 // waves per workgroup: two halves of four (K-split inside a half)
 constexpr int DNT = DNW * 64;
-constexpr int DU = 16;                 // hidden units per workgroup
-constexpr int DB = 16;                 // clips per batch tile
+constexpr int DU = kTileUnits;         // hidden units per workgroup
+constexpr int DB = kTileClips;         // clips per batch tile
 constexpr int DRP = 20;                // row pitch (words) of the reduce buffers
 constexpr int DNKR = 6;                // k-blocks of W_hh a wave keeps in registers; a seventh sits in LDS
 constexpr size_t D_LDS = 100 * 1024;   // > half of the CU's LDS (the 8 x 256 registers say "one per CU" as well)
@@ -348,21 +348,6 @@ bool launch_duo(const DuoArgs& a, hipStream_t s, const EvPair& ev) {
 }
 
 }  // namespace
-
-// At least two tiles (17+ clips), the half-CU register budget (GRU / RNN: H <= 896, LSTM: H <= 512), every tile pair of both
-// directions co-resident on `n_cus` CUs (the caller passes one gate lane's CUs first, then the whole device).
-int rnn_persist_duo_pairs(const RnnGeom& g16, int B, int n_cus) {
-    if (g16.U != DU || (g16.H % DU) != 0) return 0;
-    const int nkw = ceil_div(ceil_div(g16.H, 32), 4);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 7)) return 0;
-    const int ntiles = ceil_div(B, DB);
-    if (ntiles < 2) return 0;
-    return std::min((ntiles + 1) / 2, n_cus / (g16.nwg * g16.D));
-}
-
-bool rnn_persist_duo_eligible(const RnnGeom& g16, int B, int n_cus) {
-    return rnn_persist_duo_pairs(g16, B, n_cus) >= std::max(1, (ceil_div(B, DB) + 1) / 2);
-}
 
 bool launch_rnn_persist_duo(const RnnPersist16Launch& p, hipStream_t s) {
     DuoArgs a;

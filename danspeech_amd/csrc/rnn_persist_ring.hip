@@ -42,11 +42,11 @@ namespace dsmi {
 
 namespace {
 
-constexpr int RNT = 512;               // 8 waves: two halves of four (K-split inside a half)
-constexpr int RU = 16;                 // hidden units per half
-constexpr int RB = 16;                 // clips per batch tile
-constexpr int RRP = 20;                // row pitch (words) of the reduce buffers
-constexpr int RMINT = 4;               // schedule length in tiles = tiles a window walks at most: fewer real tiles are padded with phantom
+constexpr int RNT = kRingThreads;      // 8 waves: two halves of four (K-split inside a half)
+constexpr int RU = kTileUnits;         // hidden units per half
+constexpr int RB = kTileClips;         // clips per batch tile
+constexpr int RRP = kRingRedPitch;     // row pitch (words) of the reduce buffers
+constexpr int RMINT = kRingMaxTiles;   // schedule length in tiles = tiles a window walks at most: fewer real tiles are padded with phantom
                                        // ones (the poll of an item comes 2 * NT - 3 slots after its M slot, the signal 3: NT >= 4)
 
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
@@ -500,12 +500,7 @@ unsigned hchs = hchs_, cnts = cnts_, orows = orows_, xrows = xrows_;
     }
 }
 
-size_t ring_lds_bytes(int kind, int nkb) {
-    const int NG = kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1);
-    return (size_t)2 * nkb * 2048 + (size_t)2 * 4 * NG * 16 * RRP * 4 + (size_t)RMINT * RNT * 4 * (kind == DSMI_RNN_LSTM ? 2 : 1) +
-           (size_t)2 * NG * 256 * 4 + RMINT * 16 * 4 + 32 * 4 + 8 * 16 * 8;
-}
-
+// (dynamic LDS of a workgroup: ring_lds_bytes, rnn_plan.h -- the same formula rnn_persist_ring_tiles holds against the CU's LDS)
 template <int KIND>
 bool launch_ring(const RingArgs& a, hipStream_t s, const EvPair& ev) {
     const int nkw = ceil_div(a.nkb, 4);
@@ -553,22 +548,6 @@ bool launch_ring(const RingArgs& a, hipStream_t s, const EvPair& ev) {
 }
 
 }  // namespace
-
-// Tiles one launch of the ring kernel can walk for this shape on `n_cus` CUs (0: not this shape): the 16-unit geometry,
-// W_hh of a half in its four waves' registers (GRU / RNN: H <= 896, LSTM: H <= 512), ring + reduce buffers within the CU's LDS,
-// both directions co-resident.
-int rnn_persist_ring_tiles(const RnnGeom& g16, int B, int n_cus) {
-    if (g16.U != RU || (g16.H % RU) != 0) return 0;
-    const int nkb = ceil_div(g16.H, 32);
-    const int nkw = ceil_div(nkb, 4);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 7)) return 0;
-    if (ring_lds_bytes(g16.kind, nkb) > 160 * 1024) return 0;
-    if (((g16.nwg + 1) / 2) * g16.D > n_cus) return 0;
-    if ((size_t)g16.D * ceil_div(B, RB) * nkb * 2048 * 2 >= (1ull << 31)) return 0;      // packed state below 2 GiB (store offsets, see OOR)
-    return std::min(ceil_div(B, RB), RMINT);
-}
-
-int rnn_persist_ring_cus(const RnnGeom& g16) { return ((g16.nwg + 1) / 2) * g16.D; }
 
 bool launch_rnn_persist_ring(const RnnPersist16Launch& p, hipStream_t s) {
     RingArgs a;

@@ -10,7 +10,7 @@
 // matrix pipe, each with a cell slot of its own -- a slot as long as a GRU cell's dependent chain in ONE wave per SIMD, 0.90 us, of
 // which the partner's 63 MFMAs needed 0.58): 6.4 against 7.2 us per step of a four-tile window of cfgA alone on the chip.  The
 // eight-wave form stays for windows of one or two tiles (this form's phase has no branch: it multiplies phantom tiles like real
-// ones): api.hip picks.  Every form measured on the way, and what bounds this one: profiles/r05_ring_experiments.txt, DESIGN.md 4.
+// ones): rnn_plan.h picks.  Every form measured on the way, and what bounds this one: profiles/r05_ring_experiments.txt, DESIGN.md 4.
 //
 //   * Wave (mh, kh): the 16-unit group mh of the workgroup's two ADJACENT groups (virtual workgroups 2 w and 2 w + 1 of the
 //     16-unit geometry) and the half kh of the k-blocks.  Its W_hh -- up to 14 k-blocks x G gates x 2 planes x 4 registers = 336
@@ -54,9 +54,9 @@ namespace dsmi {
 namespace {
 
 constexpr int XNT = 256;               // 4 waves: (group mh = v & 1, K half kh = v >> 1)
-constexpr int XU = 16;                 // hidden units per group
-constexpr int XB = 16;                 // clips per batch tile
-constexpr int XMAXT = 8;               // tiles a window walks at most
+constexpr int XU = kTileUnits;         // hidden units per group
+constexpr int XB = kTileClips;         // clips per batch tile
+constexpr int XMAXT = kRing4MaxTiles;  // tiles a window walks at most
 
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
@@ -548,11 +548,7 @@ __global__ __launch_bounds__(XNT) void rnn_persist_ring4_kernel(Ring4Args p) {
     }
 }
 
-size_t ring4_lds_bytes(int kind, int nkb) {
-    const int NG = kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1);
-    return (size_t)2 * nkb * 2048 + (size_t)2 * 2 * 2 * NG * 256 * 4 + (size_t)3 * 2 * NG * 256 * 4 + 32 * 4 + 4 * 8 * 8;
-}
-
+// (dynamic LDS of a workgroup: ring4_lds_bytes, rnn_plan.h -- the same formula rnn_persist_ring4_tiles holds against the CU's LDS)
 template <int KIND, int NT>
 bool launch_ring4_nt(const Ring4Args& a, hipStream_t s, const EvPair& ev) {
     const int nkw = ceil_div(a.nkb, 2);
@@ -615,33 +611,6 @@ bool launch_ring4_nt(const Ring4Args& a, hipStream_t s, const EvPair& ev) {
 }
 
 }  // namespace
-
-size_t rnn_persist_ring4_lds(int kind, int nkb) { return ring4_lds_bytes(kind, nkb); }
-
-// Tiles one launch of the kernel can walk for this shape on `n_cus` CUs (0: not this shape): the 16-unit geometry, W_hh of a
-// group's K half in one wave's registers (GRU / RNN: H <= 896, LSTM: H <= 512), ring + reduce buffers within the CU's LDS,
-// both directions co-resident.
-int rnn_persist_ring4_tiles(const RnnGeom& g16, int B, int n_cus) {
-    if (g16.U != XU || (g16.H % XU) != 0) return 0;
-    const int nkb = ceil_div(g16.H, 32);
-    const int nkw = ceil_div(nkb, 2);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 8 : 14)) return 0;
-    // Fewer than four k-blocks per wave (H < 224): NOT this kernel.  Round 6 found that in a pipeline -- several windows of
-    // different handles running at once -- a GRU of 64..192 units comes out with the LAST tile of a window wrong now and then
-    // (tools/exp/debug_short_forms.py: garbage transcripts for the clips of tile 3, nondeterministic, from the third call of a
-    // process on; never alone on the chip, never with the eight-wave form, never from 256 units up in any test or bench run).  The
-    // cause has not been found; the shapes are fenced off (tests/test_gpu_recognizer.py::test_small_models_in_the_pipeline).  The
-    // eight-wave form takes them.  DSMI_RNN_KERNEL=ring4 (tests of the form alone on the chip) still reaches them.
-    static const bool forced = [] { const char* e = std::getenv("DSMI_RNN_KERNEL"); return e && std::string(e) == "ring4"; }();
-    if (nkw < 4 && !forced) return 0;
-    if (ring4_lds_bytes(g16.kind, nkb) > 160 * 1024) return 0;
-    if (((g16.nwg + 1) / 2) * g16.D > n_cus) return 0;
-    if ((size_t)g16.D * ceil_div(B, XB) * nkb * 2048 * 2 >= (1ull << 31)) return 0;      // packed state below 2 GiB (store offsets, see OOR)
-    // tiles per window: four (a 64-clip forward); DSMI_RING_TILES=6|8 lets a window walk more (a chain's hand-off then lies under
-    // five or seven other phases instead of three)
-    static const int most = [] { const char* e = exp_env("DSMI_RING_TILES"); const int v = e ? std::atoi(e) : 4; return v >= 4 && v <= XMAXT ? v : 4; }();
-    return std::min(ceil_div(B, XB), nkw == 14 ? 4 : most);
-}
 
 bool launch_rnn_persist_ring4(const RnnPersist16Launch& p, hipStream_t s) {
     Ring4Args a;

@@ -21,20 +21,6 @@
 
 namespace dsmi {
 
-RnnGeom make_rnn_geom(int kind, int H, int D) {
-    RnnGeom g;
-    g.kind = kind;
-    g.G = kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1);
-    g.H = H;
-    g.U = 8;
-    g.nwg = ceil_div(H, g.U);
-    g.Kp = round_up(H, 8);
-    g.nq = g.Kp / 8;
-    g.D = D;
-    g.Np = D * g.nwg * g.G * g.U;
-    return g;
-}
-
 int rnn_src_row(const RnnGeom& g, int col, int* dir_out) {
     const int GU = g.G * g.U;
     const int per_dir = g.nwg * GU;

@@ -570,14 +570,12 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
             float* cw = b.cwork + (size_t)l * n * Hs;
             bool done = false;
             if (attempt == 0 && m->rnn_mode == 1 && r.whh_sp[0] && rnn_persist_eligible(m->geom, n, m->n_cus)) {
-                RnnPersistLaunch pl;
-                pl.g = m->geom;
-                pl.whh_sp[0] = r.whh_sp[0]; pl.whh_sp[1] = nullptr; pl.bhh[0] = r.bhh[0]; pl.bhh[1] = nullptr;
-                pl.out[0] = out; pl.out[1] = nullptr;
+                RnnPersistLaunch pl = persist_launch(m, l, n, tcmax, 0);      // geometry, weights, test hooks; the pass has buffers of its own:
+                pl.whh_sp[1] = nullptr; pl.bhh[1] = nullptr; pl.out[0] = out; pl.out[1] = nullptr;
                 pl.xp = b.xp; pl.lens_dev = lens_dev + n; pl.hpack_sp = b.hpack_sp; pl.counters = b.cnt; pl.err = b.err;
-                pl.B = n; pl.T = tcmax; pl.h0 = h0; pl.cst = cw;
+                pl.h0 = h0; pl.cst = cw;
                 M_HIP(hipMemsetAsync(b.cnt, 0, sizeof(unsigned) * (size_t)nz * (tcmax + 1), s));
-                done = stream_persist_layer(m, l, pl, s);
+                done = stream_persist_layer(m, pl, s);
                 persisted = persisted || done;
             }
             if (!done) {

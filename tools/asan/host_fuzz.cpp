@@ -3,6 +3,9 @@
 // "a damaged file is refused or read, never a stray access".  tests/test_asan_host.py feeds it a few hundred mutated files.
 //   host_fuzz lm FILE...      load each file (ARPA text or KenLM binary); when it loads, look n-grams up and score sequences
 //   host_fuzz plan SEED N     random shard plans and phrase gates checked against their definitions
+//   host_fuzz rnnplan FILE    the recurrent-layer plan (rnn_plan.h) of every input row of FILE, one line of text per row, each plan
+//                             checked against the invariants below; rows: kind D H B inflight ring_windows lane KERNEL MODE DENSE n_cus
+//   host_fuzz rnnplan grid    the invariants over the grid of 29 315 520 inputs that the plan was compared on with the code it replaced
 #define __host__
 #define __device__
 #include <cmath>
@@ -15,6 +18,7 @@
 #include "lm.cpp.inc"
 #include "lm_klm.cpp.inc"
 #include "host_logic.h"
+#include "rnn_plan.h"
 
 using namespace dsmi;
 
@@ -87,9 +91,129 @@ static int run_plan(int argc, char** argv) {
     return 0;
 }
 
+
+// ---- rnnplan: one row of input as the environment and the caller's hints would give it -----------------------------------------
+// kernel: DSMI_RNN_KERNEL (- unset, duo, ring, ring4, ring8); mode: DSMI_RNN_MODE (- unset, steps, persist8); dense: DSMI_DENSE_MODE
+// (split, f32).  The fence around the four-wave form's small shapes is lifted as in a process STARTED with DSMI_RNN_KERNEL=ring4.
+static RnnPlanInput rnn_plan_input(int kind, int D, int H, int B, int inflight, int ring_windows, int lane, const std::string& kernel,
+                                   const std::string& mode, const std::string& dense, int n_cus) {
+    RnnPlanInput in;
+    in.geom = make_rnn_geom(kind, H, D);
+    in.geom16 = make_rnn_geom_u(kind, H, D, 16);
+    in.have16 = H % 16 == 0;
+    in.split16 = dense != "f32";
+    in.B = B; in.n_cus = n_cus; in.inflight = inflight; in.ring_windows = ring_windows; in.lane = lane;
+    in.rnn_mode = mode == "steps" ? 0 : 1;
+    in.persist_gen = mode == "persist8" ? 1 : 2;
+    in.rnn_kernel = kernel == "duo" ? 1 : (kernel == "ring" ? 2 : 0);
+    in.ring8 = kernel == "ring8";
+    in.ring4 = in.ring4_small_shapes = kernel == "ring4";
+    return in;
+}
+
+// "x16|" or "x8|", then per launch "kernel at n nwin gate slot0 nslots cus ticket part;" (gate "held": under the previous launch's turn)
+static std::string rnn_plan_text(const RnnPlan& plan) {
+    static const char* const names[] = {"steps", "persist8", "p16w8", "p16w4", "duo", "ring8", "ring4"};
+    std::string out = plan.x16 ? "x16|" : "x8|";
+    for (int i = 0; i < plan.launches.size(); ++i) {
+        const RnnLaunch& l = plan.launches[i];
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "%s %d %d %d %s %d %d %d %d %.17g;", names[l.kernel], l.at, l.n, l.nwin,
+                      l.join ? "held" : (l.gate == GATE_RING ? "ring" : (l.gate == GATE_LANES ? "lane" : "none")), l.slot0, l.nslots, l.cus, l.ticket, l.part);
+        out += buf;
+    }
+    return out;
+}
+
+// Every real tile, tile pair or direction in exactly one launch; the gate slots within what the device holds; windows side by side
+// within the device's CUs; tiles per window within the form's cap; the launches' shares sum to 1.  0, or the number of the broken rule.
+static int rnn_plan_check(const RnnPlanInput& in, const RnnPlan& plan) {
+    if (plan.launches.size() < 1) return 1;
+    const int ntiles = ceil_div(in.B, kTileClips), k0 = plan.launches[0].kernel;
+    const int items = k0 == RNN_RING8 || k0 == RNN_RING4 ? ntiles : (k0 == RNN_DUO ? (ntiles + 1) / 2 : (k0 == RNN_PERSIST8 ? in.geom.D : 1));
+    std::vector<int> seen((size_t)items, 0);
+    double parts = 0;
+    if (plan.x16 != rnn_kernel_is16(k0)) return 2;
+    for (int i = 0; i < plan.launches.size(); ++i) {
+        const RnnLaunch& l = plan.launches[i];
+        const bool ring = l.kernel == RNN_RING8 || l.kernel == RNN_RING4;
+        if (ring != (k0 == RNN_RING8 || k0 == RNN_RING4) || (!ring && l.kernel != k0)) return 3;      // one family per layer
+        parts += l.part;
+        if (ring) {
+            if (l.n < 1 || l.n > (l.kernel == RNN_RING8 ? kRingMaxTiles : kRing4MaxTiles) || l.nwin < 1) return 4;
+            if (l.kernel == RNN_RING8 ? l.n > rnn_persist_ring_tiles(in.geom16, in.B, l.cus)
+                                      : l.n > rnn_persist_ring4_tiles(in.geom16, in.B, l.cus, in.ring4_small_shapes, in.ring4_most)) return 4;
+            for (int w = 0; w < l.nwin; ++w)
+                for (int t = l.at + w * l.n; t < std::min(l.at + (w + 1) * l.n, ntiles); ++t) seen[(size_t)t] += 1;
+            const int held = std::min(kRingSlots, l.cus > 0 ? in.n_cus / l.cus : 0);
+            if (l.gate != GATE_RING || l.nslots != l.nwin || l.slot0 < 0 || l.slot0 + l.nslots > held) return 5;
+            if (l.cus != rnn_persist_ring_cus(in.geom16) || l.nwin * l.cus > in.n_cus) return 6;
+            if (l.ticket < 0 || l.ticket + 2 * l.nwin > 2 * ntiles + 2) return 7;      // the ticket words api.hip zeroes behind the counters
+        } else if (l.kernel != RNN_STEPS) {
+            if (l.gate != GATE_LANES || l.slot0 < 0 || l.slot0 + l.nslots > kMaxLanes || l.nslots < 1) return 5;
+            if (l.kernel == RNN_DUO || l.kernel == RNN_PERSIST8) {
+                if (l.n < 1) return 4;
+                for (int i = l.at; i < l.at + l.n; ++i) { if (i < 0 || i >= items) return 8; seen[(size_t)i] += 1; }
+                if (l.kernel == RNN_DUO && l.n * in.geom16.nwg * in.geom16.D > in.n_cus) return 6;
+                if (l.kernel == RNN_PERSIST8 && l.n * in.geom.nwg > in.n_cus) return 6;
+            } else {
+                if (l.n < 1 || l.n * in.geom16.nwg * in.geom16.D > in.n_cus) return 6;
+                if (ceil_div(ntiles, l.n) > (l.kernel == RNN_PERSIST16_HALF ? 2 : kPersist16MaxTiles)) return 4;
+                seen[0] += 1;
+            }
+        } else {
+            if (l.gate != GATE_NONE) return 5;
+            seen[0] += 1;
+        }
+    }
+    for (int c : seen) if (c != 1) return 8;
+    if (std::fabs(parts - 1.0) > 1e-12) return 9;
+    return 0;
+}
+
+static int run_rnnplan(int argc, char** argv) {
+    if (argc < 3) return 2;
+    static const char* const kernels[] = {"-", "duo", "ring", "ring4", "ring8"};
+    static const char* const modes[] = {"-", "steps", "persist8"};
+    static const char* const denses[] = {"split", "f32"};
+    if (!std::strcmp(argv[2], "grid")) {
+        long points = 0;
+        static const int Bs[] = {1, 16, 17, 20, 32, 33, 48, 56, 64, 70, 96, 128, 256};
+        std::vector<int> Hs;
+        for (int H = 16; H <= 1344; H += 16) Hs.push_back(H);      // every width the 16-unit kernels may take, and three they do not
+        for (int H : {100, 904, 1288}) Hs.push_back(H);
+        for (int kind = 0; kind < 3; ++kind) for (int D = 1; D <= 2; ++D) for (int H : Hs) for (int B : Bs)
+        for (int inflight : {1, 2, 4}) for (int rw : {0, 1, 2, 4}) for (int lane = 0; lane < 4; ++lane)
+        for (const char* k : kernels) for (const char* mo : modes) for (const char* de : denses) for (int n_cus : {256, 128, 64}) {
+            const RnnPlanInput in = rnn_plan_input(kind, D, H, B, inflight, rw, lane, k, mo, de, n_cus);
+            const int bad = rnn_plan_check(in, plan_rnn_layer(in));
+            if (bad) { std::fprintf(stderr, "rule %d broken at %d %d %d %d %d %d %d %s %s %s %d\n", bad, kind, D, H, B, inflight, rw, lane, k, mo, de, n_cus); return 6; }
+            ++points;
+        }
+        std::printf("%ld plans ok\n", points);
+        return 0;
+    }
+    std::FILE* f = std::fopen(argv[2], "r");
+    if (!f) return 2;
+    int kind, D, H, B, inflight, rw, lane, n_cus;
+    char k[16], mo[16], de[16];
+    int rc = 0;
+    while (std::fscanf(f, "%d %d %d %d %d %d %d %15s %15s %15s %d", &kind, &D, &H, &B, &inflight, &rw, &lane, k, mo, de, &n_cus) == 11) {
+        if (kind < 0 || kind > 2 || D < 1 || D > 2 || H < 1 || H > 4096 || B < 1 || B > 4096 || n_cus < 1) { rc = 2; break; }
+        const RnnPlanInput in = rnn_plan_input(kind, D, H, B, inflight, rw, lane, k, mo, de, n_cus);
+        const RnnPlan plan = plan_rnn_layer(in);
+        const int bad = rnn_plan_check(in, plan);
+        if (bad) { std::fprintf(stderr, "rule %d broken\n", bad); rc = 6; break; }
+        std::printf("%s\n", rnn_plan_text(plan).c_str());
+    }
+    std::fclose(f);
+    return rc;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]]\n");
+    if (argc >= 3 && !std::strcmp(argv[1], "rnnplan")) return run_rnnplan(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid\n");
     return 2;
 }
