@@ -113,6 +113,7 @@ _PROTOS = {
     "dsmi_reset_kernel_stats": (C.c_int, [_vp]),
     "dsmi_debug_persist_stamps": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64]),
     "dsmi_debug_step_stamps": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64]),
+    "dsmi_debug_last_rnn_plan": (C.c_int, [_vp, C.c_char_p, C.c_int64]),
     "dsmi_last_forward_stats": (C.c_int, [_vp, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dsmi_lm_open": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "dsmi_lm_close": (None, [_vp]),
@@ -324,6 +325,23 @@ class NativeModel:
 
     def recompute_count(self):
         return int(lib().dsmi_recompute_count(self._h))
+
+    RNN_LAUNCH_FIELDS = ("kernel", "at", "n", "nwin", "gate", "slot0", "nslots", "cus", "ticket", "part")
+
+    def last_rnn_plan(self):
+        """``(x16, [launch dict])``: the launches the last recurrent layer of this handle actually made, after any fallback
+        (``dsmi_debug_last_rnn_plan``; csrc/rnn_plan.h ``RnnLaunch``).  ``kernel`` is one of steps, persist8, p16w8, p16w4, duo,
+        ring8, ring4.  ``(False, [])`` before the first layer; of a layer of more than eight launches, the first eight."""
+        buf = C.create_string_buffer(1400)
+        rc = lib().dsmi_debug_last_rnn_plan(self._h, buf, len(buf))
+        if rc < 0:
+            self._check(rc)
+        order, _, rest = buf.value.decode().partition("|")
+        launches = []
+        for item in rest.split(";")[:-1]:
+            launches.append({k: (v if k in ("kernel", "gate") else (float(v) if k == "part" else int(v)))
+                             for k, v in zip(self.RNN_LAUNCH_FIELDS, item.split())})
+        return order == "x16", launches
 
     def set_inflight(self, batches):
         """How many batches the caller keeps in flight on this device (one handle + stream each): 2 selects the

@@ -750,6 +750,7 @@ static bool run_rnn_plan(dsmi_model* m, const RnnPlan& plan, int l, int B, int T
             st.ev = timer_arm(m, KK_STEP, (step & 7) == 3, 2.0 * Dd * GH * H * act, 4.0 * Dd * (GH * H + (double)B * (GH + 2.0 * H)));
             launch_rnn_step(st, s);
         }
+        m->last_plan_x16 = false; m->last_plan_n = 1; m->last_plan[0] = plan.launches[0];
         return true;
     }
     RnnPersist16Launch p16;      // a plan's launches are of one family: the 16-unit kernels or the first generation
@@ -792,6 +793,10 @@ static bool run_rnn_plan(dsmi_model* m, const RnnPlan& plan, int l, int B, int T
             turn.unlock();
         }
     }
+    if (ok) {      // what dsmi_debug_last_rnn_plan reports: only a plan that ran whole
+        m->last_plan_x16 = plan.x16; m->last_plan_n = plan.launches.size();
+        for (int i = 0; i < std::min(m->last_plan_n, (int)dsmi_model::kLastPlanKept); ++i) m->last_plan[i] = plan.launches[i];
+    }
     return ok;
 }
 
@@ -823,7 +828,7 @@ static void run_rnn_layer(dsmi_model* m, int l, GemmLaunch gl, int B, int To, in
         plan = plan_rnn_layer(in);
         if (run_rnn_plan(m, plan, l, B, To, dst, sumlen, s)) return;
     }
-    in.rnn_mode = 0;      // then: per step
+    in.rnn_mode = 0;      // then: per step (never refused: dsmi_debug_last_rnn_plan always holds THIS layer's launches, not the one before's)
     (void)run_rnn_plan(m, plan_rnn_layer(in), l, B, To, dst, sumlen, s);
 }
 
@@ -1113,6 +1118,21 @@ bool stream_persist_layer(dsmi_model* m, const RnnPersistLaunch& pl, hipStream_t
 }
 
 extern "C" int dsmi_recompute_count(const dsmi_model* m) { return m ? m->recomputed : DSMI_ERR_INVALID; }
+
+extern "C" int dsmi_debug_last_rnn_plan(const dsmi_model* m, char* buf, int64_t capacity) {
+    if (!m || !buf || capacity < 1) return DSMI_ERR_INVALID;
+    buf[0] = 0;
+    if (m->last_plan_n == 0) return 0;
+    std::string text = m->last_plan_x16 ? "x16|" : "x8|";
+    for (int i = 0; i < std::min(m->last_plan_n, (int)dsmi_model::kLastPlanKept); ++i) {
+        char one[160];
+        rnn_launch_text(m->last_plan[i], one, sizeof one);
+        text += one;
+    }
+    if ((int64_t)text.size() + 1 > capacity) return DSMI_ERR_INVALID;
+    std::memcpy(buf, text.c_str(), text.size() + 1);
+    return m->last_plan_n;
+}
 
 extern "C" int dsmi_model_set_inflight(dsmi_model* m, int batches) {
     if (!m || batches < 1) return DSMI_ERR_INVALID;

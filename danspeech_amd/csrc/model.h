@@ -86,6 +86,12 @@ struct dsmi_model {
     FwdSlot fwd[kFwdRing];
     int fwd_head = 0, fwd_count = 0;   // oldest uncollected slot, number of uncollected forwards
     int recomputed = 0;            // forwards recomputed on the per-step path so far
+    // dsmi_debug_last_rnn_plan: the launches the last recurrent layer made (run_rnn_plan, after any refusal fallback).  A fixed
+    // array and a count, so that recording allocates nothing; launches beyond the array are counted only.
+    static constexpr int kLastPlanKept = 8;
+    dsmi::RnnLaunch last_plan[kLastPlanKept];
+    int last_plan_n = 0;
+    bool last_plan_x16 = false;
     unsigned spin_limit = dsmi::kPersistSpinLimit;   // DSMI_DEBUG_SPIN_LIMIT
     int drop_layer = -1, drop_wg = -1, drop_step = -1;   // DSMI_DEBUG_DROP_SIGNAL=layer:workgroup:step (tests: force a timeout)
     int lanes = 2, lane = 0;       // persistent kernels of a handle whose caller keeps two batches in flight take half of the CUs, on this lane

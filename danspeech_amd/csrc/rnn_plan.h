@@ -6,6 +6,7 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdio>
 #include <vector>
 
 #include "../../include/dsmi.h"
@@ -196,6 +197,15 @@ struct RnnLaunch {
     int ticket = 0;         // ring kernels: offset (words) of this launch's direction tickets behind the hand-off counters
     double part = 1.0;      // its share of the layer's FLOPs and bytes
 };
+
+// One launch as text, "kernel at n nwin gate slot0 nslots cus ticket part;" (gate "held": under the previous launch's turn): what
+// host_fuzz rnnplan prints per launch behind "x16|" or "x8|", and what dsmi_debug_last_rnn_plan reports of the launches a layer made.
+// Returns the characters written (snprintf's count: at least `cap` when the buffer is too small).
+inline int rnn_launch_text(const RnnLaunch& l, char* buf, size_t cap) {
+    static const char* const names[] = {"steps", "persist8", "p16w8", "p16w4", "duo", "ring8", "ring4"};
+    return std::snprintf(buf, cap, "%s %d %d %d %s %d %d %d %d %.17g;", names[l.kernel], l.at, l.n, l.nwin,
+                         l.join ? "held" : (l.gate == GATE_RING ? "ring" : (l.gate == GATE_LANES ? "lane" : "none")), l.slot0, l.nslots, l.cus, l.ticket, l.part);
+}
 
 struct RnnPlanInput {
     RnnGeom geom{}, geom16{};

@@ -319,6 +319,13 @@ int dsmi_reset_kernel_stats(dsmi_model* m);
 int dsmi_debug_persist_stamps(dsmi_model* m, int layer, int B, int T_out, uint64_t* stamps_host, int64_t n_words);
 int dsmi_debug_step_stamps(dsmi_model* m, int layer, int B, int T_out, int step, uint64_t* stamps_host,
                            int64_t n_words);
+/* Which kernels ran: the launches the handle's LAST recurrent layer (of dsmi_forward, dsmi_rnn_layer or a recompute) actually made,
+ * after any fallback that followed a launcher's refusal, as text: "x16|" or "x8|" (the column order of the x-projection), then per
+ * launch "kernel at n nwin gate slot0 nslots cus ticket part;" with kernel one of steps, persist8, p16w8, p16w4, duo, ring8, ring4
+ * (csrc/rnn_plan.h: RnnLaunch; the format of tools/asan/host_fuzz.cpp rnnplan).  Returns the number of launches the layer made (0
+ * and an empty string before the first layer); the text holds the first eight of them.  Recording allocates nothing.
+ * DSMI_ERR_INVALID: null argument or a buffer too small (1400 bytes hold any answer). */
+int dsmi_debug_last_rnn_plan(const dsmi_model* m, char* buf, int64_t capacity);
 double dsmi_stage_time_us(const dsmi_model* m, int stage);
 /* Kernel launches the last dsmi_forward issued for stage 2 (recurrent steps) and their
  * summed algorithmic FLOPs (SURVEY 8d formula, recurrent part), for roofline maths. */

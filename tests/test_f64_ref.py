@@ -1,0 +1,67 @@
+"""tests/_f64_ref.py -- the float64 BatchRNN layer the layer-level accuracy tests compare the kernels with -- pinned on the CPU: against
+the fp32 oracle (oracle/model.py, independent code) on seeded cases of all three kinds, and against the reference's own outputs
+(tests/golden/g3_batch_rnn.npz, all 12 tags).
+
+The bounds are float32 noise, not agreement of two float64 programs: the oracle rounds every intermediate to float32.  Measured
+here (numpy 2, OpenBLAS; printed by each test): seeded cases 1.1e-7 .. 8.7e-7, held to 2e-6 -- outputs are sums of two values
+in (-1, 1), one float32 ulp there is 1.2e-7, and a chain of T <= 23 steps of K <= 96 accumulates a few of them; a semantic
+difference (gate order, a mask, the start of the reverse chain, the BatchNorm's epsilon) is 1e-3 or more.  The goldens (torch's
+float32 kernels): 6.5e-8 .. 3.8e-7, held to the 2e-6 tests/test_oracle_golden.py holds the oracle to."""
+import numpy as np
+import pytest
+
+import _f64_ref as f64
+from danspeech_amd import synthetic as syn
+from oracle import model as om
+
+# (H, lens): ragged with a clip of length 1 and one of length T; all equal; T = 1; one clip
+SHAPES = [(24, [23, 23, 17, 9, 2, 1]), (96, [12, 12, 12]), (40, [1, 1]), (16, [7])]
+
+
+@pytest.mark.parametrize("kind", ["gru", "lstm", "rnn"])
+@pytest.mark.parametrize("bidir", [True, False])
+@pytest.mark.parametrize("layer", [0, 1])
+def test_against_the_fp32_oracle(kind, bidir, layer):
+    worst = 0.0
+    for k, (H, lens) in enumerate(SHAPES):
+        sd = syn.make_state_dict(1, kind, H, 2, bidirectional=bidir, context=3, seed=40 + k, ih_gain=1.0 + 2.0 * (k % 2),
+                                 sample_rate=100, window_size=0.02)      # n_freq 2: layer 0 reads 32 features
+        lens = np.array(lens)
+        T, B = int(lens[0]), len(lens)
+        I = sd["rnns.%d.rnn.weight_ih_l0" % layer].shape[1]
+        x = (np.random.default_rng(50 + k).standard_normal((T, B, I)) * 0.7).astype(np.float32)
+        ref = f64.batch_rnn(sd, layer, kind, x, lens, bidir, batch_norm=layer > 0)
+        o32 = om.batch_rnn(sd, layer, kind, x, lens, bidir, layer > 0)
+        assert ref.dtype == np.float64 and ref.shape == o32.shape == (T, B, H)
+        for b, L in enumerate(lens):
+            assert not ref[L:, b].any()
+            assert np.abs(ref[:L, b]).min() > 0      # ... and nothing inside a clip is left unwritten
+        worst = max(worst, float(np.abs(o32 - ref).max()))
+    print("%s bidir=%d layer=%d: max |fp32 oracle - f64| = %.3g" % (kind, bidir, layer, worst))
+    assert worst <= 2e-6
+
+
+@pytest.mark.parametrize("kind", ["gru", "lstm", "rnn"])
+@pytest.mark.parametrize("bn", [0, 1])
+@pytest.mark.parametrize("bidir", [0, 1])
+def test_against_the_reference_goldens(golden, kind, bn, bidir):
+    g = golden("g3_batch_rnn")
+    tag = "%s_bn%d_bi%d" % (kind, bn, bidir)
+    sd = {"rnns.0." + k.split("__", 1)[1]: g[k] for k in g.files if k.startswith("w_%s__" % tag)}
+    y = f64.batch_rnn(sd, 0, kind, g["x_bn%d" % bn], g["lens"], bool(bidir), bool(bn))
+    err = float(np.abs(y - g["y_" + tag]).max())
+    print("%s: max |f64 - golden| = %.3g" % (tag, err))
+    assert err <= 2e-6
+    for b, L in enumerate(g["lens"]):
+        assert not y[L:, b].any()
+
+
+def test_reverse_chain_starts_at_the_clips_last_frame():
+    """A clip shorter than T, reverse direction alone: equal to the same clip run by itself at its own length."""
+    sd = syn.make_state_dict(1, "gru", 16, 2, seed=7, sample_rate=100, window_size=0.02)
+    x = np.random.default_rng(8).standard_normal((9, 2, 16)).astype(np.float32)
+    w = f64.layer_weights(sd, 1, True)
+    both = f64.direction("gru", x.astype(np.float64), [9, 4], *w, reverse=True)
+    alone = f64.direction("gru", x[:4, 1:].astype(np.float64), [4], *w, reverse=True)
+    # (two float64 programs: BLAS may sum a batch of two and a batch of one in different orders, nothing more)
+    assert np.abs(both[:4, 1] - alone[:, 0]).max() < 1e-14 and not both[4:, 1].any()

@@ -111,15 +111,12 @@ static RnnPlanInput rnn_plan_input(int kind, int D, int H, int B, int inflight, 
     return in;
 }
 
-// "x16|" or "x8|", then per launch "kernel at n nwin gate slot0 nslots cus ticket part;" (gate "held": under the previous launch's turn)
+// "x16|" or "x8|", then per launch "kernel at n nwin gate slot0 nslots cus ticket part;" (rnn_launch_text, rnn_plan.h)
 static std::string rnn_plan_text(const RnnPlan& plan) {
-    static const char* const names[] = {"steps", "persist8", "p16w8", "p16w4", "duo", "ring8", "ring4"};
     std::string out = plan.x16 ? "x16|" : "x8|";
     for (int i = 0; i < plan.launches.size(); ++i) {
-        const RnnLaunch& l = plan.launches[i];
         char buf[160];
-        std::snprintf(buf, sizeof buf, "%s %d %d %d %s %d %d %d %d %.17g;", names[l.kernel], l.at, l.n, l.nwin,
-                      l.join ? "held" : (l.gate == GATE_RING ? "ring" : (l.gate == GATE_LANES ? "lane" : "none")), l.slot0, l.nslots, l.cus, l.ticket, l.part);
+        rnn_launch_text(plan.launches[i], buf, sizeof buf);
         out += buf;
     }
     return out;
