@@ -38,7 +38,9 @@ class _StreamingSession(object):
     """Running state of one utterance that arrives in parts (reference DanSpeechRecognizer.py:97-216): the text so
     far, the model outputs of every part (for a final pass of the language-model decoder) and, when a secondary
     model gives the final text, the spectrograms of every part.  With ``lm_partials`` also the utterance's beam search,
-    carried from part to part (a ``NativeBeamStream`` of ``beam_decoder``), and its best text after the last part."""
+    carried from part to part (a ``NativeBeamStream`` of ``beam_decoder``), and its best text after the last part.  A session
+    whose source has another rate than the model's owns a ``NativeResampler`` (``resampler``; ``source`` = (rate, method)); the
+    converted samples that a pass did not take wait in ``pending`` (a float64 CUDA tensor)."""
 
     def __init__(self, secondary_model, string_parts, lm_partials=False):
         self.secondary_model = secondary_model
@@ -46,6 +48,8 @@ class _StreamingSession(object):
         self.lm_partials = lm_partials
         self.beam = None
         self.beam_decoder = None
+        self.resampler = None
+        self.source = None
         self.clear()
 
     def clear(self):
@@ -53,13 +57,36 @@ class _StreamingSession(object):
         self.outputs = []
         self.spectrograms = []
         self.beam_text = None
+        self.pending = None
         if self.beam is not None:
             self.beam.reset()
+        if self.resampler is not None:
+            self.resampler.reset()
+
+    def set_source(self, parser, sample_rate, resample):
+        """The rate of the parts to come (None, or the model's own rate: they are taken as they are) and how to convert;
+        ``parser``: the streaming parser whose frontend the resampler belongs to."""
+        from . import _native
+        if resample not in _native.RESAMPLE_METHODS:
+            raise ValueError("resample method must be one of %s" % sorted(_native.RESAMPLE_METHODS))
+        source = None if sample_rate is None or int(sample_rate) == int(parser.sampling_rate) else (int(sample_rate), resample)
+        if source == self.source:
+            return
+        if self.resampler is not None:
+            self.resampler.close()
+        self.resampler, self.source, self.pending = None, source, None
+        if source is not None:
+            # ratecv works on integers of a sample width: int16, as everywhere in the package; the polyphase filter takes float64,
+            # which holds int16 / float32 sources exactly
+            self.resampler = _native.NativeResampler(parser._frontend(), source[0], resample, dtype=np.int16 if resample == "ratecv" else np.float64)
 
     def close(self):
         if self.beam is not None:
             self.beam.close()
             self.beam = None
+        if self.resampler is not None:
+            self.resampler.close()
+            self.resampler = None
 
     def extend_text(self, piece):
         """Append a part's greedy text; a part that starts with the character the text ends with continues that
@@ -726,8 +753,11 @@ class DanSpeechRecognizer(object):
         return res
 
     # ---- utterances that arrive in parts ----------------------------------------------------------------------------
-    def enable_streaming(self, secondary_model=None, return_string_parts=True, lm_partials=False):
-        """Streaming mode.  ``lm_partials=True`` (needs a language-model decoder, else ``ValueError``) carries the beam search
+    def enable_streaming(self, secondary_model=None, return_string_parts=True, lm_partials=False, sample_rate=None, resample="polyphase"):
+        """Streaming mode.  ``sample_rate``: the rate of the parts ``streaming_transcribe`` will be given when it is not the
+        model's (telephony's 8 kHz, a sound card's 44.1 or 48 kHz): each part is then converted on the GPU as it arrives
+        (``resample``: "polyphase" or "ratecv"), with the state carried from part to part, so that the converted parts are bit
+        for bit the conversion of the whole utterance.  ``lm_partials=True`` (needs a language-model decoder, else ``ValueError``) carries the beam search
         from part to part: every middle part then returns the best beam's text of the WHOLE utterance so far -- language-model
         hypotheses revise earlier words, so ``return_string_parts`` does not apply to them -- and the final text, when no
         secondary model gives it, comes from the carried search (equal to the full decode it replaces).  The running greedy
@@ -742,6 +772,11 @@ class DanSpeechRecognizer(object):
         self._session = _StreamingSession(secondary_model or None, bool(return_string_parts), bool(lm_partials))
         self.greedy_decoder = GreedyDecoder(labels=self.labels, blank_index=self.labels.index('_'))
         self.audio_parser = InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index())
+        self.set_streaming_source(sample_rate, resample)
+
+    def set_streaming_source(self, sample_rate=None, resample="polyphase"):
+        """The rate of the parts ``streaming_transcribe`` is given from now on (see ``enable_streaming``); None: the model's."""
+        self._session.set_source(self.audio_parser, sample_rate, resample)
 
     def disable_streaming(self, keep_secondary_model=False):
         self.audio_parser = SpectrogramAudioParser(self.audio_config, device=self._device_index())
@@ -781,20 +816,71 @@ class DanSpeechRecognizer(object):
         ses.clear()
         return text
 
-    def new_streaming_session(self):
+    def new_streaming_session(self, sample_rate=None, resample="polyphase"):
         """A session of its own for ``streaming_transcribe_many``: its parser, its ``dsmi_stream`` handle on the streaming
         model and its running text, outputs and spectrograms; the secondary model and string-parts setting are those of
-        ``enable_streaming``."""
+        ``enable_streaming``.  ``sample_rate`` / ``resample``: the rate of THIS session's source when it is not the model's
+        (sessions of different rates advance together)."""
         from . import _native
         if self._session is None or not isinstance(self.audio_parser, InferenceSpectrogramAudioParser):
             raise RuntimeError("call enable_streaming first")
         native = getattr(self.model, "_native", None)
         if native is None:
             raise RuntimeError("the streaming model runs only on an MI355X: call model.to('cuda') first (no CPU path)")
+        state = _StreamingSession(self._session.secondary_model, self._session.string_parts, self._session.lm_partials)
+        # the resamplers of all sessions belong to ONE frontend (the engine's streaming parser's): one push_many serves them all
+        state.set_source(self.audio_parser, sample_rate, resample)
         return StreamingSessionHandle(InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index()),
-                                      _native.NativeStream(native),
-                                      _StreamingSession(self._session.secondary_model, self._session.string_parts,
-                                                        self._session.lm_partials))
+                                      _native.NativeStream(native), state)
+
+    def _convert_parts(self, states, parts, flush, take):
+        """The parts of the sessions whose source has another rate, converted: one upload of all of them, one
+        ``NativeResampler.push_many``, nothing synchronised.  -> ``parts`` with those entries replaced by float64 CUDA tensors
+        at the model's rate.  ``flush[k]``: session k's source ends with this part; ``take[k]``: how many converted samples
+        the session hands on now (None: all it has) -- the rest waits in the session for its next part.  Everything that can
+        refuse the call (a ratecv part that is not int16, a ``take`` beyond what is final) does so before any session moves; for
+        a session that does not convert, ``take`` can only be the part's own length."""
+        import torch
+        from . import _native
+        for k, ses in enumerate(states):
+            if ses.resampler is None and take[k] is not None and int(take[k]) != len(parts[k]):
+                raise ValueError("session %d takes its parts as they are: take must be the part's length (%d), not %d"
+                                 % (k, len(parts[k]), int(take[k])))
+        due = [k for k, ses in enumerate(states) if ses.resampler is not None]
+        if not due:
+            return parts
+        chunks, offs, size = [], [], 0
+        for k in due:
+            a = np.asarray(parts[k]).reshape(-1)
+            if states[k].source[1] == "ratecv" and a.dtype != np.int16:
+                if not np.array_equal(a, np.clip(np.round(a), -32768, 32767)):
+                    raise ValueError("resample='ratecv' needs int16 samples (or float arrays holding int16 integers, as load_audio "
+                                     "returns them for 16-bit files)")
+                a = a.astype(np.int16)
+            elif states[k].source[1] != "ratecv":
+                a = a.astype(np.float64, copy=False)
+            have = (0 if states[k].pending is None else states[k].pending.numel()) + states[k].resampler._due(len(a), bool(flush[k]))
+            if take[k] is not None and int(take[k]) > have:
+                raise ValueError("session %d: %d converted samples asked for, %d are final" % (k, int(take[k]), have))
+            a = np.ascontiguousarray(a).view(np.uint8)
+            chunks.append(a)
+            offs.append(size)
+            size += (len(a) + 7) & ~7                  # every chunk starts on 8 bytes
+        host = np.zeros(max(size, 8), dtype=np.uint8)
+        for a, o in zip(chunks, offs):
+            host[o:o + len(a)] = a
+        pcm = torch.from_numpy(host).to("cuda:%d" % self._device_index())
+        outs = _native.NativeResampler.push_many([states[k].resampler for k in due], [pcm[o:o + len(a)] for a, o in zip(chunks, offs)],
+                                                 [bool(flush[k]) for k in due])
+        parts = list(parts)
+        for k, out in zip(due, outs):
+            ses = states[k]
+            if ses.pending is not None:
+                out = torch.cat((ses.pending, out))
+            n = out.numel() if take[k] is None else int(take[k])          # (<= out.numel(): checked before the push)
+            ses.pending = out[n:] if n < out.numel() else None
+            parts[k] = out[:n]
+        return parts
 
     def _advance_lm_partials(self, items):
         """lm_partials: advance the carried beam searches of several sessions in ONE launch, [(session state, this part's
@@ -821,16 +907,22 @@ class DanSpeechRecognizer(object):
         for (ses, _), s in zip(items, strings):
             ses.beam_text = s[0]
 
-    def streaming_transcribe_many(self, sessions, recordings, is_last, is_first):
+    def streaming_transcribe_many(self, sessions, recordings, is_last, is_first, take=None, flush=None):
         """``streaming_transcribe`` for several sessions (``new_streaming_session``) at once, each on its next part of its own
         utterance; the parts' spectrograms and the model pass run batched over all sessions.  -> one string per session, each
-        what ``streaming_transcribe`` returns for that session alone."""
+        what ``streaming_transcribe`` returns for that session alone.
+        The parts of sessions with a ``sample_rate`` are at that rate: they are uploaded once and converted in ONE
+        ``push_many``; the session then goes on with what the conversion has final.  A caller that schedules passes in
+        model-rate samples (``Recognizer.stream_recordings``) says with ``take[k]`` how many converted samples pass k consists of
+        (the rest waits in the session) and with ``flush[k]`` that session k's SOURCE ends with this part (default: ``is_last``)."""
         from . import _native
         n = len(sessions)
         if not (len(recordings) == len(is_last) == len(is_first) == n):
             raise ValueError("sessions, recordings, is_last and is_first must have one entry per session")
         if len(set(id(s) for s in sessions)) != n:
             raise ValueError("a session appears twice in one call")
+        recordings = self._convert_parts([s.state for s in sessions], recordings, is_last if flush is None else flush,
+                                         [None] * n if take is None else take)
         spects = InferenceSpectrogramAudioParser.parse_audio_many([s.parser for s in sessions], recordings, is_last)
         run = [k for k in range(n) if len(spects[k]) != 0]
         for k in run:
@@ -864,11 +956,14 @@ class DanSpeechRecognizer(object):
                 said.append(self._final_text(ses) if len(ses.text) > 1 else "")
         return said
 
-    def streaming_transcribe(self, recording, is_last, is_first):
+    def streaming_transcribe(self, recording, is_last, is_first, take=None, flush=None):
         """One part of an utterance through the streaming model.  Returns this part's text (or the whole text so far
         when string parts are off); on the first part nothing (the lookahead is filling); on the last part the final
-        text of the utterance, provided more than one character was recognised."""
+        text of the utterance, provided more than one character was recognised.  With a ``sample_rate``
+        (``enable_streaming``) the part is at that rate and is converted first; ``take`` / ``flush`` as in
+        ``streaming_transcribe_many``."""
         ses = self._session
+        recording = self._convert_parts([ses], [recording], [is_last if flush is None else flush], [take])[0]
         spect = self.audio_parser.parse_audio(recording, is_last)
         said = ""
         probs = None

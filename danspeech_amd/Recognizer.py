@@ -11,7 +11,7 @@ import numpy as np
 
 from .errors.recognizer_errors import ModelNotInitialized
 from .DanSpeechRecognizer import DanSpeechRecognizer
-from .stream_plan import stream_cut_plan, stream_rounds
+from .stream_plan import stream_cut_plan, stream_rounds, resample_count, resample_feed_plan
 
 
 class Recognizer(object):
@@ -86,48 +86,89 @@ class Recognizer(object):
         else:
             print("No stream is running for the Recognizer")
 
-    def stream_recording(self, audio_data, chunk_samples=None):
+    def stream_recording(self, audio_data, chunk_samples=None, sample_rate=None, resample="polyphase"):
         """The body of ``real_time_streaming`` (Recognizer.py:560-710) driven by an array instead of the
         microphone thread: the utterance is cut with the reference's sample requirements (first pass
         ``general + 15 * samples_pr_10ms``, later passes ``general``, :598-612; ``chunk_samples`` is the size
         of the parts the source would deliver), every part goes through
         ``DanSpeechRecognizer.streaming_transcribe`` and ``(is_last, text)`` is yielded for every non-empty
-        output.  Requires ``enable_real_time_streaming``."""
+        output.  Requires ``enable_real_time_streaming``.
+        ``sample_rate``: the recording's rate when it is not the model's.  It is converted on the GPU as it streams
+        (``resample``: "polyphase" or "ratecv"): the passes are cut over the converted length (``chunk_samples`` counts
+        model-rate samples) and the source is fed just far enough for each pass (``stream_plan.resample_feed_plan``), so that
+        the yields equal ``stream_recording(audio.resample(audio_data, sample_rate, method=resample), chunk_samples)``."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
-        audio_data = np.asarray(audio_data, dtype=np.float64)
-        for lo, hi, is_first, is_last in self._cut_plan(len(audio_data), chunk_samples):
-            output = rec.streaming_transcribe(audio_data[lo:hi], is_last=is_last, is_first=is_first)
-            if output:
-                yield is_last, output
+        if not self._other_rate(sample_rate):
+            audio_data = np.asarray(audio_data, dtype=np.float64)
+            for lo, hi, is_first, is_last in self._cut_plan(len(audio_data), chunk_samples):
+                output = rec.streaming_transcribe(audio_data[lo:hi], is_last=is_last, is_first=is_first)
+                if output:
+                    yield is_last, output
+            return
+        audio_data = np.asarray(audio_data).reshape(-1)
+        plan, feed = self._feed_plan(len(audio_data), chunk_samples, sample_rate, resample)
+        before = rec._session.source
+        rec.set_streaming_source(sample_rate, resample)
+        try:
+            for (lo, hi, is_first, is_last), (a, b, flush) in zip(plan, feed):
+                output = rec.streaming_transcribe(audio_data[a:b], is_last=is_last, is_first=is_first, take=hi - lo, flush=flush)
+                if output:
+                    yield is_last, output
+        finally:
+            rec.set_streaming_source(*(before or (None, "polyphase")))
 
-    def stream_recordings(self, audio_list, chunk_samples=None):
+    def stream_recordings(self, audio_list, chunk_samples=None, sample_rate=None, resample="polyphase"):
         """``stream_recording`` for many recordings at once, one streaming session each: every recording is cut as
         ``stream_recording`` cuts it, and in each round every session that has a part due advances in ONE batched pass
         (``DanSpeechRecognizer.streaming_transcribe_many``).  Yields ``(index, is_last, text)``; for every index the
         subsequence it yields equals ``list(stream_recording(audio_list[index], chunk_samples))`` as the first recording
         after ``enable_real_time_streaming`` (every session starts with a fresh parser).  Requires
-        ``enable_real_time_streaming``."""
+        ``enable_real_time_streaming``.
+        ``sample_rate``: the recordings' rate, or a list with one rate per recording (None among them: the model's); the
+        sessions of other rates are converted together, one launch per round and method (``stream_recording``)."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
-        audio = [np.asarray(a, dtype=np.float64) for a in audio_list]
-        plans = [self._cut_plan(len(a), chunk_samples) for a in audio]
+        rates = list(sample_rate) if isinstance(sample_rate, (list, tuple)) else [sample_rate] * len(audio_list)
+        if len(rates) != len(audio_list):
+            raise ValueError("sample_rate must be one rate or one rate per recording")
+        rates = [r if self._other_rate(r) else None for r in rates]
+        audio = [np.asarray(a, dtype=np.float64) if r is None else np.asarray(a).reshape(-1) for a, r in zip(audio_list, rates)]
+        plans, feeds = [], []
+        for a, r in zip(audio, rates):
+            if r is None:
+                plans.append(self._cut_plan(len(a), chunk_samples))
+                feeds.append([(lo, hi, is_last) for lo, hi, _, is_last in plans[-1]])
+            else:
+                plan, feed = self._feed_plan(len(a), chunk_samples, r, resample)
+                plans.append(plan)
+                feeds.append(feed)
         sessions = {}
         try:
-            for due in stream_rounds(plans):
+            for r, due in enumerate(stream_rounds(plans)):
                 for k, _ in due:
                     if k not in sessions:
-                        sessions[k] = rec.new_streaming_session()
-                texts = rec.streaming_transcribe_many([sessions[k] for k, _ in due], [audio[k][c[0]:c[1]] for k, c in due],
-                                                      [c[3] for _, c in due], [c[2] for _, c in due])
+                        sessions[k] = rec.new_streaming_session(sample_rate=rates[k], resample=resample)
+                texts = rec.streaming_transcribe_many([sessions[k] for k, _ in due], [audio[k][feeds[k][r][0]:feeds[k][r][1]] for k, _ in due],
+                                                      [c[3] for _, c in due], [c[2] for _, c in due],
+                                                      take=[c[1] - c[0] for _, c in due], flush=[feeds[k][r][2] for k, _ in due])
                 for (k, c), text in zip(due, texts):
                     if text:
                         yield k, c[3], text
         finally:
             for ses in sessions.values():
                 ses.close()
+
+    def _other_rate(self, sample_rate):
+        return sample_rate is not None and int(sample_rate) != int(self.danspeech_recognizer.audio_parser.sampling_rate)
+
+    def _feed_plan(self, n_source, chunk_samples, sample_rate, resample):
+        """The passes over the converted length and what of the source each of them is fed."""
+        rate_out = int(self.danspeech_recognizer.audio_parser.sampling_rate)
+        plan = self._cut_plan(resample_count(n_source, sample_rate, rate_out, resample), chunk_samples)
+        return plan, resample_feed_plan(plan, n_source, sample_rate, rate_out, resample)
 
     def _cut_plan(self, n_samples, chunk_samples=None):
         rec = self.danspeech_recognizer

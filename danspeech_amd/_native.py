@@ -80,6 +80,13 @@ _PROTOS = {
     "dsmi_resample": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp]),
     "dsmi_resample_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
     "dsmi_resample_taps": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dsmi_resampler_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "dsmi_resampler_destroy": (None, [_vp]),
+    "dsmi_resampler_last_error": (C.c_char_p, [_vp]),
+    "dsmi_resampler_reset": (C.c_int, [_vp]),
+    "dsmi_resampler_position": (C.c_int, [_vp, _i64p, _i64p]),
+    "dsmi_resample_ready": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "dsmi_resampler_push_many": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "dsmi_stream_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dsmi_stream_destroy": (None, [_vp]),
     "dsmi_stream_last_error": (C.c_char_p, [_vp]),
@@ -539,6 +546,132 @@ def resample_taps(rate_in, rate_out=16000):
     if rc != 0:
         raise DsmiError(rc, (lib().dsmi_frontend_last_error(None) or b"").decode())
     return h, up.value, down.value
+
+
+def resample_ready(n_in, rate_in, rate_out=16000, method="polyphase"):
+    """dsmi_resample_ready (host only): how many outputs are final once the first ``n_in`` samples of an utterance are known."""
+    if method not in RESAMPLE_METHODS:
+        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
+    out = lib().dsmi_resample_ready(RESAMPLE_METHODS[method], int(rate_in), int(rate_out), int(n_in))
+    if out < 0:
+        raise DsmiError(DSMI_ERR_INVALID, "bad resample arguments (rate_in %r, n_in %r)" % (rate_in, n_in))
+    return int(out)
+
+
+RESAMPLE_STREAM_MAX = 256       # DSMI_RESAMPLE_STREAM_MAX: sessions of one dsmi_resampler_push_many call
+
+
+class NativeResampler:
+    """Owns one dsmi_resampler handle: the sample-rate conversion of one utterance that arrives in chunks, from ``rate_in`` to
+    the rate of ``frontend`` (a ``NativeFrontend``, which keeps the filters).  ``dtype``: the chunks' sample type (int16 /
+    float32 / float64), or ``wav_format=(sample_width, channels)`` for raw WAV frames.  The outputs of the pushes laid end to
+    end are bit for bit ``frontend.resample`` of the whole utterance."""
+
+    _BYTES = {0: 2, 1: 4, 2: 8, 3: 1, 4: 3, 5: 4}        # DSMI_PCM_* -> bytes per sample
+
+    def __init__(self, frontend, rate_in, method="polyphase", dtype=np.int16, wav_format=None):
+        if method not in RESAMPLE_METHODS:
+            raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
+        if wav_format is None:
+            dt = PCM_DTYPES[np.dtype(dtype)]
+        else:
+            width, channels = wav_format
+            if width not in NativeFrontend.WAV_WIDTH_DTYPE or channels not in (1, 2):
+                raise ValueError("raw WAV frames: sample width 1..4, one or two channels")
+            dt = NativeFrontend.WAV_WIDTH_DTYPE[width] | (NativeFrontend.PCM_STEREO if channels == 2 else 0)
+        self.frontend, self.rate_in, self.method, self.pcm_dtype = frontend, int(rate_in), method, dt
+        self.rate_out = int(frontend.desc.sample_rate)
+        self.frame_bytes = self._BYTES[dt & 15] * (2 if dt & NativeFrontend.PCM_STEREO else 1)
+        h = _vp()
+        rc = lib().dsmi_resampler_create(frontend._h, self.rate_in, RESAMPLE_METHODS[method], dt, C.byref(h))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_resampler_last_error(None) or b"").decode())
+        self._h = h
+
+    def position(self):
+        """(samples consumed, outputs written) since the utterance began."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        rc = lib().dsmi_resampler_position(self._h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise DsmiError(rc, "dsmi_resampler_position failed")
+        return a.value, b.value
+
+    def _due(self, n_new, is_last):
+        """Outputs the next push of ``n_new`` samples writes (host arithmetic, as the library does it)."""
+        n_in, n_out = self.position()
+        L = lib()
+        m = RESAMPLE_METHODS[self.method]
+        total = (L.dsmi_resample_count if is_last else L.dsmi_resample_ready)(m, self.rate_in, self.rate_out, n_in + n_new)
+        return max(int(total) - n_out, 0)
+
+    def _frames(self, pcm):
+        if pcm is None:
+            return 0
+        nbytes = pcm.numel() * pcm.element_size()
+        if nbytes % self.frame_bytes:
+            raise ValueError("the chunk is not a whole number of samples of the resampler's type")
+        return nbytes // self.frame_bytes
+
+    @staticmethod
+    def push_many(resamplers, pcms, is_last):
+        """dsmi_resampler_push_many: the next chunk of several utterances (distinct handles of one frontend) in one call.
+        ``pcms[i]``: a contiguous CUDA tensor holding session i's new samples in its handle's sample type (any tensor dtype:
+        the bytes are what counts; ``None`` or empty for no samples); ``is_last[i]`` flushes and ends that utterance.
+        -> a list of float64 CUDA tensors (views of one buffer): what each session emits now.  Nothing is synchronised.
+        Longer lists than RESAMPLE_STREAM_MAX run as several calls."""
+        import torch
+        n = len(resamplers)
+        if not (len(pcms) == len(is_last) == n):
+            raise ValueError("resamplers, pcms and is_last must have one entry per session")
+        if n > RESAMPLE_STREAM_MAX:
+            out = []
+            for k in range(0, n, RESAMPLE_STREAM_MAX):
+                sl = slice(k, k + RESAMPLE_STREAM_MAX)
+                out += NativeResampler.push_many(resamplers[sl], pcms[sl], is_last[sl])
+            return out
+        if n == 0:
+            return []
+        fe = resamplers[0].frontend
+        for i, r in enumerate(resamplers):
+            # the handle points into its frontend (the filters): a push after either was closed would read freed memory
+            if not getattr(r, "_h", None) or not getattr(r.frontend, "_h", None):
+                raise ValueError("session %d: the resampler or its frontend has been closed" % i)
+        for p in pcms:
+            if p is not None and not (p.is_cuda and p.is_contiguous()):
+                raise ValueError("chunks must be contiguous CUDA tensors")
+        ns = np.array([r._frames(p) for r, p in zip(resamplers, pcms)], dtype=np.int64)
+        last = np.array([int(bool(v)) for v in is_last], dtype=np.int32)
+        due = [r._due(int(k), bool(l)) for r, k, l in zip(resamplers, ns, last)]
+        total = int(sum(due))
+        out = torch.empty(max(total, 1), dtype=torch.float64, device="cuda:%d" % fe.device)
+        hs = (C.c_void_p * n)(*[r._h for r in resamplers])
+        pp = (C.c_void_p * n)(*[(p.data_ptr() if p is not None and p.numel() else None) for p in pcms])
+        n_out = np.zeros(n, dtype=np.int64)
+        rc = lib().dsmi_resampler_push_many(hs, n, pp, _np_ptr(ns), _np_ptr(last), out.data_ptr(), total, _np_ptr(n_out), _stream(fe.device))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_resampler_last_error(None) or b"").decode())
+        cuts = np.concatenate(([0], np.cumsum(n_out)))
+        return [out[int(cuts[i]):int(cuts[i + 1])] for i in range(n)]
+
+    def push(self, pcm, is_last=False):
+        """One chunk of this utterance -> the float64 CUDA tensor of the outputs that are final now."""
+        return NativeResampler.push_many([self], [pcm], [is_last])[0]
+
+    def reset(self):
+        rc = lib().dsmi_resampler_reset(self._h)
+        if rc != 0:
+            raise DsmiError(rc, "dsmi_resampler_reset failed")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dsmi_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _segment(self, pcm_dev, energy_threshold=600, step=1024, pause_hops=9, phrase_hops=4, wav_format=None,

@@ -343,36 +343,80 @@ class InferenceSpectrogramAudioParser(AudioParser):
         """Spectrogram of the next part of the utterance.  The samples not yet analysed are the carry of the previous
         call plus this part; whole hops of them are analysed now, and the last analysed hop plus the remainder are
         carried over so that consecutive parts tile the signal exactly like one long STFT without centre padding.
-        A closing part shorter than one window ends the utterance with nothing."""
+        A closing part shorter than one window ends the utterance with nothing.
+        A part may also be a float64 CUDA tensor (what ``NativeResampler`` emits): the carry then stays on the device and
+        the features are those of the same samples given as a numpy array, bit for bit."""
         import torch
         if is_last and len(part_of_recording) < self.n_fft:
             self.reset()
             return []
+        if torch.is_tensor(part_of_recording):
+            return self._frontend().features_stream(self._take_device(part_of_recording), self._state)
         samples = np.asarray(part_of_recording, dtype=np.float64).reshape(-1)
         if self.has_buffer:
-            samples = np.concatenate((self.buffer, samples))
+            samples = np.concatenate((self._host_buffer(), samples))
         usable = len(samples) - len(samples) % self.hop_length
         self.buffer = samples[max(usable - self.hop_length, 0):].copy()
         self.has_buffer = True
         pcm = torch.from_numpy(np.ascontiguousarray(samples[:usable])).to("cuda:%d" % self.device)
         return self._frontend().features_stream(pcm, self._state)
 
+    def _host_buffer(self):
+        """The carry as a numpy array (it is a device tensor after a device part)."""
+        return self.buffer if isinstance(self.buffer, np.ndarray) else self.buffer.cpu().numpy()
+
+    def _take_device(self, part):
+        """The sample bookkeeping of ``parse_audio`` on the device: carry + part -> the whole hops to analyse now (a float64
+        CUDA tensor); the new carry stays on the device.  The lengths are the tensors' shapes: nothing is synchronised."""
+        import torch
+        dev = "cuda:%d" % self.device
+        if torch.is_tensor(part):
+            if part.dtype != torch.float64 or not part.is_cuda:
+                raise ValueError("a device part must be a float64 CUDA tensor")
+            part = part.reshape(-1)
+        else:
+            part = torch.from_numpy(np.ascontiguousarray(np.asarray(part, dtype=np.float64).reshape(-1))).to(dev)
+        if self.has_buffer:
+            carry = self.buffer if torch.is_tensor(self.buffer) else torch.from_numpy(self.buffer).to(dev)
+            part = torch.cat((carry, part))
+        usable = part.numel() - part.numel() % self.hop_length
+        self.buffer = part[max(usable - self.hop_length, 0):].clone()
+        self.has_buffer = True
+        return part[:usable]
+
     @staticmethod
     def parse_audio_many(parsers, parts, is_last):
         """``[p.parse_audio(part, last) for p, part, last in zip(parsers, parts, is_last)]`` in one batched pass
         (``dsmi_features_stream_many``): every parser keeps its own carry buffer and statistics, and a closing part shorter
         than one window still ends that parser's utterance with nothing.  The parsers share one configuration; the first
-        one's frontend runs the pass."""
+        one's frontend runs the pass.  When a part is a float64 CUDA tensor the pass gathers its samples on the device
+        (numpy parts of the same call are uploaded as they are)."""
         import torch
         out = [[] for _ in parsers]
         todo, pcms = [], []
+        on_device = any(torch.is_tensor(part) for part in parts)
+        if on_device:
+            # the numpy parts of such a pass (sessions that do not convert) go up in ONE copy, as on the numpy path, and are sliced
+            host = [k for k, (p, part, last) in enumerate(zip(parsers, parts, is_last))
+                    if not torch.is_tensor(part) and not (last and len(part) < p.n_fft)]
+            if host:
+                flat = [np.asarray(parts[k], dtype=np.float64).reshape(-1) for k in host]
+                up = torch.from_numpy(np.ascontiguousarray(np.concatenate(flat))).to("cuda:%d" % parsers[host[0]].device)
+                cuts = np.cumsum([0] + [len(x) for x in flat])
+                parts = list(parts)
+                for j, k in enumerate(host):
+                    parts[k] = up[cuts[j]:cuts[j + 1]]
         for k, (p, part, last) in enumerate(zip(parsers, parts, is_last)):
             if last and len(part) < p.n_fft:
                 p.reset()
                 continue
+            if on_device:
+                todo.append(k)
+                pcms.append(p._take_device(part))
+                continue
             samples = np.asarray(part, dtype=np.float64).reshape(-1)
             if p.has_buffer:
-                samples = np.concatenate((p.buffer, samples))
+                samples = np.concatenate((p._host_buffer(), samples))
             usable = len(samples) - len(samples) % p.hop_length
             p.buffer = samples[max(usable - p.hop_length, 0):].copy()
             p.has_buffer = True
@@ -380,10 +424,13 @@ class InferenceSpectrogramAudioParser(AudioParser):
             pcms.append(samples[:usable])
         if todo:
             lead = parsers[todo[0]]
-            pcm = torch.from_numpy(np.ascontiguousarray(np.concatenate(pcms))).to("cuda:%d" % lead.device)
-            cuts = np.cumsum([0] + [len(x) for x in pcms])
-            feats = lead._frontend().features_stream_many([pcm[cuts[j]:cuts[j + 1]] for j in range(len(todo))],
-                                                          [parsers[k]._state for k in todo])
+            if on_device:
+                chunks = pcms                   # features_stream_many lays them back to back (one torch.cat)
+            else:
+                pcm = torch.from_numpy(np.ascontiguousarray(np.concatenate(pcms))).to("cuda:%d" % lead.device)
+                cuts = np.cumsum([0] + [len(x) for x in pcms])
+                chunks = [pcm[cuts[j]:cuts[j + 1]] for j in range(len(todo))]
+            feats = lead._frontend().features_stream_many(chunks, [parsers[k]._state for k in todo])
             for k, f in zip(todo, feats):
                 out[k] = f
         return out

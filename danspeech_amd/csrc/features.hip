@@ -22,7 +22,7 @@
 using namespace dsmi;
 
 // host[0..n) -> dev[0..n) on stream s through the frontend's pinned ring
-bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, int n, hipStream_t s) {
+bool fe_stage_reserve(dsmi_frontend* f, int n) {
     if (n > f->stage_cap) {
         if (hipDeviceSynchronize() != hipSuccess) return false;
         if (f->stage) (void)hipHostFree(f->stage);
@@ -35,6 +35,11 @@ bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, int n, h
             f->stage_used[i] = false;
         }
     }
+    return true;
+}
+
+bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, int n, hipStream_t s) {
+    if (!fe_stage_reserve(f, n)) return false;
     const int slot = f->stage_next++ % dsmi_frontend::kStage;
     if (f->stage_used[slot] && hipEventSynchronize(f->stage_ev[slot]) != hipSuccess) return false;
     int64_t* h = f->stage + (size_t)slot * f->stage_cap;

@@ -29,13 +29,18 @@ struct dsmi_frontend {
     // dsmi_resample: the filters made so far (one per rate_in) and the clips' [4][rs_cap] offsets / counts on the device
     std::map<int, dsmi_resample_filter> rs_filters;
     int64_t* rs_meta = nullptr; int rs_cap = 0;
+    // dsmi_resampler_push_many: the sessions' descriptor table on the device, sized for DSMI_RESAMPLE_STREAM_MAX sessions (resample_stream.hip)
+    int64_t* rss_desc = nullptr;
 };
 
 // host[0..n) -> dev[0..n) on stream s through the frontend's pinned ring (features.hip)
 bool fe_stage_copy(dsmi_frontend* f, int64_t* dev, const int64_t* host, int n, hipStream_t s);
+// makes the ring's slots at least n words each now (growing it waits for the whole device): a caller that knows its largest table
+// grows the ring once, on first use, and never on a later call (features.hip)
+bool fe_stage_reserve(dsmi_frontend* f, int n);
 // the message dsmi_frontend_last_error(NULL) returns on this thread: failures of calls that have no handle (features.hip)
 void fe_set_thread_error(const char* msg);
-// frees what dsmi_resample keeps on the handle (resample.hip; the device is current and idle)
+// frees what dsmi_resample and dsmi_resampler_push_many keep on the handle (resample.hip; the device is current and idle)
 void fe_resample_release(dsmi_frontend* f);
 
 namespace dsmi {

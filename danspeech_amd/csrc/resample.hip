@@ -21,17 +21,14 @@
 // 160 rows of 56: 72 KB, resident in L2; for 8 / 32 / 48 / 96 kHz the rows are 1..3 and every lane reads the same addresses).
 #include "common.h"
 #include "frontend.h"
-
-#include <cmath>
-#include <numeric>
-#include <algorithm>
+#include "resample.h"
 
 using namespace dsmi;
 
 namespace {
 
-constexpr int OT = 256;                 // outputs per workgroup (one per thread)
-constexpr size_t LDS_MAX = 64 * 1024;   // the staged input span must fit: guaranteed by DSMI_RESAMPLE_MAX_DECIMATION (checked)
+constexpr int OT = RS_OT;               // outputs per workgroup (one per thread)
+constexpr size_t LDS_MAX = RS_LDS_MAX;
 
 // meta: [4][B] = input offset, input samples, output offset, output samples of every clip
 __global__ __launch_bounds__(OT) void resample_poly_kernel(const void* pcm, int dtype, const int64_t* meta, int B, const double* tab,
@@ -90,60 +87,6 @@ __global__ __launch_bounds__(256) void resample_copy_kernel(const void* pcm, int
     out[meta[2 * B + b] + j] = ld_sample(pcm, dtype, meta[b] + j);
 }
 
-// I0(x), 0 <= x: the power series (every term positive: no cancellation)
-double bessel_i0(double x) {
-    const double t = x * x / 4.0;
-    double term = 1.0, sum = 1.0;
-    for (int k = 1; k < 500; ++k) {
-        term *= t / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
-}
-
-struct Ratio { int up, down; int64_t half, n_taps; };
-
-// up / down of rate_in -> rate_out and the filter's size; the message of a refusal, or nullptr
-const char* poly_ratio(int rate_in, int rate_out, Ratio* r) {
-    if (rate_in <= 0 || rate_out <= 0) return "resample: rates must be positive";
-    const int g = std::gcd(rate_in, rate_out);
-    r->up = rate_out / g; r->down = rate_in / g;
-    r->half = 10 * (int64_t)std::max(r->up, r->down);
-    r->n_taps = 2 * r->half + 1;
-    if (r->n_taps > DSMI_RESAMPLE_MAX_TAPS) return "resample: the filter of this rate pair has more than DSMI_RESAMPLE_MAX_TAPS taps";
-    if ((int64_t)rate_in > (int64_t)DSMI_RESAMPLE_MAX_DECIMATION * rate_out) return "resample: rate_in above DSMI_RESAMPLE_MAX_DECIMATION x rate_out";
-    return nullptr;
-}
-
-// scipy.signal.resample_poly's default filter: firwin(2 half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up
-void poly_taps(const Ratio& r, double* h) {
-    // fc * sinc(fc * m) with fc = 1 / max(up, down) rounded first, as firwin does: the taps on the sinc's zeros are nothing but the
-    // rounding of that argument, and only the same argument gives the same taps there
-    const double pi = 3.14159265358979323846, fc = 1.0 / (double)std::max(r.up, r.down), i0b = bessel_i0(5.0);
-    long double sum = 0.0L;
-    for (int64_t m = -r.half; m <= r.half; ++m) {
-        const double y = pi * (fc * (double)m);
-        const double sinc = m == 0 ? 1.0 : std::sin(y) / y;
-        const double a = (double)m / (double)r.half;
-        const double w = bessel_i0(5.0 * std::sqrt(std::max(0.0, 1.0 - a * a))) / i0b;
-        const double v = fc * sinc * w;
-        h[m + r.half] = v;
-        sum += (long double)v;
-    }
-    const double scale = (double)((long double)r.up / sum);
-    for (int64_t k = 0; k < r.n_taps; ++k) h[k] *= scale;
-}
-
-int ratecv_shift(int dtype) {
-    switch (dtype & 15) {
-        case DSMI_PCM_U8: return 24;
-        case DSMI_PCM_I16: return 16;
-        case DSMI_PCM_I24: return 8;
-        default: return 0;
-    }
-}
-
 }  // namespace
 
 void fe_resample_release(dsmi_frontend* f) {
@@ -151,6 +94,8 @@ void fe_resample_release(dsmi_frontend* f) {
     f->rs_filters.clear();
     if (f->rs_meta) (void)hipFree(f->rs_meta);
     f->rs_meta = nullptr; f->rs_cap = 0;
+    if (f->rss_desc) (void)hipFree(f->rss_desc);
+    f->rss_desc = nullptr;
 }
 
 extern "C" int64_t dsmi_resample_count(int method, int rate_in, int rate_out, int64_t n) {
@@ -204,8 +149,8 @@ extern "C" int dsmi_resample(dsmi_frontend* f, const void* pcm, int dtype, const
         counts[b] = c; off_in += n_samples[b]; off_out += c; max_cnt = std::max(max_cnt, c);
     }
     if (off_out > out_capacity) return bad(DSMI_ERR_CAPACITY, "resample: out_dev is smaller than the clips' resampled lengths (dsmi_resample_count)");
-    const int kmax = (int)((r.n_taps + r.up - 1) / r.up), kstride = (kmax + 1) & ~1;
-    const size_t lds = sizeof(double) * ((size_t)(((int64_t)(OT - 1) * r.down + r.up - 1) / r.up) + kmax + 1);
+    const int kmax = poly_kmax(r), kstride = poly_kstride(kmax);
+    const size_t lds = poly_lds_bytes(r);
     if (method == DSMI_RESAMPLE_POLYPHASE && !same && lds > LDS_MAX) return bad(DSMI_ERR_CAPACITY, "resample: the input span of one workgroup does not fit LDS");
     if (max_cnt > (int64_t)INT32_MAX * 128) return bad(DSMI_ERR_INVALID, "resample: clip too long");
     if (hipSetDevice(f->device) != hipSuccess) return bad(DSMI_ERR_HIP, "hipSetDevice failed");
@@ -213,25 +158,9 @@ extern "C" int dsmi_resample(dsmi_frontend* f, const void* pcm, int dtype, const
     // ---- the filter of this rate_in: made once, kept on the handle
     const dsmi_resample_filter* flt = nullptr;
     if (method == DSMI_RESAMPLE_POLYPHASE && !same) {
-        auto it = f->rs_filters.find(rate_in);
-        if (it == f->rs_filters.end()) {
-            std::vector<double> h(r.n_taps), tab((size_t)r.up * kstride, 0.0);
-            poly_taps(r, h.data());
-            for (int ph = 0; ph < r.up; ++ph)
-                for (int t = 0; t < kmax; ++t) {
-                    const int64_t idx = ph + (int64_t)t * r.up;
-                    if (idx < r.n_taps) tab[(size_t)ph * kstride + t] = h[idx];
-                }
-            dsmi_resample_filter nf;
-            nf.up = r.up; nf.down = r.down; nf.half = (int)r.half; nf.kmax = kmax;
-            if (hipMalloc((void**)&nf.tab, sizeof(double) * tab.size()) != hipSuccess) return bad(DSMI_ERR_NOMEM, "hipMalloc failed");
-            if (hipMemcpy(nf.tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(nf.tab);
-                return bad(DSMI_ERR_HIP, "uploading the resampling filter failed");
-            }
-            it = f->rs_filters.emplace(rate_in, nf).first;
-        }
-        flt = &it->second;
+        int code = DSMI_OK; const char* msg = nullptr;
+        flt = fe_resample_filter(f, rate_in, r, &code, &msg);
+        if (!flt) return bad(code, msg);
     }
     if (B > f->rs_cap) {
         if (f->rs_meta) { (void)hipStreamSynchronize(s); (void)hipFree(f->rs_meta); f->rs_meta = nullptr; f->rs_cap = 0; }

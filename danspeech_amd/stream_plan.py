@@ -34,3 +34,68 @@ def stream_rounds(plans):
     for r in range(max([len(p) for p in plans] + [0])):
         rounds.append([(k, p[r]) for k, p in enumerate(plans) if r < len(p)])
     return rounds
+
+
+# ---- streaming from a source of another rate: the arithmetic of dsmi_resample_count / dsmi_resample_ready, restated here so that
+# the schedule needs neither the library nor a GPU
+def _ratio(rate_in, rate_out):
+    from math import gcd
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in <= 0 or rate_out <= 0:
+        raise ValueError("rates must be positive")
+    g = gcd(rate_in, rate_out)
+    return rate_out // g, rate_in // g          # up, down
+
+
+def _method(method):
+    if method not in ("polyphase", "ratecv"):
+        raise ValueError("resample method must be 'polyphase' or 'ratecv'")
+    return method
+
+
+def resample_count(n_in, rate_in, rate_out=16000, method="polyphase"):
+    """Length ``n_in`` samples at ``rate_in`` have at ``rate_out`` (``dsmi_resample_count``)."""
+    up, down = _ratio(rate_in, rate_out)
+    if n_in <= 0:
+        return 0
+    return (n_in - 1) * up // down + 1 if _method(method) == "ratecv" else -((-n_in * up) // down)
+
+
+def resample_ready(n_in, rate_in, rate_out=16000, method="polyphase"):
+    """Outputs that are final once the first ``n_in`` source samples are known (``dsmi_resample_ready``): the polyphase filter
+    looks ``half / up`` samples ahead, ``ratecv`` and equal rates do not."""
+    up, down = _ratio(rate_in, rate_out)
+    if _method(method) == "ratecv" or up == down or n_in <= 0:
+        return resample_count(n_in, rate_in, rate_out, method)
+    half = 10 * max(up, down)
+    return min(resample_count(n_in, rate_in, rate_out, method), max(0, -((half - n_in * up) // down)))
+
+
+def resample_need(n_out, rate_in, rate_out=16000, method="polyphase"):
+    """The fewest source samples after which ``n_out`` outputs are final -- ``k_hi(n_out - 1) + 1`` for the polyphase filter.  It
+    may exceed the source's length: the last outputs need the zeros behind the source's end, i.e. the flush."""
+    up, down = _ratio(rate_in, rate_out)
+    if n_out <= 0:
+        return 0
+    if up == down:
+        return n_out
+    if _method(method) == "ratecv":
+        return -((-(n_out - 1) * down) // up) + 1
+    return ((n_out - 1) * down + 10 * max(up, down)) // up + 1
+
+
+def resample_feed_plan(plan, n_source, rate_in, rate_out=16000, method="polyphase"):
+    """How a source of ``n_source`` samples at ``rate_in`` is fed to a session whose passes ``plan`` (``stream_cut_plan`` over the
+    converted length) are counted in ``rate_out`` samples: one ``(src_lo, src_hi, flush)`` per pass.  Before pass ``(lo, hi)``
+    the source is pushed up to ``resample_need(hi)`` samples, just enough for the pass's last sample to be final; the pass that
+    reaches the source's end also flushes (its last outputs need the end), and later passes push nothing.  Nothing is pushed
+    twice; outputs beyond ``hi`` wait in the session."""
+    feed, pos, flushed = [], 0, False
+    for lo, hi, _, is_last in plan:
+        upto = n_source if is_last else min(n_source, resample_need(hi, rate_in, rate_out, method))
+        upto = max(upto, pos)
+        flush = upto >= n_source and not flushed
+        feed.append((pos, upto, flush))
+        flushed = flushed or flush
+        pos = upto
+    return feed

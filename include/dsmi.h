@@ -158,6 +158,42 @@ int dsmi_resample(dsmi_frontend* f, const void* pcm_dev, int pcm_dtype, const in
 int64_t dsmi_resample_count(int method, int rate_in, int rate_out, int64_t n);
 int dsmi_resample_taps(int rate_in, int rate_out, double* taps_out, int64_t capacity, int* up, int* down);
 
+/* ---- The same conversion for LIVE audio: an utterance that arrives in chunks of any size (no reference counterpart beyond the
+ * state argument of audioop.ratecv).  A dsmi_resampler is one utterance in flight.  It belongs to a frontend, whose sample_rate
+ * is the rate converted to and which keeps the polyphase filters (shared with dsmi_resample); rate_in, method and pcm_dtype (any
+ * DSMI_PCM_*, DSMI_PCM_STEREO included) are fixed at creation, which applies the refusals of dsmi_resample.  Destroy the handles
+ * of a frontend before the frontend.
+ * The defining property: however the utterance is cut into chunks -- chunks of one sample, empty chunks --, the outputs of its
+ * pushes laid end to end are BIT FOR BIT those of one dsmi_resample call over the whole utterance, for both methods, every
+ * sample type and equal rates.
+ * dsmi_resample_ready (host only): how many outputs are final once the first n_in samples of an utterance are known, < 0 for
+ * bad arguments.  POLYPHASE: the j with (j down + half) / up <= n_in - 1, i.e. min(dsmi_resample_count(n_in),
+ * max(0, ceil((n_in up - half) / down))) -- the filter looks half / up input samples ahead, under a millisecond.  RATECV:
+ * dsmi_resample_count(n_in) (linear interpolation looks no further than the sample it stands on).  Equal rates: n_in.
+ * dsmi_resampler_push_many advances n distinct handles of one frontend by one chunk each (1 <= n <= DSMI_RESAMPLE_STREAM_MAX;
+ * rates, methods and sample types may differ): pcm_dev[i] holds n_samples[i] >= 0 new samples of session i (frames for stereo;
+ * may be NULL for 0).  Session i writes ready(total_in) - emitted outputs -- with is_last[i] the rest, up to
+ * dsmi_resample_count(total_in), and then stands at the start of a new utterance -- as float64 at integer scale, the sessions
+ * back to back in out_dev (what dsmi_features_stream_many takes); n_out_host[i] receives its count, which is host arithmetic:
+ * the call waits for nothing the device does and is asynchronous on `stream` (a frontend's FIRST push sizes the descriptor
+ * table and the pinned staging ring for DSMI_RESAMPLE_STREAM_MAX sessions, which waits for the device once; later on the host can
+ * only wait for the descriptor copy of the fourth call before, the ring having four slots).  At most one launch per method present (polyphase / ratecv /
+ * copy), whatever n.  What a session still needs of its past input (at most 20 max(1, down / up) samples) waits on the device.
+ * Refused before any launch, with every handle left exactly as it was and nothing written: n out of range, a handle listed
+ * twice, handles of different frontends, a negative count (DSMI_ERR_INVALID), out_capacity below the sum of the outputs
+ * (DSMI_ERR_CAPACITY); the error text (dsmi_resampler_last_error(NULL): the thread's last refusal) names the session index.
+ * dsmi_resampler_position: samples consumed / outputs written since the utterance began.  dsmi_resampler_reset: a new utterance. */
+typedef struct dsmi_resampler dsmi_resampler;
+#define DSMI_RESAMPLE_STREAM_MAX 256
+int dsmi_resampler_create(dsmi_frontend* f, int rate_in, int method, int pcm_dtype, dsmi_resampler** out);
+void dsmi_resampler_destroy(dsmi_resampler* r);
+const char* dsmi_resampler_last_error(const dsmi_resampler* r);
+int dsmi_resampler_reset(dsmi_resampler* r);
+int dsmi_resampler_position(const dsmi_resampler* r, int64_t* n_in, int64_t* n_out);
+int64_t dsmi_resample_ready(int method, int rate_in, int rate_out, int64_t n_in);
+int dsmi_resampler_push_many(dsmi_resampler* const* rs, int n, const void* const* pcm_dev, const int64_t* n_samples,
+                             const int* is_last, double* out_dev, int64_t out_capacity, int64_t* n_out_host, void* stream);
+
 /* ---- InferenceSpectrogramAudioParser.parse_audio (parsers.py:102-164), the arithmetic half: STFT of the
  * samples WITHOUT centre padding (librosa.stft(center=False), :137-138: 1 + (n - n_fft)/hop frames), log1p|.|,
  * then the adaptive normalisation of :146-161.  state3 = {input_mean, input_std, alpha} is read and updated
