@@ -24,6 +24,7 @@ import numpy as np
 from .deepspeech.decoder import GreedyDecoder, BeamCTCDecoder
 from .errors.recognizer_errors import ModelNotInitialized
 from .audio.parsers import SpectrogramAudioParser, InferenceSpectrogramAudioParser, DeviceClips, StagedClips
+from . import batch_plan
 
 
 class NoLmInstantiatedWarning(Warning):
@@ -233,7 +234,7 @@ class DanSpeechRecognizer(object):
     def _stage_batch(self, recordings, parser=None):
         """Host clips, longest first (pack_padded_sequence's order, reference model.py:117), copied to pinned memory and on
         their way to the device: (order, StagedClips).  Needs no model handle, so a pipeline calls it before it waits for one."""
-        order = np.argsort([-len(r) for r in recordings], kind="stable")
+        order = batch_plan.longest_first([len(r) for r in recordings])
         return order, (parser or self.audio_parser).stage([recordings[i] for i in order])
 
     def _enqueue_batch(self, recordings, model=None, parser=None, decode_slot=None, staged=None):
@@ -255,7 +256,7 @@ class DanSpeechRecognizer(object):
             if staged is not None:
                 order, clips = staged
             else:
-                order = np.argsort([-len(r) for r in recordings], kind="stable")
+                order = batch_plan.longest_first([len(r) for r in recordings])
                 clips = [recordings[i] for i in order]
             feats, frames = (parser or self.audio_parser).parse_batch(clips)
         probs, sizes = model.enqueue(feats, torch.from_numpy(frames.astype(np.int32)))
@@ -312,7 +313,7 @@ class DanSpeechRecognizer(object):
         if len(recordings) == 0:
             return []
         if sample_rate is not None and int(sample_rate) != int(self.audio_parser.sampling_rate) and not isinstance(recordings, DeviceClips):
-            order = np.argsort([-len(r) for r in recordings], kind="stable")
+            order = batch_plan.longest_first([len(r) for r in recordings])
             clips = self.audio_parser.resample_batch([recordings[i] for i in order], int(sample_rate), resample)
             clips.order = order
             return self._finish_batch(self._enqueue_batch(clips), show_all)
@@ -323,7 +324,7 @@ class DanSpeechRecognizer(object):
     # 16-clip tiles per workgroup, and its cost per clip falls with the tiles it walks)
     pipeline_lanes = 4
     pipeline_merge_clips = 64
-    pipeline_balance_tail = True         # a sized source's last round of forwards is dealt evenly over the lanes (tail_plan)
+    pipeline_balance_tail = True         # a sized source's last round of forwards is dealt evenly over the lanes (batch_plan.ForwardGrouper)
 
     def _lanes(self, count):
         """The model handles, parsers and streams of the pipeline's forwards in flight: the engine's own and `count - 1` replicas."""
@@ -336,16 +337,38 @@ class DanSpeechRecognizer(object):
         streams = [torch.cuda.current_stream(self._device_index())] + [self._side_stream("lane %d" % k) for k in range(1, len(handles))]
         return handles, parsers, streams
 
+    def _set_up_lanes(self, count, searching):
+        """``_lanes(count)``, configured for a pipelined call; ``_tear_down_lanes`` is the other half."""
+        handles, parsers, streams = self._lanes(count)
+        for h in handles:
+            if hasattr(h, "set_inflight"):
+                h.set_inflight(max(2, len(handles)) if len(handles) > 1 else 1)     # (re-stated per forward: batch_plan.chip_forms)
+        for p, st in zip(parsers, streams):
+            p.share_copy_stream = searching      # a search kernel on the decode stream: fewer streams
+            p.upload_on_compute_stream = True    # no copy stream in the pipeline: see SpectrogramAudioParser.stage
+            # ... and the upload is ISSUED where the clips are staged, on the helper thread, into the lane's own stream: the first
+            # copy a process hands a DMA engine holds its caller for 6-12 ms (hipMemcpyAsync creating the engine's queue; which
+            # engine a copy gets depends on which are busy, so new ones are met well into a process's second call:
+            # profiles/r06_second_call_stall.txt) -- the thread that feeds the other lanes must not be the one held
+            p.upload_stream = st
+        return handles, parsers, streams
+
+    def _tear_down_lanes(self, handles, parsers):
+        """The end of a pipelined call: the handles take a lone batch's kernel forms again, and no parser keeps the call's stream --
+        a later ``transcribe_batch`` uploads on whatever stream runs its features (``parse_batch``), which may be another one.
+        ``share_copy_stream`` and ``upload_on_compute_stream`` stay as the call left them: that later batch keeps uploading by
+        kernel rather than by hipMemcpyAsync on a copy stream."""
+        for h in handles:
+            if hasattr(h, "set_inflight"):
+                h.set_inflight(1)
+            if hasattr(h, "set_ring_windows"):
+                h.set_ring_windows(0)
+        for p in parsers:
+            p.upload_stream = None
+
     def _lanes_that_pay(self, most, clips):
-        """Forwards in flight when the caller did not say.  Several forwards side by side pay where the recurrent kernel of
-        each holds a fifth of the chip (the ring form: GRU / RNN up to 896 units, LSTM up to 512, one window of up to 64
-        clips -- ``transcribe_batches`` cuts larger batches to that) and the dense kernels of the others fill the rest.  A model
-        whose recurrent kernel takes the whole device runs two: their recurrent launches take turns (csrc/api.hip, the turn
-        lock) and each forward's GEMM runs beside the other's launch; a third forward only slows those launches down (config 4:
-        33.7 ms per batch with two, 35.0 with three, 37.1 with four; profiles/r06_config4.txt)."""
-        hidden, kind = getattr(self.model, "rnn_hidden_size", 0), getattr(self.model, "rnn_type", "gru")
-        ring = hidden % 16 == 0 and hidden <= (512 if kind == "lstm" else 896)
-        return most if ring and clips <= 64 else min(most, 2)
+        """Forwards in flight when the caller did not say: ``batch_plan.lanes_that_pay`` for this engine's model."""
+        return batch_plan.lanes_that_pay(getattr(self.model, "rnn_hidden_size", 0), getattr(self.model, "rnn_type", "gru"), most, clips)
 
     def transcribe_batches(self, batches, show_all=False, lanes=None, merge_clips=None):
         """Generator over ``transcribe_batch(b)`` for every ``b`` of ``batches`` through the pipeline of ``_transcribe_forwards``
@@ -356,49 +379,51 @@ class DanSpeechRecognizer(object):
         of 128 leave it to one recurrent window at a time (config 5's share, 128 x 30 s: DESIGN.md 6)."""
         import collections
         merge = self.pipeline_merge_clips if merge_clips is None else int(merge_clips)
-        shapes = collections.deque()          # per caller batch: None (handed through) or (clips, [caller positions of piece k])
+        shapes = collections.deque()          # per caller batch: None (handed through) or its cuts, [caller positions of piece k]
 
         def pieces():
             for b in batches:
-                n = len(b)
-                if merge <= 0 or n <= merge:
-                    shapes.append(None)
+                on_device = isinstance(b, DeviceClips)      # longest first already: consecutive parts
+                cuts = batch_plan.cut_batch(len(b), None if on_device else [len(r) for r in b], merge)
+                shapes.append(cuts)
+                if cuts is None:
                     yield b
                     continue
-                if isinstance(b, DeviceClips):       # longest first already: consecutive parts
-                    cuts = [np.arange(lo, min(lo + merge, n)) for lo in range(0, n, merge)]
-                    parts = [b.part(int(c[0]), int(c[-1]) + 1) for c in cuts]
-                else:
-                    order = np.argsort([-len(r) for r in b], kind="stable")
-                    cuts = [order[lo:lo + merge] for lo in range(0, n, merge)]
-                    parts = [[b[i] for i in c] for c in cuts]
-                shapes.append((n, cuts))
-                for part in parts:
-                    yield part
+                for c in cuts:
+                    yield b.part(c[0], c[-1] + 1) if on_device else [b[i] for i in c]
 
-        # a sized source (a list of lists): how many pieces the pipeline will see -- it then knows when it is enqueueing its last
-        # forwards and gives a forward that has the chip to itself the kernels of a lone batch (short calls: _transcribe_forwards)
-        total = None
-        try:
-            total = sum(1 if (merge <= 0 or len(b) <= merge) else -(-len(b) // merge) for b in batches) if hasattr(batches, "__len__") else None
-        except TypeError:
-            total = None
+        total = batch_plan.count_pieces(batches, merge)
         inner = self._transcribe_forwards(pieces(), show_all=show_all, lanes=lanes, merge_clips=merge_clips, total=total)
         try:
             for res in inner:
-                shape = shapes.popleft()
-                if shape is None:
+                cuts = shapes.popleft()
+                if cuts is None:
                     yield res
                     continue
-                n, cuts = shape
-                whole = [None] * n
+                whole = [None] * sum(len(c) for c in cuts)
                 for k, cut in enumerate(cuts):
                     part = res if k == 0 else next(inner)
                     for pos, i in enumerate(cut):
-                        whole[int(i)] = part[pos]
+                        whole[i] = part[pos]
                 yield whole
         finally:
             inner.close()
+
+    def _stage_group(self, parts, parser, caller_stream):
+        """The batches of one forward (``batch_plan.ForwardGrouper.next_group``) on their way to the device: -> (merged recordings,
+        what ``_enqueue_batch`` needs of the staging).  Runs where the group was formed: on the pipeline's helper thread."""
+        import torch
+        live = [b for b in parts if len(b)]
+        if not live:
+            return [], None
+        if isinstance(live[0], DeviceClips):
+            # device-resident clips: ordered behind whatever produced them on the caller's stream (the lanes' streams are
+            # ordered behind nothing else); merged into one longest-first buffer on the LANE's stream, behind that point
+            ahead = torch.cuda.Event()
+            ahead.record(caller_stream)
+            return (live[0] if len(live) == 1 else _UnmergedDeviceClips(live)), ahead
+        merged = live[0] if len(live) == 1 else [clip for b in live for clip in b]
+        return merged, (self._stage_batch(merged, parser) if hasattr(parser, "stage") else None)
 
     def _transcribe_forwards(self, batches, show_all=False, lanes=None, merge_clips=None, total=None):
         """Generator over ``transcribe_batch(b)`` for every ``b`` of ``batches``, software-pipelined: consecutive batches are
@@ -413,121 +438,38 @@ class DanSpeechRecognizer(object):
         other mode ``batches`` is advanced on a HELPER THREAD (one, the same for the whole call), concurrently with the
         consumer's loop body: a source with thread-affine state (a GUI toolkit's objects, a thread-local CUDA stream of its own)
         must be wrapped accordingly or use the sequential mode.  Latency: with the defaults (four forwards of up to 64 clips in
-        flight and one staged) a result comes out eight to ten batches of 32 clips after its batch was read."""
+        flight and one staged) a result comes out eight to ten batches of 32 clips after its batch was read.
+
+        The schedule -- which batches share a forward, a sized source's last round, the kernel forms of a forward -- is decided in
+        ``batch_plan``; this method runs it: set up the lanes, then get a group, enqueue it, drain, repeat, then tear down."""
         import torch
         import collections
         auto_lanes = lanes is None
         lanes = self.pipeline_lanes if auto_lanes else max(1, int(lanes))
         merge_clips = self.pipeline_merge_clips if merge_clips is None else int(merge_clips)
         searching = hasattr(self.decoder, "decode_enqueue") and not getattr(self.decoder, "on_lane", False)
+        grouper = batch_plan.ForwardGrouper(batches, merge_clips, lanes, total, self.pipeline_balance_tail,
+                                            kind=lambda b: b.pcm.dtype if isinstance(b, DeviceClips) else None)     # (one sample type per device-resident forward)
         # (the lanes are set up once the first forward has been put together: how many pay depends on its size)
         handles, parsers, streams = self._lanes(1)
-
-        def set_up(count):
-            hs, ps, ss = self._lanes(count)
-            for h in hs:
-                if hasattr(h, "set_inflight"):
-                    h.set_inflight(max(2, len(hs)) if len(hs) > 1 else 1)     # (re-stated per forward in the loop below)
-            for p, st in zip(ps, ss):
-                p.share_copy_stream = searching      # a search kernel on the decode stream: fewer streams
-                p.upload_on_compute_stream = True    # no copy stream in the pipeline: see SpectrogramAudioParser.stage
-                # ... and the upload is ISSUED where the clips are staged, on the helper thread, into the lane's own stream: the first
-                # copy a process hands a DMA engine holds its caller for 6-12 ms (hipMemcpyAsync creating the engine's queue; which
-                # engine a copy gets depends on which are busy, so new ones are met well into a process's second call:
-                # profiles/r06_second_call_stall.txt) -- the thread that feeds the other lanes must not be the one held
-                p.upload_stream = st
-            return hs, ps, ss
-        # Depth of the pipeline in forwards.  Greedy decoding is a short host-synchronous step.  A beam search is a kernel of its
-        # own that starts when its forward ends: one more job in flight (the oldest forward's search) keeps every lane's forward
-        # running while the host waits for that search.
+        caller_stream, device_index = streams[0], self._device_index()
         pending, turn, count, job, done = collections.deque(), 0, 0, None, None
-        end = object()
-        source = iter(batches)
-        held = [end, False]                      # a batch read from the source that did not fit the group being put together
-        taken = [0, False]                       # batches read from the source so far; the source has ended
 
-        def next_batch():
-            if held[1]:
-                held[1] = False
-                return held[0]
-            b = next(source, end)
-            if b is end:
-                taken[1] = True
-            else:
-                taken[0] += 1
-            return b
+        def drain(keep):
+            """Results of the oldest forwards, one list per batch, until `keep` forwards are pending."""
+            nonlocal done
+            while len(pending) > keep:
+                done = pending.popleft()
+                parts, finished = done
+                res = self._finish_batch(finished, show_all) if finished is not None else []
+                done = finished = None
+                for r in batch_plan.split_results([len(b) for b in parts], res):
+                    yield r
 
-        plan = [None, 0]                         # the call's last round, once it is known: batches per forward; forwards put together so far
-
-        def tail_plan(first_len):
-            """A sized source's LAST ROUND of forwards is dealt evenly over the lanes: 20 batches of 32 clips on four lanes are
-            eight forwards of 64 clips and then four of 32 -- not ten of 64, whose last two run on two lanes while the other two
-            stand empty (a 20-batch call: 115 -> @@ ms, profiles/r06_short_calls.txt).  -> batches this forward may merge, or None."""
-            index, plan[1] = plan[1], plan[1] + 1
-            if total is None or merge_clips <= 0 or lanes < 2 or not self.pipeline_balance_tail:
-                return None
-            if plan[0] is None:
-                if index % lanes:                     # rounds start on the first lane
-                    return None
-                full = max(1, merge_clips // max(first_len, 1))
-                rem = total - taken[0] + (1 if held[1] else 0) + 1           # batches not yet in a forward, this one's first included
-                if rem > lanes * full:
-                    return None
-                k = min(lanes, rem)
-                plan[0] = [rem // k + (1 if i < rem % k else 0) for i in range(k)]
-            return plan[0].pop(0) if plan[0] else None
-
-        def forwards_to_come(per_forward):
-            """Forwards that will follow the one being enqueued (which merged `per_forward` batches), as far as this call can know
-            WITHOUT asking the source for anything (a live source must not be waited for here): from the batch count of a sized
-            source (`total`), otherwise none once the source has ended and 'plenty' before."""
-            if taken[1]:
-                return 1 if held[1] else 0
-            if total is not None:
-                left = total - taken[0] + (1 if held[1] else 0)
-                return min(-(-left // max(per_forward, 1)), lanes)
-            return lanes
-
-        def fetch(parser):
-            """The next forward: consecutive batches of one kind (host clips / device-resident clips) up to merge_clips clips.
-            -> (parts, merged recordings, what _enqueue_batch needs of the staging) or None at the end of the source."""
-            first = next_batch()
-            if first is end:
-                return None
-            parts, nclips, on_device = [first], len(first), isinstance(first, DeviceClips)
-            most = tail_plan(len(first))
-            while nclips and nclips < merge_clips and (most is None or len(parts) < most):
-                nxt = next_batch()
-                if nxt is end:
-                    break
-                if isinstance(nxt, DeviceClips) != on_device or nclips + len(nxt) > merge_clips or \
-                        (on_device and nxt.pcm.dtype != first.pcm.dtype):          # (one sample type per device-resident forward)
-                    held[0], held[1] = nxt, True
-                    break
-                parts.append(nxt)
-                nclips += len(nxt)
-            live = [b for b in parts if len(b)]
-            if not live:
-                return parts, [], None
-            if on_device:
-                # device-resident clips: ordered behind whatever produced them on the caller's stream (the lanes' streams are
-                # ordered behind nothing else); merged into one longest-first buffer on the LANE's stream, behind that point
-                ahead = torch.cuda.Event()
-                ahead.record(streams[0])
-                return parts, (live[0] if len(live) == 1 else _UnmergedDeviceClips(live)), ahead
-            merged = live[0] if len(live) == 1 else [clip for b in live for clip in b]
-            staged = self._stage_batch(merged, parser) if hasattr(parser, "stage") else None
-            return parts, merged, staged
-
-        def results_of(done):
-            """A finished forward -> one result list per batch it was merged from."""
-            parts, job = done
-            res = self._finish_batch(job, show_all) if job is not None else []
-            out, lo = [], 0
-            for b in parts:
-                out.append(res[lo:lo + len(b)])
-                lo += len(b)
-            return out
+        def next_forward(parser):
+            """-> (batches, merged recordings, staging) of the next forward, or None at the end of the source."""
+            parts = grouper.next_group()
+            return None if parts is None else (parts,) + self._stage_group(parts, parser, caller_stream)
 
         # The next forward is put together by a helper thread (reading the source, the copy into pinned memory, the upload's start)
         # while this thread waits for the GPU, makes strings and runs the caller's loop body: on a busy host the staging of 80 MB
@@ -537,44 +479,40 @@ class DanSpeechRecognizer(object):
         if lanes > 1 or merge_clips > 0:
             from concurrent.futures import ThreadPoolExecutor
             helper = ThreadPoolExecutor(max_workers=1)
-        device_index = self._device_index()
 
         def fetch_ahead(parser):
             if helper is None:
-                return fetch(parser)
+                return next_forward(parser)
 
             def work():
                 torch.cuda.set_device(device_index)
-                torch.cuda.set_stream(streams[0])        # a source that launches GPU work does so on the caller's stream, as inline
-                return fetch(parser)
+                torch.cuda.set_stream(caller_stream)     # a source that launches GPU work does so on the caller's stream, as inline
+                return next_forward(parser)
             return helper.submit(work)
 
         try:
-            set_up(1)
+            handles, parsers, streams = self._set_up_lanes(1, searching)
             ahead = fetch_ahead(parsers[0])
             group = ahead.result() if helper is not None else ahead
             if auto_lanes and group is not None:
                 lanes = self._lanes_that_pay(lanes, sum(len(b) for b in group[0]))
-            handles, parsers, streams = set_up(lanes)
-            lanes = len(handles)
+            handles, parsers, streams = self._set_up_lanes(lanes, searching)
+            grouper.lanes = lanes = len(handles)     # (the first group was formed with the count the call started with: batch_plan)
+            # Depth of the pipeline in forwards.  Greedy decoding is a short host-synchronous step.  A beam search is a kernel of its
+            # own that starts when its forward ends: one more job in flight (the oldest forward's search) keeps every lane's forward
+            # running while the host waits for that search.
             depth = lanes + 1 if searching else lanes
             while group is not None:
                 parts, merged, staged = group
-                job = None
                 if len(merged):
                     for older in pending:            # this forward's model handle gives back its previous forward first
                         if older[1] is not None and older[1].model is handles[turn]:
                             older[1].collect_forward()
-                    # Kernel forms follow what will BE on the chip, not what the call was set up for: a forward that is enqueued
-                    # with nothing else running and nothing to come (a call of one or two batches) takes the forms of a lone batch
-                    # (the whole-device recurrent kernel, or two ring windows side by side); two forwards that will share the chip
-                    # between them (a call of three or four batches, the last forwards of a sized source) take two ring windows
-                    # each; anything more, one window each.  profiles/r06_short_calls.txt
                     if lanes > 1 and hasattr(handles[turn], "set_ring_windows"):
                         busy = sum(1 for _p, j in pending if j is not None and not j.collected and not j.model.ready())
-                        expect = busy + 1 + forwards_to_come(len(parts))
-                        handles[turn].set_inflight(1 if expect <= 1 else max(2, lanes))
-                        handles[turn].set_ring_windows(2 if expect == 2 else 0)
+                        inflight, ring_windows = batch_plan.chip_forms(busy, grouper.forwards_to_come(len(parts)), lanes)
+                        handles[turn].set_inflight(inflight)
+                        handles[turn].set_ring_windows(ring_windows)
                     with torch.cuda.stream(streams[turn]):
                         if isinstance(merged, _UnmergedDeviceClips):
                             streams[turn].wait_event(staged)
@@ -587,28 +525,13 @@ class DanSpeechRecognizer(object):
                 if helper is None:
                     # strictly sequential (lanes=1, merge_clips=0): every result is out before the source is asked for its next
                     # batch -- a source may wait for result k before it produces batch k + 1
-                    while pending:
-                        done = pending.popleft()
-                        res = results_of(done)
-                        done = None
-                        for r in res:
-                            yield r
+                    yield from drain(0)
                 ahead = fetch_ahead(parsers[turn])   # the next forward: staged now, beside the waits below
                 # (one more than `depth` may be pending for a moment: the oldest forward has been waited for above -- it ran on the
                 # lane that was just refilled -- and only its strings are still to be made, while every lane is busy again)
-                while len(pending) > depth:
-                    done = pending.popleft()
-                    res = results_of(done)
-                    done = None
-                    for r in res:
-                        yield r
+                yield from drain(depth)
                 group = ahead.result() if helper is not None else ahead
-            while pending:
-                done = pending.popleft()
-                res = results_of(done)
-                done = None
-                for r in res:
-                    yield r
+            yield from drain(0)
         finally:
             if helper is not None:
                 helper.shutdown(wait=True)       # (a staging in progress finishes: its pinned slot must not be refilled under it)
@@ -617,11 +540,7 @@ class DanSpeechRecognizer(object):
             for left in [done[1] if done else None, job] + [pj[1] for pj in pending]:
                 if isinstance(left, _BatchJob):
                     self._abandon(left)
-            for h in handles:
-                if hasattr(h, "set_inflight"):
-                    h.set_inflight(1)
-                if hasattr(h, "set_ring_windows"):
-                    h.set_ring_windows(0)
+            self._tear_down_lanes(handles, parsers)
 
     def _abandon(self, job):
         """Wait for an enqueued batch and drop its results."""

@@ -113,6 +113,10 @@ class SpectrogramAudioParser(AudioParser):
     _stage_high = 1 << 20
     _STAGE_SHARED_CAP = 256 << 20
     _stage_lock = __import__("threading").Lock()
+    # how stage() / parse_batch upload: the batch pipeline configures its lanes' parsers (DanSpeechRecognizer._set_up_lanes)
+    share_copy_stream = False          # set by the pipeline when a beam search keeps a decode stream busy; stays set
+    upload_on_compute_stream = False   # set by the pipeline: upload by kernel on the forward's stream, no copy stream; stays set
+    upload_stream = None               # set by the pipeline to the lane's stream for the length of a call, cleared at its end
 
     def _staging(self, nbytes):
         """Two pinned host buffers used alternately, each with the event of the upload that last read it: the host
@@ -126,7 +130,7 @@ class SpectrogramAudioParser(AudioParser):
         self._turn ^= 1
         if slot["done"] is not None:
             slot["done"].synchronize()                    # the upload issued two batches ago
-        if getattr(self, "upload_on_compute_stream", False) and slot["used"] is not None:
+        if self.upload_on_compute_stream and slot["used"] is not None:
             slot["used"].synchronize()                    # ... or the forward that uploaded from this buffer itself
         # Sized by the largest forward ANY parser of the process has staged, not by this slot's own history: a pipeline's lanes take
         # forwards of different sizes in turn (merged pairs, single batches at a call's end), and a slot that met only small ones
@@ -206,7 +210,7 @@ class SpectrogramAudioParser(AudioParser):
         # the parser's own upload stream, or the one all parsers of the device share (share_copy_stream: set by a pipeline
         # that also keeps a decode stream busy -- see _shared_copy_stream)
         nbytes = total * dtype.itemsize
-        if getattr(self, "upload_on_compute_stream", False):
+        if self.upload_on_compute_stream:
             # the pipeline's choice: no copy stream at all -- parse_batch uploads on the stream that runs the forward (1.7 ms of a
             # 40 ms forward, while the other forwards in flight keep the device busy).  A forward enqueued behind a cross-stream wait
             # for an upload on another stream found that upload taking 20 ms; measured again at the end of round 4 with
@@ -214,7 +218,7 @@ class SpectrogramAudioParser(AudioParser):
             # 7.58, this 5.89-5.98.
             if slot["dev"] is None or slot["dev"].numel() < nbytes:
                 slot["dev"] = torch.empty(max(nbytes, slot["high"]), dtype=torch.uint8, device="cuda:%d" % self.device)
-            up = getattr(self, "upload_stream", None)
+            up = self.upload_stream
             if up is not None:
                 # the lane's stream is known: the upload goes into it from HERE (the staging thread), behind the lane's running
                 # forward and ahead of this one's kernels -- it starts the moment that forward ends, and a hipMemcpyAsync that
@@ -223,7 +227,7 @@ class SpectrogramAudioParser(AudioParser):
                 self._upload(pcm, slot["buf"][:nbytes], up)
                 return StagedClips(pcm, n, dtype.itemsize, None, slot)
             return StagedClips(slot["buf"][:nbytes], n, dtype.itemsize, None, slot)
-        if getattr(self, "share_copy_stream", False):
+        if self.share_copy_stream:
             up = _shared_copy_stream(self.device)
         else:
             if self._copy_stream is None:

@@ -151,6 +151,33 @@ def test_sequential_mode_reads_a_batch_only_after_the_previous_result():
         assert seen == [want, want, want[:1], want, want]
 
 
+def test_a_pipelined_call_leaves_no_lane_stream_on_the_parsers():
+    """A ``transcribe_batches`` call hands every lane's parser the lane's stream for the uploads issued where the clips are staged;
+    at its end -- run to the end or closed early -- it takes the stream off again.  A parser that kept it would upload a later
+    ``transcribe_batch`` on that stream while the features run on whatever stream is current then, with nothing to order the two.
+    (The attribute is the deterministic part; the strings would show the race only when it is lost.)"""
+    from danspeech_amd import Recognizer
+    model, sd, cfg = _model("small", 64, 3, seed=12)
+    rec = Recognizer(model=model)
+    eng = rec.danspeech_recognizer
+    clips = [syn.make_clip(i, n) for i, n in enumerate([16000, 8000, 12345, 9000, 16000, 11000])]      # 0.5 - 1 s
+    want = eng.transcribe_batch(clips)
+
+    def check():
+        parsers = [eng.audio_parser] + [r[1] for r in eng._replicas]
+        assert len(parsers) == 4 and all(p.upload_stream is None for p in parsers)
+        assert all(p.upload_on_compute_stream for p in parsers)          # (stays: the later batch still uploads by kernel)
+        with torch.cuda.stream(torch.cuda.Stream()):
+            assert eng.transcribe_batch(clips) == want
+
+    assert list(eng.transcribe_batches([clips] * 3)) == [want] * 3
+    check()
+    gen = eng.transcribe_batches([clips] * 3)
+    assert next(gen) == want
+    gen.close()
+    check()
+
+
 def test_staging_slots_are_sized_by_the_largest_forward_of_the_process():
     """A lane's pinned staging slot that has met only small forwards must not re-pin in the middle of a later call when its first
     large forward arrives (82 MB: 16 ms on the staging thread and a blocking upload behind it): every slot in use is as large as
