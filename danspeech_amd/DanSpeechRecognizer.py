@@ -98,6 +98,20 @@ class _StreamingSession(object):
         return piece
 
 
+class LiveSessionHandle:
+    """One live source of ``streaming_listen_many``: its gate (``NativeEndpointer``), the polyphase resampler behind the gate when
+    the source's rate is not the model's, the pass rule (``stream_plan.LivePasses``) and a streaming session of its own."""
+
+    def __init__(self, endpointer, resampler, passes, session, dtype):
+        self.endpointer, self.resampler, self.passes, self.session, self.dtype = endpointer, resampler, passes, session, dtype
+
+    def close(self):
+        self.endpointer.close()
+        if self.resampler is not None:
+            self.resampler.close()
+        self.session.close()
+
+
 class StreamingSessionHandle(object):
     """One utterance of ``DanSpeechRecognizer.streaming_transcribe_many``: its streaming parser, its ``dsmi_stream`` handle
     (conv contexts, recurrent state, lookahead buffer on the GPU) and its running text / outputs / spectrograms."""
@@ -751,6 +765,93 @@ class DanSpeechRecognizer(object):
         state.set_source(self.audio_parser, sample_rate, resample)
         return StreamingSessionHandle(InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index()),
                                       _native.NativeStream(native), state)
+
+    def new_live_session(self, chunk=1024, sample_rate=None, resample="polyphase", energy_threshold=1000, pause_threshold=0.8,
+                         phrase_threshold=0.3, non_speaking_duration=0.35, dtype=np.int16, channels=1):
+        """A live source for ``streaming_listen_many``: continuous audio that nobody has cut into utterances.  ``chunk`` and the
+        four gate parameters are ``listen_stream``'s (reference Recognizer.py:218-324); ``sample_rate`` is the source's rate when
+        it is not the model's -- the gate then runs at the source's rate and what it emits goes through a polyphase
+        ``dsmi_resampler``.  ``resample="ratecv"`` is refused: the gate hands on float64 samples, ``audioop.ratecv`` is defined on
+        integers.  ``dtype`` / ``channels``: the sample type of the parts (int16, two channels allowed; float32; float64)."""
+        from . import _native
+        from .stream_plan import LivePasses
+        if resample == "ratecv":
+            raise ValueError("resample='ratecv' cannot follow the gate (it hands on float64 samples): use 'polyphase'")
+        if resample != "polyphase":
+            raise ValueError("resample method must be 'polyphase'")
+        if not pause_threshold >= non_speaking_duration >= 0:
+            raise ValueError("the gate needs pause_threshold >= non_speaking_duration >= 0")
+        session = self.new_streaming_session()
+        model_rate = int(self.audio_parser.sampling_rate)
+        rate = model_rate if sample_rate is None else int(sample_rate)
+        fe = self.audio_parser._frontend()          # every gate and resampler on ONE frontend: one push_many serves them all
+        ep = rs = None
+        try:
+            ep = _native.NativeEndpointer(fe, chunk, rate, energy_threshold, pause_threshold, phrase_threshold, non_speaking_duration,
+                                          dtype=dtype, channels=channels)
+            if rate != model_rate:
+                rs = _native.NativeResampler(fe, rate, "polyphase", dtype=np.float64)
+        except Exception:
+            if ep is not None:
+                ep.close()
+            session.close()
+            raise
+        return LiveSessionHandle(ep, rs, LivePasses(self.model.context, model_rate), session, np.dtype(dtype))
+
+    def streaming_listen_many(self, sessions, parts, end_of_stream):
+        """One round of live audio for several sources (``new_live_session``): ``parts[k]`` holds session k's new samples, of any
+        length (None or empty for none), ``end_of_stream[k]`` ends its stream after them.  The gate runs for all sessions in one
+        ``dsmi_endpointer_push_many``; what it emits is converted for the sessions of another rate (one ``push_many`` per
+        segment rank), accumulates under ``real_time_streaming``'s pass rule, and the sessions that have a pass due advance in
+        one ``streaming_transcribe_many`` (a session whose round closes an utterance and opens the next has several passes:
+        they run in as many batched calls).  Samples stay on the device from the upload on.
+        -> per session, the ``(is_last, text)`` pairs ``real_time_streaming`` would yield, empty texts left out."""
+        import torch
+        from . import _native
+        n = len(sessions)
+        if not (len(parts) == len(end_of_stream) == n):
+            raise ValueError("sessions, parts and end_of_stream must have one entry per session")
+        if len(set(id(s) for s in sessions)) != n:
+            raise ValueError("a session appears twice in one call")
+        dev = "cuda:%d" % self._device_index()
+        # ---- one upload of all the parts, each in its session's sample type, every part on 8 bytes
+        chunks, offs, size = [], [], 0
+        for k, ses in enumerate(sessions):
+            a = np.zeros(0, dtype=ses.dtype) if parts[k] is None else np.ascontiguousarray(np.asarray(parts[k], dtype=ses.dtype))
+            a = a.reshape(-1).view(np.uint8)
+            if len(a) % ses.endpointer.frame_bytes:
+                raise ValueError("session %d: the part is not a whole number of frames" % k)
+            chunks.append(a)
+            offs.append(size)
+            size += (len(a) + 7) & ~7
+        host = np.zeros(max(size, 8), dtype=np.uint8)
+        for a, o in zip(chunks, offs):
+            host[o:o + len(a)] = a
+        pcm = torch.from_numpy(host).to(dev)
+        segs = _native.NativeEndpointer.push_many([s.endpointer for s in sessions], [pcm[o:o + len(a)] if len(a) else None for a, o in zip(chunks, offs)],
+                                                  [bool(v) for v in end_of_stream])
+        # ---- the sessions of another rate: segment j of each of them in one resampler push; a last mark flushes the utterance
+        conv = [k for k in range(n) if sessions[k].resampler is not None]
+        for j in range(max([len(segs[k]) for k in conv] + [0])):
+            due = [k for k in conv if j < len(segs[k])]
+            outs = _native.NativeResampler.push_many([sessions[k].resampler for k in due], [segs[k][j][0] if segs[k][j][0].numel() else None for k in due],
+                                                     [segs[k][j][1] for k in due])
+            for k, out in zip(due, outs):
+                segs[k][j] = (out, segs[k][j][1])
+        # ---- the passes that are due, rank by rank over the sessions
+        due = [s.passes.feed(segs[k]) for k, s in enumerate(sessions)]
+        said = [[] for _ in sessions]
+        for r in range(max([len(d) for d in due] + [0])):
+            ks = [k for k in range(n) if r < len(due[k])]
+            recs = []
+            for k in ks:
+                tensors = [t for t in due[k][r][0] if t.numel()]
+                recs.append(torch.cat(tensors) if len(tensors) > 1 else (tensors[0] if tensors else torch.empty(0, dtype=torch.float64, device=dev)))
+            texts = self.streaming_transcribe_many([sessions[k].session for k in ks], recs, [due[k][r][2] for k in ks], [due[k][r][1] for k in ks])
+            for k, text in zip(ks, texts):
+                if text:
+                    said[k].append((due[k][r][2], text))
+        return said
 
     def _convert_parts(self, states, parts, flush, take):
         """The parts of the sessions whose source has another rate, converted: one upload of all of them, one

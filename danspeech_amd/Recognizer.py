@@ -17,6 +17,13 @@ from .stream_plan import stream_cut_plan, stream_rounds, resample_count, resampl
 class Recognizer(object):
 
     def __init__(self, model=None, lm=None, with_gpu=False, **kwargs):
+        # the live gate's parameters (reference Recognizer.py:42-62): read when a gate is made (``new_endpointer``)
+        self.energy_threshold = 1000
+        self.pause_threshold = 0.8
+        self.phrase_threshold = 0.3
+        self.non_speaking_duration = 0.35
+        self.dynamic_energy_adjustment_damping = 0.15
+        self.dynamic_energy_ratio = 1.5
         self.danspeech_recognizer = DanSpeechRecognizer(with_gpu=with_gpu, **kwargs)
         self.stream = False
         self.stream_thread_stopper = None
@@ -160,6 +167,128 @@ class Recognizer(object):
         finally:
             for ses in sessions.values():
                 ses.close()
+
+    def stream_live(self, sources, chunk=1024, sample_rate=None, resample="polyphase"):
+        """Continuous audio from many sources -> per-utterance texts: ``real_time_streaming`` (Recognizer.py:560-715) for every
+        source at once, with the listener's gate (``listen_stream``, :218-324), the conversion to the model's rate and the
+        model passes all on the GPU.  ``sources``: a list of iterables of sample arrays of any lengths (int16 -- ``[n, 2]``
+        for two channels --, float32 or float64; a source's first array fixes its type).  Each round takes the next array of
+        every source that still has one; a source that is exhausted ends its stream.  Yields ``(index, is_last, text)`` until
+        every source is exhausted.  ``chunk``: the gate's buffer; ``sample_rate``: the sources' rate, or one per source, when it
+        is not the model's (``resample`` must be "polyphase").  The gate's parameters are this recognizer's
+        ``energy_threshold``, ``pause_threshold``, ``phrase_threshold`` and ``non_speaking_duration`` as they are when a source
+        delivers its first array.  Requires ``enable_real_time_streaming``."""
+        if not getattr(self, "stream", False):
+            raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
+        if resample != "polyphase":
+            raise ValueError("resample='%s' cannot follow the gate (it hands on float64 samples): use 'polyphase'" % (resample,))
+        rec = self.danspeech_recognizer
+        rates = list(sample_rate) if isinstance(sample_rate, (list, tuple)) else [sample_rate] * len(sources)
+        if len(rates) != len(sources):
+            raise ValueError("sample_rate must be one rate or one rate per source")
+        its = [iter(s) for s in sources]
+        live, sessions = set(range(len(its))), {}
+        try:
+            while live:
+                ks, parts, eos = [], [], []
+                for k in sorted(live):
+                    try:
+                        part = np.asarray(next(its[k]))
+                    except StopIteration:
+                        live.discard(k)
+                        if k in sessions:
+                            ks.append(k); parts.append(None); eos.append(True)
+                        continue
+                    if k not in sessions:
+                        if part.dtype not in (np.int16, np.float32, np.float64):
+                            part = part.astype(np.float64)
+                        sessions[k] = rec.new_live_session(chunk, rates[k], resample, self.energy_threshold, self.pause_threshold,
+                                                           self.phrase_threshold, self.non_speaking_duration, dtype=part.dtype,
+                                                           channels=2 if part.ndim == 2 else 1)
+                    ks.append(k); parts.append(part); eos.append(False)
+                if not ks:
+                    continue
+                for k, said in zip(ks, rec.streaming_listen_many([sessions[k] for k in ks], parts, eos)):
+                    for is_last, text in said:
+                        yield k, is_last, text
+        finally:
+            for ses in sessions.values():
+                ses.close()
+
+    # ---- the live gate (Recognizer.py:218-324, :717-818): its parameters, and the two ways the reference tunes the threshold
+    def update_stream_parameters(self, energy_threshold=None, pause_threshold=None, phrase_threshold=None, non_speaing_duration=None):
+        """Recognizer.py:800-818, its misspelt keyword included."""
+        if energy_threshold:
+            self.energy_threshold = energy_threshold
+        if pause_threshold:
+            self.pause_threshold = pause_threshold
+        if phrase_threshold:
+            self.phrase_threshold = phrase_threshold
+        if non_speaing_duration:
+            self.non_speaking_duration = non_speaing_duration
+
+    def new_endpointer(self, chunk=1024, sample_rate=None, dtype=np.int16, channels=1):
+        """A ``NativeEndpointer`` (``dsmi_endpointer``: the gate of ``listen_stream`` over one live stream, on the GPU) with this
+        recognizer's gate parameters as they are now, on the frontend of the engine's parser (``sample_rate``: the stream's
+        rate when it is not the model's)."""
+        from . import _native
+        if not self.pause_threshold >= self.non_speaking_duration >= 0:
+            raise ValueError("the gate needs pause_threshold >= non_speaking_duration >= 0 (Recognizer.py:237)")
+        parser = self.danspeech_recognizer.audio_parser
+        if parser is not None:
+            frontend, model_rate = parser._frontend(), parser.sampling_rate
+        else:                               # no model yet: the gate needs none (the reference tunes its threshold before loading one)
+            if getattr(self, "_gate_frontend", None) is None:
+                self._gate_frontend = _native.NativeFrontend()
+            frontend, model_rate = self._gate_frontend, 16000
+        rate = int(model_rate if sample_rate is None else sample_rate)
+        return _native.NativeEndpointer(frontend, chunk, rate, self.energy_threshold, self.pause_threshold, self.phrase_threshold,
+                                        self.non_speaking_duration, dtype=dtype, channels=channels)
+
+    def _buffer_energies(self, audio, duration, chunk, sample_rate):
+        """``audioop.rms`` of the buffers of ``chunk`` samples the reference would read within ``duration`` seconds
+        (:742-749: while the time elapsed, this buffer included, does not exceed it) -- the ``energies_host`` of one push."""
+        import torch
+        audio = np.asarray(audio)
+        if audio.dtype not in (np.int16, np.float32, np.float64):
+            audio = audio.astype(np.float64)
+        if not torch.cuda.is_available():
+            raise RuntimeError("the gate runs on the GPU")
+        if audio.ndim == 2 and audio.dtype != np.int16:
+            raise ValueError("two channels ([n, 2]) are taken as int16 frames only; fold float audio to one channel first")
+        if audio.ndim > 2 or (audio.ndim == 2 and audio.shape[1] != 2):
+            raise ValueError("audio must be [n] samples or [n, 2] int16 frames")
+        ep = self.new_endpointer(chunk, sample_rate, dtype=audio.dtype, channels=2 if audio.ndim == 2 else 1)
+        try:
+            seconds_per_buffer = (chunk + 0.0) / ep.rate
+            elapsed_time, n = 0, 0
+            while True:
+                elapsed_time += seconds_per_buffer
+                if elapsed_time > duration or (n + 1) * chunk > len(audio):
+                    break
+                n += 1
+            if n == 0:
+                raise ValueError("audio holds less than one whole buffer of %d samples within %r s" % (chunk, duration))
+            pcm = torch.from_numpy(np.ascontiguousarray(audio[:n * chunk])).to("cuda:%d" % ep.frontend.device)
+            return [int(e) for e in ep.push(pcm, return_energies=True)[1]], seconds_per_buffer
+        finally:
+            ep.close()
+
+    def adjust_for_speech(self, audio, duration=4, chunk=1024, sample_rate=None):
+        """Recognizer.py:717-757 over an array holding speech: the threshold becomes the mean buffer energy, less 80 when it is
+        above 80.  Only whole buffers of ``audio`` count."""
+        energy_levels, _ = self._buffer_energies(audio, duration, chunk, sample_rate)
+        energy_average = sum(energy_levels) / len(energy_levels)
+        self.energy_threshold = energy_average - 80 if energy_average > 80 else energy_average
+
+    def adjust_for_ambient_noise(self, audio, duration=2, chunk=1024, sample_rate=None):
+        """Recognizer.py:759-797 over an array holding background noise: the damped average towards
+        ``dynamic_energy_ratio`` times each buffer's energy."""
+        energy_levels, seconds_per_buffer = self._buffer_energies(audio, duration, chunk, sample_rate)
+        for energy in energy_levels:
+            damping = self.dynamic_energy_adjustment_damping ** seconds_per_buffer
+            target_energy = energy * self.dynamic_energy_ratio
+            self.energy_threshold = self.energy_threshold * damping + target_energy * (1 - damping)
 
     def _other_rate(self, sample_rate):
         return sample_rate is not None and int(sample_rate) != int(self.danspeech_recognizer.audio_parser.sampling_rate)

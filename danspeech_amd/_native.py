@@ -50,6 +50,13 @@ class ModelDesc(C.Structure):
     ]
 
 
+class EndpointerDesc(C.Structure):
+    _fields_ = [
+        ("chunk", C.c_int32), ("rate", C.c_int32), ("pcm_dtype", C.c_int32), ("energy_threshold", C.c_double),
+        ("pause_threshold", C.c_double), ("phrase_threshold", C.c_double), ("non_speaking_duration", C.c_double),
+    ]
+
+
 class FrontendDesc(C.Structure):
     _fields_ = [
         ("sample_rate", C.c_int32), ("window_size", C.c_double), ("window_stride", C.c_double),
@@ -87,6 +94,16 @@ _PROTOS = {
     "dsmi_resampler_position": (C.c_int, [_vp, _i64p, _i64p]),
     "dsmi_resample_ready": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
     "dsmi_resampler_push_many": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "dsmi_endpoint_counts": (C.c_int, [_vp, _vp]),
+    "dsmi_endpoint_gate": (C.c_int64, [C.c_double, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp,
+                                       C.c_int64, _vp]),
+    "dsmi_endpointer_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "dsmi_endpointer_destroy": (None, [_vp]),
+    "dsmi_endpointer_last_error": (C.c_char_p, [_vp]),
+    "dsmi_endpointer_reset": (C.c_int, [_vp]),
+    "dsmi_endpointer_position": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    "dsmi_endpointer_push_many": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp,
+                                            _vp]),
     "dsmi_stream_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dsmi_stream_destroy": (None, [_vp]),
     "dsmi_stream_last_error": (C.c_char_p, [_vp]),
@@ -665,6 +682,175 @@ class NativeResampler:
     def close(self):
         if getattr(self, "_h", None):
             lib().dsmi_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ENDPOINT_MAX = 256       # DSMI_ENDPOINT_MAX: sessions of one dsmi_endpointer_push_many call
+
+
+def endpoint_counts(chunk, rate, pause_threshold=0.8, phrase_threshold=0.3, non_speaking_duration=0.35, energy_threshold=1000, pcm_dtype=0):
+    """dsmi_endpoint_counts (host only): (pause_n, phrase_n, keep_n), the gate's buffer counts for a source of ``chunk`` / ``rate``."""
+    d = EndpointerDesc(int(chunk), int(rate), int(pcm_dtype), float(energy_threshold), float(pause_threshold), float(phrase_threshold),
+                       float(non_speaking_duration))
+    out = np.zeros(3, dtype=np.int64)
+    rc = lib().dsmi_endpoint_counts(C.byref(d), _np_ptr(out))
+    if rc != 0:
+        raise DsmiError(rc, "bad endpointer parameters")
+    return tuple(int(v) for v in out)
+
+
+def endpoint_gate(energy_threshold, pause_n, phrase_n, keep_n, state, sums, lens, end_of_stream=False, max_events=None):
+    """dsmi_endpoint_gate (host only): one session's gate over a run of buffers given by their sums of squares and sample counts.
+    ``state``: int64[4], updated in place.  -> (events int64 [k, 3] of (first_buffer, n_buffers, last), energies uint32[n])."""
+    sums = np.ascontiguousarray(sums, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.int64)
+    n = len(sums)
+    if len(lens) != n or state.dtype != np.int64 or len(state) != 4:
+        raise ValueError("sums and lens must have one entry per buffer; state is int64[4]")
+    cap = n + 1 if max_events is None else int(max_events)
+    first = np.zeros(max(cap, 1), dtype=np.int64); count = np.zeros(max(cap, 1), dtype=np.int64); last = np.zeros(max(cap, 1), dtype=np.int32)
+    e = np.zeros(max(n, 1), dtype=np.uint32)
+    k = lib().dsmi_endpoint_gate(float(energy_threshold), int(pause_n), int(phrase_n), int(keep_n), _np_ptr(state), _np_ptr(sums), _np_ptr(lens),
+                                 n, int(bool(end_of_stream)), _np_ptr(first), _np_ptr(count), _np_ptr(last), cap, _np_ptr(e))
+    if k < 0:
+        raise DsmiError(int(k), "bad gate arguments")
+    if k > cap:
+        raise DsmiError(DSMI_ERR_CAPACITY, "%d events, room for %d" % (k, cap))
+    return np.stack([first[:k], count[:k], last[:k].astype(np.int64)], axis=1), e[:n]
+
+
+class NativeEndpointer:
+    """Owns one dsmi_endpointer handle: the energy gate of ``Recognizer.listen_stream`` over one continuous stream that arrives in
+    pushes of any size.  ``dtype``: the pushes' sample type (int16 / float32 / float64), ``channels=2`` for interleaved int16
+    frames.  However the stream is cut into pushes, the segments laid end to end and the last marks are those of one push."""
+
+    def __init__(self, frontend, chunk=1024, rate=16000, energy_threshold=1000, pause_threshold=0.8, phrase_threshold=0.3,
+                 non_speaking_duration=0.35, dtype=np.int16, channels=1, pcm_dtype=None):
+        if pcm_dtype is None:
+            pcm_dtype = PCM_DTYPES[np.dtype(dtype)] | (NativeFrontend.PCM_STEREO if channels == 2 else 0)
+        self.frontend, self.chunk, self.rate, self.pcm_dtype = frontend, int(chunk), int(rate), int(pcm_dtype)
+        self.frame_bytes = NativeResampler._BYTES.get(self.pcm_dtype & 15, 1) * (2 if self.pcm_dtype & NativeFrontend.PCM_STEREO else 1)
+        d = EndpointerDesc(self.chunk, self.rate, self.pcm_dtype, float(energy_threshold), float(pause_threshold), float(phrase_threshold),
+                           float(non_speaking_duration))
+        h = _vp()
+        rc = lib().dsmi_endpointer_create(frontend._h, C.byref(d), C.byref(h))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_endpointer_last_error(None) or b"").decode())
+        self._h = h
+        self._ended = False
+
+    def position(self):
+        """(samples consumed since the stream began, utterances closed, samples held on the device)."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = lib().dsmi_endpointer_position(self._h, C.byref(a), C.byref(b), C.byref(c))
+        if rc != 0:
+            raise DsmiError(rc, "dsmi_endpointer_position failed")
+        return a.value, b.value, c.value
+
+    def _frames(self, pcm):
+        if pcm is None:
+            return 0
+        nbytes = pcm.numel() * pcm.element_size()
+        if nbytes % self.frame_bytes:
+            raise ValueError("the push is not a whole number of samples of the endpointer's type")
+        return nbytes // self.frame_bytes
+
+    @staticmethod
+    def push_many(endpointers, pcms, end_of_stream, return_energies=False):
+        """dsmi_endpointer_push_many: the next samples of several streams (distinct handles of one frontend) in one call.
+        ``pcms[i]``: a contiguous CUDA tensor in the handle's sample type (``None`` or empty for no samples);
+        ``end_of_stream[i]`` ends that stream after them.  -> a list, per session, of its segments ``(float64 CUDA tensor, last)``
+        in order (views of one buffer) -- and, with ``return_energies``, a list of uint32 arrays: the energy of every buffer the
+        session gated in this call.  One host synchronisation.  Longer lists than ENDPOINT_MAX run as several calls, after
+        everything that could refuse one of them has been looked for in all of them."""
+        import torch
+        n = len(endpointers)
+        if not (len(pcms) == len(end_of_stream) == n):
+            raise ValueError("endpointers, pcms and end_of_stream must have one entry per session")
+        if n > ENDPOINT_MAX:
+            # several native calls: what would refuse a later one is looked for in all of them first, so that a refusal finds
+            # every handle as it was
+            if len(set(id(e) for e in endpointers)) != n:
+                raise ValueError("an endpointer appears twice")
+            for i, (e, p) in enumerate(zip(endpointers, pcms)):
+                if not getattr(e, "_h", None) or not getattr(e.frontend, "_h", None):
+                    raise ValueError("session %d: the endpointer or its frontend has been closed" % i)
+                if e.frontend is not endpointers[0].frontend:
+                    raise ValueError("session %d: the endpointer belongs to another frontend" % i)
+                if p is not None and not (p.is_cuda and p.is_contiguous()):
+                    raise ValueError("pushes must be contiguous CUDA tensors")
+                if e._frames(p) > 0 and e._ended:
+                    raise ValueError("session %d: samples after end_of_stream: reset the session first" % i)
+            segs, ens = [], []
+            for k in range(0, n, ENDPOINT_MAX):
+                sl = slice(k, k + ENDPOINT_MAX)
+                r = NativeEndpointer.push_many(endpointers[sl], pcms[sl], end_of_stream[sl], return_energies)
+                segs += r[0] if return_energies else r
+                ens += r[1] if return_energies else []
+            return (segs, ens) if return_energies else segs
+        if n == 0:
+            return ([], []) if return_energies else []
+        fe = endpointers[0].frontend
+        for i, e in enumerate(endpointers):
+            if not getattr(e, "_h", None) or not getattr(e.frontend, "_h", None):
+                raise ValueError("session %d: the endpointer or its frontend has been closed" % i)
+        for p in pcms:
+            if p is not None and not (p.is_cuda and p.is_contiguous()):
+                raise ValueError("pushes must be contiguous CUDA tensors")
+        ns = np.array([e._frames(p) for e, p in zip(endpointers, pcms)], dtype=np.int64)
+        # (a stream that has ended gates nothing more until it is reset)
+        eos = np.array([int(bool(v) and not e._ended) for e, v in zip(endpointers, end_of_stream)], dtype=np.int32)
+        # the worst case the library sizes: all a session holds and is given, one segment per gated buffer and one more
+        nb = np.zeros(n, dtype=np.int64)
+        cap_out = 0
+        for i, e in enumerate(endpointers):
+            n_in, _, held = e.position()
+            total = n_in + int(ns[i])
+            nb[i] = total // e.chunk - n_in // e.chunk + (1 if eos[i] and total % e.chunk else 0)
+            cap_out += held + int(ns[i])
+        cap_seg = int(nb.sum()) + n
+        out = torch.empty(max(cap_out, 1), dtype=torch.float64, device="cuda:%d" % fe.device)
+        seg_session = np.zeros(cap_seg, dtype=np.int32); seg_len = np.zeros(cap_seg, dtype=np.int64); seg_last = np.zeros(cap_seg, dtype=np.int32)
+        energies = np.zeros(max(int(nb.sum()), 1), dtype=np.uint32)
+        hs = (C.c_void_p * n)(*[e._h for e in endpointers])
+        pp = (C.c_void_p * n)(*[(p.data_ptr() if p is not None and p.numel() else None) for p in pcms])
+        found = C.c_int(0)
+        rc = lib().dsmi_endpointer_push_many(hs, n, pp, _np_ptr(ns), _np_ptr(eos), out.data_ptr(), cap_out, _np_ptr(seg_session), _np_ptr(seg_len),
+                                             _np_ptr(seg_last), cap_seg, C.byref(found), _np_ptr(energies), _stream(fe.device))
+        if rc != 0:
+            raise DsmiError(rc, (lib().dsmi_endpointer_last_error(None) or b"").decode())
+        for e, v in zip(endpointers, eos):
+            e._ended = e._ended or bool(v)
+        segs = [[] for _ in range(n)]
+        off = 0
+        for k in range(found.value):
+            segs[int(seg_session[k])].append((out[off:off + int(seg_len[k])], bool(seg_last[k])))
+            off += int(seg_len[k])
+        if not return_energies:
+            return segs
+        cuts = np.concatenate(([0], np.cumsum(nb)))
+        return segs, [energies[int(cuts[i]):int(cuts[i + 1])].copy() for i in range(n)]
+
+    def push(self, pcm, end_of_stream=False, return_energies=False):
+        """One push of this stream -> its segments [(float64 CUDA tensor, last), ...]."""
+        r = NativeEndpointer.push_many([self], [pcm], [end_of_stream], return_energies)
+        return (r[0][0], r[1][0]) if return_energies else r[0]
+
+    def reset(self):
+        rc = lib().dsmi_endpointer_reset(self._h)
+        if rc != 0:
+            raise DsmiError(rc, "dsmi_endpointer_reset failed")
+        self._ended = False
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dsmi_endpointer_destroy(self._h)
             self._h = None
 
     def __del__(self):

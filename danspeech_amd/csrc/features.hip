@@ -539,6 +539,7 @@ extern "C" void dsmi_frontend_destroy(dsmi_frontend* f) {
     if (f->offs) (void)hipFree(f->offs);
     if (f->stage) (void)hipHostFree(f->stage);
     fe_resample_release(f);
+    fe_endpoint_release(f);
     for (hipEvent_t e : f->stage_ev) if (e) (void)hipEventDestroy(e);
     delete f;
 }

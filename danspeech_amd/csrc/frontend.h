@@ -31,6 +31,9 @@ struct dsmi_frontend {
     int64_t* rs_meta = nullptr; int rs_cap = 0;
     // dsmi_resampler_push_many: the sessions' descriptor table on the device, sized for DSMI_RESAMPLE_STREAM_MAX sessions (resample_stream.hip)
     int64_t* rss_desc = nullptr;
+    // dsmi_endpointer_push_many: the device table (sessions, then kernel 2's copies) and the pinned per-buffer sums (endpoint.hip)
+    int64_t* ep_tab = nullptr; int64_t ep_tab_cap = 0;
+    uint64_t* ep_sums = nullptr; int64_t ep_sums_cap = 0;
 };
 
 // host[0..n) -> dev[0..n) on stream s through the frontend's pinned ring (features.hip)
@@ -42,6 +45,8 @@ bool fe_stage_reserve(dsmi_frontend* f, int n);
 void fe_set_thread_error(const char* msg);
 // frees what dsmi_resample and dsmi_resampler_push_many keep on the handle (resample.hip; the device is current and idle)
 void fe_resample_release(dsmi_frontend* f);
+// frees what dsmi_endpointer_push_many keeps on the handle (endpoint.hip; the device is current and idle)
+void fe_endpoint_release(dsmi_frontend* f);
 
 namespace dsmi {
 

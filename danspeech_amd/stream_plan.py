@@ -99,3 +99,50 @@ def resample_feed_plan(plan, n_source, rate_in, rate_out=16000, method="polyphas
         flushed = flushed or flush
         pos = upto
     return feed
+
+
+# ---- live audio: the pass rule of real_time_streaming (reference Recognizer.py:602-611, :664-715) without its sleeps
+def live_requirements(lookahead_context, sample_rate):
+    """(first_sample_requirement, general_sample_requirement) of :602-611."""
+    required_spec_frames = (lookahead_context - 1) * 2
+    samples_pr_10ms = int(sample_rate / 100)
+    general = samples_pr_10ms * 2 + (samples_pr_10ms * (required_spec_frames - 1))
+    return general + samples_pr_10ms * 15, general
+
+
+class LivePasses:
+    """One live session's side of ``real_time_streaming``: the segments the gate emits accumulate, and ``feed`` says which
+    ``streaming_transcribe`` passes are due.  A round's segments are taken up to a ``last`` mark (the reference drains its queue
+    the same way, :627-662), then the rule runs once: the first pass of an utterance as soon as ``first`` samples are there,
+    later ones at ``general``, a ``last`` mark passes whatever has accumulated with ``is_last``.  A ``last`` mark that arrives
+    before the first pass makes no pass (:668-669) -- and, as in the reference, what had accumulated is not cleared: those
+    samples stand in front of the next utterance's.  Segments are anything with a ``len``; they are handed back, not joined."""
+
+    def __init__(self, lookahead_context, sample_rate):
+        self.first, self.general = live_requirements(lookahead_context, sample_rate)
+        self.parts, self.n, self.is_first_pass = [], 0, True
+
+    def feed(self, segments):
+        """``segments``: [(samples, last), ...] in order -> [(parts, is_first, is_last), ...], the passes to make now, each a
+        list of segments to lay end to end."""
+        out = []
+        queue = list(segments)
+        while queue:
+            is_last = False
+            while queue and not is_last:
+                samples, is_last = queue.pop(0)
+                self.parts.append(samples)
+                self.n += len(samples)
+            if self.is_first_pass:
+                if not is_last and self.n >= self.first:
+                    out.append((self._take(), True, False))
+                    self.is_first_pass = False
+            elif is_last or self.n >= self.general:
+                out.append((self._take(), False, bool(is_last)))
+            if is_last:
+                self.is_first_pass = True
+        return out
+
+    def _take(self):
+        parts, self.parts, self.n = self.parts, [], 0
+        return parts

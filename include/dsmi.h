@@ -194,6 +194,83 @@ int64_t dsmi_resample_ready(int method, int rate_in, int rate_out, int64_t n_in)
 int dsmi_resampler_push_many(dsmi_resampler* const* rs, int n, const void* const* pcm_dev, const int64_t* n_samples,
                              const int* is_last, double* out_dev, int64_t out_capacity, int64_t* n_out_host, void* stream);
 
+/* ---- Utterances in LIVE audio: Recognizer.listen_stream (Recognizer.py:218-324), the energy gate that cuts a continuous stream
+ * into utterances, for up to DSMI_ENDPOINT_MAX sessions per call.  A dsmi_endpointer is one stream in flight.  It belongs to a
+ * frontend; everything in dsmi_endpointer_desc is fixed at creation.  Destroy the handles of a frontend before the frontend.
+ * The stream is read in buffers of `chunk` samples (16 .. 65536; the stream's final buffer may be shorter).  A buffer's energy is
+ * audioop.rms(buffer, 2) = (unsigned) sqrt(S / (double) len), S the sum of its squared samples: the device delivers the exact
+ * integer S, the host takes the root with libm.  With spb = chunk / rate (float64), pause_n = ceil(pause_threshold / spb),
+ * phrase_n and keep_n (non_speaking_duration) likewise (:239-245):
+ *   waiting   the last keep_n buffers are kept, the one just read among them; energy > energy_threshold emits the kept buffers
+ *             and starts a phrase with both counts at 0;
+ *   phrase    phrase_count += 1; energy > threshold sets pause_count = 0, otherwise pause_count += 1; while pause_count <= pause_n
+ *             the buffer is emitted; else the phrase ends: phrase_count -= pause_count, and with phrase_count >= phrase_n the
+ *             breaking buffer is emitted with last = 1 (the session stands at the start of a new utterance), otherwise the
+ *             breaking buffer is dropped and the session waits again, with nothing kept, inside the same utterance;
+ *   end       end_of_stream behaves as the empty read does: the stream's short final buffer is gated like any other, then a waiting
+ *             session emits what it keeps, and a segment of 0 samples closes the utterance with last = 1.
+ * timeout and phrase_time_limit are not taken over.
+ * Sample types: DSMI_PCM_I16, I16 | STEREO (the saturating fold of audioop.tomono(.., 1, 1), as SpeechFileStream.read applies it),
+ * F32 and F64.  Float samples enter S as llrint(x) saturated to int16 and are FORWARDED UNCHANGED.  U8, I24 and I32 are refused at
+ * creation (DSMI_ERR_INVALID): the reference's 8-bit rms reads the unsigned bytes as signed, and sums of squared 24/32-bit samples
+ * are not exact in float64, so neither could be matched exactly.
+ * dsmi_endpoint_counts (host only): {pause_n, phrase_n, keep_n} of a desc, < 0 for a desc that create would refuse.
+ * dsmi_endpoint_gate (host only): the state machine over n_buffers buffers given by their sums S[i] and sample counts len[i].
+ * state4 = {phase (0 waiting, 1 phrase), kept, phrase_count, pause_count}, all 0 at the start of a stream, is read and updated.
+ * Events (first_buffer, n_buffers, last) are appended: first_buffer counts from the run's first buffer and is negative where the
+ * event begins in the buffers kept from earlier runs.  What the reference yields one buffer at a time is joined: an event is a run
+ * of consecutive buffers, ended by a last mark, a dropped buffer or the end of the run.  Returns the number of events (at most
+ * n_buffers + 1 ; only max_events are stored), < 0 for bad arguments.  energies (optional) receives the n_buffers energies.
+ * dsmi_endpointer_push_many hands n distinct handles of one frontend their next samples (1 <= n <= DSMI_ENDPOINT_MAX; chunks,
+ * thresholds and sample types may differ): pcm_dev[i] holds n_samples[i] >= 0 new samples of session i (frames for stereo; may be
+ * NULL for 0); end_of_stream[i] ends the stream after them.  Kernel 1 sums the squares of every buffer that is complete now (one
+ * wave per buffer) into pinned host memory; one synchronisation of `stream`; the host runs dsmi_endpoint_gate for every session;
+ * kernel 2 writes the emitted segments back to back to out_dev, in event order (session by session), as float64 at integer scale
+ * -- what dsmi_features_stream_many(DSMI_PCM_F64) and a polyphase dsmi_resampler take -- and each session's retained tail: the
+ * kept buffers of a waiting session and the incomplete buffer at the end of the push, at most (keep_n + 1) chunk samples.
+ * seg_session / seg_len / seg_last [max_segments] receive the segments, *n_segments their number.  energies_host (optional)
+ * receives the energy of every buffer gated in this call, session by session: session i gates
+ * (consumed + n_samples) / chunk - consumed / chunk buffers, and one more at end_of_stream when a short final buffer remains.
+ * Two launches and one synchronisation per call whatever n (no first launch and no synchronisation for a call that completes no
+ * buffer; the second launch is repeated per 65535 copies, which takes a push of tens of thousands of buffers).  No device or pinned
+ * memory is allocated after a frontend's first push unless one call gates more than 16 buffers per session of 256 (the tables then
+ * grow, which waits for the device); the call's host-side scratch (the plan, the tables' host images, the events) is ordinary
+ * heap memory taken and released per call.  More than 2^27 buffers in one call are refused like the other bad arguments.
+ * The defining property: however a stream is cut into pushes -- pushes of one sample, empty pushes, a push that spans three
+ * utterances --, the segments laid end to end and the positions of the last marks are BIT FOR BIT those of one push of the whole
+ * stream with end_of_stream.  Where a cut falls may split or join segments, never change the samples or the marks.
+ * Refused before any launch, with every handle left exactly as it was and nothing written: n out of range, a handle listed twice,
+ * handles of two frontends, a negative count, samples after a session's end_of_stream without a reset (DSMI_ERR_INVALID);
+ * out_capacity below the worst case sum(held_i + n_samples_i), or max_segments below the worst case, the sum over the sessions
+ * that gate b_i > 0 buffers or end of b_i + 1 (DSMI_ERR_CAPACITY).  The error text (dsmi_endpointer_last_error(NULL): the thread's
+ * last refusal) names the session index.
+ * dsmi_endpointer_position: samples consumed since the stream began, utterances closed, samples held on the device.
+ * dsmi_endpointer_reset: a fresh stream. */
+typedef struct dsmi_endpointer dsmi_endpointer;
+#define DSMI_ENDPOINT_MAX 256
+typedef struct {
+    int32_t chunk;                  /* samples per buffer (source.chunk), 16 .. 65536            */
+    int32_t rate;                   /* the source's sampling rate                               */
+    int32_t pcm_dtype;              /* DSMI_PCM_I16, I16 | STEREO, F32, F64                      */
+    double  energy_threshold;       /* Recognizer.energy_threshold (1000)                        */
+    double  pause_threshold;        /* seconds (0.8)                                             */
+    double  phrase_threshold;       /* seconds (0.3)                                             */
+    double  non_speaking_duration;  /* seconds (0.35); pause_threshold >= non_speaking_duration >= 0 */
+} dsmi_endpointer_desc;
+int dsmi_endpoint_counts(const dsmi_endpointer_desc* desc, int64_t* counts3);
+int64_t dsmi_endpoint_gate(double energy_threshold, int64_t pause_n, int64_t phrase_n, int64_t keep_n, int64_t* state4,
+                           const uint64_t* S, const int64_t* len, int64_t n_buffers, int end_of_stream, int64_t* ev_first,
+                           int64_t* ev_count, int32_t* ev_last, int64_t max_events, uint32_t* energies);
+int dsmi_endpointer_create(dsmi_frontend* f, const dsmi_endpointer_desc* desc, dsmi_endpointer** out);
+void dsmi_endpointer_destroy(dsmi_endpointer* e);
+const char* dsmi_endpointer_last_error(const dsmi_endpointer* e);
+int dsmi_endpointer_reset(dsmi_endpointer* e);
+int dsmi_endpointer_position(const dsmi_endpointer* e, int64_t* n_in, int64_t* n_utterances, int64_t* n_held);
+int dsmi_endpointer_push_many(dsmi_endpointer* const* es, int n, const void* const* pcm_dev, const int64_t* n_samples,
+                              const int* end_of_stream, double* out_dev, int64_t out_capacity, int32_t* seg_session,
+                              int64_t* seg_len, int32_t* seg_last, int max_segments, int* n_segments, uint32_t* energies_host,
+                              void* stream);
+
 /* ---- InferenceSpectrogramAudioParser.parse_audio (parsers.py:102-164), the arithmetic half: STFT of the
  * samples WITHOUT centre padding (librosa.stft(center=False), :137-138: 1 + (n - n_fft)/hop frames), log1p|.|,
  * then the adaptive normalisation of :146-161.  state3 = {input_mean, input_std, alpha} is read and updated

@@ -86,6 +86,35 @@ static int run_plan(int argc, char** argv) {
         if (found < 0 || s0[(size_t)cap] != -7 || s1[(size_t)cap] != -7) return 5;
         for (int k = 0; k < std::min(found, cap); ++k)
             if (s0[(size_t)k] < 0 || s1[(size_t)k] <= s0[(size_t)k] || s1[(size_t)k] > nhops * step || (k && s0[(size_t)k] < s1[(size_t)k - 1] - 2 * (int64_t)step)) return 5;
+        // the live gate: random energies in random runs, fewer event slots than events now and then; nothing past the slots is
+        // written, every event lies inside the buffers seen so far (kept ones before the run included) and in stream order
+        {
+            const GateParams gp{1000.0, (int64_t)(rng() % 5), (int64_t)(rng() % 4), (int64_t)(rng() % 4)};
+            GateState st;
+            int64_t seen = 0, end_prev = 0;
+            for (int run = 0; run < 4; ++run) {
+                const int64_t nb = (int64_t)(rng() % 40);
+                std::vector<uint64_t> S((size_t)nb);
+                std::vector<int64_t> len((size_t)nb, 1024);
+                for (auto& v : S) v = (rng() % 3) ? 0u : (uint64_t)2000 * 2000 * 1024;
+                const int64_t gcap = (int64_t)(rng() % 8);
+                std::vector<int64_t> f0((size_t)gcap + 1, -7), c0((size_t)gcap + 1, -7);
+                std::vector<int32_t> l0((size_t)gcap + 1, -7);
+                std::vector<uint32_t> en((size_t)nb + 1, 7u);
+                GateEvents ev{f0.data(), c0.data(), l0.data(), gcap};
+                const int64_t kept_before = st.kept;
+                const int64_t closed = endpoint_gate(gp, st, S.data(), len.data(), nb, run == 3, ev, en.data());
+                if (closed < 0 || ev.n < 0 || ev.n > nb + 1 || f0[(size_t)gcap] != -7 || c0[(size_t)gcap] != -7 || l0[(size_t)gcap] != -7 || en[(size_t)nb] != 7u) return 6;
+                if (st.kept < 0 || st.kept > gp.keep_n || (st.phase != 0 && st.phase != 1)) return 6;
+                for (int64_t k = 0; k < std::min(ev.n, gcap); ++k) {
+                    const int64_t a = seen + f0[(size_t)k], b = a + c0[(size_t)k];
+                    if (f0[(size_t)k] < -kept_before || c0[(size_t)k] < 0 || b > seen + nb || a < end_prev) return 6;
+                    end_prev = b;
+                }
+                if (ev.n > gcap) end_prev = 0;      // events past the slots are counted, not stored: their ranges are unknown here
+                seen += nb;
+            }
+        }
     }
     std::printf("plans and gates ok\n");
     return 0;
