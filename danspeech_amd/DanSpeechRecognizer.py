@@ -171,6 +171,20 @@ def _words(text, spans, token_probs, frame_s):
     return words
 
 
+def _packed_upload(chunks, device):
+    """uint8 arrays -> (one uint8 tensor on ``device`` that holds them all, where each starts): one host buffer of at least 8
+    bytes in which every chunk starts on 8 bytes, one copy to the device."""
+    import torch
+    offs, size = [], 0
+    for a in chunks:
+        offs.append(size)
+        size += (len(a) + 7) & ~7
+    host = np.zeros(max(size, 8), dtype=np.uint8)
+    for a, o in zip(chunks, offs):
+        host[o:o + len(a)] = a
+    return torch.from_numpy(host).to(device), offs
+
+
 _SIDE_STREAMS = {}        # (name, device index) -> torch.cuda.Stream, shared by every engine of the process: see _side_stream
 
 
@@ -815,19 +829,14 @@ class DanSpeechRecognizer(object):
             raise ValueError("a session appears twice in one call")
         dev = "cuda:%d" % self._device_index()
         # ---- one upload of all the parts, each in its session's sample type, every part on 8 bytes
-        chunks, offs, size = [], [], 0
+        chunks = []
         for k, ses in enumerate(sessions):
             a = np.zeros(0, dtype=ses.dtype) if parts[k] is None else np.ascontiguousarray(np.asarray(parts[k], dtype=ses.dtype))
             a = a.reshape(-1).view(np.uint8)
             if len(a) % ses.endpointer.frame_bytes:
                 raise ValueError("session %d: the part is not a whole number of frames" % k)
             chunks.append(a)
-            offs.append(size)
-            size += (len(a) + 7) & ~7
-        host = np.zeros(max(size, 8), dtype=np.uint8)
-        for a, o in zip(chunks, offs):
-            host[o:o + len(a)] = a
-        pcm = torch.from_numpy(host).to(dev)
+        pcm, offs = _packed_upload(chunks, dev)
         segs = _native.NativeEndpointer.push_many([s.endpointer for s in sessions], [pcm[o:o + len(a)] if len(a) else None for a, o in zip(chunks, offs)],
                                                   [bool(v) for v in end_of_stream])
         # ---- the sessions of another rate: segment j of each of them in one resampler push; a last mark flushes the utterance
@@ -869,7 +878,7 @@ class DanSpeechRecognizer(object):
         due = [k for k, ses in enumerate(states) if ses.resampler is not None]
         if not due:
             return parts
-        chunks, offs, size = [], [], 0
+        chunks = []
         for k in due:
             a = np.asarray(parts[k]).reshape(-1)
             if states[k].source[1] == "ratecv" and a.dtype != np.int16:
@@ -882,14 +891,8 @@ class DanSpeechRecognizer(object):
             have = (0 if states[k].pending is None else states[k].pending.numel()) + states[k].resampler._due(len(a), bool(flush[k]))
             if take[k] is not None and int(take[k]) > have:
                 raise ValueError("session %d: %d converted samples asked for, %d are final" % (k, int(take[k]), have))
-            a = np.ascontiguousarray(a).view(np.uint8)
-            chunks.append(a)
-            offs.append(size)
-            size += (len(a) + 7) & ~7                  # every chunk starts on 8 bytes
-        host = np.zeros(max(size, 8), dtype=np.uint8)
-        for a, o in zip(chunks, offs):
-            host[o:o + len(a)] = a
-        pcm = torch.from_numpy(host).to("cuda:%d" % self._device_index())
+            chunks.append(np.ascontiguousarray(a).view(np.uint8))
+        pcm, offs = _packed_upload(chunks, "cuda:%d" % self._device_index())
         outs = _native.NativeResampler.push_many([states[k].resampler for k in due], [pcm[o:o + len(a)] for a, o in zip(chunks, offs)],
                                                  [bool(flush[k]) for k in due])
         parts = list(parts)

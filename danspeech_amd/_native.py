@@ -15,11 +15,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instantiations and A/B switches that libdsmi.so does not carry)
 LIB_PATH = os.environ.get("DSMI_LIBRARY") or os.path.join(_HERE, "lib", "libdsmi.so")
 
+# The values of include/dsmi.h, restated (tests/test_native_binding_host.py holds every one of them against the header).
 RNN_TYPES = {"gru": 0, "lstm": 1, "rnn": 2}
 WINDOWS = {"hamming": 0, "hann": 1, "blackman": 2, "bartlett": 3}
 PCM_DTYPES = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
+WAV_WIDTH_DTYPE = {1: 3, 2: 0, 3: 4, 4: 5}            # sample width in bytes -> DSMI_PCM_{U8,I16,I24,I32}
+PCM_STEREO = 16
+_PCM_BYTES = (2, 4, 8, 1, 3, 4)                       # DSMI_PCM_* (without the stereo bit) -> bytes per sample
 PAD_MODES = {"reflect": 0, "constant": 1}
 RESAMPLE_METHODS = {"polyphase": 0, "ratecv": 1}      # DSMI_RESAMPLE_*
+RESAMPLE_STREAM_MAX = 256       # sessions of one dsmi_resampler_push_many call
+ENDPOINT_MAX = 256              # sessions of one dsmi_endpointer_push_many call
+STREAM_MANY_MAX = 256           # sessions of one dsmi_stream_forward_many call
+BEAM_STREAM_MANY_MAX = 4096     # streams of one dsmi_beam_stream_advance_many launch
+ALIGN_MAX_TOKENS = 4096         # the longest transcript dsmi_align takes (L_stride)
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -233,11 +242,131 @@ def lib():
 
 
 def _np_ptr(a):
-    return a.ctypes.data_as(_vp)
+    return a.ctypes.data_as(_vp)       # (the pointer keeps ``a`` alive)
 
 
-class NativeModel:
+def _stream(device=None):
+    """The torch stream current on ``device`` (the HANDLE's device, not torch's current device)."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class _Handle:
+    """Owns one native handle, ``_h``.  A subclass names the two entry points that go with it: ``_destroy`` and ``_last_error``
+    (which, given no handle, tells the calling thread's last error: that of a failed create or of a call over many handles)."""
+    _destroy = _last_error = None
+    _host_only = False      # no GPU behind the handle: making one says nothing to want_hw_queues
+    _finalise = True        # close when the object is collected
+
+    def _create(self, create, *args):
+        if not self._host_only:
+            _handles[0] += 1
+        h = _vp()
+        self._check_thread(getattr(lib(), create)(*args, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def _error(cls, h=None):
+        return (getattr(lib(), cls._last_error)(h) or b"").decode()
+
+    @classmethod
+    def _check_thread(cls, rc):
+        if rc != 0:
+            raise DsmiError(rc, cls._error())
+
+    def _check(self, rc):
+        if rc != 0:
+            raise DsmiError(rc, self._error(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        if self._finalise:
+            try:
+                self.close()
+            except Exception:
+                pass
+
+
+# ---- the DSMI_PCM_* code of a buffer
+_TORCH_CODES = {}       # torch dtype -> DSMI_PCM_*: PCM_DTYPES by name, made when the first tensor arrives (torch stays a lazy import)
+
+
+def _pcm_code(dtype, wav_format=None, n_frames=None, nbytes=None):
+    """DSMI_PCM_* of samples of ``dtype`` (numpy or torch: int16 / float32 / float64) -- or, with ``wav_format=(sample_width,
+    channels)``, of the raw frames of a PCM WAV file, which a tensor holds as uint8 (``dtype`` None: there is no tensor yet).
+    ``n_frames`` with ``nbytes``: the frames must fill a buffer of that many bytes."""
+    of_torch = type(dtype).__module__ == "torch"
+    if of_torch:
+        import torch
+    if wav_format is None:
+        if not of_torch:
+            return PCM_DTYPES[np.dtype(dtype)]
+        if not _TORCH_CODES:
+            _TORCH_CODES.update((getattr(torch, d.name), code) for d, code in PCM_DTYPES.items())
+        return _TORCH_CODES[dtype]
+    width, channels = wav_format
+    raw = dtype is None or (dtype == torch.uint8 if of_torch else np.dtype(dtype) == np.uint8)
+    if not raw or width not in WAV_WIDTH_DTYPE or channels not in (1, 2):
+        raise ValueError("raw WAV frames: %ssample width 1..4, one or two channels" % ("" if dtype is None else "uint8 tensor, "))
+    if nbytes is not None and int(n_frames) * width * channels != nbytes:
+        raise ValueError("frame counts do not add up to the size of the byte buffer")
+    return WAV_WIDTH_DTYPE[width] | (PCM_STEREO if channels == 2 else 0)
+
+
+def _pcm_frame_bytes(code):
+    return _PCM_BYTES[code & 15] * (2 if code & PCM_STEREO else 1)
+
+
+# ---- the calls over many sessions: everything Python checks is checked for all of them before the first native call
+def _cut(max_n, *lists):
+    """Parallel lists -> the tuples of their slices of at most ``max_n`` entries, in order: the lists themselves when they are
+    no longer than that, nothing when they are empty."""
+    n = len(lists[0])
+    if n <= max_n:
+        return [lists] if n else []
+    return [tuple(l[k:k + max_n] for l in lists) for k in range(0, n, max_n)]
+
+
+def _handle_array(objs):
+    return (C.c_void_p * len(objs))(*[o._h for o in objs])
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _flag_array(flags):
+    return np.array([int(bool(v)) for v in flags], dtype=np.int32)
+
+
+def _pushes(sessions, pcms, kind, push, pushes):
+    """Of the sessions of a ``push_many`` (handles on a frontend, with ``frame_bytes``) and what each is given: refuse a closed
+    handle, a tensor the library cannot read and a tensor that is no whole number of frames.
+    -> (frames per session, the tensors with None for every empty one)."""
+    for i, s in enumerate(sessions):
+        # the handle points into its frontend (the filters): a push after either was closed would read freed memory
+        if not getattr(s, "_h", None) or not getattr(s.frontend, "_h", None):
+            raise ValueError("session %d: the %s or its frontend has been closed" % (i, kind))
+    for p in pcms:
+        if p is not None and not (p.is_cuda and p.is_contiguous()):
+            raise ValueError("%s must be contiguous CUDA tensors" % pushes)
+    frames, given = [], []
+    for s, p in zip(sessions, pcms):
+        nbytes = 0 if p is None else p.numel() * p.element_size()
+        if nbytes % s.frame_bytes:
+            raise ValueError("the %s is not a whole number of samples of the %s's type" % (push, kind))
+        frames.append(nbytes // s.frame_bytes)
+        given.append(p if nbytes else None)
+    return frames, given
+
+
+class NativeModel(_Handle):
     """Owns one dsmi_model handle (one GPU)."""
+    _destroy, _last_error = "dsmi_model_destroy", "dsmi_last_error"
 
     def __init__(self, cfg, state_dict, device=0, audio_conf=None, n_labels=33):
         L = lib()
@@ -255,12 +384,7 @@ class NativeModel:
         self.desc = d
         self.n_labels = int(n_labels)
         self.device = device
-        h = _vp()
-        _handles[0] += 1
-        rc = L.dsmi_model_create(C.byref(d), device, C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (L.dsmi_last_error(None) or b"").decode())
-        self._h = h
+        self._create("dsmi_model_create", C.byref(d), device)
         for name, t in state_dict.items():
             a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
             if a.dtype == np.int64:   # num_batches_tracked
@@ -269,21 +393,6 @@ class NativeModel:
             shape = (C.c_int64 * max(a.ndim, 1))(*a.shape)
             self._check(L.dsmi_model_load_tensor(self._h, name.encode(), _np_ptr(a), shape, a.ndim))
         self._check(L.dsmi_model_finalize(self._h))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- host arithmetic
     def seq_lens(self, lens):
@@ -335,7 +444,7 @@ class NativeModel:
             self._inflight.pop(0)
         if rc == DSMI_RECOMPUTED:
             import warnings
-            warnings.warn((lib().dsmi_last_error(self._h) or b"").decode(), RuntimeWarning)
+            warnings.warn(self._error(self._h), RuntimeWarning)
             return True
         self._check(rc)
         return False
@@ -427,17 +536,19 @@ class NativeModel:
         return n.value, a.value, b.value
 
 
-def _stream(device=None):
-    """The torch stream current on ``device`` (the HANDLE's device, not torch's current device)."""
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def _resample_method(method):
+    if method not in RESAMPLE_METHODS:
+        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
+    return RESAMPLE_METHODS[method]
 
 
-class NativeFrontend:
+class NativeFrontend(_Handle):
     """Owns one dsmi_frontend handle: SpectrogramAudioParser on one GPU."""
+    _destroy, _last_error = "dsmi_frontend_destroy", "dsmi_frontend_last_error"
+    PCM_STEREO = PCM_STEREO
+    WAV_WIDTH_DTYPE = WAV_WIDTH_DTYPE
 
     def __init__(self, audio_conf=None, device=0, pad_mode="reflect"):
-        L = lib()
         ac = audio_conf or {}
         d = FrontendDesc()
         d.sample_rate = int(ac.get("sampling_rate", 16000))
@@ -451,26 +562,7 @@ class NativeFrontend:
         self.n_fft = int(d.sample_rate * d.window_size)
         self.hop = int(d.sample_rate * d.window_stride)
         self.n_freq = self.n_fft // 2 + 1
-        h = _vp()
-        _handles[0] += 1
-        rc = L.dsmi_frontend_create(C.byref(d), device, C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (L.dsmi_frontend_last_error(None) or b"").decode())
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_frontend_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    PCM_STEREO = 16
-    WAV_WIDTH_DTYPE = {1: 3, 2: 0, 3: 4, 4: 5}       # sample width in bytes -> DSMI_PCM_{U8,I16,I24,I32}
+        self._create("dsmi_frontend_create", C.byref(d), device)
 
     def features(self, pcm_dev, n_samples, t_stride=None, wav_format=None, device=None):
         """pcm_dev: 1-D CUDA tensor (int16/float32/float64), clips back to back; or, with
@@ -483,74 +575,93 @@ class NativeFrontend:
         frames = 1 + n_samples // self.hop
         if t_stride is None:
             t_stride = int(frames.max())
-        if wav_format is None:
-            dt = {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcm_dev.dtype]
-        else:
-            width, channels = wav_format
-            if pcm_dev.dtype != torch.uint8 or width not in self.WAV_WIDTH_DTYPE or channels not in (1, 2):
-                raise ValueError("raw WAV frames: uint8 tensor, sample width 1..4, one or two channels")
-            if int(n_samples.sum()) * width * channels != pcm_dev.numel():
-                raise ValueError("frame counts do not add up to the size of the byte buffer")
-            dt = self.WAV_WIDTH_DTYPE[width] | (self.PCM_STEREO if channels == 2 else 0)
+        dt = _pcm_code(pcm_dev.dtype, wav_format, n_samples.sum(), pcm_dev.numel())
         feat = torch.empty((B, 1, self.n_freq, t_stride), dtype=torch.float32, device=device if device is not None else pcm_dev.device)
         fr = np.empty(B, dtype=np.int32)
-        rc = lib().dsmi_features(self._h, pcm_dev.data_ptr(), dt, _np_ptr(n_samples), B, feat.data_ptr(),
-                                 int(t_stride), _np_ptr(fr), _stream(self.device))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
+        self._check(lib().dsmi_features(self._h, pcm_dev.data_ptr(), dt, _np_ptr(n_samples), B, feat.data_ptr(),
+                                        int(t_stride), _np_ptr(fr), _stream(self.device)))
         return feat, fr
 
+    def resample_count(self, n_samples, rate_in, method="polyphase"):
+        """dsmi_resample_count: the lengths clips of ``n_samples`` samples at ``rate_in`` have at the frontend's rate (int64 array)."""
+        m = _resample_method(method)
+        out = np.array([lib().dsmi_resample_count(m, int(rate_in), int(self.desc.sample_rate), int(n))
+                        for n in np.atleast_1d(n_samples)], dtype=np.int64)
+        if (out < 0).any():
+            raise DsmiError(DSMI_ERR_INVALID, "bad resample arguments (rate_in %r)" % (rate_in,))
+        return out
 
-def _pcm_dtype(self, pcm_dev, n_samples, wav_format):
-    """DSMI_PCM_* of a device buffer: a sample tensor, or (``wav_format=(sample_width, channels)``) a file's raw frames."""
-    import torch
-    if wav_format is None:
-        return {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcm_dev.dtype]
-    width, channels = wav_format
-    if pcm_dev.dtype != torch.uint8 or width not in self.WAV_WIDTH_DTYPE or channels not in (1, 2):
-        raise ValueError("raw WAV frames: uint8 tensor, sample width 1..4, one or two channels")
-    if int(n_samples.sum()) * width * channels != pcm_dev.numel():
-        raise ValueError("frame counts do not add up to the size of the byte buffer")
-    return self.WAV_WIDTH_DTYPE[width] | (self.PCM_STEREO if channels == 2 else 0)
+    def resample(self, pcm_dev, n_samples, rate_in, method="polyphase", wav_format=None):
+        """dsmi_resample: clips of ``rate_in`` Hz back to back in ``pcm_dev`` (a sample tensor, or raw WAV frames with
+        ``wav_format=(sample_width, channels)``, as for ``features``) -> (float64 CUDA tensor with the clips at the frontend's
+        rate back to back, their lengths int64[B]).  One launch on the current stream; nothing is synchronised."""
+        import torch
+        m = _resample_method(method)
+        n_samples = np.ascontiguousarray(n_samples, dtype=np.int64)
+        dt = _pcm_code(pcm_dev.dtype, wav_format, n_samples.sum(), pcm_dev.numel())
+        if wav_format is None and int(n_samples.sum()) != pcm_dev.numel():
+            raise ValueError("sample counts do not add up to the size of the buffer")
+        counts = self.resample_count(n_samples, rate_in, method)
+        total = int(counts.sum())
+        if pcm_dev.numel() == 0:            # nothing but empty clips: nothing to launch
+            return torch.empty(0, dtype=torch.float64, device=pcm_dev.device), counts
+        out = torch.empty(max(total, 1), dtype=torch.float64, device=pcm_dev.device)
+        n_out = np.zeros(len(n_samples), dtype=np.int64)
+        self._check(lib().dsmi_resample(self._h, pcm_dev.data_ptr(), dt, _np_ptr(n_samples), len(n_samples), int(rate_in), m,
+                                        out.data_ptr(), total, _np_ptr(n_out), _stream(self.device)))
+        return out[:total], n_out
 
+    def segment(self, pcm_dev, energy_threshold=600, step=1024, pause_hops=9, phrase_hops=4, wav_format=None,
+                max_segments=None, return_energies=False):
+        """dsmi_segment over ONE recording resident on the GPU -> int64 [n,2] sample ranges [start, end)
+        (and the float64 hop energies)."""
+        dt = _pcm_code(pcm_dev.dtype if wav_format is None else None, wav_format)
+        n = pcm_dev.numel() if wav_format is None else pcm_dev.numel() // _pcm_frame_bytes(dt)
+        nhops = max((n - 1) // step, 0) if n > step else 0
+        cap = int(max_segments) if max_segments is not None else nhops // 2 + 1
+        st = np.zeros(max(cap, 1), dtype=np.int64); en = np.zeros(max(cap, 1), dtype=np.int64)
+        e = np.zeros(max(nhops, 1), dtype=np.float64)
+        found = C.c_int(0)
+        self._check(lib().dsmi_segment(self._h, pcm_dev.data_ptr(), dt, n, int(step), float(energy_threshold), int(pause_hops),
+                                       int(phrase_hops), _np_ptr(st), _np_ptr(en), cap, C.byref(found), _np_ptr(e), _stream(self.device)))
+        seg = np.stack([st[:found.value], en[:found.value]], axis=1)
+        return (seg, e[:nhops]) if return_energies else seg
 
-def _resample_count(self, n_samples, rate_in, method="polyphase"):
-    """dsmi_resample_count: the lengths clips of ``n_samples`` samples at ``rate_in`` have at the frontend's rate (int64 array)."""
-    if method not in RESAMPLE_METHODS:
-        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
-    out = np.array([lib().dsmi_resample_count(RESAMPLE_METHODS[method], int(rate_in), int(self.desc.sample_rate), int(n))
-                    for n in np.atleast_1d(n_samples)], dtype=np.int64)
-    if (out < 0).any():
-        raise DsmiError(DSMI_ERR_INVALID, "bad resample arguments (rate_in %r)" % (rate_in,))
-    return out
+    def _stream_frames(self, n):
+        """Frames the streaming parser makes of a chunk of ``n`` samples."""
+        n_fft = 2 * (self.n_freq - 1)
+        return 1 + (n - n_fft) // self.hop if n >= n_fft else 0
 
+    def features_stream(self, pcm_dev, state):
+        """dsmi_features_stream: one chunk of the streaming parser.  ``state`` = float64[3] (input_mean, input_std,
+        alpha), updated in place.  -> feat [n_freq, frames] float32 CUDA."""
+        import torch
+        n = pcm_dev.numel()
+        feat = torch.empty((self.n_freq, max(self._stream_frames(n), 1)), dtype=torch.float32, device=pcm_dev.device)
+        fr = np.zeros(1, dtype=np.int32)
+        self._check(lib().dsmi_features_stream(self._h, pcm_dev.data_ptr(), _pcm_code(pcm_dev.dtype), n, _np_ptr(state), feat.data_ptr(),
+                                               feat.shape[1], _np_ptr(fr), _stream(self.device)))
+        return feat[:, :int(fr[0])]
 
-def _resample(self, pcm_dev, n_samples, rate_in, method="polyphase", wav_format=None):
-    """dsmi_resample: clips of ``rate_in`` Hz back to back in ``pcm_dev`` (a sample tensor, or raw WAV frames with
-    ``wav_format=(sample_width, channels)``, as for ``features``) -> (float64 CUDA tensor with the clips at the frontend's
-    rate back to back, their lengths int64[B]).  One launch on the current stream; nothing is synchronised."""
-    import torch
-    if method not in RESAMPLE_METHODS:
-        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
-    n_samples = np.ascontiguousarray(n_samples, dtype=np.int64)
-    dt = _pcm_dtype(self, pcm_dev, n_samples, wav_format)
-    if wav_format is None and int(n_samples.sum()) != pcm_dev.numel():
-        raise ValueError("sample counts do not add up to the size of the buffer")
-    counts = self.resample_count(n_samples, rate_in, method)
-    total = int(counts.sum())
-    if pcm_dev.numel() == 0:            # nothing but empty clips: nothing to launch
-        return torch.empty(0, dtype=torch.float64, device=pcm_dev.device), counts
-    out = torch.empty(max(total, 1), dtype=torch.float64, device=pcm_dev.device)
-    n_out = np.zeros(len(n_samples), dtype=np.int64)
-    rc = lib().dsmi_resample(self._h, pcm_dev.data_ptr(), dt, _np_ptr(n_samples), len(n_samples), int(rate_in), RESAMPLE_METHODS[method],
-                             out.data_ptr(), total, _np_ptr(n_out), _stream(self.device))
-    if rc != 0:
-        raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
-    return out[:total], n_out
-
-
-NativeFrontend.resample_count = _resample_count
-NativeFrontend.resample = _resample
+    def features_stream_many(self, pcms, states):
+        """dsmi_features_stream_many: the next chunk of several streaming parsers in one pass.  ``pcms``: CUDA tensors of one
+        dtype (one chunk per parser, each at least one window long), ``states``: their float64[3] running statistics, updated in
+        place.  -> [feat [n_freq, frames_i] float32 CUDA] (views of one batch buffer), equal to ``features_stream`` one by one."""
+        import torch
+        n = len(pcms)
+        if n == 0:
+            return []
+        ns = np.array([p.numel() for p in pcms], dtype=np.int64)
+        pcm = torch.cat([p.reshape(-1) for p in pcms]).contiguous()
+        t_stride = max(max(self._stream_frames(int(k)) for k in ns), 1)
+        feat = torch.empty((n, self.n_freq, t_stride), dtype=torch.float32, device=pcm.device)
+        st = np.ascontiguousarray(np.stack([np.asarray(s, dtype=np.float64).reshape(3) for s in states]))
+        fr = np.zeros(n, dtype=np.int32)
+        self._check(lib().dsmi_features_stream_many(self._h, pcm.data_ptr(), _pcm_code(pcms[0].dtype), _np_ptr(ns), n, _np_ptr(st),
+                                                    feat.data_ptr(), t_stride, _np_ptr(fr), _stream(self.device)))
+        for s_, row in zip(states, st):
+            s_[:] = row
+        return [feat[i, :, :int(fr[i])] for i in range(n)]
 
 
 def resample_taps(rate_in, rate_out=16000):
@@ -560,50 +671,32 @@ def resample_taps(rate_in, rate_out=16000):
     if rc == 0:
         h = np.empty(20 * max(up.value, down.value) + 1, dtype=np.float64)
         rc = lib().dsmi_resample_taps(int(rate_in), int(rate_out), _np_ptr(h), len(h), C.byref(up), C.byref(down))
-    if rc != 0:
-        raise DsmiError(rc, (lib().dsmi_frontend_last_error(None) or b"").decode())
+    NativeFrontend._check_thread(rc)
     return h, up.value, down.value
 
 
 def resample_ready(n_in, rate_in, rate_out=16000, method="polyphase"):
     """dsmi_resample_ready (host only): how many outputs are final once the first ``n_in`` samples of an utterance are known."""
-    if method not in RESAMPLE_METHODS:
-        raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
-    out = lib().dsmi_resample_ready(RESAMPLE_METHODS[method], int(rate_in), int(rate_out), int(n_in))
+    out = lib().dsmi_resample_ready(_resample_method(method), int(rate_in), int(rate_out), int(n_in))
     if out < 0:
         raise DsmiError(DSMI_ERR_INVALID, "bad resample arguments (rate_in %r, n_in %r)" % (rate_in, n_in))
     return int(out)
 
 
-RESAMPLE_STREAM_MAX = 256       # DSMI_RESAMPLE_STREAM_MAX: sessions of one dsmi_resampler_push_many call
-
-
-class NativeResampler:
+class NativeResampler(_Handle):
     """Owns one dsmi_resampler handle: the sample-rate conversion of one utterance that arrives in chunks, from ``rate_in`` to
     the rate of ``frontend`` (a ``NativeFrontend``, which keeps the filters).  ``dtype``: the chunks' sample type (int16 /
     float32 / float64), or ``wav_format=(sample_width, channels)`` for raw WAV frames.  The outputs of the pushes laid end to
     end are bit for bit ``frontend.resample`` of the whole utterance."""
-
-    _BYTES = {0: 2, 1: 4, 2: 8, 3: 1, 4: 3, 5: 4}        # DSMI_PCM_* -> bytes per sample
+    _destroy, _last_error = "dsmi_resampler_destroy", "dsmi_resampler_last_error"
 
     def __init__(self, frontend, rate_in, method="polyphase", dtype=np.int16, wav_format=None):
-        if method not in RESAMPLE_METHODS:
-            raise ValueError("resample method must be one of %s" % sorted(RESAMPLE_METHODS))
-        if wav_format is None:
-            dt = PCM_DTYPES[np.dtype(dtype)]
-        else:
-            width, channels = wav_format
-            if width not in NativeFrontend.WAV_WIDTH_DTYPE or channels not in (1, 2):
-                raise ValueError("raw WAV frames: sample width 1..4, one or two channels")
-            dt = NativeFrontend.WAV_WIDTH_DTYPE[width] | (NativeFrontend.PCM_STEREO if channels == 2 else 0)
+        m = _resample_method(method)
+        dt = _pcm_code(dtype if wav_format is None else None, wav_format)
         self.frontend, self.rate_in, self.method, self.pcm_dtype = frontend, int(rate_in), method, dt
         self.rate_out = int(frontend.desc.sample_rate)
-        self.frame_bytes = self._BYTES[dt & 15] * (2 if dt & NativeFrontend.PCM_STEREO else 1)
-        h = _vp()
-        rc = lib().dsmi_resampler_create(frontend._h, self.rate_in, RESAMPLE_METHODS[method], dt, C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_resampler_last_error(None) or b"").decode())
-        self._h = h
+        self.frame_bytes = _pcm_frame_bytes(dt)
+        self._create("dsmi_resampler_create", frontend._h, self.rate_in, m, dt)
 
     def position(self):
         """(samples consumed, outputs written) since the utterance began."""
@@ -621,54 +714,30 @@ class NativeResampler:
         total = (L.dsmi_resample_count if is_last else L.dsmi_resample_ready)(m, self.rate_in, self.rate_out, n_in + n_new)
         return max(int(total) - n_out, 0)
 
-    def _frames(self, pcm):
-        if pcm is None:
-            return 0
-        nbytes = pcm.numel() * pcm.element_size()
-        if nbytes % self.frame_bytes:
-            raise ValueError("the chunk is not a whole number of samples of the resampler's type")
-        return nbytes // self.frame_bytes
-
     @staticmethod
     def push_many(resamplers, pcms, is_last):
         """dsmi_resampler_push_many: the next chunk of several utterances (distinct handles of one frontend) in one call.
         ``pcms[i]``: a contiguous CUDA tensor holding session i's new samples in its handle's sample type (any tensor dtype:
         the bytes are what counts; ``None`` or empty for no samples); ``is_last[i]`` flushes and ends that utterance.
         -> a list of float64 CUDA tensors (views of one buffer): what each session emits now.  Nothing is synchronised.
-        Longer lists than RESAMPLE_STREAM_MAX run as several calls."""
+        Longer lists than RESAMPLE_STREAM_MAX run as several calls, after Python's own checks have passed for all of them."""
         import torch
-        n = len(resamplers)
-        if not (len(pcms) == len(is_last) == n):
+        if not (len(pcms) == len(is_last) == len(resamplers)):
             raise ValueError("resamplers, pcms and is_last must have one entry per session")
-        if n > RESAMPLE_STREAM_MAX:
-            out = []
-            for k in range(0, n, RESAMPLE_STREAM_MAX):
-                sl = slice(k, k + RESAMPLE_STREAM_MAX)
-                out += NativeResampler.push_many(resamplers[sl], pcms[sl], is_last[sl])
-            return out
-        if n == 0:
-            return []
-        fe = resamplers[0].frontend
-        for i, r in enumerate(resamplers):
-            # the handle points into its frontend (the filters): a push after either was closed would read freed memory
-            if not getattr(r, "_h", None) or not getattr(r.frontend, "_h", None):
-                raise ValueError("session %d: the resampler or its frontend has been closed" % i)
-        for p in pcms:
-            if p is not None and not (p.is_cuda and p.is_contiguous()):
-                raise ValueError("chunks must be contiguous CUDA tensors")
-        ns = np.array([r._frames(p) for r, p in zip(resamplers, pcms)], dtype=np.int64)
-        last = np.array([int(bool(v)) for v in is_last], dtype=np.int32)
-        due = [r._due(int(k), bool(l)) for r, k, l in zip(resamplers, ns, last)]
-        total = int(sum(due))
-        out = torch.empty(max(total, 1), dtype=torch.float64, device="cuda:%d" % fe.device)
-        hs = (C.c_void_p * n)(*[r._h for r in resamplers])
-        pp = (C.c_void_p * n)(*[(p.data_ptr() if p is not None and p.numel() else None) for p in pcms])
-        n_out = np.zeros(n, dtype=np.int64)
-        rc = lib().dsmi_resampler_push_many(hs, n, pp, _np_ptr(ns), _np_ptr(last), out.data_ptr(), total, _np_ptr(n_out), _stream(fe.device))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_resampler_last_error(None) or b"").decode())
-        cuts = np.concatenate(([0], np.cumsum(n_out)))
-        return [out[int(cuts[i]):int(cuts[i + 1])] for i in range(n)]
+        frames, pcms = _pushes(resamplers, pcms, "resampler", "chunk", "chunks")
+        outs = []
+        for rs, ps, ks, flags in _cut(RESAMPLE_STREAM_MAX, resamplers, pcms, frames, is_last):
+            n, fe = len(rs), rs[0].frontend
+            total = sum([r._due(k, bool(l)) for r, k, l in zip(rs, ks, flags)])
+            out = torch.empty(max(total, 1), dtype=torch.float64, device="cuda:%d" % fe.device)
+            ns, last, n_out = np.array(ks, dtype=np.int64), _flag_array(flags), np.zeros(n, dtype=np.int64)
+            NativeResampler._check_thread(lib().dsmi_resampler_push_many(
+                _handle_array(rs), n, _ptr_array(ps), _np_ptr(ns), _np_ptr(last), out.data_ptr(), total, _np_ptr(n_out), _stream(fe.device)))
+            off = 0
+            for k in n_out.tolist():
+                outs.append(out[off:off + k])
+                off += k
+        return outs
 
     def push(self, pcm, is_last=False):
         """One chunk of this utterance -> the float64 CUDA tensor of the outputs that are final now."""
@@ -678,20 +747,6 @@ class NativeResampler:
         rc = lib().dsmi_resampler_reset(self._h)
         if rc != 0:
             raise DsmiError(rc, "dsmi_resampler_reset failed")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-ENDPOINT_MAX = 256       # DSMI_ENDPOINT_MAX: sessions of one dsmi_endpointer_push_many call
 
 
 def endpoint_counts(chunk, rate, pause_threshold=0.8, phrase_threshold=0.3, non_speaking_duration=0.35, energy_threshold=1000, pcm_dtype=0):
@@ -725,24 +780,21 @@ def endpoint_gate(energy_threshold, pause_n, phrase_n, keep_n, state, sums, lens
     return np.stack([first[:k], count[:k], last[:k].astype(np.int64)], axis=1), e[:n]
 
 
-class NativeEndpointer:
+class NativeEndpointer(_Handle):
     """Owns one dsmi_endpointer handle: the energy gate of ``Recognizer.listen_stream`` over one continuous stream that arrives in
     pushes of any size.  ``dtype``: the pushes' sample type (int16 / float32 / float64), ``channels=2`` for interleaved int16
     frames.  However the stream is cut into pushes, the segments laid end to end and the last marks are those of one push."""
+    _destroy, _last_error = "dsmi_endpointer_destroy", "dsmi_endpointer_last_error"
 
     def __init__(self, frontend, chunk=1024, rate=16000, energy_threshold=1000, pause_threshold=0.8, phrase_threshold=0.3,
                  non_speaking_duration=0.35, dtype=np.int16, channels=1, pcm_dtype=None):
         if pcm_dtype is None:
-            pcm_dtype = PCM_DTYPES[np.dtype(dtype)] | (NativeFrontend.PCM_STEREO if channels == 2 else 0)
+            pcm_dtype = _pcm_code(dtype) | (PCM_STEREO if channels == 2 else 0)
         self.frontend, self.chunk, self.rate, self.pcm_dtype = frontend, int(chunk), int(rate), int(pcm_dtype)
-        self.frame_bytes = NativeResampler._BYTES.get(self.pcm_dtype & 15, 1) * (2 if self.pcm_dtype & NativeFrontend.PCM_STEREO else 1)
         d = EndpointerDesc(self.chunk, self.rate, self.pcm_dtype, float(energy_threshold), float(pause_threshold), float(phrase_threshold),
                            float(non_speaking_duration))
-        h = _vp()
-        rc = lib().dsmi_endpointer_create(frontend._h, C.byref(d), C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_endpointer_last_error(None) or b"").decode())
-        self._h = h
+        self._create("dsmi_endpointer_create", frontend._h, C.byref(d))      # (refuses a code that is no DSMI_PCM_*)
+        self.frame_bytes = _pcm_frame_bytes(self.pcm_dtype)
         self._ended = False
 
     def position(self):
@@ -753,14 +805,6 @@ class NativeEndpointer:
             raise DsmiError(rc, "dsmi_endpointer_position failed")
         return a.value, b.value, c.value
 
-    def _frames(self, pcm):
-        if pcm is None:
-            return 0
-        nbytes = pcm.numel() * pcm.element_size()
-        if nbytes % self.frame_bytes:
-            raise ValueError("the push is not a whole number of samples of the endpointer's type")
-        return nbytes // self.frame_bytes
-
     @staticmethod
     def push_many(endpointers, pcms, end_of_stream, return_energies=False):
         """dsmi_endpointer_push_many: the next samples of several streams (distinct handles of one frontend) in one call.
@@ -770,72 +814,55 @@ class NativeEndpointer:
         session gated in this call.  One host synchronisation.  Longer lists than ENDPOINT_MAX run as several calls, after
         everything that could refuse one of them has been looked for in all of them."""
         import torch
-        n = len(endpointers)
-        if not (len(pcms) == len(end_of_stream) == n):
+        if not (len(pcms) == len(end_of_stream) == len(endpointers)):
             raise ValueError("endpointers, pcms and end_of_stream must have one entry per session")
-        if n > ENDPOINT_MAX:
-            # several native calls: what would refuse a later one is looked for in all of them first, so that a refusal finds
-            # every handle as it was
-            if len(set(id(e) for e in endpointers)) != n:
+        frames, pcms = _pushes(endpointers, pcms, "endpointer", "push", "pushes")
+        if len(endpointers) > ENDPOINT_MAX:
+            # what the library refuses before it touches a handle, it refuses for the handles of ONE call: with several calls to
+            # make, it is looked for in all of them first
+            if len(set(id(e) for e in endpointers)) != len(endpointers):
                 raise ValueError("an endpointer appears twice")
-            for i, (e, p) in enumerate(zip(endpointers, pcms)):
-                if not getattr(e, "_h", None) or not getattr(e.frontend, "_h", None):
-                    raise ValueError("session %d: the endpointer or its frontend has been closed" % i)
+            for i, e in enumerate(endpointers):
                 if e.frontend is not endpointers[0].frontend:
                     raise ValueError("session %d: the endpointer belongs to another frontend" % i)
-                if p is not None and not (p.is_cuda and p.is_contiguous()):
-                    raise ValueError("pushes must be contiguous CUDA tensors")
-                if e._frames(p) > 0 and e._ended:
+                if frames[i] > 0 and e._ended:
                     raise ValueError("session %d: samples after end_of_stream: reset the session first" % i)
-            segs, ens = [], []
-            for k in range(0, n, ENDPOINT_MAX):
-                sl = slice(k, k + ENDPOINT_MAX)
-                r = NativeEndpointer.push_many(endpointers[sl], pcms[sl], end_of_stream[sl], return_energies)
-                segs += r[0] if return_energies else r
-                ens += r[1] if return_energies else []
-            return (segs, ens) if return_energies else segs
-        if n == 0:
-            return ([], []) if return_energies else []
-        fe = endpointers[0].frontend
-        for i, e in enumerate(endpointers):
-            if not getattr(e, "_h", None) or not getattr(e.frontend, "_h", None):
-                raise ValueError("session %d: the endpointer or its frontend has been closed" % i)
-        for p in pcms:
-            if p is not None and not (p.is_cuda and p.is_contiguous()):
-                raise ValueError("pushes must be contiguous CUDA tensors")
-        ns = np.array([e._frames(p) for e, p in zip(endpointers, pcms)], dtype=np.int64)
-        # (a stream that has ended gates nothing more until it is reset)
-        eos = np.array([int(bool(v) and not e._ended) for e, v in zip(endpointers, end_of_stream)], dtype=np.int32)
-        # the worst case the library sizes: all a session holds and is given, one segment per gated buffer and one more
-        nb = np.zeros(n, dtype=np.int64)
-        cap_out = 0
-        for i, e in enumerate(endpointers):
-            n_in, _, held = e.position()
-            total = n_in + int(ns[i])
-            nb[i] = total // e.chunk - n_in // e.chunk + (1 if eos[i] and total % e.chunk else 0)
-            cap_out += held + int(ns[i])
-        cap_seg = int(nb.sum()) + n
-        out = torch.empty(max(cap_out, 1), dtype=torch.float64, device="cuda:%d" % fe.device)
-        seg_session = np.zeros(cap_seg, dtype=np.int32); seg_len = np.zeros(cap_seg, dtype=np.int64); seg_last = np.zeros(cap_seg, dtype=np.int32)
-        energies = np.zeros(max(int(nb.sum()), 1), dtype=np.uint32)
-        hs = (C.c_void_p * n)(*[e._h for e in endpointers])
-        pp = (C.c_void_p * n)(*[(p.data_ptr() if p is not None and p.numel() else None) for p in pcms])
-        found = C.c_int(0)
-        rc = lib().dsmi_endpointer_push_many(hs, n, pp, _np_ptr(ns), _np_ptr(eos), out.data_ptr(), cap_out, _np_ptr(seg_session), _np_ptr(seg_len),
-                                             _np_ptr(seg_last), cap_seg, C.byref(found), _np_ptr(energies), _stream(fe.device))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_endpointer_last_error(None) or b"").decode())
-        for e, v in zip(endpointers, eos):
-            e._ended = e._ended or bool(v)
-        segs = [[] for _ in range(n)]
-        off = 0
-        for k in range(found.value):
-            segs[int(seg_session[k])].append((out[off:off + int(seg_len[k])], bool(seg_last[k])))
-            off += int(seg_len[k])
-        if not return_energies:
-            return segs
-        cuts = np.concatenate(([0], np.cumsum(nb)))
-        return segs, [energies[int(cuts[i]):int(cuts[i + 1])].copy() for i in range(n)]
+        all_segs, all_energies = [], []
+        for es, ps, ks, flags in _cut(ENDPOINT_MAX, endpointers, pcms, frames, end_of_stream):
+            n, fe = len(es), es[0].frontend
+            # (a stream that has ended gates nothing more until it is reset)
+            ends = [int(bool(v) and not e._ended) for e, v in zip(es, flags)]
+            # the worst case the library sizes: all a session holds and is given, one segment per gated buffer and one more
+            nb, cap_out = [], 0
+            for e, k, end in zip(es, ks, ends):
+                n_in, _, held = e.position()
+                total = n_in + k
+                nb.append(total // e.chunk - n_in // e.chunk + (1 if end and total % e.chunk else 0))
+                cap_out += held + k
+            n_gated = sum(nb)
+            cap_seg = n_gated + n
+            out = torch.empty(max(cap_out, 1), dtype=torch.float64, device="cuda:%d" % fe.device)
+            ns, eos = np.array(ks, dtype=np.int64), np.array(ends, dtype=np.int32)
+            seg_session = np.zeros(cap_seg, dtype=np.int32); seg_len = np.zeros(cap_seg, dtype=np.int64); seg_last = np.zeros(cap_seg, dtype=np.int32)
+            energies = np.zeros(max(n_gated, 1), dtype=np.uint32)
+            found = C.c_int(0)
+            NativeEndpointer._check_thread(lib().dsmi_endpointer_push_many(
+                _handle_array(es), n, _ptr_array(ps), _np_ptr(ns), _np_ptr(eos), out.data_ptr(), cap_out, _np_ptr(seg_session), _np_ptr(seg_len),
+                _np_ptr(seg_last), cap_seg, C.byref(found), _np_ptr(energies), _stream(fe.device)))
+            for e, end in zip(es, ends):
+                e._ended = e._ended or bool(end)
+            segs = [[] for _ in range(n)]
+            off, k = 0, found.value
+            for i, length, last in zip(seg_session[:k].tolist(), seg_len[:k].tolist(), seg_last[:k].tolist()):
+                segs[i].append((out[off:off + length], bool(last)))
+                off += length
+            all_segs += segs
+            if return_energies:
+                off = 0
+                for k in nb:
+                    all_energies.append(energies[off:off + k].copy())
+                    off += k
+        return (all_segs, all_energies) if return_energies else all_segs
 
     def push(self, pcm, end_of_stream=False, return_energies=False):
         """One push of this stream -> its segments [(float64 CUDA tensor, last), ...]."""
@@ -848,111 +875,14 @@ class NativeEndpointer:
             raise DsmiError(rc, "dsmi_endpointer_reset failed")
         self._ended = False
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_endpointer_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _segment(self, pcm_dev, energy_threshold=600, step=1024, pause_hops=9, phrase_hops=4, wav_format=None,
-             max_segments=None, return_energies=False):
-    """dsmi_segment over ONE recording resident on the GPU -> int64 [n,2] sample ranges [start, end)
-    (and the float64 hop energies)."""
-    import torch
-    if wav_format is None:
-        dt = {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcm_dev.dtype]
-        n = pcm_dev.numel()
-    else:
-        width, channels = wav_format
-        dt = self.WAV_WIDTH_DTYPE[width] | (self.PCM_STEREO if channels == 2 else 0)
-        n = pcm_dev.numel() // (width * channels)
-    nhops = max((n - 1) // step, 0) if n > step else 0
-    cap = int(max_segments) if max_segments is not None else nhops // 2 + 1
-    st = np.zeros(max(cap, 1), dtype=np.int64); en = np.zeros(max(cap, 1), dtype=np.int64)
-    e = np.zeros(max(nhops, 1), dtype=np.float64)
-    found = C.c_int(0)
-    rc = lib().dsmi_segment(self._h, pcm_dev.data_ptr(), dt, n, int(step), float(energy_threshold), int(pause_hops),
-                            int(phrase_hops), _np_ptr(st), _np_ptr(en), cap, C.byref(found), _np_ptr(e), _stream(self.device))
-    if rc != 0:
-        raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
-    seg = np.stack([st[:found.value], en[:found.value]], axis=1)
-    return (seg, e[:nhops]) if return_energies else seg
-
-
-NativeFrontend.segment = _segment
-
-
-def _features_stream(self, pcm_dev, state):
-    """dsmi_features_stream: one chunk of the streaming parser.  ``state`` = float64[3] (input_mean, input_std,
-    alpha), updated in place.  -> feat [n_freq, frames] float32 CUDA."""
-    import torch
-    dt = {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcm_dev.dtype]
-    n = pcm_dev.numel()
-    n_fft = 2 * (self.n_freq - 1)
-    nfr = 1 + (n - n_fft) // self.hop if n >= n_fft else 0
-    feat = torch.empty((self.n_freq, max(nfr, 1)), dtype=torch.float32, device=pcm_dev.device)
-    fr = np.zeros(1, dtype=np.int32)
-    rc = lib().dsmi_features_stream(self._h, pcm_dev.data_ptr(), dt, n, _np_ptr(state), feat.data_ptr(), feat.shape[1],
-                                    _np_ptr(fr), _stream(self.device))
-    if rc != 0:
-        raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
-    return feat[:, :int(fr[0])]
-
-
-NativeFrontend.features_stream = _features_stream
-
-
-def _features_stream_many(self, pcms, states):
-    """dsmi_features_stream_many: the next chunk of several streaming parsers in one pass.  ``pcms``: CUDA tensors of one
-    dtype (one chunk per parser, each at least one window long), ``states``: their float64[3] running statistics, updated in
-    place.  -> [feat [n_freq, frames_i] float32 CUDA] (views of one batch buffer), equal to ``features_stream`` one by one."""
-    import torch
-    n = len(pcms)
-    if n == 0:
-        return []
-    dt = {torch.int16: 0, torch.float32: 1, torch.float64: 2}[pcms[0].dtype]
-    ns = np.array([p.numel() for p in pcms], dtype=np.int64)
-    n_fft = 2 * (self.n_freq - 1)
-    nfr = [1 + (int(k) - n_fft) // self.hop if k >= n_fft else 0 for k in ns]
-    pcm = torch.cat([p.reshape(-1) for p in pcms]).contiguous()
-    t_stride = max(max(nfr), 1)
-    feat = torch.empty((n, self.n_freq, t_stride), dtype=torch.float32, device=pcm.device)
-    st = np.ascontiguousarray(np.stack([np.asarray(s, dtype=np.float64).reshape(3) for s in states]))
-    fr = np.zeros(n, dtype=np.int32)
-    rc = lib().dsmi_features_stream_many(self._h, pcm.data_ptr(), dt, _np_ptr(ns), n, _np_ptr(st), feat.data_ptr(), t_stride,
-                                         _np_ptr(fr), _stream(self.device))
-    if rc != 0:
-        raise DsmiError(rc, (lib().dsmi_frontend_last_error(self._h) or b"").decode())
-    for s_, row in zip(states, st):
-        s_[:] = row
-    return [feat[i, :, :int(fr[i])] for i in range(n)]
-
-
-NativeFrontend.features_stream_many = _features_stream_many
-
-STREAM_MANY_MAX = 256       # DSMI_STREAM_MANY_MAX: sessions of one dsmi_stream_forward_many call
-
-
-class NativeStream:
+class NativeStream(_Handle):
     """Owns one dsmi_stream handle: the carried state of one utterance streamed through a unidirectional model."""
+    _destroy, _last_error = "dsmi_stream_destroy", "dsmi_stream_last_error"
 
     def __init__(self, model):
         self.model = model
-        h = _vp()
-        rc = lib().dsmi_stream_create(model._h, C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_stream_last_error(None) or b"").decode())
-        self._h = h
-
-    def _check(self, rc):
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_stream_last_error(self._h) or b"").decode())
+        self._create("dsmi_stream_create", model._h)
 
     def forward(self, feat, is_first, is_last):
         """feat: CUDA float32 [F,T] (or [1,1,F,T]) -> probs [1,T_out,C] CUDA, or None while the lookahead buffers."""
@@ -982,84 +912,57 @@ class NativeStream:
         session.  -> a list of probs [1,T_out,C] CUDA, or None for a session whose lookahead is still buffering, each equal to
         what ``forward`` returns for that session alone.  Longer lists than STREAM_MANY_MAX run as several passes."""
         import torch
-        n = len(streams)
-        if not (len(feats) == len(is_first) == len(is_last) == n):
+        if not (len(feats) == len(is_first) == len(is_last) == len(streams)):
             raise ValueError("streams, feats, is_first and is_last must have one entry per session")
-        if n > STREAM_MANY_MAX:
-            out = []
-            for k in range(0, n, STREAM_MANY_MAX):
-                sl = slice(k, k + STREAM_MANY_MAX)
-                out += NativeStream.forward_many(streams[sl], feats[sl], is_first[sl], is_last[sl])
-            return out
-        if n == 0:
-            return []
-        model = streams[0].model
-        fs = [f.reshape(f.shape[-2], f.shape[-1]).contiguous() for f in feats]
-        for f in fs:
+        feats = [f.reshape(f.shape[-2], f.shape[-1]).contiguous() for f in feats]
+        for f in feats:
             assert f.is_cuda and f.dtype == torch.float32
-        T = np.array([f.shape[1] for f in fs], dtype=np.int32)
-        hs = (C.c_void_p * n)(*[s._h for s in streams])
-        fp = (C.c_void_p * n)(*[f.data_ptr() for f in fs])
-        first = np.array([int(bool(v)) for v in is_first], dtype=np.int32)
-        last = np.array([int(bool(v)) for v in is_last], dtype=np.int32)
-        cap = int(T.max()) + 4 * int(model.desc.context) + 2048
-        while True:
-            probs = torch.empty((n, cap, model.n_labels), dtype=torch.float32, device=fs[0].device)
-            tout = np.zeros(n, dtype=np.int32)
-            rc = lib().dsmi_stream_forward_many(hs, n, fp, _np_ptr(T), _np_ptr(first), _np_ptr(last), probs.data_ptr(), cap,
-                                                _np_ptr(tout), _stream(model.device))
-            if rc == DSMI_ERR_CAPACITY and cap < (1 << 24):
-                cap *= 4               # refused before any state changed
-                continue
-            if rc != 0:
-                raise DsmiError(rc, (lib().dsmi_stream_last_error(None) or b"").decode())
-            break
-        return [probs[i, :int(tout[i])].unsqueeze(0) if tout[i] > 0 else None for i in range(n)]
+        outs = []
+        for ss, fs, firsts, lasts in _cut(STREAM_MANY_MAX, streams, feats, is_first, is_last):
+            n, model = len(ss), ss[0].model
+            T = np.array([f.shape[1] for f in fs], dtype=np.int32)
+            hs, fp, first, last = _handle_array(ss), _ptr_array(fs), _flag_array(firsts), _flag_array(lasts)
+            cap = int(T.max()) + 4 * int(model.desc.context) + 2048
+            while True:
+                probs = torch.empty((n, cap, model.n_labels), dtype=torch.float32, device=fs[0].device)
+                tout = np.zeros(n, dtype=np.int32)
+                rc = lib().dsmi_stream_forward_many(hs, n, fp, _np_ptr(T), _np_ptr(first), _np_ptr(last), probs.data_ptr(), cap,
+                                                    _np_ptr(tout), _stream(model.device))
+                if rc == DSMI_ERR_CAPACITY and cap < (1 << 24):
+                    cap *= 4               # refused before any state changed
+                    continue
+                NativeStream._check_thread(rc)
+                break
+            outs += [probs[i, :int(tout[i])].unsqueeze(0) if tout[i] > 0 else None for i in range(n)]
+        return outs
 
     def reset(self):
         self._check(lib().dsmi_stream_reset(self._h))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_stream_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _sizes_ptr(sizes):
+    """Optional int32 sizes -> what a native call takes for them."""
+    return None if sizes is None else _np_ptr(np.ascontiguousarray(sizes, dtype=np.int32))
 
 
-class NativeDecoder:
+def _greedy_arrays(B, T):
+    """What a greedy decode of [B,T] fills: (ids [B,T], offsets [B,T], counts [B])."""
+    return np.empty((B, T), dtype=np.int32), np.empty((B, T), dtype=np.int32), np.empty(B, dtype=np.int32)
+
+
+def _greedy_results(ids, offs, n):
+    return [(ids[b, :n[b]].copy(), offs[b, :n[b]].copy()) for b in range(len(n))]
+
+
+class NativeDecoder(_Handle):
     """Owns one dsmi_decoder handle: greedy and beam-search CTC decoding on one GPU."""
+    _destroy, _last_error = "dsmi_decoder_destroy", "dsmi_decoder_last_error"
 
     def __init__(self, labels, blank_index=0, device=0):
-        L = lib()
         self.labels = labels
         self.device = device
         arr = (C.c_char_p * len(labels))(*[c.encode("utf-8") for c in labels])
-        h = _vp()
-        _handles[0] += 1
-        rc = L.dsmi_decoder_create(device, arr, len(labels), int(blank_index), C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (L.dsmi_decoder_last_error(None) or b"").decode())
-        self._h = h
-
-    def _check(self, rc):
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_decoder_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_decoder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("dsmi_decoder_create", device, arr, len(labels), int(blank_index))
 
     def set_lm(self, lm_path, alpha, beta):
         self._check(lib().dsmi_decoder_set_lm(self._h, lm_path.encode() if lm_path else None, float(alpha), float(beta)))
@@ -1067,29 +970,23 @@ class NativeDecoder:
     def greedy(self, probs, sizes=None):
         """probs: CUDA [B,T,C] -> list of (ids, offsets) int32 arrays per utterance."""
         B, T = probs.shape[0], probs.shape[1]
-        ids = np.empty((B, T), dtype=np.int32)
-        offs = np.empty((B, T), dtype=np.int32)
-        n = np.empty(B, dtype=np.int32)
-        sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.int32)
-        self._check(lib().dsmi_greedy(self._h, probs.data_ptr(), None if sz is None else _np_ptr(sz), B, T,
-                                      _np_ptr(ids), _np_ptr(offs), _np_ptr(n), _stream(self.device)))
-        return [(ids[b, :n[b]].copy(), offs[b, :n[b]].copy()) for b in range(B)]
+        ids, offs, n = _greedy_arrays(B, T)
+        self._check(lib().dsmi_greedy(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(ids), _np_ptr(offs), _np_ptr(n),
+                                      _stream(self.device)))
+        return _greedy_results(ids, offs, n)
 
     def greedy_enqueue(self, probs, sizes=None):
         """Launch the greedy decode and the copies of its results on the current stream and return at once."""
         B, T = probs.shape[0], probs.shape[1]
-        sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.int32)
-        self._check(lib().dsmi_greedy_enqueue(self._h, probs.data_ptr(), None if sz is None else _np_ptr(sz), B, T, _stream(self.device)))
+        self._check(lib().dsmi_greedy_enqueue(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _stream(self.device)))
         self._greedy_pending = (probs, B, T)                     # keeps the probabilities alive until the collect
 
     def greedy_collect(self):
         _, B, T = self._greedy_pending
         self._greedy_pending = None
-        ids = np.empty((B, T), dtype=np.int32)
-        offs = np.empty((B, T), dtype=np.int32)
-        n = np.empty(B, dtype=np.int32)
+        ids, offs, n = _greedy_arrays(B, T)
         self._check(lib().dsmi_greedy_collect(self._h, _np_ptr(ids), _np_ptr(offs), _np_ptr(n)))
-        return [(ids[b, :n[b]].copy(), offs[b, :n[b]].copy()) for b in range(B)]
+        return _greedy_results(ids, offs, n)
 
     def beam(self, probs, sizes=None, beam_width=64, cutoff_top_n=40, cutoff_prob=1.0):
         """probs: CUDA [B,T,C] -> (tokens [B,beam,T], timesteps [B,beam,T], lens [B,beam], scores [B,beam])."""
@@ -1099,8 +996,7 @@ class NativeDecoder:
     def beam_enqueue(self, probs, sizes=None, beam_width=64, cutoff_top_n=40, cutoff_prob=1.0):
         """Launch the search on the current stream and return at once; ``beam_collect`` waits and returns the arrays."""
         B, T = probs.shape[0], probs.shape[1]
-        sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.int32)
-        self._check(lib().dsmi_beam_enqueue(self._h, probs.data_ptr(), None if sz is None else _np_ptr(sz), B, T, int(beam_width),
+        self._check(lib().dsmi_beam_enqueue(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, int(beam_width),
                                             int(cutoff_top_n), float(cutoff_prob), _stream(self.device)))
         self._beam_pending = (probs, B, T, int(beam_width))        # keeps the probabilities alive until the collect
 
@@ -1144,35 +1040,25 @@ class NativeDecoder:
             target_lens = np.ascontiguousarray(target_lens, dtype=np.int32)
         Ls = tg.shape[1]
         tg = np.ascontiguousarray(tg)
-        sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.int32)
         spans = np.zeros((B, Ls, 2), dtype=np.int32)
         tp = np.zeros((B, Ls), dtype=np.float32)
         lp = np.zeros(B, dtype=np.float32)
         st = np.zeros(B, dtype=np.int32)
-        self._check(lib().dsmi_align(self._h, probs.data_ptr(), None if sz is None else _np_ptr(sz), B, T, _np_ptr(tg),
+        self._check(lib().dsmi_align(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(tg),
                                      _np_ptr(target_lens), Ls, _np_ptr(spans), _np_ptr(tp), _np_ptr(lp), _np_ptr(st),
                                      _stream(self.device)))
         return spans, tp, lp, st
 
 
-ALIGN_MAX_TOKENS = 4096         # DSMI_ALIGN_MAX_TOKENS: the longest transcript dsmi_align takes (L_stride)
-
-
-BEAM_STREAM_MANY_MAX = 4096     # DSMI_BEAM_STREAM_MANY_MAX: streams of one dsmi_beam_stream_advance_many launch
-
-
-class NativeBeamStream:
+class NativeBeamStream(_Handle):
     """Owns one dsmi_beam_stream handle: one utterance's beam search carried from chunk to chunk, with the language model,
     alpha and beta of ``decoder`` (a ``NativeDecoder``, kept alive by the stream)."""
+    _destroy, _last_error = "dsmi_beam_stream_destroy", "dsmi_beam_stream_last_error"
 
     def __init__(self, decoder, beam_width=64, cutoff_top_n=40, cutoff_prob=1.0):
         self.decoder = decoder
         self.beam_width = int(beam_width)
-        h = _vp()
-        rc = lib().dsmi_beam_stream_create(decoder._h, self.beam_width, int(cutoff_top_n), float(cutoff_prob), C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_beam_stream_last_error(None) or b"").decode())
-        self._h = h
+        self._create("dsmi_beam_stream_create", decoder._h, self.beam_width, int(cutoff_top_n), float(cutoff_prob))
 
     @property
     def frames(self):
@@ -1189,44 +1075,36 @@ class NativeBeamStream:
         far, T = its frame count: what ``NativeDecoder.beam`` returns first for the concatenated probabilities.  Longer lists
         than BEAM_STREAM_MANY_MAX run as several launches."""
         import torch
-        n = len(streams)
-        if len(probs_list) != n:
+        if len(probs_list) != len(streams):
             raise ValueError("streams and probs_list must have one entry per stream")
-        if n > BEAM_STREAM_MANY_MAX:
-            out = []
-            for k in range(0, n, BEAM_STREAM_MANY_MAX):
-                r = NativeBeamStream.advance_many(streams[k:k + BEAM_STREAM_MANY_MAX], probs_list[k:k + BEAM_STREAM_MANY_MAX], n_best)
-                out = None if r is None else out + r
-            return out
-        if n == 0:
-            return None if not n_best else []
-        ps = []
+        probs, new = [], []
         for p in probs_list:
-            if p is None:
-                ps.append(None)
+            t = 0
+            if p is not None:
+                t = p.shape[-2]
+                p = p.reshape(t, p.shape[-1]).contiguous()
+                assert p.is_cuda and p.dtype == torch.float32
+            probs.append(p if t > 0 else None)
+            new.append(t)
+        outs = []
+        for ss, ps, ts in _cut(BEAM_STREAM_MANY_MAX, streams, probs, new):
+            n, hs = len(ss), _handle_array(ss)
+            fr = np.array(ts, dtype=np.int32)
+            NativeBeamStream._check_thread(lib().dsmi_beam_stream_advance_many(hs, n, _ptr_array(ps), _np_ptr(fr), int(n_best),
+                                                                               _stream(ss[0].decoder.device)))
+            if not n_best:
                 continue
-            p = p.reshape(p.shape[-2], p.shape[-1]).contiguous()
-            assert p.is_cuda and p.dtype == torch.float32
-            ps.append(p if p.shape[0] > 0 else None)
-        hs = (C.c_void_p * n)(*[s._h for s in streams])
-        fp = (C.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in ps])
-        fr = np.array([0 if p is None else p.shape[0] for p in ps], dtype=np.int32)
-        dev = streams[0].decoder.device
-        rc = lib().dsmi_beam_stream_advance_many(hs, n, fp, _np_ptr(fr), int(n_best), _stream(dev))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_beam_stream_last_error(None) or b"").decode())
-        if not n_best:
-            return None
-        T = max(1, max(s.frames for s in streams))
-        tok = np.zeros((n, n_best, T), dtype=np.int32)
-        ts = np.zeros((n, n_best, T), dtype=np.int32)
-        ln = np.zeros((n, n_best), dtype=np.int32)
-        sc = np.zeros((n, n_best), dtype=np.float32)
-        cnt = np.zeros(n, dtype=np.int32)
-        rc = lib().dsmi_beam_stream_collect_many(hs, n, int(n_best), T, _np_ptr(tok), _np_ptr(ts), _np_ptr(ln), _np_ptr(sc), _np_ptr(cnt))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_beam_stream_last_error(None) or b"").decode())
-        return [(tok[i, :, :max(1, s.frames)], ts[i, :, :max(1, s.frames)], ln[i], sc[i]) for i, s in enumerate(streams)]
+            frames = [max(1, s.frames) for s in ss]
+            T = max(frames)
+            tok = np.zeros((n, n_best, T), dtype=np.int32)
+            ts = np.zeros((n, n_best, T), dtype=np.int32)
+            ln = np.zeros((n, n_best), dtype=np.int32)
+            sc = np.zeros((n, n_best), dtype=np.float32)
+            cnt = np.zeros(n, dtype=np.int32)
+            NativeBeamStream._check_thread(lib().dsmi_beam_stream_collect_many(hs, n, int(n_best), T, _np_ptr(tok), _np_ptr(ts), _np_ptr(ln),
+                                                                               _np_ptr(sc), _np_ptr(cnt)))
+            outs += [(tok[i, :, :t], ts[i, :, :t], ln[i], sc[i]) for i, t in enumerate(frames)]
+        return outs if n_best else None
 
     def advance(self, probs, n_best=0):
         r = NativeBeamStream.advance_many([self], [probs], n_best)
@@ -1236,42 +1114,17 @@ class NativeBeamStream:
         if lib().dsmi_beam_stream_reset(self._h) != 0:
             raise DsmiError(DSMI_ERR_INVALID, "closed beam stream")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_beam_stream_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class NativeLM:
+class NativeLM(_Handle):
     """Host-only view of a language-model file through libdsmi.so's reader (``dsmi_lm_*``): no GPU needed."""
+    _destroy, _last_error, _host_only = "dsmi_lm_close", "dsmi_lm_last_error", True
     KINDS = {0: "arpa", 1: "klm-probing", 2: "klm-trie"}
 
     def __init__(self, path):
-        h = _vp()
-        rc = lib().dsmi_lm_open(str(path).encode(), C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_lm_last_error(None) or b"").decode())
-        self._h = h
+        self._create("dsmi_lm_open", str(path).encode())
         o = C.c_int(); v = C.c_int64(); k = C.c_int()
         lib().dsmi_lm_info(self._h, C.byref(o), C.byref(v), C.byref(k))
         self.order, self.vocab_size, self.kind = o.value, v.value, self.KINDS[k.value]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dsmi_lm_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def word_index(self, word):
         return int(lib().dsmi_lm_word_index(self._h, word.encode("utf-8")))
@@ -1290,9 +1143,6 @@ class NativeLM:
         return float(lib().dsmi_lm_cond_log10(self._h, _np_ptr(a), len(a)))
 
 
-_PCM_CODE = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
-
-
 def plan_shards(n_samples, world):
     """dsmi_plan_shards: (rank_of, slot_of) int32 arrays."""
     n = np.ascontiguousarray(n_samples, dtype=np.int64)
@@ -1305,44 +1155,30 @@ def plan_shards(n_samples, world):
     return rank_of, slot_of
 
 
-class NativeSession:
+class NativeSession(_Handle):
     """dsmi_session_*: the fused recognise call a host without the Python layer uses (tests drive it through ctypes).
     ``frontend`` / ``model`` / ``decoder``: NativeFrontend / NativeModel / NativeDecoder; they must outlive the session."""
+    _destroy, _last_error = "dsmi_session_destroy", "dsmi_session_last_error"
+    _finalise = False       # at interpreter exit the object may outlive the model (as a NativeComm may the RCCL runtime): close() only
 
     def __init__(self, frontend, model, decoder):
         self._keep = (frontend, model, decoder)
-        h = _vp()
-        rc = lib().dsmi_session_create(frontend._h, model._h, decoder._h, C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_session_last_error(None) or b"").decode())
-        self._h = h
-
-    def close(self):
-        if self._h:
-            lib().dsmi_session_destroy(self._h)
-            self._h = None
-
-    def _err(self, rc):
-        return DsmiError(rc, (lib().dsmi_session_last_error(self._h) or b"").decode())
+        self._create("dsmi_session_create", frontend._h, model._h, decoder._h)
 
     def enqueue(self, clips):
         clips = [np.ascontiguousarray(c) for c in clips]
         kinds = {c.dtype for c in clips}
-        if len(kinds) != 1 or next(iter(kinds)) not in _PCM_CODE:
+        if len(kinds) != 1 or next(iter(kinds)) not in PCM_DTYPES:
             raise ValueError("clips of one sample type: int16, float32 or float64")
         n = np.array([len(c) for c in clips], dtype=np.int64)
         ptrs = (_vp * len(clips))(*[c.ctypes.data for c in clips])
-        rc = lib().dsmi_recognize_enqueue(self._h, ptrs, _np_ptr(n), _PCM_CODE[clips[0].dtype], len(clips))
-        if rc != 0:
-            raise self._err(rc)
+        self._check(lib().dsmi_recognize_enqueue(self._h, ptrs, _np_ptr(n), _pcm_code(clips[0].dtype), len(clips)))
         self._count = len(clips)
 
     def enqueue_device(self, pcm_dev, n_samples, dtype_code):
         n = np.ascontiguousarray(n_samples, dtype=np.int64)
         ptr = pcm_dev.data_ptr() if hasattr(pcm_dev, "data_ptr") else int(pcm_dev)
-        rc = lib().dsmi_recognize_enqueue_device(self._h, ptr, _np_ptr(n), int(dtype_code), len(n))
-        if rc != 0:
-            raise self._err(rc)
+        self._check(lib().dsmi_recognize_enqueue_device(self._h, ptr, _np_ptr(n), int(dtype_code), len(n)))
         self._count = len(n)
         self._keep_pcm = pcm_dev
 
@@ -1354,7 +1190,7 @@ class NativeSession:
         rc = lib().dsmi_recognize_collect(self._h, int(beam_width), int(cutoff_top_n), float(cutoff_prob), text.ctypes.data, text_stride,
                                           _np_ptr(nbytes), _np_ptr(scores))
         if rc < 0:
-            raise self._err(rc)
+            self._check(rc)
         self.last_status = rc
         if raw:
             return text, nbytes, scores
@@ -1365,39 +1201,28 @@ class NativeSession:
         return self.collect(**kw)
 
 
-class NativeComm:
+class NativeComm(_Handle):
     """dsmi_comm_*: scatter / gather over RCCL for hosts without torch.distributed."""
+    _destroy, _last_error = "dsmi_comm_destroy", "dsmi_comm_last_error"
+    _finalise = False       # (see NativeSession)
 
     @staticmethod
     def unique_id():
         buf = (C.c_ubyte * 128)()
-        rc = lib().dsmi_comm_unique_id(buf)
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_comm_last_error(None) or b"").decode())
+        NativeComm._check_thread(lib().dsmi_comm_unique_id(buf))
         return bytes(buf)
 
     def __init__(self, unique_id, rank, world, device):
-        h = _vp()
         buf = (C.c_ubyte * 128).from_buffer_copy(unique_id)
-        rc = lib().dsmi_comm_init(buf, int(rank), int(world), int(device), C.byref(h))
-        if rc != 0:
-            raise DsmiError(rc, (lib().dsmi_comm_last_error(None) or b"").decode())
-        self._h, self.rank, self.world, self.device = h, rank, world, device
-
-    def close(self):
-        if self._h:
-            lib().dsmi_comm_destroy(self._h)
-            self._h = None
-
-    def _err(self, rc):
-        return DsmiError(rc, (lib().dsmi_comm_last_error(self._h) or b"").decode())
+        self._create("dsmi_comm_init", buf, int(rank), int(world), int(device))
+        self.rank, self.world, self.device = rank, world, device
 
     def scatter(self, clips, root=0, cap=4096):
         """-> (device address of the shard, n_samples int64[count], positions int32[count], sample-type code, total)."""
         ptrs, n, code, count = None, None, 0, 0
         if self.rank == root:
             clips = [np.ascontiguousarray(c) for c in clips]
-            code = _PCM_CODE[clips[0].dtype] if clips else 0
+            code = _pcm_code(clips[0].dtype) if clips else 0
             n = np.array([len(c) for c in clips], dtype=np.int64)
             ptrs = (_vp * max(len(clips), 1))(*[c.ctypes.data for c in clips])
             count = len(clips)
@@ -1407,8 +1232,7 @@ class NativeComm:
         cnt, dt, tot = C.c_int(), C.c_int(), C.c_int()
         rc = lib().dsmi_comm_scatter(self._h, root, ptrs, _np_ptr(n) if n is not None and len(n) else None, code, count, C.byref(dev),
                                      _np_ptr(sn), _np_ptr(si), cap, C.byref(cnt), C.byref(dt), C.byref(tot), _stream(self.device))
-        if rc != 0:
-            raise self._err(rc)
+        self._check(rc)
         return dev.value, sn[:cnt.value].copy(), si[:cnt.value].copy(), dt.value, tot.value
 
     def gather_text(self, text, positions, total, root=0):
@@ -1419,8 +1243,7 @@ class NativeComm:
         out = np.zeros((max(total, 1), stride), dtype=np.uint8)
         rc = lib().dsmi_comm_gather_text(self._h, root, text.ctypes.data if len(pos) else None, stride, _np_ptr(pos) if len(pos) else None,
                                          len(pos), total, out.ctypes.data, _stream(self.device))
-        if rc != 0:
-            raise self._err(rc)
+        self._check(rc)
         if self.rank != root:
             return None
         return [bytes(out[i]).split(b"\0", 1)[0].decode("utf-8") for i in range(total)]

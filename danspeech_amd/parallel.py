@@ -14,8 +14,9 @@ on a width).
 """
 import numpy as np
 
-_PCM_CODES = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
-_PCM_TYPES = {v: k for k, v in _PCM_CODES.items()}
+from ._native import PCM_DTYPES
+
+_PCM_TYPES = {v: k for k, v in PCM_DTYPES.items()}
 
 
 def plan_shards(lengths, world):
@@ -96,8 +97,8 @@ def scatter_ragged(clips, rank, world, device):
     head = torch.zeros(2, dtype=torch.int64, device=device)
     if rank == 0:
         kinds = {np.asarray(c).dtype for c in clips}
-        dtype = kinds.pop() if len(kinds) == 1 and next(iter(kinds)) in _PCM_CODES else np.dtype(np.float64)
-        head[0], head[1] = len(clips), _PCM_CODES[dtype]
+        dtype = kinds.pop() if len(kinds) == 1 and next(iter(kinds)) in PCM_DTYPES else np.dtype(np.float64)
+        head[0], head[1] = len(clips), PCM_DTYPES[dtype]
     if not _alone(world):
         dist.broadcast(head, src=0)
     count, dtype = int(head[0]), _PCM_TYPES[int(head[1])]

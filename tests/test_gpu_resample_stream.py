@@ -411,3 +411,27 @@ def test_live_parts_through_the_engine_equal_the_converted_utterance(native):
         eng.streaming_transcribe(x[cuts[k]:cuts[k + 1]], is_last=k == len(cuts) - 2, is_first=k == 0)
     assert np.array_equal(np.concatenate(seen), audio.resample(x, 8000))
     eng.disable_streaming()
+
+
+def test_push_many_cuts_at_the_maximum_and_checks_every_session_first(native, fe):
+    """257 sessions are two native calls (RESAMPLE_STREAM_MAX = 256): each session's outputs are those of the same push made alone
+    on a fresh handle, and a closed handle in the second call is refused before the first call moves a session."""
+    n = native.RESAMPLE_STREAM_MAX + 1
+    rng = np.random.default_rng(257)
+    x = np.round(rng.normal(0, 8000, (n, 8))).astype(np.int16)
+    rs = [native.NativeResampler(fe, 8000, "polyphase", dtype=np.int16) for _ in range(n)]
+    pcms = [_dev(row) for row in x]
+    outs = native.NativeResampler.push_many(rs, pcms, [True] * n)
+    assert len(outs) == n
+    for i in range(n):
+        alone = native.NativeResampler(fe, 8000, "polyphase", dtype=np.int16)
+        want = alone.push(pcms[i], True).cpu().numpy()
+        alone.close()
+        assert len(want) == 16 and np.array_equal(outs[i].cpu().numpy(), want), i
+    before = rs[0].position(), rs[255].position()
+    rs[256].close()
+    with pytest.raises(ValueError, match="session 256"):
+        native.NativeResampler.push_many(rs, pcms, [False] * n)
+    assert (rs[0].position(), rs[255].position()) == before
+    for r in rs:
+        r.close()
