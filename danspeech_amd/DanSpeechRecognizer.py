@@ -630,6 +630,35 @@ class DanSpeechRecognizer(object):
         """``align_batch`` of one recording."""
         return self.align_batch([recording], [transcript])[0]
 
+    # ---- where given phrases are spoken (CTC phrase search) -----------------------------------------------------------
+    def find_phrases_batch(self, recordings, phrases, max_hits=5, min_confidence=0.0):
+        """Where in ``recordings[i]`` is ``phrases[k]`` spoken?  ``result[i][k]`` is a list of ``(start_s, end_s, confidence,
+        logp)``, best first and pairwise disjoint, at most ``max_hits``.  ``logp`` is the natural-log probability of the best
+        path that emits exactly the phrase (normalised with ``Decoder.normalise_transcript``) over the span, ``confidence`` its
+        per-frame geometric mean ``exp(logp / frames)``; ``min_confidence > 0`` keeps only the hits at or above it.  A hit
+        starts inside the phrase's first character and ends inside its last one (``dsmi_spot``).  Every phrase is checked before
+        any GPU work (``ValueError`` for characters that are not labels, an empty phrase, one longer than 128 labels)."""
+        if self.model is None:
+            raise ModelNotInitialized("Trying to find phrases without a DanSpeech model.")
+        ids = [self.decoder.phrase_ids(p) for p in phrases]
+        if len(recordings) == 0:
+            return []
+        if len(ids) == 0:
+            return [[] for _ in recordings]
+        floor = float(np.log(min_confidence)) if min_confidence > 0 else -np.inf
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        found = self.decoder.spot_ids(job.probs, ids, job.sizes, max_hits, floor)
+        frame_s = self.frame_seconds()
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            results[i] = [[(a * frame_s, e * frame_s, float(np.exp(lp / (e - a))), lp) for a, e, lp in hits] for hits in found[pos]]
+        return results
+
+    def find_phrases(self, recording, phrases, max_hits=5, min_confidence=0.0):
+        """``find_phrases_batch`` of one recording: ``result[k]`` for ``phrases[k]``."""
+        return self.find_phrases_batch([recording], phrases, max_hits, min_confidence)[0]
+
     # ---- long recordings and files ----------------------------------------------------------------------------------
     def transcribe_long(self, recording, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
                         max_batch=32, show_all=False, sample_rate=None, resample="polyphase"):

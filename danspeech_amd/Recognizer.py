@@ -58,6 +58,15 @@ class Recognizer(object):
         """``align`` for a list of clips in one batched pass over the GPU; results in the caller's order."""
         return self.danspeech_recognizer.align_batch(audio_list, transcripts)
 
+    def find_phrases(self, audio_data, phrases, max_hits=5, min_confidence=0.0):
+        """Where in the clip each of ``phrases`` is spoken: per phrase a list of ``(start_s, end_s, confidence, logp)``, best
+        first (``DanSpeechRecognizer.find_phrases_batch``)."""
+        return self.danspeech_recognizer.find_phrases(audio_data, phrases, max_hits, min_confidence)
+
+    def find_phrases_batch(self, audio_list, phrases, max_hits=5, min_confidence=0.0):
+        """``find_phrases`` for a list of clips in one batched pass over the GPU; ``result[i][k]`` for clip i and phrase k."""
+        return self.danspeech_recognizer.find_phrases_batch(audio_list, phrases, max_hits, min_confidence)
+
     def recognize_batches(self, batches, show_all=False):
         """Generator: ``recognize_batch`` over a sequence of batches, with the upload of the next batch and the
         decoding of the previous one overlapped with the GPU's work on the current one."""

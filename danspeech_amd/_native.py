@@ -29,6 +29,9 @@ ENDPOINT_MAX = 256              # sessions of one dsmi_endpointer_push_many call
 STREAM_MANY_MAX = 256           # sessions of one dsmi_stream_forward_many call
 BEAM_STREAM_MANY_MAX = 4096     # streams of one dsmi_beam_stream_advance_many launch
 ALIGN_MAX_TOKENS = 4096         # the longest transcript dsmi_align takes (L_stride)
+SPOT_MAX_TOKENS = 128           # the longest phrase dsmi_spot takes (L_stride)
+SPOT_MAX_PHRASES = 4096         # phrases of one dsmi_spot call
+SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -167,6 +170,8 @@ _PROTOS = {
     "dsmi_beam_stream_advance_many": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "dsmi_beam_stream_collect_many": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_align": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_spot_plan": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "dsmi_spot": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1048,6 +1053,40 @@ class NativeDecoder(_Handle):
                                      _np_ptr(target_lens), Ls, _np_ptr(spans), _np_ptr(tp), _np_ptr(lp), _np_ptr(st),
                                      _stream(self.device)))
         return spans, tp, lp, st
+
+    def spot(self, probs, sizes, phrases, max_hits, min_mean_logp, tracks=False):
+        """CTC phrase search (``dsmi_spot``): every phrase in every clip.  probs: CUDA [B,T,C]; sizes: [B] frames or None (= T);
+        phrases: a list of K label-id sequences.  Returns numpy arrays (hits int32 [B,K,max_hits,2] frames [start, end), scores
+        float32 [B,K,max_hits] natural-log probabilities, counts int32 [B,K]; rows past the count are 0), best hit first; with
+        ``tracks`` also the end scores float32 [B,K,T] and the start frames int32 [B,K,T] behind them."""
+        B, T = probs.shape[0], probs.shape[1]
+        seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in phrases]
+        K, M = len(seqs), int(max_hits)
+        lens = np.array([len(t) for t in seqs], dtype=np.int32)
+        ph = np.zeros((K, max(1, int(lens.max()) if K else 1)), dtype=np.int32)
+        for k, t in enumerate(seqs):
+            ph[k, :len(t)] = t
+        rows = max(M, 0)
+        hits = np.zeros((B, K, rows, 2), dtype=np.int32)
+        scores = np.zeros((B, K, rows), dtype=np.float32)
+        counts = np.zeros((B, K), dtype=np.int32)
+        E = np.zeros((B, K, T), dtype=np.float32) if tracks else None
+        ST = np.zeros((B, K, T), dtype=np.int32) if tracks else None
+        self._check(lib().dsmi_spot(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(ph), _np_ptr(lens), K, ph.shape[1],
+                                    M, float(min_mean_logp), _np_ptr(hits), _np_ptr(scores), _np_ptr(counts),
+                                    _np_ptr(E) if tracks else None, _np_ptr(ST) if tracks else None, _stream(self.device)))
+        return (hits, scores, counts, E, ST) if tracks else (hits, scores, counts)
+
+
+def spot_plan(phrase_lens):
+    """dsmi_spot_plan (host only): (n_groups, group_of, first_state) of phrases with these token counts, as dsmi_spot packs them."""
+    lens = np.ascontiguousarray(phrase_lens, dtype=np.int32).reshape(-1)
+    group_of = np.zeros(len(lens), dtype=np.int32)
+    first_state = np.zeros(len(lens), dtype=np.int32)
+    rc = lib().dsmi_spot_plan(_np_ptr(lens) if len(lens) else None, len(lens), _np_ptr(group_of), _np_ptr(first_state))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_spot_plan: 1 .. %d phrases of 1 .. %d tokens" % (SPOT_MAX_PHRASES, SPOT_MAX_TOKENS))
+    return rc, group_of, first_state
 
 
 class NativeBeamStream(_Handle):

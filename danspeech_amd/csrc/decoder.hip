@@ -10,6 +10,7 @@
 // histogram selection); the parity tests compare with both.  DESIGN.md 4 "Beam search" describes the frame's six phases.
 #include "common.h"
 #include "align.h"
+#include "spot.h"
 #include <cstring>
 #include <mutex>
 #include "lm.h"
@@ -63,6 +64,9 @@ struct dsmi_decoder {
     // dsmi_align: inputs and outputs of the launch (int32 words), backpointers [B][T_out][S_stride] bytes
     int32_t* al_io = nullptr; size_t al_io_cap = 0;
     unsigned char* al_bp = nullptr; size_t al_bp_cap = 0;
+    // dsmi_spot: inputs and hits of the launch (int32 words), the E and ST tracks 2 x [B][K][T_out] words
+    int32_t* sp_io = nullptr; size_t sp_io_cap = 0;
+    int32_t* sp_tr = nullptr; size_t sp_tr_cap = 0;
 };
 
 // ONE stream per device for the device-to-host copies of every decoder handle's collect, made at the first collect and kept for
@@ -133,6 +137,8 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     if (d->bs_pin) (void)hipHostFree(d->bs_pin);
     if (d->al_io) (void)hipFree(d->al_io);
     if (d->al_bp) (void)hipFree(d->al_bp);
+    if (d->sp_io) (void)hipFree(d->sp_io);
+    if (d->sp_tr) (void)hipFree(d->sp_tr);
     delete d;
 }
 
@@ -532,6 +538,113 @@ extern "C" int dsmi_align(dsmi_decoder* d, const float* probs, const int32_t* si
         status[b] = tl[b] < 0 ? 1 : 0;
         if (tl[b] < 0) path_logp[b] = -INFINITY;
     }
+    return DSMI_OK;
+}
+
+
+// ---- CTC phrase search (the kernels: spot.hip).  Every refusal comes before any launch or output write.
+extern "C" int dsmi_spot_plan(const int32_t* phrase_lens, int K, int32_t* group_of, int32_t* first_state) {
+    if (!phrase_lens || !group_of || !first_state || K < 1 || K > DSMI_SPOT_MAX_PHRASES) return DSMI_ERR_INVALID;
+    for (int k = 0; k < K; ++k)
+        if (phrase_lens[k] < 1 || phrase_lens[k] > DSMI_SPOT_MAX_TOKENS) return DSMI_ERR_INVALID;
+    return spot_plan(phrase_lens, K, group_of, first_state);
+}
+
+extern "C" int dsmi_spot(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* phrases,
+                         const int32_t* phrase_lens, int K, int L_stride, int max_hits, float min_mean_logp, int32_t* hits,
+                         float* scores, int32_t* counts, float* track_scores, int32_t* track_starts, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !phrases || !phrase_lens || !hits || !scores || !counts) { d->err = "bad spot arguments"; return DSMI_ERR_INVALID; }
+    if (B <= 0 || To <= 0 || K <= 0) { d->err = "spot: B, T_out and K must be positive"; return DSMI_ERR_INVALID; }
+    if (max_hits < 1 || max_hits > DSMI_SPOT_MAX_HITS) {
+        d->err = "spot: max_hits outside 1 .. DSMI_SPOT_MAX_HITS (" + std::to_string(DSMI_SPOT_MAX_HITS) + ")"; return DSMI_ERR_INVALID;
+    }
+    if (std::isnan(min_mean_logp)) { d->err = "spot: min_mean_logp is not a number"; return DSMI_ERR_INVALID; }
+    if (L_stride > DSMI_SPOT_MAX_TOKENS) {
+        d->err = "spot: L_stride " + std::to_string(L_stride) + " exceeds DSMI_SPOT_MAX_TOKENS (" + std::to_string(DSMI_SPOT_MAX_TOKENS) + ")";
+        return DSMI_ERR_CAPACITY;
+    }
+    if (K > DSMI_SPOT_MAX_PHRASES) {
+        d->err = "spot: " + std::to_string(K) + " phrases exceed DSMI_SPOT_MAX_PHRASES (" + std::to_string(DSMI_SPOT_MAX_PHRASES) + ")";
+        return DSMI_ERR_CAPACITY;
+    }
+    constexpr uint64_t kTrackCap = (uint64_t)1 << 27;
+    if ((uint64_t)B * (uint64_t)K > kTrackCap || (uint64_t)B * (uint64_t)K * (uint64_t)To > kTrackCap) {
+        d->err = "spot: B * K * T_out exceeds 2^27 (the track workspace)"; return DSMI_ERR_CAPACITY;
+    }
+    std::vector<int32_t> sz(B);
+    for (int b = 0; b < B; ++b) {
+        sz[b] = sizes ? sizes[b] : To;
+        if (sz[b] < 0 || sz[b] > To) { d->err = "spot: clip " + std::to_string(b) + ": size outside 0 .. T_out"; return DSMI_ERR_INVALID; }
+    }
+    for (int k = 0; k < K; ++k) {
+        const int L = phrase_lens[k];
+        if (L < 1 || L > L_stride) { d->err = "spot: phrase " + std::to_string(k) + ": length outside 1 .. L_stride"; return DSMI_ERR_INVALID; }
+        const int32_t* ph = phrases + (size_t)k * L_stride;
+        for (int j = 0; j < L; ++j)
+            if (ph[j] < 0 || ph[j] >= C || ph[j] == d->blank) {
+                d->err = "spot: phrase " + std::to_string(k) + ": token id " + std::to_string(ph[j]) + " is the blank or not a label";
+                return DSMI_ERR_INVALID;
+            }
+    }
+    // ---- the packing: per state its label and flags, groups of kSpotThreads states
+    std::vector<int32_t> group_of(K), first_state(K);
+    const int n_groups = spot_plan(phrase_lens, K, group_of.data(), first_state.data());
+    std::vector<int32_t> words((size_t)n_groups * kSpotThreads, 0);
+    for (int k = 0; k < K; ++k) {
+        const int L = phrase_lens[k], S = 2 * L - 1;
+        const int32_t* ph = phrases + (size_t)k * L_stride;
+        int32_t* w = words.data() + (size_t)group_of[k] * kSpotThreads + first_state[k];
+        for (int s = 0; s < S; ++s) {
+            const int j = s >> 1;
+            int32_t q = kSpotLive | ((s & 1) ? d->blank : ph[j]);
+            if (!(s & 1) && j >= 1 && ph[j] != ph[j - 1]) q |= kSpotSkip;
+            if (s == 0) q |= kSpotFirst;
+            if (s == S - 1) q |= kSpotLast | (k << kSpotPhraseShift);
+            w[s] = q;
+        }
+    }
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces, grown on demand: io = sizes [B], words [n_groups][256], hits [B][K][M][2], scores [B][K][M], counts [B][K]
+    const size_t BK = (size_t)B * K, BKM = BK * max_hits, n_words = words.size(), n_tr = BK * To;
+    const size_t io_words = (size_t)B + n_words + 3 * BKM + BK;
+    if (io_words > d->sp_io_cap || 2 * n_tr > d->sp_tr_cap) {
+        DEC_HIP(d, hipDeviceSynchronize());
+        if (io_words > d->sp_io_cap) {
+            if (d->sp_io) (void)hipFree(d->sp_io);
+            d->sp_io = nullptr; d->sp_io_cap = 0;
+            DEC_HIP(d, hipMalloc((void**)&d->sp_io, sizeof(int32_t) * io_words));
+            d->sp_io_cap = io_words;
+        }
+        if (2 * n_tr > d->sp_tr_cap) {
+            if (d->sp_tr) (void)hipFree(d->sp_tr);
+            d->sp_tr = nullptr; d->sp_tr_cap = 0;
+            DEC_HIP(d, hipMalloc((void**)&d->sp_tr, sizeof(int32_t) * 2 * n_tr));
+            d->sp_tr_cap = 2 * n_tr;
+        }
+    }
+    int32_t* w_sz = d->sp_io; int32_t* w_wd = w_sz + B; int32_t* w_hit = w_wd + n_words;
+    float* w_sc = reinterpret_cast<float*>(w_hit + 2 * BKM); int32_t* w_cnt = w_hit + 3 * BKM;
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_wd, words.data(), sizeof(int32_t) * n_words, hipMemcpyHostToDevice, s));
+    SpotArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.K = K; a.n_groups = n_groups;
+    a.sizes = w_sz; a.words = w_wd;
+    a.E = reinterpret_cast<float*>(d->sp_tr); a.ST = d->sp_tr + n_tr;
+    a.max_hits = max_hits; a.min_mean_logp = min_mean_logp;
+    a.hits = w_hit; a.scores = w_sc; a.counts = w_cnt;
+    DEC_HIP(d, launch_spot(a, B, s));
+    // hits, scores and counts lie back to back: one copy into a host image, then the caller's three arrays
+    std::vector<int32_t> out(3 * BKM + BK);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_hit, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, s));
+    if (track_scores) DEC_HIP(d, hipMemcpyAsync(track_scores, a.E, sizeof(float) * n_tr, hipMemcpyDeviceToHost, s));
+    if (track_starts) DEC_HIP(d, hipMemcpyAsync(track_starts, a.ST, sizeof(int32_t) * n_tr, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    std::memcpy(hits, out.data(), sizeof(int32_t) * 2 * BKM);
+    std::memcpy(scores, out.data() + 2 * BKM, sizeof(float) * BKM);
+    std::memcpy(counts, out.data() + 3 * BKM, sizeof(int32_t) * BK);
     return DSMI_OK;
 }
 

@@ -124,6 +124,36 @@ class Decoder(object):
             out.append(None if status[b] else (spans[b, :L].copy(), tp[b, :L].copy(), float(lp[b])))
         return out
 
+    # ---- CTC phrase search (dsmi_spot): where are given phrases spoken; the same on every decoder, no language model
+    def spot(self, probs, phrases, sizes=None, max_hits=5, min_mean_logp=-np.inf):
+        """Occurrences of ``phrases[k]`` (normalised with ``normalise_transcript``) in the probabilities of every clip
+        (``probs`` [B,T,C], ``sizes`` frames per clip): ``result[b][k]`` is a list of ``(start_frame, end_frame, logp)``, best
+        first and pairwise disjoint, at most ``max_hits``, each with ``logp >= min_mean_logp * frames``.  ``logp`` is the
+        natural-log probability of the best path that emits exactly the phrase over frames [start, end)."""
+        ids = [self.phrase_ids(p) for p in phrases]                                          # every check before any GPU work
+        return self.spot_ids(probs, ids, sizes, max_hits, min_mean_logp)
+
+    def phrase_ids(self, phrase):
+        """Label ids of a search phrase; ``ValueError`` for characters that are not labels, a phrase that is empty after
+        normalisation, or one longer than ``SPOT_MAX_TOKENS`` labels."""
+        from .. import _native
+        ids = self.transcript_ids(self.normalise_transcript(phrase))
+        if len(ids) == 0:
+            raise ValueError("phrase %r is empty after normalisation" % (phrase,))
+        if len(ids) > _native.SPOT_MAX_TOKENS:
+            raise ValueError("phrase of %d labels is longer than %d: %r" % (len(ids), _native.SPOT_MAX_TOKENS, phrase))
+        return ids
+
+    def spot_ids(self, probs, ids, sizes=None, max_hits=5, min_mean_logp=-np.inf):
+        """``spot`` for label-id sequences as they are (no normalisation)."""
+        import torch
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        hits, scores, counts = dec.spot(probs, sz, ids, max_hits, min_mean_logp)
+        return [[[(int(hits[b, k, n, 0]), int(hits[b, k, n, 1]), float(scores[b, k, n])) for n in range(counts[b, k])]
+                 for k in range(len(ids))] for b in range(hits.shape[0])]
+
 
 class GreedyDecoder(Decoder):
     """decoder.py:147-198: argmax per frame, collapse repeats, drop blanks; one path per utterance."""

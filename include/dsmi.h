@@ -530,6 +530,51 @@ int dsmi_align(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_hos
                int32_t* spans_host, float* token_probs_host, float* path_logp_host, int32_t* status_host,
                void* stream);
 
+/* ---- CTC phrase search (no reference counterpart): where in each clip is each of K phrases spoken?  The same trellis as
+ * dsmi_align with a free start and a free end, over the probabilities dsmi_forward wrote; every phrase is searched in every
+ * clip.  The decoder's language model plays no part.
+ * probs_dev [B][T_out][n_labels]; sizes_host[B] frames per clip (NULL = T_out for all); phrases_host [K][L_stride] label ids,
+ * phrase k's first phrase_lens_host[k] valid, 1 <= length <= L_stride <= DSMI_SPOT_MAX_TOKENS, never the blank.
+ * The recurrence (the contract).  A phrase t_1..t_L has S = 2L - 1 states with no leading and no trailing blank: state 2j is
+ * token j+1, state 2j+1 the blank between two tokens.  lp(f, c) = logf(fmaxf(p(f, c), FLT_MIN)), accumulated in float32 over
+ * frames in order, as dsmi_align does.  Each state carries a score a_f(s) and the frame b_f(s) at which its path began;
+ * a_{-1}(s) = -inf, b_{-1}(s) = -1.  For frames f = 0 .. sizes[b]-1:
+ *     state 0:  a_f(0) = lp(f, t_1), b_f(0) = f.  (A fresh start scores 0 before the frame's lp and every carried score is
+ *               <= 0, so state 0 always restarts: on a tie the later start wins.)
+ *     s >= 1:   the predecessor is the best of a_{f-1}(s) and a_{f-1}(s-1) and, for an even s >= 2 with
+ *               label(s) != label(s-2), a_{f-1}(s-2); ties as dsmi_align: s before s-1 before s-2, strict > to move.
+ *               a_f(s) = best + lp(f, label(s)), b_f(s) = the chosen predecessor's b; a -inf best stays -inf with b = -1.
+ * Tracks: E[f] = a_f(S-1), the log probability of the best path that emits exactly the phrase and ends in its last token at
+ * frame f, and ST[f] = b_f(S-1), where that path began.
+ * Picking, per (clip, phrase).  Candidates: every f with E[f] > -inf and E[f] >= min_mean_logp * (float)(f - ST[f] + 1) (a
+ * float32 multiply, no division; min_mean_logp = -inf admits every finite frame).  Up to max_hits times: take the candidate
+ * with the largest E (on a tie the lowest f), emit the hit [ST[e], e+1) with score E[e], and drop every candidate f whose
+ * [ST[f], f] intersects [ST[e], e]; stop when none is left.  Hits come out best first and are pairwise disjoint.
+ * The raw-score optimum is tight: every frame costs, so the first and the last token occupy ONE frame each in the reported
+ * span -- a hit starts inside the first character's run and ends inside the last character's run; it is not their extent.
+ * Outputs: hits_host [B][K][max_hits][2] frames [start, end); scores_host [B][K][max_hits]; counts_host [B][K]; rows past
+ * the count are 0.  track_scores_host / track_starts_host [B][K][T_out] are optional (each is copied back only when
+ * not NULL): the E / ST tracks, -inf / -1 at the frames past sizes[b].  A clip with fewer frames than a phrase needs (0
+ * frames included) gives count 0.
+ * Refused before any launch with nothing written: DSMI_ERR_INVALID for B, T_out or K <= 0, sizes[b] outside 0 .. T_out, a
+ * length outside 1 .. L_stride, a token that is the blank or not a label, max_hits outside 1 .. DSMI_SPOT_MAX_HITS, a NaN
+ * min_mean_logp; DSMI_ERR_CAPACITY for L_stride > DSMI_SPOT_MAX_TOKENS, K > DSMI_SPOT_MAX_PHRASES, B * K * T_out > 2^27 (the
+ * track workspace, kept on the handle).  Two kernel launches whatever B and K.  Synchronises `stream`.
+ *
+ * dsmi_spot_plan (host only) is the packing dsmi_spot uses: the phrases, in the caller's order, fill groups of at most 256
+ * states (one workgroup per group and clip); a phrase that does not fit opens the next group.  group_of[k] / first_state[k]
+ * = the group of phrase k and the index of its state 0 in it.  Returns the number of groups; < 0 for NULL arguments, K outside
+ * 1 .. DSMI_SPOT_MAX_PHRASES or a length outside 1 .. DSMI_SPOT_MAX_TOKENS. */
+#define DSMI_SPOT_MAX_TOKENS 128
+#define DSMI_SPOT_MAX_PHRASES 4096
+#define DSMI_SPOT_MAX_HITS 64
+int dsmi_spot_plan(const int32_t* phrase_lens, int K, int32_t* group_of, int32_t* first_state);
+int dsmi_spot(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+              const int32_t* phrases_host, const int32_t* phrase_lens_host, int K, int L_stride,
+              int max_hits, float min_mean_logp,
+              int32_t* hits_host, float* scores_host, int32_t* counts_host,
+              float* track_scores_host, int32_t* track_starts_host, void* stream);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off
