@@ -140,6 +140,7 @@ _PROTOS = {
     "dsmi_upload": (C.c_int, [C.c_int, _vp, _vp, C.c_int64, _vp]),
     "dsmi_conv_stack": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "dsmi_rnn_layer": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "dsmi_head": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "dsmi_greedy": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "dsmi_greedy_enqueue": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "dsmi_greedy_collect": (C.c_int, [_vp, _vp, _vp, _vp]),
@@ -512,6 +513,19 @@ class NativeModel(_Handle):
         y = torch.empty((T, B, self.desc.rnn_hidden_size), dtype=torch.float32, device=x.device)
         self._check(lib().dsmi_rnn_layer(self._h, int(layer), x.data_ptr(), _np_ptr(out_lens), B, T, y.data_ptr(), self._stream()))
         return y
+
+    def head(self, x_fwd, x_rev=None):
+        """x_fwd, x_rev: CUDA float32 [T,B,H], the last layer's outputs per direction (x_rev exactly when the model is
+        bidirectional) -> probs [B,T,n_labels]: (Lookahead + Hardtanh for a unidirectional model,) BatchNorm1d, Linear, softmax."""
+        import torch
+        for x in (x_fwd,) + (() if x_rev is None else (x_rev,)):
+            assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == tuple(x_fwd.shape) and x.dim() == 3
+            assert x.shape[2] == self.desc.rnn_hidden_size, "rows of %d units, the model has %d" % (x.shape[2], self.desc.rnn_hidden_size)
+            self._on_device(x)
+        T, B = x_fwd.shape[0], x_fwd.shape[1]
+        probs = torch.empty((B, T, self.n_labels), dtype=torch.float32, device=x_fwd.device)
+        self._check(lib().dsmi_head(self._h, x_fwd.data_ptr(), None if x_rev is None else x_rev.data_ptr(), B, T, probs.data_ptr(), self._stream()))
+        return probs
 
     KERNEL_KINDS = ["unused", "conv1", "conv2", "conv3", "gemm_l0", "gemm", "rnn_step", "head", "greedy", "beam", "rnn_layer_persistent"]
 

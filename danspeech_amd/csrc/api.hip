@@ -511,6 +511,9 @@ static int seq_len(const dsmi_model* m, int L) {  // model.py:540-551
     return L;
 }
 
+// The fewest input frames whose seq_len is To: only the first conv layer strides in time, by 2 ((L - 1) / 2 + 1).
+static int frames_for(int To) { return 2 * To - 1; }
+
 extern "C" int dsmi_seq_lens(const dsmi_model* m, const int32_t* lens, int n, int32_t* out) {
     if (!m || !lens || !out) return DSMI_ERR_INVALID;
     for (int i = 0; i < n; ++i) out[i] = seq_len(m, lens[i]);
@@ -1067,9 +1070,7 @@ extern "C" int dsmi_rnn_layer(dsmi_model* m, int layer, const float* x, const in
         if (out_lens[i] < 1 || out_lens[i] > To) return fail(m, DSMI_ERR_INVALID, "length outside 1..T");
         if (i && out_lens[i] > out_lens[i - 1]) return fail(m, DSMI_ERR_UNSORTED, "`lengths` array must be sorted in decreasing order");
     }
-    // workspaces are sized by input frames; find a T whose seq_len covers To
-    int Tin = To;
-    while (seq_len(m, Tin) < To) Tin += 1;
+    const int Tin = frames_for(To);      // workspaces are sized by input frames
     int rc;
     if ((rc = dsmi_reserve(m, B, Tin))) return rc;
     HIP_OK(m, hipSetDevice(m->device));
@@ -1102,6 +1103,41 @@ extern "C" int dsmi_rnn_layer(dsmi_model* m, int layer, const float* x, const in
         m->rnn_mode = 0;
         m->recomputed += 1;
     }
+    return DSMI_OK;
+}
+
+// See include/dsmi.h: the output head by itself, on rows the caller supplies (the last layer's outputs per direction).
+extern "C" int dsmi_head(dsmi_model* m, const float* x_fwd, const float* x_rev, int B, int To, float* probs, void* stream) {
+    if (!m) return DSMI_ERR_INVALID;
+    if (!m->finalized) return fail(m, DSMI_ERR_NOT_READY, "dsmi_model_finalize has not been called");
+    const dsmi_model_desc& d = m->desc;
+    if (!x_fwd || !probs || B < 1 || To < 1) return fail(m, DSMI_ERR_INVALID, "bad head arguments");
+    if ((x_rev != nullptr) != (d.bidirectional != 0))
+        return fail(m, DSMI_ERR_INVALID, d.bidirectional ? "a bidirectional model's head needs the reverse direction's rows"
+                                                         : "a unidirectional model's head takes no reverse direction");
+    if ((int64_t)To * B > (int64_t)1 << 24) return fail(m, DSMI_ERR_INVALID, "more than 2^24 rows");      // (head_kernel counts rows in an int)
+    const int Tin = frames_for(To);      // workspaces are sized by input frames
+    int rc;
+    if ((rc = dsmi_reserve(m, B, Tin))) return rc;
+    HIP_OK(m, hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int H = d.rnn_hidden_size;
+    const size_t rows = (size_t)To * B;
+    launch_pad_rows(x_fwd, m->hbuf[0][0], rows, H, m->Hs, s);
+    if (x_rev) launch_pad_rows(x_rev, m->hbuf[0][1], rows, H, m->Hs, s);
+    HeadLaunch h;
+    h.bn_a = m->fc_a; h.bn_b = m->fc_b; h.w_packed = m->fc_wp; h.H = H; h.C = d.n_labels;
+    h.T = To; h.B = B; h.probs = probs;
+    if (!d.bidirectional) {   // model.py:508-509
+        launch_lookahead(m->hbuf[0][0], m->look_w, m->look_buf, To, B, H, d.context, s);
+        h.x1 = m->look_buf; h.x2 = nullptr;
+    } else {
+        h.x1 = m->hbuf[0][0]; h.x2 = m->hbuf[0][1];
+    }
+    h.ev = timer_arm(m, KK_HEAD, true, 2.0 * rows * H * d.n_labels, 4.0 * rows * ((d.bidirectional ? 2.0 : 1.0) * m->Hs + d.n_labels));
+    launch_head(h, s);
+    HIP_OK(m, hipStreamSynchronize(s));
+    HIP_OK(m, hipGetLastError());
     return DSMI_OK;
 }
 

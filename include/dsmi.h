@@ -392,6 +392,12 @@ int dsmi_conv_stack(dsmi_model* m, const float* feat_dev, const int32_t* lens_ho
                     float* conv_out_dev, void* stream);
 int dsmi_rnn_layer(dsmi_model* m, int layer, const float* x_dev, const int32_t* out_lens_host,
                    int B, int T_out, float* y_dev, void* stream);
+/* The output head by itself (model.py:508-514): x_fwd_dev / x_rev_dev are the last recurrent layer's outputs per direction,
+ * dense [T_out][B][H] float32; x_rev_dev is required exactly when the model is bidirectional (NULL otherwise).  Unidirectional
+ * models run the Lookahead + Hardtanh first.  probs_dev: [B][T_out][n_labels] float32.  Bad arguments are refused before any
+ * launch; the call returns when the result is there. */
+int dsmi_head(dsmi_model* m, const float* x_fwd_dev, const float* x_rev_dev, int B, int T_out,
+              float* probs_dev, void* stream);
 
 /* ---- Decoder.__init__ (decoder.py:35-43): labels as n_labels UTF-8 strings (labels may be
  * multi-byte, e.g. the Danish letters), blank_index as DanSpeechRecognizer passes it

@@ -1,4 +1,5 @@
-"""One ``BatchRNN`` layer in float64: the reference the layer-level accuracy tests hold the kernels (and the fp32 oracle) to.
+"""The model's stages in float64 -- one ``BatchRNN`` layer, the conv stack, the lookahead and the output head: the references the
+stage-level accuracy tests hold the kernels (and the fp32 oracle) to.
 
 Plain numpy, float64 throughout.  Inputs and weights are the float32 values widened exactly; nothing is rounded in between.  The
 semantics are the ones oracle/model.py documents (reference model.py:114-122) -- restated here, not called:
@@ -12,6 +13,14 @@ semantics are the ones oracle/model.py documents (reference model.py:114-122) --
 
 ``step`` may be replaced (tests/_split_emu.py puts the split-fp16 product and its mutants there): it gets the direction's float64
 state and returns ``h W_hh^T`` without the bias.
+
+The dense stages, restated the same way (oracle/model.py:77-96, 163-171, 199-205 document them; nothing of it is called):
+
+* ``conv_stack``: per layer a cross-correlation with zero padding (geometry from ``synthetic.CONV_SPECS``) + bias, eval-mode
+  BatchNorm2d as ``x * a + b``, clip to [0, 20]; zero at ``t >= out_len`` after each of the three modules (the mask only zeroes:
+  one mask after the clip is the same thing).  The convolution reads input values past a clip's length like any other.
+* ``lookahead``: ``y[t] = clip(sum_k w[:, k] * x[t + k], 0, 20)``, zeros past the end.
+* ``head``: BatchNorm1d affine, ``x W^T``, softmax over the classes with the maximum subtracted; [T, B, H] -> [B, T, C].
 """
 import numpy as np
 
@@ -100,3 +109,84 @@ def batch_rnn(sd, layer, kind, x, lens, bidirectional, batch_norm, hooks=None):
         y = direction(kind, x, lens, *layer_weights(sd, layer, reverse), reverse=reverse, **((hooks or {}).get(reverse) or {}))
         out = y if out is None else out + y
     return out
+
+
+# ---- the dense stages ------------------------------------------------------------------------------------------------------------
+def correlate(x, w, stride, pad):
+    """Cross-correlation [B, Ci, Fi, Ti] x [Co, Ci, kf, kt] -> [B, Co, Fo, To] with zero padding, no bias, in the arrays' own type
+    (float64 here; tests/_split_emu.py calls it on float32 arrays that hold fp16 values).  The time taps are unfolded once per clip,
+    then one matrix product per kernel row contracts (ci, kt)."""
+    assert x.dtype == w.dtype and x.dtype in (np.float32, np.float64)
+    B, Ci, Fi, Ti = x.shape
+    Co, ci_w, kf, kt = w.shape
+    assert ci_w == Ci
+    (sf, st), (pf, pt) = stride, pad
+    Fo, To = (Fi + 2 * pf - kf) // sf + 1, (Ti + 2 * pt - kt) // st + 1
+    out = np.zeros((B, Co, Fo, To), dtype=x.dtype)
+    wk = [np.ascontiguousarray(w[:, :, a, :].reshape(Co, Ci * kt)) for a in range(kf)]
+    for b in range(B):
+        xp = np.zeros((Ci, Fi + 2 * pf, Ti + 2 * pt), dtype=x.dtype)
+        xp[:, pf:pf + Fi, pt:pt + Ti] = x[b]
+        u = np.stack([xp[:, :, c:c + st * (To - 1) + 1:st] for c in range(kt)], axis=1)      # [Ci, kt, rows, To]
+        acc = out[b].reshape(Co, Fo * To)
+        for a in range(kf):
+            if not wk[a].any():
+                continue
+            acc += wk[a] @ u[:, :, a:a + sf * (Fo - 1) + 1:sf, :].reshape(Ci * kt, Fo * To)
+    return out
+
+
+def bn2d_affine(sd, li):
+    p = "conv.seq_module.%d." % (3 * li + 1)
+    a = _f64(sd[p + "weight"]) / np.sqrt(_f64(sd[p + "running_var"]) + BN_EPS)
+    return a, _f64(sd[p + "bias"]) - _f64(sd[p + "running_mean"]) * a
+
+
+def mask_time(x, out_lens):
+    """zero [B, C, F, T] at t >= out_len, in place"""
+    for b, L in enumerate(out_lens):
+        x[b, :, :, int(L):] = 0
+    return x
+
+
+def conv_stack(sd, x, out_lens, conv_layers, layers_out=None):
+    """MaskConv over (Conv2d, BatchNorm2d, Hardtanh(0, 20)) triples in float64.  x: [B, 1, F, T] float32 (widened exactly);
+    out_lens: [B] output steps per clip.  -> [B, C, F', T'] float64.  layers_out: a list that receives every layer's output."""
+    from danspeech_amd.synthetic import CONV_SPECS
+    x = _f64(x)
+    for li, (_, co, _, _, sf, st, pf, pt) in enumerate(CONV_SPECS[:conv_layers]):
+        y = correlate(x, _f64(sd["conv.seq_module.%d.weight" % (3 * li)]), (sf, st), (pf, pt))
+        y = mask_time(y + _f64(sd["conv.seq_module.%d.bias" % (3 * li)]).reshape(1, co, 1, 1), out_lens)
+        a, b = bn2d_affine(sd, li)
+        y = mask_time(y * a.reshape(1, co, 1, 1) + b.reshape(1, co, 1, 1), out_lens)
+        x = mask_time(np.clip(y, 0.0, 20.0), out_lens)
+        if layers_out is not None:
+            layers_out.append(x)
+    return x
+
+
+def lookahead(sd, x, context):
+    """Lookahead + Hardtanh(0, 20): x [T, B, H] float32 -> [T, B, H] float64."""
+    x = _f64(x)
+    w = _f64(sd["lookahead.0.conv.weight"])[:, 0, :]
+    assert w.shape == (x.shape[2], context)
+    T = x.shape[0]
+    out = np.zeros_like(x)
+    for k in range(min(context, T)):
+        out[:T - k] += x[k:] * w[:, k]
+    return np.clip(out, 0.0, 20.0)
+
+
+def head_logits(sd, x):
+    """BatchNorm1d affine and the linear layer: x [T, B, H] (float32 widened, or float64) -> logits [B, T, C] float64."""
+    p = "fc.0.module.0."
+    a = _f64(sd[p + "weight"]) / np.sqrt(_f64(sd[p + "running_var"]) + BN_EPS)
+    b = _f64(sd[p + "bias"]) - _f64(sd[p + "running_mean"]) * a
+    return np.transpose((_f64(x) * a + b) @ _f64(sd["fc.0.module.1.weight"]).T, (1, 0, 2))
+
+
+def head(sd, x):
+    """... and the softmax over the classes, the maximum subtracted first.  -> probs [B, T, C] float64."""
+    z = head_logits(sd, x)
+    e = np.exp(z - z.max(axis=-1, keepdims=True))
+    return e / e.sum(axis=-1, keepdims=True)

@@ -1,4 +1,5 @@
-"""tests/_f64_ref.py -- the float64 BatchRNN layer the layer-level accuracy tests compare the kernels with -- pinned on the CPU: against
+"""tests/_f64_ref.py -- the float64 BatchRNN layer, conv stack, lookahead and head the stage-level accuracy tests compare the kernels
+with -- pinned on the CPU.  The BatchRNN layer: against
 the fp32 oracle (oracle/model.py, independent code) on seeded cases of all three kinds, and against the reference's own outputs
 (tests/golden/g3_batch_rnn.npz, all 12 tags).
 
@@ -6,7 +7,12 @@ The bounds are float32 noise, not agreement of two float64 programs: the oracle 
 here (numpy 2, OpenBLAS; printed by each test): seeded cases 1.1e-7 .. 8.7e-7, held to 2e-6 -- outputs are sums of two values
 in (-1, 1), one float32 ulp there is 1.2e-7, and a chain of T <= 23 steps of K <= 96 accumulates a few of them; a semantic
 difference (gate order, a mask, the start of the reverse chain, the BatchNorm's epsilon) is 1e-3 or more.  The goldens (torch's
-float32 kernels): 6.5e-8 .. 3.8e-7, held to the 2e-6 tests/test_oracle_golden.py holds the oracle to."""
+float32 kernels): 6.5e-8 .. 3.8e-7, held to the 2e-6 tests/test_oracle_golden.py holds the oracle to.
+
+The dense stages: against oracle/model.py's conv_stack, lookahead and the fc + softmax part of its forward, one tiny case per conv
+depth.  Conv outputs are sums of up to 7392 float32 products of magnitude 1 and below, clipped to [0, 20]: measured 1.1e-6 (depth
+1) .. 3e-7, held to 4e-6; a semantic difference (padding, stride, a mask, the BatchNorm's epsilon, the clip) is 1e-3 or more.
+Probabilities are at most 1: measured 4e-7, held to 2e-6."""
 import numpy as np
 import pytest
 
@@ -65,3 +71,60 @@ def test_reverse_chain_starts_at_the_clips_last_frame():
     alone = f64.direction("gru", x[:4, 1:].astype(np.float64), [4], *w, reverse=True)
     # (two float64 programs: BLAS may sum a batch of two and a batch of one in different orders, nothing more)
     assert np.abs(both[:4, 1] - alone[:, 0]).max() < 1e-14 and not both[4:, 1].any()
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3])
+def test_conv_stack_against_the_fp32_oracle(depth):
+    """3 clips of 21 / 20 / 6 frames (11 / 10 / 3 output steps), n_freq 81, features left in place past the lengths."""
+    sd = syn.make_state_dict(depth, "gru", 8, 1, seed=60 + depth, sample_rate=8000)
+    lens = np.array([21, 20, 6])
+    x = np.random.default_rng(61).standard_normal((3, 1, 81, 21)).astype(np.float32)
+    out_lens = om.get_seq_lens(lens, depth)
+    layers = []
+    ref = f64.conv_stack(sd, x, out_lens, depth, layers_out=layers)
+    o32 = om.conv_stack(sd, x, out_lens, depth)
+    assert ref.dtype == np.float64 and ref.shape == o32.shape == (3, syn.CONV_SPECS[depth - 1][1], syn.conv_out_freq(81, depth), 11)
+    assert len(layers) == depth and layers[-1] is ref
+    for b, L in enumerate(out_lens):
+        assert not ref[b, :, :, L:].any() and ref[b, :, :, :L].any()
+    assert ref.min() >= 0.0 and ref.max() <= 20.0 and (ref == 0).any()
+    err = float(np.abs(o32 - ref).max())
+    print("depth %d: max |fp32 oracle - f64| = %.3g" % (depth, err))
+    assert err <= 4e-6
+    # the convolution reads the features past a clip's length: zeroing them changes outputs inside the clip
+    xz = x.copy()
+    xz[2, :, :, 6:] = 0
+    assert np.abs(f64.conv_stack(sd, xz, out_lens, depth)[2] - ref[2]).max() > 1e-3
+
+
+def test_conv_clip_reaches_the_ceiling():
+    sd = syn.make_state_dict(1, "gru", 8, 1, seed=62, sample_rate=8000)
+    sd["conv.seq_module.0.weight"] = sd["conv.seq_module.0.weight"] * np.float32(20)
+    x = np.random.default_rng(63).standard_normal((1, 1, 81, 9)).astype(np.float32)
+    ref, o32 = f64.conv_stack(sd, x, [5], 1), om.conv_stack(sd, x, [5], 1)
+    assert (ref == 20.0).any() and np.array_equal(ref == 20.0, o32 == 20.0) and np.abs(o32 - ref).max() <= 2e-5
+
+
+@pytest.mark.parametrize("context,T", [(1, 5), (3, 5), (20, 7), (20, 25)])
+def test_lookahead_against_the_fp32_oracle(context, T):
+    sd = syn.make_state_dict(1, "gru", 24, 1, bidirectional=False, context=context, seed=64, sample_rate=100)
+    sd["lookahead.0.conv.weight"] = sd["lookahead.0.conv.weight"] * np.float32(8)
+    x = (np.random.default_rng(65).standard_normal((T, 3, 24)) * 3).astype(np.float32)
+    ref, o32 = f64.lookahead(sd, x, context), om.lookahead(sd, x, context)
+    assert ref.shape == o32.shape and (ref == 0).any() and (ref == 20).any()
+    assert np.abs(o32 - ref).max() <= 2e-5         # values up to 20: one float32 ulp is 1.9e-6, `context` terms
+
+
+@pytest.mark.parametrize("C,H", [(1, 8), (33, 40), (97, 13)])
+def test_head_against_the_fp32_oracle(C, H):
+    """oracle/model.py forward's last lines: BatchNorm affine, matmul, transpose, softmax."""
+    sd = syn.make_state_dict(1, "gru", H, 1, n_labels=C, seed=66, sample_rate=100)
+    x = np.random.default_rng(67).uniform(-2, 2, (6, 2, H)).astype(np.float32)
+    ref = f64.head(sd, x)
+    a, b = om._bn_affine(sd, "fc.0.module.0")
+    y = (x * a + b).astype(np.float32)
+    o32 = om.softmax((y.reshape(12, -1) @ sd["fc.0.module.1.weight"].T).reshape(6, 2, -1).transpose(1, 0, 2).astype(np.float32))
+    assert ref.shape == o32.shape == (2, 6, C) and np.abs(ref.sum(axis=-1) - 1).max() < 1e-12
+    err = float(np.abs(o32 - ref).max())
+    print("C %d H %d: max |fp32 oracle - f64| = %.3g" % (C, H, err))
+    assert err <= 2e-6
