@@ -146,7 +146,7 @@ struct RnnPersistLaunch {
     int B, T;
     int d0 = 0, ny = 1;          // this launch covers directions d0 .. d0+ny-1 (grid = nwg x ny workgroups, all co-resident)
     unsigned spin_limit = kPersistSpinLimit;
-    int drop_wg = -1, drop_step = -1;    // test hook: see DSMI_DEBUG_DROP_SIGNAL in api.hip
+    int drop_wg = -1, drop_step = -1;    // test hook: see DSMI_DEBUG_DROP_SIGNAL in model_build.hip
     EvPair ev;
     unsigned long long* dbg = nullptr;   // diagnostics: accumulated per-wave phase times
     // carried-state variant (D = 1): h0 [B][Hs] seeds the chains; counters are then [D * ceil(B/32)][1 + T] words (each chain's seed
@@ -172,7 +172,7 @@ struct RnnPersist16Launch {
     int tile0 = 0, ntw = 0, nwin = 1;   // ring kernel: nwin windows of ntw tiles each, from tile0, side by side (ntw 0: all tiles in one window)
     unsigned* tickets = nullptr;        // four-wave ring kernel: [nwin][2] words zeroed before the launch -> directions by XCD half (null: by blockIdx)
     unsigned spin_limit = kPersistSpinLimit;
-    int drop_wg = -1, drop_step = -1;    // test hook: see DSMI_DEBUG_DROP_SIGNAL in api.hip
+    int drop_wg = -1, drop_step = -1;    // test hook: see DSMI_DEBUG_DROP_SIGNAL in model_build.hip
     EvPair ev;
     unsigned long long* dbg = nullptr;   // diagnostics: accumulated per-wave phase times
 };

@@ -75,7 +75,7 @@ struct dsmi_model {
     uint16_t* a_sp = nullptr;       // split A operand of the x-projection GEMM
     unsigned* pcnt = nullptr;     // persistent-kernel step counters [layers][D*ceil(B/32)][T]
     unsigned* perr = nullptr;     // persistent-kernel timeout word (device)
-    // ---- a forward whose persistent kernel timed out is recomputed by dsmi_forward_status (api.hip).  Forwards are
+    // ---- a forward whose persistent kernel timed out is recomputed by dsmi_forward_status (api.hip: collect_oldest).  Forwards are
     // asynchronous, so a small ring remembers the ones whose status has not been collected yet (oldest first).
     struct FwdSlot {
         const float* feat = nullptr; float* probs = nullptr; std::vector<int32_t> lens; int B = 0, T = 0; void* stream = nullptr;
@@ -94,8 +94,7 @@ struct dsmi_model {
     bool last_plan_x16 = false;
     unsigned spin_limit = dsmi::kPersistSpinLimit;   // DSMI_DEBUG_SPIN_LIMIT
     int drop_layer = -1, drop_wg = -1, drop_step = -1;   // DSMI_DEBUG_DROP_SIGNAL=layer:workgroup:step (tests: force a timeout)
-    int lanes = 2, lane = 0;       // persistent kernels of a handle whose caller keeps two batches in flight take half of the CUs, on this lane
-    int persist_lock_fd = -1;      // this process holds the device's persistent-kernel lock file
+    int lane = 0;                  // the handle's home slot at the device's gate (gate.h: persist_next_lane; rnn_plan.h: gate_first)
     // pinned staging of the per-batch lengths (pageable memory must not back an async copy)
     static constexpr int kStage = 4;
     int32_t* lens_stage = nullptr; int stage_cap = 0, stage_next = 0;
@@ -111,7 +110,7 @@ struct dsmi_model {
     int persist_gen = 2;          // 2: rnn_persist16.hip where eligible (DSMI_RNN_MODE=persist8 selects the first generation)
     float* xin = nullptr;
     std::vector<int32_t> host_out_lens;   // output lengths of the batch being processed
-    int32_t *lens_dev = nullptr, *sizes_dev = nullptr, *raw_ids = nullptr, *ids = nullptr, *offs = nullptr, *nout = nullptr;
+    int32_t* lens_dev = nullptr;
 
     // dsmi_stream_forward_many: the batched pass's workspaces (stream.hip), grown on demand
     struct StreamBatch* sbatch = nullptr;
@@ -125,11 +124,43 @@ struct dsmi_model {
     double step_flops = 0, total_flops = 0;
 };
 
+// ---- what the translation units of the model share (model_build.hip, api.hip, profile.hip, stream.hip)
+#define HIP_OK(m, expr)                                                                   \
+    do {                                                                                  \
+        hipError_t e_ = (expr);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            (m)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
+            return DSMI_ERR_HIP;                                                          \
+        }                                                                                 \
+    } while (0)
+
+inline int fail(dsmi_model* m, int code, const std::string& msg) {
+    m->err = msg;
+    return code;
+}
+
+// Words of dsmi_model::pcnt that a layer of B clips and To steps hands off through, zeroed before its launches: the first generation's
+// counters, or the 16-unit kernels' -- `tickets`: with the ring kernels' direction tickets behind them, two words per window.
+inline size_t persist_cnt_words(const dsmi_model* m, int B, int To, bool x16, bool tickets) {
+    if (!x16) return (size_t)m->geom.D * dsmi::ceil_div(B, 32) * To;
+    return (size_t)m->geom.D * dsmi::ceil_div(B, 16) * To * dsmi::kPersist16CntWords + (tickets ? 2 * dsmi::ceil_div(B, 16) + 2 : 0);
+}
+
+// model_build.hip: output frames of L input frames, and the fewest input frames whose seq_len is To
+int seq_len(const dsmi_model* m, int L);
+int frames_for(int To);
+
+// profile.hip
 dsmi::EvPair timer_arm(dsmi_model* m, int kind, bool sample, double flops, double bytes);
+void timer_resolve(dsmi_model* m);
 
 // stream.hip / api.hip: the batched streaming pass
 void stream_batch_free(dsmi_model* m);
 bool stream_persist_layer(dsmi_model* m, const dsmi::RnnPersistLaunch& pl, hipStream_t s);
-// api.hip: the launch descriptions of layer l's persistent kernels on the model's own buffers, test hooks included
+// api.hip: the launch descriptions of layer l's recurrent kernels on the model's own buffers, test hooks included
 dsmi::RnnPersist16Launch persist16_launch(const dsmi_model* m, int l, int B, int To, int dst);
 dsmi::RnnPersistLaunch persist_launch(const dsmi_model* m, int l, int B, int To, int dst);
+dsmi::RnnStepLaunch rnn_step_launch(const dsmi_model* m, int l, int B, int To, int dst);
+// api.hip: what the ring kernels' predicates and plan take from the environment
+struct RingEnv { bool small_shapes; int most, slot_cap; };
+const RingEnv& ring_env();

@@ -167,7 +167,7 @@ inline int rnn_persist_ring4_tiles(const RnnGeom& g16, int B, int n_cus, bool sm
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------------
 
-// The per-device gate (api.hip, PersistGate): four lane slots of a quarter of the CUs each for the kernels sized by halves and
+// The per-device gate (gate.hip, PersistGate; what a launch waits for there: gate_plan.h): four lane slots of a quarter of the CUs each for the kernels sized by halves and
 // quarters of the device, and up to five slots of their own for the ring kernels' windows.
 constexpr int kMaxLanes = 4;
 constexpr int kRingSlots = 5;

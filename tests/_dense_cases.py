@@ -42,7 +42,7 @@ three 32-channel tiles per clip in blockIdx.z); n_freq 161, 81 (fo = 41 / 21 / 1
 layer's in-length outputs (float64 reference) at least 1 % sit at the ceiling of 20 and at least 20 % strictly inside (0, 20)
 (test_dense_accuracy_sensitivity.py asserts it): the clamp, inputs up to 20 in layers 2 and 3, lo terms up to 2^-7 --;
 ``DSMI_DENSE_MODE=f32``; and ``range``: one weight of the last layer set to 1000.0, above 60000 / 64, with no environment variable
--- the whole stack then has to run on conv.hip (api.hip: conv_mode) and meets the conv_f32 bound.  (1000 * 64 is an fp16 number, so the
+-- the whole stack then has to run on conv.hip (model_build.hip: conv_mode) and meets the conv_f32 bound.  (1000 * 64 is an fp16 number, so the
 split kernels would compute the case as well: the bound cannot tell which path ran.  The case's output must therefore equal, bit for
 bit, that of a DSMI_DENSE_MODE=f32 model of the same weights -- and the same comparison at default weights, F32_CONTROL, must differ.)
 

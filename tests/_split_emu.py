@@ -108,7 +108,7 @@ def _only(w, kf=None, kt=None):
 
 
 def _bn32(sd, li):
-    """a, b of the eval BatchNorm2d as api.hip computes them: float32 throughout"""
+    """a, b of the eval BatchNorm2d as model_build.hip computes them: float32 throughout"""
     p = "conv.seq_module.%d." % (3 * li + 1)
     f = lambda n: np.asarray(sd[p + n], dtype=np.float32)
     a = f("weight") * (np.float32(1) / np.sqrt(f("running_var") + np.float32(1e-5)))

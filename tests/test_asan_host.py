@@ -1,7 +1,8 @@
 """The host-only code of libdsmi.so under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not
 available on the pool): the ARPA and KenLM-binary readers against a few hundred damaged files, the shard plan and the phrase
-gate against their definitions.  `make -C danspeech_amd/csrc asan` builds tools/asan/host_fuzz.cpp with the product's own
-sources (lm.cpp.inc, lm_klm.cpp.inc, host_logic.h).  A sanitizer report or a crash fails the test; a refused file is fine."""
+gate against their definitions, the device gate's admission of persistent launches (gate_plan.h) against a table written out by
+hand and its invariants.  `make -C danspeech_amd/csrc asan` builds tools/asan/host_fuzz.cpp with the product's own
+sources (lm.cpp.inc, lm_klm.cpp.inc, host_logic.h, rnn_plan.h, gate_plan.h).  A sanitizer report or a crash fails the test; a refused file is fine."""
 import os
 import shutil
 import subprocess
@@ -34,6 +35,14 @@ def _run(exe, args):
 
 def test_shard_plans_and_phrase_gates(exe):
     assert "ok" in _run(exe, ["plan", "7", "400"])
+
+
+def test_device_gate_admission(exe):
+    """What a persistent launch waits for and records at the per-device gate: the literal cases (two models of different widths
+    beyond the device among them), then random sequences of planned launches on 256, 128 and 64 CUs -- which must reach the
+    case where a ring launch waits for windows on slots that are not its own."""
+    out = _run(exe, ["gate", "7", "400"]).split()
+    assert out[1:3] == ["gate", "cases"] and out[4:7] == ["1200", "sequences", "ok,"] and int(out[0]) >= 16 and int(out[7]) > 0, out
 
 
 def test_language_model_readers_on_damaged_files(exe, tmp_path):

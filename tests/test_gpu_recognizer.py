@@ -259,7 +259,7 @@ def test_small_models_in_the_pipeline(hidden):
 
 def test_a_ring_model_and_a_whole_device_model_in_flight_together():
     """Two engines used at once from two threads: one model the ring kernels take (slot-sized windows, ordered by events) and one
-    whose recurrent kernel takes the whole device (turns through the device lock, api.hip) -- the two families are ordered
+    whose recurrent kernel takes the whole device (turns through the device lock, gate.hip) -- the two families are ordered
     against each other by events in enqueue order.  Every batch equals its engine's single call; no hand-off timed out."""
     import threading
     from danspeech_amd import Recognizer

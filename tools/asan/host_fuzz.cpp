@@ -6,6 +6,8 @@
 //   host_fuzz rnnplan FILE    the recurrent-layer plan (rnn_plan.h) of every input row of FILE, one line of text per row, each plan
 //                             checked against the invariants below; rows: kind D H B inflight ring_windows lane KERNEL MODE DENSE n_cus
 //   host_fuzz rnnplan grid    the invariants over the grid of 29 315 520 inputs that the plan was compared on with the code it replaced
+//   host_fuzz gate SEED N     the device gate's admission (gate_plan.h): a table of launches with the masks written out by hand, then N
+//                             random sequences of planned launches of models of different widths, checked against the invariants below
 #define __host__
 #define __device__
 #include <cmath>
@@ -19,6 +21,7 @@
 #include "lm_klm.cpp.inc"
 #include "host_logic.h"
 #include "rnn_plan.h"
+#include "gate_plan.h"
 
 using namespace dsmi;
 
@@ -174,7 +177,7 @@ static int rnn_plan_check(const RnnPlanInput& in, const RnnPlan& plan) {
             const int held = std::min(kRingSlots, l.cus > 0 ? in.n_cus / l.cus : 0);
             if (l.gate != GATE_RING || l.nslots != l.nwin || l.slot0 < 0 || l.slot0 + l.nslots > held) return 5;
             if (l.cus != rnn_persist_ring_cus(in.geom16) || l.nwin * l.cus > in.n_cus) return 6;
-            if (l.ticket < 0 || l.ticket + 2 * l.nwin > 2 * ntiles + 2) return 7;      // the ticket words api.hip zeroes behind the counters
+            if (l.ticket < 0 || l.ticket + 2 * l.nwin > 2 * ntiles + 2) return 7;      // the ticket words run_rnn_plan zeroes behind the counters (model.h: persist_cnt_words)
         } else if (l.kernel != RNN_STEPS) {
             if (l.gate != GATE_LANES || l.slot0 < 0 || l.slot0 + l.nslots > kMaxLanes || l.nslots < 1) return 5;
             if (l.kernel == RNN_DUO || l.kernel == RNN_PERSIST8) {
@@ -236,10 +239,130 @@ static int run_rnnplan(int argc, char** argv) {
     return rc;
 }
 
+// ---- gate: what a launch waits for and records at the per-device gate ----------------------------------------------------------
+// The expected masks are written out by hand from the four functions gate_plan.h replaced (gate_wait, ring_gate_wait, gate_record,
+// ring_gate_record): bit i = lane slot i / ring slot i.
+struct GateCase {
+    const char* name;
+    int ring_cus[kRingSlots];
+    int gate, slot0, nslots, cus, n_cus;
+    bool turn;
+    unsigned w_lanes, w_ring; bool w_full, w_acquire;
+    unsigned r_lanes, r_ring; bool r_full, r_release;
+    int after[kRingSlots];
+};
+static const GateCase kGateCases[] = {
+    // lane launches: their own lanes, every ring slot and the whole-device event, with or without the turn word
+    {"lane width 1, turn", {0, 0, 0, 0, 0}, GATE_LANES, 2, 1, 0, 256, true, 0x4, 0x1f, true, false, 0x4, 0, false, false, {0, 0, 0, 0, 0}},
+    {"lane width 1, no turn", {0, 0, 0, 0, 0}, GATE_LANES, 2, 1, 0, 256, false, 0x4, 0x1f, true, false, 0x4, 0, false, false, {0, 0, 0, 0, 0}},
+    {"lane width 2, turn", {50, 0, 0, 0, 0}, GATE_LANES, 2, 2, 0, 256, true, 0xc, 0x1f, true, false, 0xc, 0, false, false, {50, 0, 0, 0, 0}},
+    {"lane width 2, no turn", {50, 0, 0, 0, 0}, GATE_LANES, 0, 2, 0, 256, false, 0x3, 0x1f, true, false, 0x3, 0, false, false, {50, 0, 0, 0, 0}},
+    // the whole device: every event but the whole-device one and the lock -- or, without the word, the events alone
+    {"lane width 4, turn", {0, 50, 0, 0, 0}, GATE_LANES, 0, 4, 0, 256, true, 0xf, 0x1f, false, true, 0, 0, true, true, {0, 50, 0, 0, 0}},
+    {"lane width 4, no turn", {0, 50, 0, 0, 0}, GATE_LANES, 0, 4, 0, 256, false, 0xf, 0x1f, true, false, 0xf, 0, false, false, {0, 50, 0, 0, 0}},
+    // ring windows
+    {"ring on empty slots", {0, 0, 0, 0, 0}, GATE_RING, 1, 1, 50, 256, true, 0xf, 0x02, true, false, 0, 0x02, false, false, {0, 50, 0, 0, 0}},
+    {"four of 56 CUs and one of 50 on 256", {56, 56, 56, 56, 0}, GATE_RING, 4, 1, 50, 256, true, 0xf, 0x11, true, false, 0, 0x10, false, false, {56, 56, 56, 56, 50}},
+    {"the same on 304 CUs", {56, 56, 56, 56, 0}, GATE_RING, 4, 1, 50, 304, true, 0xf, 0x10, true, false, 0, 0x10, false, false, {56, 56, 56, 56, 50}},
+    {"own slot busy", {50, 50, 0, 0, 0}, GATE_RING, 1, 1, 50, 256, false, 0xf, 0x02, true, false, 0, 0x02, false, false, {50, 50, 0, 0, 0}},
+    {"own slot busy, the others too wide", {56, 56, 56, 56, 56}, GATE_RING, 2, 1, 50, 256, true, 0xf, 0x05, true, false, 0, 0x04, false, false, {56, 56, 50, 56, 56}},
+    {"own slot first: the next one in index order", {0, 56, 56, 56, 56}, GATE_RING, 0, 1, 50, 256, true, 0xf, 0x03, true, false, 0, 0x01, false, false, {50, 56, 56, 56, 56}},
+    {"two windows that fit", {50, 50, 50, 50, 50}, GATE_RING, 2, 2, 50, 256, true, 0xf, 0x0c, true, false, 0, 0x0c, false, false, {50, 50, 50, 50, 50}},
+    {"two windows, one other to wait for", {70, 70, 56, 56, 0}, GATE_RING, 2, 2, 64, 256, true, 0xf, 0x0d, true, false, 0, 0x0c, false, false, {70, 70, 64, 64, 0}},
+    {"exactly the device: no more waits", {100, 100, 0, 0, 56}, GATE_RING, 2, 1, 100, 256, true, 0xf, 0x05, true, false, 0, 0x04, false, false, {100, 100, 100, 0, 56}},
+    {"one CU beyond: two others", {100, 100, 0, 0, 57}, GATE_RING, 2, 1, 100, 256, true, 0xf, 0x07, true, false, 0, 0x04, false, false, {100, 100, 100, 0, 57}},
+};
+
+static int gate_literal_cases() {
+    for (const GateCase& c : kGateCases) {
+        DeviceGateState st;
+        for (int i = 0; i < kRingSlots; ++i) st.ring_cus[i] = c.ring_cus[i];
+        RnnLaunch l;
+        l.gate = c.gate; l.slot0 = c.slot0; l.nslots = c.nslots; l.cus = c.cus;
+        const DeviceGateWait w = gate_plan_wait(st, l, c.n_cus, c.turn);
+        const DeviceGateRecord r = gate_plan_record(st, l, c.turn);
+        bool ok = w.lanes == c.w_lanes && w.ring == c.w_ring && w.full == c.w_full && w.acquire == c.w_acquire &&
+                  r.lanes == c.r_lanes && r.ring == c.r_ring && r.full == c.r_full && r.release == c.r_release;
+        for (int i = 0; i < kRingSlots; ++i) ok = ok && r.after.ring_cus[i] == c.after[i];
+        if (!ok) {
+            std::fprintf(stderr, "gate case '%s': wait %x %x %d %d, record %x %x %d %d\n", c.name, w.lanes, w.ring, w.full, w.acquire, r.lanes, r.ring, r.full, r.release);
+            return 7;
+        }
+    }
+    return 0;
+}
+
+// Random sequences: two or three models of different widths on one device, layers planned by plan_rnn_layer in random order.  The
+// simulation takes every recorded ring window for running until a later launch has waited for its slot.  0, or the broken rule:
+//   1  the CUs of the windows not waited for plus the new launch's exceed the device
+//   2  a lane launch waits for every ring slot (and its own lanes); a ring launch for every lane, its own slots and the whole-device event
+//   3  a whole-device launch waits for every lane and ring slot, and takes the turn exactly when the word exists (else the event)
+//   4  what is recorded is exactly the launch's own slots (a whole-device launch under the lock: the lock given back, the whole-device event)
+static long g_extra_waits = 0;      // ring launches that had to wait for a slot not their own
+static int gate_sequence(std::mt19937& rng, int n_cus, bool turn) {
+    static const int Hs[] = {256, 512, 640, 800, 832, 896, 1024};
+    const int nmodels = 2 + (int)(rng() % 2);
+    int kind[3], H[3], D[3];
+    for (int k = 0; k < nmodels; ++k) { kind[k] = (int)(rng() % 3); H[k] = Hs[rng() % 7]; D[k] = 1 + (int)(rng() % 2); }
+    DeviceGateState st;
+    int running[kRingSlots] = {0, 0, 0, 0, 0};
+    const unsigned all_lanes = (1u << kMaxLanes) - 1, all_ring = (1u << kRingSlots) - 1;
+    for (int step = 0; step < 60; ++step) {
+        const int k = (int)(rng() % (unsigned)nmodels);
+        static const int Bs[] = {1, 16, 32, 33, 64, 96, 128};
+        static const char* const kernels[] = {"-", "-", "-", "duo", "ring"};
+        const RnnPlanInput in = rnn_plan_input(kind[k], D[k], H[k], Bs[rng() % 7], 1 + (int)(rng() % 4), (int)(rng() % 3), (int)(rng() % 8),
+                                               kernels[rng() % 5], (rng() % 8) ? "-" : "persist8", "split", n_cus);
+        const RnnPlan plan = plan_rnn_layer(in);
+        for (int i = 0; i < plan.launches.size(); ++i) {
+            const RnnLaunch& l = plan.launches[i];
+            if (l.gate == GATE_NONE || l.join) continue;
+            const unsigned own = ((1u << l.nslots) - 1) << l.slot0;
+            const DeviceGateWait w = gate_plan_wait(st, l, n_cus, turn);
+            const DeviceGateRecord r = gate_plan_record(st, l, turn);
+            for (int s = 0; s < kRingSlots; ++s) if (w.ring >> s & 1) running[s] = 0;
+            int busy = l.gate == GATE_RING ? l.nslots * l.cus : 0;
+            for (int s = 0; s < kRingSlots; ++s) busy += running[s];
+            if (busy > n_cus) return 1;
+            if (l.gate == GATE_RING && (w.ring & ~own)) ++g_extra_waits;
+            const bool whole = l.gate == GATE_LANES && l.nslots >= kMaxLanes;
+            if (l.gate == GATE_RING) {
+                if (w.lanes != all_lanes || !w.full || w.acquire || (w.ring & own) != own) return 2;
+                if (r.ring != own || r.lanes || r.full || r.release) return 4;
+            } else if (!whole) {
+                if (w.ring != all_ring || w.lanes != own || !w.full || w.acquire) return 2;
+                if (r.lanes != own || r.ring || r.full || r.release) return 4;
+            } else {
+                if (w.ring != all_ring || w.lanes != all_lanes || w.acquire != turn || w.full != !turn) return 3;
+                if (r.ring || r.lanes != (turn ? 0u : all_lanes) || r.full != turn || r.release != turn) return 4;
+            }
+            for (int s = 0; s < kRingSlots; ++s) {
+                const bool mine = l.gate == GATE_RING && (own >> s & 1);
+                if (r.after.ring_cus[s] != (mine ? l.cus : st.ring_cus[s])) return 4;
+                if (mine) running[s] = l.cus;
+            }
+            st = r.after;
+        }
+    }
+    return 0;
+}
+
+static int run_gate(int argc, char** argv) {
+    if (const int bad = gate_literal_cases()) return bad;
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    for (int rep = 0; rep < reps; ++rep)
+        for (int n_cus : {256, 128, 64})
+            if (const int bad = gate_sequence(rng, n_cus, rep % 2 == 0)) { std::fprintf(stderr, "gate rule %d broken on %d CUs (sequence %d)\n", bad, n_cus, rep); return 8; }
+    std::printf("%d gate cases and %d sequences ok, %ld launches waited for other windows\n", (int)(sizeof kGateCases / sizeof kGateCases[0]), 3 * reps, g_extra_waits);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "rnnplan")) return run_rnnplan(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "gate")) return run_gate(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]]\n");
     return 2;
 }
