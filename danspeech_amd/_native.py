@@ -648,8 +648,7 @@ class NativeFrontend(_Handle):
 
     def _stream_frames(self, n):
         """Frames the streaming parser makes of a chunk of ``n`` samples."""
-        n_fft = 2 * (self.n_freq - 1)
-        return 1 + (n - n_fft) // self.hop if n >= n_fft else 0
+        return 1 + (n - self.n_fft) // self.hop if n >= self.n_fft else 0
 
     def features_stream(self, pcm_dev, state):
         """dsmi_features_stream: one chunk of the streaming parser.  ``state`` = float64[3] (input_mean, input_std,

@@ -58,6 +58,8 @@ namespace {
 constexpr int FT = 8;   // frames per workgroup
 constexpr int PAD_NONE = 2;   // internal third pad mode: no centre padding
 
+size_t direct_lds_bytes(int n_fft) { return sizeof(double) * ((size_t)2 * n_fft + (size_t)n_fft * FT); }   // stft_logmag_kernel: s_tw + s_x
+
 __global__ __launch_bounds__(256) void stft_logmag_kernel(const void* pcm, int dtype, const int64_t* offs, const int64_t* nsamp,
                                                           const double* tw, const double* win, int n_fft, int hop, int n_freq,
                                                           int pad_mode, float* feat, int t_stride) {
@@ -442,7 +444,7 @@ extern "C" int dsmi_features_stream(dsmi_frontend* f, const void* pcm, int dtype
     if (stft_on_mfma(f->n_fft, dtype)) {
         launch_stft_mfma(dim3(ceil_div(nfr, MF), 1), s, pcm, dtype, f->offs, f->offs + f->cap, f->tw, f->win, f->hop, PAD_NONE, feat, t_stride);
     } else {
-        const size_t lds = sizeof(double) * ((size_t)2 * f->n_fft + (size_t)f->n_fft * FT);
+        const size_t lds = direct_lds_bytes(f->n_fft);
         hipLaunchKernelGGL(stft_logmag_kernel, dim3(ceil_div(nfr, FT), 1), dim3(256), lds, s, pcm, dtype, f->offs, f->offs + f->cap,
                            f->tw, f->win, f->n_fft, f->hop, f->n_freq, PAD_NONE, feat, t_stride);
     }
@@ -503,6 +505,22 @@ extern "C" int dsmi_frontend_create(const dsmi_frontend_desc* d, int device, dsm
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) {
         g_fe_error = "no such HIP device";
         return DSMI_ERR_HIP;
+    }
+    // the direct kernel keeps the twiddles and FT frames in dynamic LDS (80 bytes per tap): above the 64 KB a kernel gets by default from
+    // n_fft = 820 on (44.1 kHz at 20 ms: 882), above what a workgroup of this device can have at all from about 2000 on
+    {
+        const size_t lds = direct_lds_bytes(n);
+        int lds_max = 0;
+        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) { g_fe_error = "frontend: no LDS size from the device"; return DSMI_ERR_HIP; }
+        if (lds > (size_t)lds_max) {
+            g_fe_error = "audio_conf gives n_fft = " + std::to_string(n) + ": the direct STFT kernel needs " + std::to_string(lds) +
+                         " bytes of LDS per workgroup, the device's limit is " + std::to_string(lds_max);
+            return DSMI_ERR_INVALID;
+        }
+        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(stft_logmag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            g_fe_error = "frontend: raising the direct STFT kernel's LDS limit failed";
+            return DSMI_ERR_HIP;
+        }
     }
     dsmi_frontend* f = new dsmi_frontend();
     f->desc = *d; f->device = device; f->n_fft = n; f->hop = hop; f->n_freq = n / 2 + 1;
@@ -590,7 +608,7 @@ extern "C" int dsmi_features(dsmi_frontend* m, const void* pcm, int dtype, const
     if (stft_on_mfma(m->n_fft, dtype)) {
         launch_stft_mfma(dim3(ceil_div(maxfr, MF), B), s, pcm, dtype, f->offs, f->offs + f->cap, f->tw, f->win, m->hop, m->desc.pad_mode, feat, t_stride);
     } else {
-        const size_t lds = sizeof(double) * ((size_t)2 * m->n_fft + (size_t)m->n_fft * FT);
+        const size_t lds = direct_lds_bytes(m->n_fft);
         DSMI_LAUNCH(stft_logmag_kernel, dim3(ceil_div(maxfr, FT), B), dim3(256), lds, s, ev, pcm, dtype, f->offs, f->offs + f->cap,
                     f->tw, f->win, m->n_fft, m->hop, m->n_freq, m->desc.pad_mode, feat, t_stride);
     }
@@ -637,7 +655,7 @@ extern "C" int dsmi_features_stream_many(dsmi_frontend* f, const void* pcm, int 
     if (stft_on_mfma(f->n_fft, dtype)) {
         launch_stft_mfma(dim3(ceil_div(maxfr, MF), n), s, pcm, dtype, f->offs, f->offs + f->cap, f->tw, f->win, f->hop, PAD_NONE, feat, t_stride);
     } else {
-        const size_t lds = sizeof(double) * ((size_t)2 * f->n_fft + (size_t)f->n_fft * FT);
+        const size_t lds = direct_lds_bytes(f->n_fft);
         hipLaunchKernelGGL(stft_logmag_kernel, dim3(ceil_div(maxfr, FT), n), dim3(256), lds, s, pcm, dtype, f->offs, f->offs + f->cap,
                            f->tw, f->win, f->n_fft, f->hop, f->n_freq, PAD_NONE, feat, t_stride);
     }

@@ -119,7 +119,9 @@ int dsmi_seq_lens(const dsmi_model* m, const int32_t* lens_host, int n, int32_t*
  * sample offset sum(n_samples_host[:b]); dtype DSMI_PCM_* (float arrays as load_audio returns
  * them, or a WAV file's raw frames: the file never has to be decoded on the host).
  * feat_dev: [B][n_freq][t_stride] float32, frames past a clip's own count are zero.
- * frames_host[b] = 1 + n_samples[b] / hop.  Asynchronous on `stream`. */
+ * frames_host[b] = 1 + n_samples[b] / hop.  Asynchronous on `stream`.
+ * dsmi_frontend_create: DSMI_ERR_INVALID for a window length (sample_rate * window_size) whose direct transform needs more LDS per
+ * workgroup (80 bytes per sample of the window) than the device has; the message names both. */
 int dsmi_frontend_create(const dsmi_frontend_desc* desc, int device, dsmi_frontend** out);
 void dsmi_frontend_destroy(dsmi_frontend* f);
 const char* dsmi_frontend_last_error(const dsmi_frontend* f);

@@ -21,6 +21,15 @@ The dense stages, restated the same way (oracle/model.py:77-96, 163-171, 199-205
   one mask after the clip is the same thing).  The convolution reads input values past a clip's length like any other.
 * ``lookahead``: ``y[t] = clip(sum_k w[:, k] * x[t + k], 0, 20)``, zeros past the end.
 * ``head``: BatchNorm1d affine, ``x W^T``, softmax over the classes with the maximum subtracted; [T, B, H] -> [B, T, C].
+
+The spectrogram front end (oracle/features.py and oracle/streaming.py document it, reference parsers.py:43-72 and 101-163; nothing of
+them is called):
+
+* ``spectrogram``: frames of ``n_fft`` samples every ``hop``, after ``n_fft // 2`` samples of ``reflect`` or ``constant`` (zero)
+  padding on both sides, or with no padding at all (``none``: the streaming parser, ``1 + (N - n_fft) // hop`` frames); times the
+  symmetric window; the real DFT; ``log1p(hypot(re, im))``; with ``normalize`` minus the mean, over the unbiased standard deviation,
+  of the clip's own ``n_freq x frames`` values.  Nothing is rounded to float32 anywhere.
+* ``stream_norm``: the running statistics of the streaming parser after a chunk, and the mean / std that normalise the chunk.
 """
 import numpy as np
 
@@ -190,3 +199,62 @@ def head(sd, x):
     z = head_logits(sd, x)
     e = np.exp(z - z.max(axis=-1, keepdims=True))
     return e / e.sum(axis=-1, keepdims=True)
+
+
+# ---- the spectrogram front end ---------------------------------------------------------------------------------------------------
+WINDOWS = ("hamming", "hann", "blackman", "bartlett")
+DATASET_MEAN, DATASET_STD, ALPHA_INCREMENT = 5.492418704733003, 1.7552755216970917, 0.1      # parsers.py:89-94
+
+
+def sym_window(name, n):
+    """scipy.signal.windows.<name>(n, sym=True), as dsmi_frontend_create writes them: x = j / (n - 1)."""
+    x = np.arange(n, dtype=np.float64) / (n - 1) if n > 1 else np.zeros(n)
+    if name == "hamming":
+        return 0.54 - 0.46 * np.cos(2.0 * np.pi * x)
+    if name == "hann":
+        return 0.5 - 0.5 * np.cos(2.0 * np.pi * x)
+    if name == "blackman":
+        return 0.42 - 0.5 * np.cos(2.0 * np.pi * x) + 0.08 * np.cos(4.0 * np.pi * x)
+    assert name == "bartlett", name
+    return 1.0 - np.abs(2.0 * x - 1.0)
+
+
+def samples_f64(samples):
+    """The sample values widened exactly: float32 / float64 as they are, integers (decoded WAV frames) below 2^53."""
+    a = np.asarray(samples)
+    if a.dtype.kind == "i":
+        assert a.size == 0 or np.abs(a).max() < 1 << 53
+        return a.astype(np.float64)
+    return _f64(a)
+
+
+def spectrogram(samples, n_fft, hop, window="hamming", pad="reflect", normalize=True):
+    """[N] samples -> float64 [n_fft // 2 + 1, frames]."""
+    y = samples_f64(samples)
+    assert y.ndim == 1 and pad in ("reflect", "constant", "none")
+    if pad != "none":
+        assert pad == "constant" or len(y) > n_fft // 2
+        y = np.pad(y, n_fft // 2, mode=pad)
+    assert len(y) >= n_fft
+    T = 1 + (len(y) - n_fft) // hop
+    idx = np.arange(n_fft)[:, None] + hop * np.arange(T)[None, :]
+    D = np.fft.rfft(y[idx] * sym_window(window, n_fft)[:, None], axis=0)
+    spect = np.log1p(np.hypot(D.real, D.imag))
+    if normalize:
+        with np.errstate(invalid="ignore", divide="ignore"):       # an all-zero clip: 0 / 0, as the parser's
+            spect = (spect - spect.mean()) / spect.std(ddof=1)
+    return spect
+
+
+def stream_norm(stats, state3):
+    """parsers.py:146-158.  stats = (mean, population std) of the chunk's log1p|D|; state3 = [input_mean, input_std, alpha] before
+    the chunk.  -> (state3 after it, the mean and the std that normalise the chunk), float64."""
+    input_mean, input_std, alpha = (float(v) for v in state3)
+    alpha += ALPHA_INCREMENT
+    input_mean = (input_mean + float(stats[0])) / 2
+    input_std = (input_std + float(stats[1])) / 2
+    mean, std = input_mean, input_std
+    if alpha < 1.0:
+        mean = input_mean * alpha + (1 - alpha) * DATASET_MEAN
+        std = input_std * alpha + (1 - alpha) * DATASET_STD
+    return np.array([input_mean, input_std, alpha]), mean, std

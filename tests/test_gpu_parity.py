@@ -198,7 +198,8 @@ def test_errors(native):
 
 
 def test_features_window_and_pad_variants(native):
-    """hann / constant-padding front ends against the oracle's generic path."""
+    """Constant-padding and un-normalised front ends (Hamming window) against the oracle.  The other three windows are cases of
+    tests/test_gpu_frontend_accuracy.py."""
     from oracle import features as of
     import scipy.signal.windows as W
     clip = syn.make_clip(5, 20000)

@@ -429,7 +429,9 @@ def _wav_bytes(samples, width):
 @pytest.mark.parametrize("width,channels", [(1, 1), (2, 1), (2, 2), (3, 1), (3, 2), (4, 1), (4, 2)])
 def test_raw_wav_frames_decoded_on_device_equal_host_load_audio(width, channels):
     """dsmi_features on a file's raw frames == dsmi_features on load_audio's float64 output, bit for bit
-    (same STFT kernel; only the sample decode and the saturating L+R fold move to the GPU)."""
+    (two STFT kernels: raw frames take the direct kernel, float64 samples the matrix-pipe one -- the same float64 sums rounded once;
+    the sample decode and the saturating L+R fold move to the GPU.  The direct kernel at n_fft 320 against a reference of its own:
+    the direct-wav cases of tests/test_gpu_frontend_accuracy.py)."""
     from danspeech_amd import _native
     from danspeech_amd.audio.resources import _frames_to_int
     rng = np.random.default_rng(50 + 10 * width + channels)

@@ -53,3 +53,43 @@ def test_scipy_stft_agreement():
             got = of.spectrogram(y, pad_mode=pad_mode)
             assert got.shape == s.shape
             np.testing.assert_allclose(got, s, rtol=0, atol=3e-5)
+
+
+def _spectrogram_before_windows(y, sample_rate=16000, window_size=0.02, window_stride=0.01, normalize=True, pad_mode="reflect"):
+    """oracle.features.spectrogram as it was before it took ``window=`` and ``pad_mode="none"``, kept word for word."""
+    n_fft = int(sample_rate * window_size)
+    hop = int(sample_rate * window_stride)
+    y = np.asarray(y, dtype=np.float64)
+    yp = np.pad(y, n_fft // 2, mode=pad_mode)
+    T = 1 + (len(yp) - n_fft) // hop
+    idx = np.arange(n_fft)[:, None] + hop * np.arange(T)[None, :]
+    frames = yp[idx] * of.hamming_sym(n_fft)[:, None]
+    D = np.fft.rfft(frames, axis=0).astype(np.complex64)
+    spect = np.log1p(np.abs(D)).astype(np.float32)
+    if normalize:
+        mean = np.float32(spect.mean(dtype=np.float64))
+        std = np.float32(spect.std(dtype=np.float64, ddof=1))
+        spect = ((spect - mean) / std).astype(np.float32)
+    return spect
+
+
+def test_existing_callers_keep_their_results_bit_for_bit():
+    """The window and the un-padded mode are additions: every call that names neither gives the bits it gave before."""
+    for n in (161, 4000, 66944):
+        y = syn.make_clip(2, n)
+        for kw in (dict(), dict(pad_mode="constant"), dict(normalize=False), dict(sample_rate=8000), dict(sample_rate=100, window_size=0.02)):
+            got, want = of.spectrogram(y, **kw), _spectrogram_before_windows(y, **kw)
+            assert got.dtype == want.dtype and np.array_equal(got, want), (n, kw)
+    assert np.array_equal(of.spectrogram(y, window="hamming"), of.spectrogram(y))
+
+
+def test_windows_and_the_unpadded_mode():
+    import scipy.signal.windows as W
+    for name in ("hamming", "hann", "blackman", "bartlett"):
+        np.testing.assert_allclose(of.window_sym(name, 320), getattr(W, name)(320), rtol=0, atol=1e-15)
+    y = syn.make_clip(4, 4000)
+    win = torch.from_numpy(W.hann(320))
+    D = torch.stft(torch.from_numpy(y), n_fft=320, hop_length=160, win_length=320, window=win, center=False, return_complex=True)
+    s = of.spectrogram(y, normalize=False, pad_mode="none", window="hann")
+    assert s.shape == (161, 1 + (4000 - 320) // 160)
+    np.testing.assert_allclose(s, torch.log1p(D.abs().float()).numpy(), rtol=0, atol=2e-5)
