@@ -195,7 +195,8 @@ static void run_rnn_layer(dsmi_model* m, int l, GemmLaunch gl, int B, int To, in
     gl.ev = timer_arm(m, gl.mode == GEMM_A_CONV ? KK_GEMM0 : KK_GEMM, true, 2.0 * Dd * GH * gl.K * sumlen,
                       4.0 * ((double)gl.M * gl.K * (gl.a2 ? 2 : 1) + (double)gl.N * gl.K + (double)gl.M * gl.N));
     DenseHold hold(m->device, m->inflight, DENSE_GEMM, s);      // one forward's dense kernel at a time
-    launch_gemm(gl, s);
+    m->last_xp_wgs = launch_gemm(gl, s);
+    m->last_xp_rows = gl.M; m->last_xp_cols = gl.ldc;
     hold.leave();
     if (run_rnn_plan(m, plan, l, B, To, dst, sumlen, s)) return;
     // Launchers refuse what the predicates let through only by mistake; the layer still runs.
@@ -203,7 +204,8 @@ static void run_rnn_layer(dsmi_model* m, int l, GemmLaunch gl, int B, int To, in
         // first: the x-projection is in the 16-unit column order, so redo it in the other, and plan without the 16-unit kernels
         // (the first-generation kernel if eligible)
         gl.w_sp = m->rnn[l].wih_sp; gl.bias = m->rnn[l].bih; gl.N = m->geom.Np; gl.ldc = m->geom.Np; gl.ev = EvPair{};
-        launch_gemm(gl, s);
+        m->last_xp_wgs = launch_gemm(gl, s);
+        m->last_xp_cols = gl.ldc;
         in.have16 = false;
         plan = plan_rnn_layer(in);
         if (run_rnn_plan(m, plan, l, B, To, dst, sumlen, s)) return;
@@ -217,7 +219,7 @@ static GemmLaunch xproj_gemm(dsmi_model* m, int l, int B, int To) {
     const RnnW& r = m->rnn[l];
     gl.w = r.wih; gl.bias = r.bih; gl.c = m->xp;
     gl.w_sp = m->gemm_mode == 1 ? r.wih_sp : nullptr;
-    gl.a_sp = m->a_sp;
+    gl.a_sp = m->a_sp; gl.tile_cnt = m->dense_tiles ? m->tile_cnt : nullptr; gl.n_cus = m->n_cus;
     gl.M = To * B; gl.N = m->geom.Np; gl.K = r.K; gl.ldw = r.ldw; gl.ldc = m->geom.Np;
     gl.B = B; gl.T = To;
     return gl;

@@ -10,6 +10,7 @@
 #include <map>
 
 #include "../../include/dsmi.h"
+#include "dense_tiles.h"   // the order in which the dense kernels take their output tiles (host and device)
 #include "rnn_plan.h"      // RnnGeom, ceil_div / round_up, the recurrent kernels' shape predicates and the layer plan (host-only)
 
 namespace dsmi {
@@ -98,12 +99,15 @@ struct GemmLaunch {
     const float* w; const float* bias; float* c;
     const uint16_t* w_sp = nullptr;   // pack_gemm_w_split image of w: when set (with a_sp), the split-fp16 path runs
     uint16_t* a_sp = nullptr;         // workspace for the split A operand: [m-tiles][k-tiles][2][128][32] fp16
+    unsigned* tile_cnt = nullptr;     // split-fp16 path: kDenseCntWords counters (dense_tiles.h), zero between launches -> tiles by demand
+    int n_cus = 0;                    // ... on this many CUs
     int M, N, K;       // N, K as stored (W is [N][K] row-major, K % 4 == 0 guaranteed by packing)
     int lda, ldw, ldc;
     int B, T, ys;      // GEMM_A_CONV: batch, frames per clip, time stride
     EvPair ev;
 };
-void launch_gemm(const GemmLaunch& p, hipStream_t s);
+int launch_gemm(const GemmLaunch& p, hipStream_t s);      // returns the workgroups the GEMM kernel was launched with
+bool dense_tiles_on(bool dense_token_on);     // DSMI_DENSE_TILES, read once per process when the first model is made (gemm.hip)
 std::vector<uint16_t> pack_gemm_w_split(const float* w, int N, int K, int ldw);
 
 // rnn_step.hip: one time step of both directions of one recurrent layer.

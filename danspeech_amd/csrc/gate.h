@@ -37,6 +37,7 @@ private:
 // token (DSMI_DEBUG_DENSE_SCOPE in the experiments build).  No destructor: leave() is a launch on the stream and belongs at its
 // place in the launch order, so the caller calls it -- and must not return between the two.
 enum DenseScope { DENSE_CONV_STACK, DENSE_CONV_LAYER, DENSE_GEMM };
+int dense_token_limit();      // forwards that may be in a dense kernel at a time; 0: the token is off (DSMI_DENSE_TOKENS, hardware queues)
 class DenseHold {
 public:
     DenseHold(int device, int inflight, DenseScope scope, hipStream_t s);      // enters

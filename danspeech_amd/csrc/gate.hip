@@ -88,6 +88,7 @@ static int dense_tokens() {
     }();
     return k;
 }
+int dense_token_limit() { return dense_tokens(); }
 // (experiments: what runs behind the token -- 0 the conv stack as one and every GEMM, 1 the GEMMs only, 2 every conv layer by itself and every GEMM)
 static int dense_scope() {
     static const int k = [] { const char* e = exp_env("DSMI_DEBUG_DENSE_SCOPE"); return e ? std::atoi(e) : 0; }();

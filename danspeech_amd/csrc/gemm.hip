@@ -18,6 +18,7 @@
 // all 64 banks (stride 36 dwords = 4 mod 64 * 9).
 #include "common.h"
 #include <cstdlib>
+#include <mutex>
 
 namespace dsmi {
 
@@ -214,7 +215,18 @@ struct GemmSplitArgs {
     int ntiles, mtiles;       // output tiles (gemm kernel's XCD-aware tile order)
     int pn;                   // n-tiles of a W panel: what an XCD keeps in its L2 while it walks the m-tiles (gemm_panel_width)
     int pn2;                  // the same in PAIRS of n-tiles (the 128 x 256 form)
+    unsigned* tile_cnt;       // tiles by demand (dense_tiles.h): kDenseCntWords words, zero between launches; null: the static order
+#ifdef DSMI_EXPERIMENTS
+    unsigned long long* stamps;   // this launch's kTileStampWords words (dsmi_debug_dense_stamps), or null
+#endif
 };
+
+// Experiments build: where the XCDs end inside a launch of the 128 x 256 form.  Per launch one slot of 32 words, zero before it:
+//   [0..8)   by label (blockIdx.x & 7): the s_memrealtime (100 MHz) at which its last workgroup left
+//   [8..16)  the same by the XCD the workgroup found itself on (HW_REG_XCC_ID)
+//   [16..24) tiles computed on that XCD
+//   [24]     ~(the earliest workgroup's start), [25] 1 + CONV_ROWS, [26] workgroups, [27] tiles by demand
+[[maybe_unused]] constexpr int kTileStampWords = 32, kTileStampSlots = 4096;
 
 // Pass 1: form the A operand ONCE (producer transforms + two-term split) as tiled fp16 planes
 // [m-tile][k-tile][plane][128][32]; every one of the N/128 column tiles then reads it as is.
@@ -405,27 +417,76 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_f16x3_kernel(Ge
 // 768 cycles the MFMAs take.  Here a wave's four A fragments (per plane) serve eight W tiles instead of four: 24 reads per 96 MFMAs
 // (-25 % per MFMA), 48 KB requested per k-tile for twice the products (-25 %), half the barriers per MFMA.  One LDS stage (48 KB)
 // and the registers as the second buffer, as before; 224 registers of fragments and accumulators: two workgroups per CU.
-template <bool CONV_ROWS, int GAP = 6>
+// TILES_BY_DEMAND (dense_tiles.h): min(tiles, 2 x CUs) workgroups, each of which takes tile after tile from the counter of its label
+// (blockIdx.x & 7: the workgroups that share an XCD) in the static order, and from the other labels' counters once its own share is
+// used up.  Beside the other kernels of the pipeline the XCDs do not have the same CUs free -- measured: by demand they take 516 to
+// 674 tiles of a mean 597; NOT measured: by what (a 50-workgroup ring window would put 7 workgroups on two XCDs and 6 on the others,
+// and without the dense token the other lanes' dense kernels take CUs as well; nothing counts the ring workgroups per XCD) --, and
+// an equal share per XCD ends when the slowest one does; by demand the median launch's last XCD ends 1 % behind the mean.  One
+// lane draws, the ticket reaches the workgroup through a word of LDS behind the stage.  The draw for the next tile goes out between
+// the k-loop and the epilogue and is redeemed behind it, so its way to memory and back lies under the epilogue's stores.  The
+// workgroup that leaves last (the "done" word) zeroes the counters for the next launch on the stream.  Nobody waits for anybody.
+constexpr int kWideStage = 49152;           // one stage: A and two W tiles, two 8-KiB planes each
+template <bool CONV_ROWS, int GAP = 6, bool TILES_BY_DEMAND = false>
 __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p, const uint16_t* a_sp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wid >> 1, wc = wid & 1;
-    int nt2, mt;
     const int ntiles2 = (p.ntiles + 1) >> 1;
+    const DenseGrid grid{p.mtiles, ntiles2, p.pn2};
+    const int total = dense_total(grid);
+    const int label = blockIdx.x & 7;
+    // [0]: the linear index of the workgroup's tile (-1: none left), [1]: the labels this workgroup has found used up; lane 0's
+    volatile int* const tk_lds = reinterpret_cast<volatile int*>(smem3 + kWideStage);
+#ifdef DSMI_EXPERIMENTS
+    unsigned xcc = 0;
+    if (p.stamps && tid == 0) {
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        xcc &= 7u;
+        atomicMax(p.stamps + 24, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
+        if (blockIdx.x == 0) { p.stamps[25] = 1 + (CONV_ROWS ? 1 : 0); p.stamps[26] = gridDim.x; p.stamps[27] = TILES_BY_DEMAND ? 1 : 0; }
+    }
+    auto stamp_tile = [&] { if (p.stamps && tid == 0) atomicAdd(p.stamps + 16 + xcc, 1ull); };
+    auto stamp_end = [&] {
+        if (p.stamps && tid == 0) {
+            const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+            atomicMax(p.stamps + label, t);
+            atomicMax(p.stamps + 8 + xcc, t);
+        }
+    };
+#endif
+    auto cnt_add = [&](int l) { return __hip_atomic_fetch_add(p.tile_cnt + l * kDenseCntStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto cnt_peek = [&](int l) { return __hip_atomic_load(p.tile_cnt + l * kDenseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    if (TILES_BY_DEMAND) {
+        if (tid == 0) {
+            unsigned dead = 0;
+            tk_lds[0] = dense_draw(total, label, dead, cnt_add, cnt_peek);
+            tk_lds[1] = (int)dead;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+  for (;;) {
+    int nt2, mt;
     {
-        const int mtiles = p.mtiles, total = ntiles2 * mtiles;
-        const int share = (total + 7) / 8;
-        const int idx = (blockIdx.x & 7) * share + (blockIdx.x >> 3);
-        if ((int)(blockIdx.x >> 3) >= share || idx >= total) return;
-        const int PN = p.pn2;
-        const int panel = idx / (PN * mtiles), rem = idx - panel * (PN * mtiles);
-        const int pw = min(PN, ntiles2 - panel * PN);
-        mt = rem / pw; nt2 = panel * PN + (rem - mt * pw);
+        int idx;
+        if (TILES_BY_DEMAND) {
+            idx = __builtin_amdgcn_readfirstlane(tk_lds[0]);
+            if (idx < 0) break;
+        } else {
+            idx = dense_base(total, label) + (int)(blockIdx.x >> 3);
+            if ((int)(blockIdx.x >> 3) >= dense_count(total, label)) return;
+        }
+        const DenseTile t = dense_tile_at(grid, idx);
+        mt = t.mt; nt2 = t.nu;
     }
     const int nta = 2 * nt2, ntb = min(2 * nt2 + 1, p.ntiles - 1);      // (an odd number of n-tiles: the last pair multiplies its tile twice, stores it once)
-    const int drow = lane >> 2;
-    const int doff = (16 * wid + drow) * 64 + (((lane & 3) ^ ((drow >> 1) & 3) ^ ((drow >> 2) & 3)) * 16);
+    // (by demand: what a tile derives from the lane is derived per tile -- hoisted out of the tile loop it would stay in registers
+    // across the k-loop, which has none to spare)
+    int lane_t = lane;
+    if (TILES_BY_DEMAND) asm volatile("" : "+v"(lane_t));
+    const int drow = lane_t >> 2;
+    const int doff = (16 * wid + drow) * 64 + (((lane_t & 3) ^ ((drow >> 1) & 3) ^ ((drow >> 2) & 3)) * 16);
     const unsigned char* asrc = reinterpret_cast<const unsigned char*>(a_sp) + (size_t)mt * p.ktiles * 16384 + doff;
     const unsigned char* wsa = reinterpret_cast<const unsigned char*>(p.w_sp) + (size_t)nta * p.ktiles * 16384 + doff;
     const unsigned char* wsb = reinterpret_cast<const unsigned char*>(p.w_sp) + (size_t)ntb * p.ktiles * 16384 + doff;
@@ -486,12 +547,23 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");           // the next tile has landed, for everybody
     }
 
+    // the next tile's ticket is requested now and redeemed behind the epilogue
+    unsigned own_ticket = 0, dead = 0;
+    bool own_asked = false;
+    if (TILES_BY_DEMAND && tid == 0) {
+        dead = (unsigned)tk_lds[1];
+        own_asked = !((dead >> label) & 1u);
+        if (own_asked) own_ticket = cnt_add(label);
+    }
+
     // ---- epilogue: as the 128 x 128 form's, once per n-tile of the pair
     int m0 = mt * BM, bb = 0, t0 = 0;
     if (CONV_ROWS) { bb = mt / p.tiles_per_b; t0 = (mt % p.tiles_per_b) * BM; }
     constexpr int TP = 68;
+    int lane_e = lane;
+    if (TILES_BY_DEMAND) asm volatile("" : "+v"(lane_e));
     float* turn = reinterpret_cast<float*>(lds) + wid * (16 * TP);
-    const int cn = (lane & 15) * 4, cr = lane >> 4;
+    const int cn = (lane_e & 15) * 4, cr = lane_e >> 4;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if (2 * nt2 + h >= p.ntiles) break;
@@ -507,7 +579,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) turn[((lane >> 4) * 4 + r) * TP + ni * 16 + (lane & 15)] = acc[mi][4 * h + ni][r];
+                for (int r = 0; r < 4; ++r) turn[((lane_e >> 4) * 4 + r) * TP + ni * 16 + (lane_e & 15)] = acc[mi][4 * h + ni][r];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // (wave-private region: no barrier)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -527,6 +599,31 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
                         if (ncol + q < p.N) dst[q] = v[q];
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the reads are done before the next sixteen rows overwrite them
+        }
+    }
+#ifdef DSMI_EXPERIMENTS
+    stamp_tile();
+#endif
+    if (!TILES_BY_DEMAND) break;
+    if (tid == 0) {
+        int idx = own_asked ? dense_redeem(total, label, own_ticket, dead) : -1;
+        if (idx < 0) idx = dense_steal(total, dead, cnt_add, cnt_peek);
+        tk_lds[0] = idx;
+        tk_lds[1] = (int)dead;
+    }
+    // Every wave's last read of the turn buffer was retired by the lgkmcnt(0) that closes its epilogue, lane 0's ticket by this
+    // one: behind the barrier the next tile's first requests may overwrite the stage, and everybody reads the ticket.
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+#ifdef DSMI_EXPERIMENTS
+    stamp_end();
+#endif
+    if (TILES_BY_DEMAND && tid == 0) {
+        // the last workgroup to leave: everybody else has drawn for the last time
+        unsigned* const done = p.tile_cnt + kDenseLabels * kDenseCntStride;
+        if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+#pragma unroll
+            for (int l = 0; l <= kDenseLabels; ++l) __hip_atomic_store(p.tile_cnt + l * kDenseCntStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -562,9 +659,62 @@ static int gemm_panel_width(int ktiles) {
     return forced > 0 ? forced : 5;
 }
 
-void launch_gemm(const GemmLaunch& g, hipStream_t s) {
+// Tiles by demand in the 128 x 256 form (gemm_f16x3_wide_kernel)?  DSMI_DENSE_TILES=0: the static order, every XCD an equal share;
+// any other value: by demand (A/B runs, tests/test_gpu_dense_tiles.py).  Not set: by demand where the dense token is off, the static
+// order where it is on -- the gain is measured only with the token off (profiles/dense_tiles.txt); with it on a GEMM already has
+// the chip's free CUs to itself and the effect of 512 resident workgroups on the ring windows beside it is not measured.  Read once
+// per process, when its first model is made (model_build.hip keeps the answer in the handle), like DSMI_DENSE_TOKENS.
+bool dense_tiles_on(bool dense_token_on) {
+    static const bool on = [dense_token_on] {
+        const char* e = std::getenv("DSMI_DENSE_TILES");
+        if (e && *e) return !(e[0] == '0' && e[1] == 0);
+        return !dense_token_on;
+    }();
+    return on;
+}
+
+#ifdef DSMI_EXPERIMENTS
+static std::mutex g_tile_stamp_mu;      // guards the two below: launches take slots on any thread, dsmi_debug_dense_stamps reads them
+static unsigned long long* g_tile_stamps = nullptr;
+static int g_tile_stamp_next = 0;
+// DSMI_DEBUG_TILE_STAMPS=1: every launch of the 128 x 256 form takes the next slot (the first kTileStampSlots launches of the process)
+static unsigned long long* tile_stamp_slot() {
+    static const bool on = [] { const char* e = exp_env("DSMI_DEBUG_TILE_STAMPS"); return e && std::atoi(e) != 0; }();
+    if (!on) return nullptr;
+    std::lock_guard<std::mutex> lk(g_tile_stamp_mu);
+    if (!g_tile_stamps) {
+        const size_t bytes = sizeof(unsigned long long) * kTileStampWords * kTileStampSlots;
+        if (hipMalloc((void**)&g_tile_stamps, bytes) != hipSuccess) { g_tile_stamps = nullptr; return nullptr; }
+        (void)hipMemset(g_tile_stamps, 0, bytes);
+    }
+    if (g_tile_stamp_next >= kTileStampSlots) return nullptr;
+    return g_tile_stamps + (size_t)kTileStampWords * g_tile_stamp_next++;
+}
+#endif
+
+// See include/dsmi.h.  (The product build records nothing: 0 launches.)
+extern "C" int dsmi_debug_dense_stamps(uint64_t* stamps_host, int64_t n_words) {
+#ifdef DSMI_EXPERIMENTS
+    if (!stamps_host || n_words < 0) return DSMI_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(g_tile_stamp_mu);
+    const int n = (int)std::min<int64_t>(g_tile_stamp_next, n_words / kTileStampWords);
+    if (n == 0) return 0;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(stamps_host, g_tile_stamps, sizeof(unsigned long long) * kTileStampWords * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return DSMI_ERR_HIP;
+    return n;
+#else
+    (void)stamps_host; (void)n_words;
+    return 0;
+#endif
+}
+
+int launch_gemm(const GemmLaunch& g, hipStream_t s) {
     if (g.w_sp && g.a_sp) {
         GemmSplitArgs a;
+        a.tile_cnt = nullptr;
+#ifdef DSMI_EXPERIMENTS
+        a.stamps = nullptr;
+#endif
         a.a = g.a; a.a2 = g.a2; a.alpha = g.alpha; a.beta = g.beta; a.w_sp = g.w_sp; a.bias = g.bias; a.c = g.c;
         a.M = g.M; a.N = g.N; a.K = g.K; a.lda = g.lda; a.ldc = g.ldc; a.B = g.B; a.T = g.T; a.ys = g.ys;
         a.tiles_per_b = 0; a.ktiles = ceil_div(g.K, BK);
@@ -594,11 +744,23 @@ void launch_gemm(const GemmLaunch& g, hipStream_t s) {
         if (wide) {
 #endif
             const int ntiles2 = (a.ntiles + 1) / 2;
-            const dim3 gridw(8 * ceil_div(ntiles2 * a.mtiles, 8));
-            const size_t ldsw = 49152;                  // one stage: A and two W tiles, two 8-KiB planes each
+            const int total = ntiles2 * a.mtiles;
+            a.tile_cnt = g.n_cus > 0 ? g.tile_cnt : nullptr;
+#ifdef DSMI_EXPERIMENTS
+            a.stamps = tile_stamp_slot();
+#endif
+            if (a.tile_cnt) {      // tiles by demand: two workgroups per CU (the kernel's occupancy), each takes tile after tile
+                const dim3 gridd(std::min(total, 2 * g.n_cus));
+                const size_t ldsd = kWideStage + 16;        // ... and the ticket's words behind the stage
+                if (g.mode == GEMM_A_CONV) DSMI_LAUNCH((gemm_f16x3_wide_kernel<true, 6, true>), gridd, dim3(256), ldsd, s, g.ev, a, (const uint16_t*)g.a_sp);
+                else DSMI_LAUNCH((gemm_f16x3_wide_kernel<false, 6, true>), gridd, dim3(256), ldsd, s, g.ev, a, (const uint16_t*)g.a_sp);
+                return (int)gridd.x;
+            }
+            const dim3 gridw(8 * ceil_div(total, 8));
+            const size_t ldsw = kWideStage;
             if (g.mode == GEMM_A_CONV) DSMI_LAUNCH(gemm_f16x3_wide_kernel<true>, gridw, dim3(256), ldsw, s, g.ev, a, (const uint16_t*)g.a_sp);
             else DSMI_LAUNCH(gemm_f16x3_wide_kernel<false>, gridw, dim3(256), ldsw, s, g.ev, a, (const uint16_t*)g.a_sp);
-            return;
+            return (int)gridw.x;
         }
 #ifdef DSMI_EXPERIMENTS       // the 128 x 128 forms: rounds 3-4, kept for A/B runs
         static const int stages = [] { const char* e = exp_env("DSMI_DEBUG_GEMM_STAGES"); return e && std::atoi(e) == 2 ? 2 : 1; }();
@@ -612,12 +774,12 @@ void launch_gemm(const GemmLaunch& g, hipStream_t s) {
             }
             if (g.mode == GEMM_A_CONV) DSMI_LAUNCH((gemm_f16x3_kernel<true, 2>), grid3, dim3(256), lds2, s, g.ev, a, (const uint16_t*)g.a_sp);
             else DSMI_LAUNCH((gemm_f16x3_kernel<false, 2>), grid3, dim3(256), lds2, s, g.ev, a, (const uint16_t*)g.a_sp);
-            return;
+            return (int)grid3.x;
         }
         const size_t lds3 = 32768;                      // one stage: four 8-KiB operand planes of a 32-deep k-tile
         if (g.mode == GEMM_A_CONV) DSMI_LAUNCH((gemm_f16x3_kernel<true, 1>), grid3, dim3(256), lds3, s, g.ev, a, (const uint16_t*)g.a_sp);
         else DSMI_LAUNCH((gemm_f16x3_kernel<false, 1>), grid3, dim3(256), lds3, s, g.ev, a, (const uint16_t*)g.a_sp);
-        return;
+        return (int)grid3.x;
 #endif
     }
     GemmArgs a;
@@ -642,6 +804,7 @@ void launch_gemm(const GemmLaunch& g, hipStream_t s) {
         default:
             DSMI_LAUNCH(gemm_f32_kernel<GEMM_A_CONV>, grid, dim3(256), lds_cv, s, g.ev, a); break;
     }
+    return (int)(grid.x * grid.y);
 }
 
 }  // namespace dsmi

@@ -73,6 +73,9 @@ struct dsmi_model {
     uint16_t* hpack_sp = nullptr;
     uint16_t* hpack16 = nullptr;   // packed split state of rnn_persist16.hip
     uint16_t* a_sp = nullptr;       // split A operand of the x-projection GEMM
+    int last_xp_rows = 0, last_xp_cols = 0, last_xp_wgs = 0;      // dsmi_debug_xproj: what the last layer's GEMM wrote into xp, and with how many workgroups
+    bool dense_tiles = false;       // the x-projection GEMM takes its tiles by demand (DSMI_DENSE_TILES, read when the model is made)
+    unsigned* tile_cnt = nullptr;   // ... and its tile counters (dense_tiles.h): zeroed here, and by every launch behind itself
     unsigned* pcnt = nullptr;     // persistent-kernel step counters [layers][D*ceil(B/32)][T]
     unsigned* perr = nullptr;     // persistent-kernel timeout word (device)
     // ---- a forward whose persistent kernel timed out is recomputed by dsmi_forward_status (api.hip: collect_oldest).  Forwards are

@@ -70,6 +70,17 @@ extern "C" int dsmi_debug_last_rnn_plan(const dsmi_model* m, char* buf, int64_t 
     return m->last_plan_n;
 }
 
+extern "C" int dsmi_debug_xproj(dsmi_model* m, float* xp_host, int64_t capacity, int32_t* rows, int32_t* cols, int32_t* workgroups) {
+    if (!m) return DSMI_ERR_INVALID;
+    const int64_t n = (int64_t)m->last_xp_rows * m->last_xp_cols;
+    if (!xp_host || !rows || !cols || !workgroups || n == 0 || !m->xp || capacity < n) return fail(m, DSMI_ERR_INVALID, "dsmi_debug_xproj: no layer has run, or the buffer is too small");
+    HIP_OK(m, hipSetDevice(m->device));
+    HIP_OK(m, hipDeviceSynchronize());
+    HIP_OK(m, hipMemcpy(xp_host, m->xp, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    *rows = m->last_xp_rows; *cols = m->last_xp_cols; *workgroups = m->last_xp_wgs;
+    return DSMI_OK;
+}
+
 extern "C" int dsmi_set_profiling(dsmi_model* m, int level) {
     if (!m) return DSMI_ERR_INVALID;
     m->profiling = level < 0 ? 0 : (level > 2 ? 2 : level);

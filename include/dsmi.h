@@ -447,6 +447,16 @@ int dsmi_debug_step_stamps(dsmi_model* m, int layer, int B, int T_out, int step,
  * and an empty string before the first layer); the text holds the first eight of them.  Recording allocates nothing.
  * DSMI_ERR_INVALID: null argument or a buffer too small (1400 bytes hold any answer). */
 int dsmi_debug_last_rnn_plan(const dsmi_model* m, char* buf, int64_t capacity);
+/* The x-projection the handle's LAST recurrent layer ran on (the GEMM's output, bias included, in the column order the layer's
+ * kernels read): rows [T_out * B] of *cols floats, copied to xp_host once the device is idle; *workgroups: how many workgroups that
+ * GEMM was launched with (one per tile, rounded up to eight, in the static order; at most two per CU by demand).  For tests that
+ * compare two forms of the GEMM bit for bit and must know that two forms ran.  DSMI_ERR_INVALID: null argument, no layer yet, or
+ * capacity (in floats) below rows * cols. */
+int dsmi_debug_xproj(dsmi_model* m, float* xp_host, int64_t capacity, int32_t* rows, int32_t* cols, int32_t* workgroups);
+/* Experiments build of the library, with DSMI_DEBUG_TILE_STAMPS=1: where the XCDs ended inside each of the process's first 4096
+ * launches of the x-projection GEMM, 32 words per launch (csrc/gemm.hip: kTileStampWords; tools/exp/dense_tile_spread.py prints
+ * them).  Returns the number of launches copied to stamps_host (at most n_words / 32); the product library records nothing: 0. */
+int dsmi_debug_dense_stamps(uint64_t* stamps_host, int64_t n_words);
 double dsmi_stage_time_us(const dsmi_model* m, int stage);
 /* Kernel launches the last dsmi_forward issued for stage 2 (recurrent steps) and their
  * summed algorithmic FLOPs (SURVEY 8d formula, recurrent part), for roofline maths. */

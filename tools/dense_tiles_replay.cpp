@@ -1,0 +1,178 @@
+// Replays the dense kernels' tile hand-out (danspeech_amd/csrc/dense_tiles.h) on the CPU: the counters are plain words, a
+// "workgroup" is a label and a dead mask, and a schedule says which workgroup draws next.  tests/test_dense_tiles_host.py builds
+// this file with -fsanitize=address,undefined and runs it.
+//
+//   dense_tiles_replay check            every grid x every draw order: each tile exactly once, nothing past the end; prints "ok ..."
+//   dense_tiles_replay map M N PN       the tiles of every label's own share, one "label ticket mt nu" per line (no stealing)
+#include "../danspeech_amd/csrc/dense_tiles.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+using namespace dsmi;
+
+static int g_fail = 0;
+#define REQUIRE(cond, ...)                                            \
+    do {                                                              \
+        if (!(cond)) {                                                \
+            std::fprintf(stderr, "FAILED %s:%d %s: ", __FILE__, __LINE__, #cond); \
+            std::fprintf(stderr, __VA_ARGS__);                        \
+            std::fprintf(stderr, "\n");                               \
+            if (++g_fail > 20) std::exit(1);                          \
+        }                                                             \
+    } while (0)
+
+struct Rng {      // xorshift64*: the same sequence everywhere
+    uint64_t s;
+    explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
+    uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
+    int below(int n) { return (int)(next() % (uint64_t)n); }
+};
+
+struct Sim {
+    int total, nwg;
+    std::vector<unsigned> cnt;          // laid out as on the device: kDenseCntWords words
+    std::vector<unsigned> dead;         // per workgroup
+    std::vector<char> left;             // workgroup has drawn -1 and gone
+    std::vector<int> hits;              // per linear tile index
+    long draws = 0, stolen = 0;
+    Sim(int total_, int nwg_) : total(total_), nwg(nwg_), cnt(kDenseCntWords, 0u), dead(nwg_, 0u), left(nwg_, 0), hits(total_, 0) {}
+    // One draw of workgroup w, as ONE indivisible step: the schedules interleave whole draws.  The kernel's lane 0 is finer grained
+    // -- other workgroups draw between a steal's peeks and its add, and between the early add on the own counter and its redeem
+    // behind the epilogue -- which this replay does not simulate.  What it asserts does not depend on that: a tile is handed out by
+    // the value a fetch-and-add returned, and every value is returned once, wherever the add falls; a peek only chooses the label.
+    int draw(int w) {
+        const int label = w & (kDenseLabels - 1);
+        auto add = [&](int l) { REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l); return cnt[(size_t)l * kDenseCntStride]++; };
+        auto peek = [&](int l) { REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l); return cnt[(size_t)l * kDenseCntStride]; };
+        const int idx = dense_draw(total, label, dead[w], add, peek);
+        ++draws;
+        if (idx < 0) { left[w] = 1; return idx; }
+        REQUIRE(idx < total, "index %d of %d handed out", idx, total);
+        if (idx < total) {
+            hits[idx] += 1;
+            if (idx < dense_base(total, label) || idx >= dense_base(total, label) + dense_count(total, label)) ++stolen;
+        }
+        return idx;
+    }
+    void finish(const char* what) {
+        for (int i = 0; i < total; ++i) REQUIRE(hits[i] == 1, "%s: total %d, tile %d handed out %d times", what, total, i, hits[i]);
+        for (int l = 0; l < kDenseLabels; ++l)
+            REQUIRE(cnt[(size_t)l * kDenseCntStride] <= (unsigned)(dense_count(total, l) + nwg), "%s: counter %d ran to %u", what, l, cnt[(size_t)l * kDenseCntStride]);
+    }
+};
+
+// the workgroups of a launch: min(tiles, 2 x CUs)
+static int launch_wgs(int total, int n_cus) { return std::min(total, 2 * n_cus); }
+
+static long replay_orders(int total, int n_cus, int n_random) {
+    const int nwg = launch_wgs(total, n_cus);
+    long draws = 0;
+    {   // labels take strict turns; inside a label its workgroups take turns
+        Sim s(total, nwg);
+        std::vector<int> next_of(kDenseLabels, 0);
+        for (bool any = true; any;) {
+            any = false;
+            for (int l = 0; l < kDenseLabels; ++l) {
+                const int n_l = (nwg - l + kDenseLabels - 1) / kDenseLabels;      // workgroups with this label
+                for (int tries = 0; tries < n_l; ++tries) {
+                    const int w = l + kDenseLabels * (next_of[l]++ % n_l);
+                    if (s.left[w]) continue;
+                    s.draw(w);
+                    any = true;
+                    break;
+                }
+            }
+        }
+        s.finish("turns");
+        draws += s.draws;
+    }
+    for (int l = 0; l < kDenseLabels && l < nwg; ++l) {      // one label draws everything: every other share is stolen
+        Sim s(total, nwg);
+        for (bool any = true; any;) {
+            any = false;
+            for (int w = l; w < nwg; w += kDenseLabels)
+                if (!s.left[w]) { s.draw(w); any = true; }
+        }
+        s.finish("one label");
+        REQUIRE(s.stolen == total - dense_count(total, l), "one label: %ld stolen of %d", s.stolen, total);
+        draws += s.draws;
+    }
+    for (int it = 0; it < n_random; ++it) {      // seeded random interleavings, some of them with a few workgroups far slower than the rest
+        Sim s(total, nwg);
+        Rng rng(1000003ull * (uint64_t)total + (uint64_t)it);
+        std::vector<int> live(nwg);
+        for (int w = 0; w < nwg; ++w) live[w] = w;
+        const int slow = it % 3 == 0 ? rng.below(nwg) + 1 : 0;      // the first `slow` workgroups draw 16 times less often
+        while (!live.empty()) {
+            const int k = rng.below((int)live.size());
+            const int w = live[k];
+            if (w < slow && rng.below(16) != 0) continue;
+            s.draw(w);
+            if (s.left[w]) { live[k] = live.back(); live.pop_back(); }
+        }
+        s.finish("random");
+        draws += s.draws;
+    }
+    return draws;
+}
+
+// every linear index maps to a tile of the grid, no two to the same one; a label's tickets are its share of the linear order
+static void check_map(const DenseGrid& g) {
+    const int total = dense_total(g);
+    std::vector<char> seen((size_t)total, 0);
+    int sum = 0;
+    for (int l = 0; l < kDenseLabels; ++l) {
+        const int n = dense_count(total, l);
+        REQUIRE(n >= 0 && n <= dense_share(total), "share of label %d: %d", l, n);
+        REQUIRE(n == 0 || dense_base(total, l) == sum, "label %d starts at %d, not %d", l, dense_base(total, l), sum);
+        for (int t = 0; t < n; ++t) {
+            const DenseTile tl = tile_of(g, l, t);
+            REQUIRE(tl.mt >= 0 && tl.mt < g.mtiles && tl.nu >= 0 && tl.nu < g.nunits, "%d x %d pn %d: label %d ticket %d -> (%d, %d)", g.mtiles, g.nunits, g.pn, l, t, tl.mt, tl.nu);
+            if (tl.mt < 0 || tl.mt >= g.mtiles || tl.nu < 0 || tl.nu >= g.nunits) continue;
+            char& c = seen[(size_t)tl.mt * g.nunits + tl.nu];
+            REQUIRE(!c, "%d x %d pn %d: tile (%d, %d) twice", g.mtiles, g.nunits, g.pn, tl.mt, tl.nu);
+            c = 1;
+        }
+        sum += n;
+    }
+    REQUIRE(sum == total, "%d x %d: the shares add up to %d", g.mtiles, g.nunits, sum);
+}
+
+int main(int argc, char** argv) {
+    if (argc >= 5 && !std::strcmp(argv[1], "map")) {
+        const DenseGrid g{std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4])};
+        if (g.mtiles < 1 || g.nunits < 1 || g.pn < 1) return 2;
+        const int total = dense_total(g);
+        for (int l = 0; l < kDenseLabels; ++l)
+            for (int t = 0; t < dense_count(total, l); ++t) {
+                const DenseTile tl = tile_of(g, l, t);
+                std::printf("%d %d %d %d\n", l, t, tl.mt, tl.nu);
+            }
+        return 0;
+    }
+    if (argc >= 2 && !std::strcmp(argv[1], "check")) {
+        const int n_random = argc >= 3 ? std::atoi(argv[2]) : 1000;
+        // m-tiles x n-units (pairs of n-tiles in the 128 x 256 form); the last two: a single unit
+        static const int grids[][2] = {{1, 1}, {1, 7}, {3, 3}, {2, 19}, {251, 19}, {256, 19}, {5, 1}, {251, 1}};
+        long draws = 0;
+        int maps = 0;
+        for (const auto& mn : grids) {
+            // every panel width: the launcher's three, and whatever DSMI_DEBUG_GEMM_PN makes of it (wider than the grid acts as the grid's width)
+            for (int pn = 1; pn <= std::max(mn[1], 3) + 1; ++pn) { check_map(DenseGrid{mn[0], mn[1], pn}); ++maps; }
+            // (the draw order does not depend on the panel width: it hands out linear indices); 256 CUs, and a small device on which
+            // the workgroups loop at every size
+            draws += replay_orders(mn[0] * mn[1], 256, n_random);
+            draws += replay_orders(mn[0] * mn[1], 4, n_random / 10);
+        }
+        if (g_fail) return 1;
+        std::printf("ok %d maps %ld draws\n", maps, draws);
+        return 0;
+    }
+    std::fprintf(stderr, "usage: %s check [random-orders] | map M N PN\n", argv[0]);
+    return 2;
+}
