@@ -152,6 +152,7 @@ _PROTOS = {
     "dsmi_debug_step_stamps": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64]),
     "dsmi_debug_last_rnn_plan": (C.c_int, [_vp, C.c_char_p, C.c_int64]),
     "dsmi_debug_xproj": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    "dsmi_debug_conv_workgroups": (C.c_int, [_vp, _vp, C.c_int32]),
     "dsmi_debug_dense_stamps": (C.c_int, [_vp, C.c_int64]),
     "dsmi_last_forward_stats": (C.c_int, [_vp, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dsmi_lm_open": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),

@@ -45,7 +45,8 @@ static int run_conv(dsmi_model* m, const float* feat, int B, int T, int To, int 
             c.out_lens_dev = m->lens_dev; c.y = next_split ? nullptr : m->conv_buf[l & 1]; c.y_sp = next_split ? m->conv_buf_sp[l] : nullptr;
             c.B = B; c.co = sp.co; c.fi = m->conv_fi[l]; c.fo = m->conv_fo[l]; c.ti = ti; c.to = To; c.ys = ys;
             c.ev = timer_arm(m, KK_CONV1 + l, true, fl, by);
-            launch_conv_split(c, s);
+            c.tile_cnt = m->conv_tiles ? m->conv_tile_cnt[l] : nullptr; c.n_cus = m->n_cus;
+            m->last_conv_wgs[l] = launch_conv_split(c, s);
             x = c.y; x_sp = c.y_sp;
         } else {
             ConvLaunch c;
@@ -56,7 +57,9 @@ static int run_conv(dsmi_model* m, const float* feat, int B, int T, int To, int 
             c.y_sp = next_split ? m->conv_buf_sp[l] : nullptr;
             c.ev = timer_arm(m, KK_CONV1 + l, true, fl, by);
             // layer 0 on the split-fp16 MFMA (features are z-normalised log magnitudes: far inside fp16's range)
-            if (l == 0 && m->conv_mode == 1 && m->conv1_split) launch_conv1_split(c, m->conv[0].wp_sp, s);
+            c.tile_cnt = m->conv_tiles ? m->conv_tile_cnt[l] : nullptr; c.n_cus = m->n_cus;
+            m->last_conv_wgs[l] = 0;      // (conv.hip, the fp32 statement: not reported)
+            if (l == 0 && m->conv_mode == 1 && m->conv1_split) m->last_conv_wgs[l] = launch_conv1_split(c, m->conv[0].wp_sp, s);
             else launch_conv(c, s);
             x = c.y; x_sp = c.y_sp;
         }

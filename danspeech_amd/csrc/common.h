@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 
 #include "../../include/dsmi.h"
 #include "dense_tiles.h"   // the order in which the dense kernels take their output tiles (host and device)
+#include "conv_rows.h"     // the conv kernels' real kernel rows and their tile order (host and device)
 #include "rnn_plan.h"      // RnnGeom, ceil_div / round_up, the recurrent kernels' shape predicates and the layer plan (host-only)
 
 namespace dsmi {
@@ -19,6 +21,7 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kWave = 64;  // gfx950 wavefront
+constexpr int kLdsOnceDevices = 64;   // devices for which a kernel's raised LDS limit is remembered (conv_split.hip, conv1_split.hip); beyond: set per launch
 
 // Optional per-dispatch timestamps: when both events are set the kernel is launched with
 // hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin/end times (the same
@@ -63,6 +66,8 @@ struct ConvLaunch {
     const int32_t* out_lens_dev;
     int B, ci, co, fi, fo, ti, to, xs, ys, layer;  // layer index selects the compile-time geometry
     uint16_t* y_sp = nullptr;   // optional: split channels-last output [B][fo][2][to][32] fp16 terms (hi, lo unscaled) (32-channel layers)
+    unsigned* tile_cnt = nullptr;   // conv1_split.hip: kDenseCntWords counters of this layer's own, zero between launches -> tiles by demand
+    int n_cus = 0;                  // ... on this many CUs
     EvPair ev;
 };
 void launch_conv(const ConvLaunch& p, hipStream_t s);
@@ -75,9 +80,11 @@ struct ConvSplitLaunch {
     float* y;                 // [B][co][fo][ys] fp32 (last conv layer) ...
     uint16_t* y_sp;             // ... or split channels-last for another split-fp16 conv layer (co == 32)
     int B, co, fi, fo, ti, to, ys;
+    unsigned* tile_cnt = nullptr;   // kDenseCntWords counters of this layer's own, zero between launches -> tiles by demand
+    int n_cus = 0;                  // ... on this many CUs
     EvPair ev;
 };
-void launch_conv_split(const ConvSplitLaunch& p, hipStream_t s);
+int launch_conv_split(const ConvSplitLaunch& p, hipStream_t s);      // returns the workgroups the kernel was launched with
 std::vector<uint16_t> pack_conv_w_split(const float* w, int co_total);
 // Host-side weight packer: w [co][ci][kf][kt] -> kernel layout. Returns packed floats.
 std::vector<float> pack_conv_weights(const float* w, int layer);
@@ -85,7 +92,7 @@ std::vector<float> pack_conv_weights(const float* w, int layer);
 // conv1_split.hip: the first conv layer (1 input channel) on the fp16 MFMA with two-term split operands; takes the same
 // launch description as launch_conv (layer 0) plus the pack_conv1_w_split image of the weights.
 std::vector<uint16_t> pack_conv1_w_split(const float* w);
-void launch_conv1_split(const ConvLaunch& p, const uint16_t* wp_sp, hipStream_t s);
+int launch_conv1_split(const ConvLaunch& p, const uint16_t* wp_sp, hipStream_t s);      // returns the workgroups of the launch
 
 // gemm.hip: C[m][n] = sum_k A[m][k] * W[n][k] + bias[n]   (fp32 MFMA 32x32x2)
 enum GemmAMode {
@@ -108,6 +115,7 @@ struct GemmLaunch {
 };
 int launch_gemm(const GemmLaunch& p, hipStream_t s);      // returns the workgroups the GEMM kernel was launched with
 bool dense_tiles_on(bool dense_token_on);     // DSMI_DENSE_TILES, read once per process when the first model is made (gemm.hip)
+bool conv_tiles_on();                               // DSMI_CONV_TILES, else a DSMI_DENSE_TILES that is set, else the static order: the conv layers (gemm.hip)
 std::vector<uint16_t> pack_gemm_w_split(const float* w, int N, int K, int ldw);
 
 // rnn_step.hip: one time step of both directions of one recurrent layer.

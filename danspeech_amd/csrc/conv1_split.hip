@@ -13,6 +13,7 @@
 // conflicts).  The window of a workgroup (8 output rows x 64 output steps: 55 input rows x 137 samples) is split into its
 // two fp16 terms once while it is staged.  Weight fragments come from L2 (82 KB for all 41 kernel rows), one row ahead.
 #include "common.h"
+#include <algorithm>
 
 namespace dsmi {
 
@@ -38,20 +39,62 @@ struct Conv1Args {
     const float* x; const uint16_t* wp; const float* bias; const float* bn_a; const float* bn_b; const int32_t* out_lens;
     float* y; uint16_t* y_sp;
     int B, fi, fo, ti, to, xs, ys;
+    unsigned* tile_cnt;     // tiles by demand (conv_rows.h, dense_tiles.h): kDenseCntWords words, zero between launches; null: one workgroup per tile
 };
 
-template <bool SPLIT_OUT>
+// Kernel rows that read only the frequency padding are neither staged nor multiplied (conv_rows.h: a wave walks its own row's range;
+// the rows no live wave reads stay unwritten).  BY_DEMAND: min(tiles, 2 x CUs) workgroups take tile after tile from their label's
+// counter, then from the others' (the scheme of gemm_f16x3_wide_kernel and conv_f16x3_kernel).
+// (Two workgroups per CU are sixteen waves: 128 registers each.  The static form takes 94; the by-demand form takes 128 / 126, exactly the
+// limit -- any addition to its tile loop can spill: check -Rpass-analysis=kernel-resource-usage after a change.)
+template <bool SPLIT_OUT, bool BY_DEMAND = false>
 __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char c1sm[];
     _Float16* Xs = reinterpret_cast<_Float16*>(c1sm);      // [plane 2][copy 2][ROWS][PITCH]; copy 1 holds the row shifted by 2 samples
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, hk = lane >> 5;
-    const int t0 = blockIdx.x * C1TT, f0 = blockIdx.y * C1NF, b = blockIdx.z;
+    const int tid0 = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    const ConvGrid grid{(p.to + C1TT - 1) / C1TT, (p.fo + C1NF - 1) / C1NF, p.B};
+    const int total = conv_total(grid);
+    const int label = blockIdx.x & 7;
+    // the linear index of the workgroup's tile (-1: none left); lane 0 writes it, everybody reads it behind a barrier
+    volatile int* const tk_lds = reinterpret_cast<volatile int*>(c1sm + C1_LDS);
+    auto cnt_add = [&](int l) { return __hip_atomic_fetch_add(p.tile_cnt + l * kDenseCntStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto cnt_peek = [&](int l) { return __hip_atomic_load(p.tile_cnt + l * kDenseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    unsigned dead = 0;      // lane 0's: the labels this workgroup has found used up
+    if (BY_DEMAND) {
+        if (tid0 == 0) tk_lds[0] = dense_draw(total, label, dead, cnt_add, cnt_peek, grid.nf);
+        __syncthreads();
+    }
+  // Every barrier below is reached by all eight waves of the workgroup, tile after tile: f < p.fo guards multiplications and stores
+  // only, and a masked tile is uniform over the workgroup.
+  for (;;) {
+    // (by demand: what a tile derives from the lane is derived per tile -- hoisted out of the tile loop it would stay in registers
+    // through the kernel rows)
+    int tid = tid0;
+    if (BY_DEMAND) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, li = lane & 31, hk = lane >> 5;
+    ConvTile tile;
+    if (BY_DEMAND) {
+        const int idx = __builtin_amdgcn_readfirstlane(tk_lds[0]);
+        if (idx < 0) break;
+        tile = conv_tile_at(grid, idx);
+    } else {
+        tile = ConvTile{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
+    }
+    const int t0 = tile.tt * C1TT, f0 = tile.ft * C1NF, b = tile.z;
     const int f = f0 + wv;
     const int olen = p.out_lens[b];
+    // (by demand: the epilogue's per-channel constants are loaded per tile -- hoisted out of the tile loop they would stay in registers
+    // through the kernel rows)
+    const float *bias = p.bias, *bn_a = p.bn_a, *bn_b = p.bn_b;
+    if (BY_DEMAND) asm volatile("" : "+s"(bias), "+s"(bn_a), "+s"(bn_b));
+    // the next tile's ticket goes out in front of this tile's stores and is redeemed behind them
+    bool own_asked = false;
+    unsigned own_ticket = 0;
+    auto ask = [&] { if (BY_DEMAND && tid == 0 && !((dead >> label) & 1u)) { own_asked = true; own_ticket = cnt_add(label); } };
 
     if (t0 >= olen) {     // fully masked tile: zeros in the consumer's format
+        ask();
         if (SPLIT_OUT) {
             for (int idx = tid; idx < C1NF * 2 * C1TT * 4; idx += C1NT) {
                 const int part = idx & 3, tl = (idx >> 2) % C1TT, pl = (idx / (4 * C1TT)) % 2, ff = idx / (4 * C1TT * 2);
@@ -64,16 +107,19 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
                 if (f0 + ff < p.fo && t0 + tl < p.to) p.y[(((size_t)b * CO + co) * p.fo + f0 + ff) * p.ys + t0 + tl] = 0.f;
             }
         }
-        return;
-    }
-
-    // ---- stage the window, split into (hi, lo * 2^11), twice: thread -> (row, pair of adjacent samples)
+        if (BY_DEMAND) __syncthreads();      // everybody has read this tile's ticket before lane 0 writes the next one
+    } else {
+    // ---- stage the window, split into (hi, lo * 2^11), twice: thread -> (row, pair of adjacent samples).  Wave w at kernel row kf
+    // reads staged row SF w + kf = input row fin0 + SF w + kf, and only where that is a real row (its range below): the staged rows
+    // anybody reads are the real input rows up to the last live wave's last one, and only those are written.
     const int fin0 = SF * f0 - PF, tin0 = ST * t0 - PT;        // input row / column of staged (0, 0)
-    for (int idx = tid; idx < ROWS * (PITCH / 2); idx += C1NT) {
+    const int nlive = min(C1NF, p.fo - f0);
+    const int row_lo = max(0, -fin0), row_hi = min(SF * (nlive - 1) + KF - 1, p.fi - 1 - fin0);
+    for (int idx = tid + row_lo * (PITCH / 2); idx < (row_hi + 1) * (PITCH / 2); idx += C1NT) {
         const int row = idx / (PITCH / 2), q = 2 * (idx - row * (PITCH / 2));
         const int fin = fin0 + row;
         float v[2] = {0.f, 0.f};
-        if (fin >= 0 && fin < p.fi) {
+        {
             const float* src = p.x + ((size_t)b * p.fi + fin) * p.xs;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
@@ -96,7 +142,8 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
         }
     }
     __syncthreads();
-    if (f >= p.fo) return;
+    if (f < p.fo) {
+    const ConvRows myr = conv_rows_of(f, p.fi, KF, PF, SF);
 
     f32x16 acc[2], acl[2];      // [column tile: even / odd steps]  hi.hi ; (hi.lo + lo.hi) * 2^11
 #pragma unroll
@@ -108,9 +155,10 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
     //   tt = 0: copy 0 at index 4 li + 8 hk;   tt = 1: copy 1 at index (4 li + 2 + 8 hk) - 2 = 4 li + 8 hk
     const _Float16* xb = Xs + (SF * wv) * PITCH + 4 * li + 8 * hk;
     const u32x4* wq = reinterpret_cast<const u32x4*>(p.wp) + lane;          // [kf][plane][lane] 16-byte fragments
-    u32x4 wn[2] = {wq[0], wq[64]};
+    const int kfirst = min(myr.lo, KF - 1);                                   // (an empty range multiplies nothing)
+    u32x4 wn[2] = {wq[(size_t)kfirst * 128], wq[(size_t)kfirst * 128 + 64]};
 #pragma unroll 1
-    for (int kf = 0; kf < KF; ++kf) {
+    for (int kf = myr.lo; kf <= myr.hi; ++kf) {
         const f16x8 wh = __builtin_bit_cast(f16x8, wn[0]), wl = __builtin_bit_cast(f16x8, wn[1]);
         if (kf + 1 < KF) { wn[0] = wq[(size_t)(kf + 1) * 128]; wn[1] = wq[(size_t)(kf + 1) * 128 + 64]; }     // next row's weights, from L2
         const _Float16* xr = xb + kf * PITCH;
@@ -130,6 +178,7 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
         for (int tt = 0; tt < 2; ++tt) acl[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[tt], acl[tt], 0, 0, 0);
     }
 
+    ask();
     // ---- epilogue: D[i = output channel][j = li]: output step t0 + 2 li + tt
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
@@ -142,7 +191,7 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int co = q + 8 * g + 4 * hk;
-                    float v = (acc[tt][4 * g + q] + acl[tt][4 * g + q] * kLoInv + p.bias[co]) * p.bn_a[co] + p.bn_b[co];
+                    float v = (acc[tt][4 * g + q] + acl[tt][4 * g + q] * kLoInv + bias[co]) * bn_a[co] + bn_b[co];
                     v = fminf(fmaxf(v, 0.f), 20.f);
                     v = t < olen ? v : 0.f;
                     const _Float16 a = (_Float16)v;
@@ -156,10 +205,31 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = (r & 3) + 8 * (r >> 2) + 4 * hk;
-                float v = (acc[tt][r] + acl[tt][r] * kLoInv + p.bias[co]) * p.bn_a[co] + p.bn_b[co];
+                float v = (acc[tt][r] + acl[tt][r] * kLoInv + bias[co]) * bn_a[co] + bn_b[co];
                 v = fminf(fmaxf(v, 0.f), 20.f);
                 p.y[(((size_t)b * CO + co) * p.fo + f) * p.ys + t] = t < olen ? v : 0.f;
             }
+        }
+    }
+    }      // f < p.fo
+    }      // not a masked tile
+    if (!BY_DEMAND) break;
+    if (tid == 0) {
+        int idx = own_asked ? dense_redeem(total, label, own_ticket, dead, grid.nf) : -1;
+        if (idx < 0) idx = dense_steal(total, dead, cnt_add, cnt_peek, grid.nf);
+        tk_lds[0] = idx;
+    }
+    // Every live wave is past its last read of the window (its kernel-row loop has ended: the fragments are in registers before the
+    // MFMAs that take them) and everybody past this tile's ticket (the barrier behind the staging, or the masked tile's own): behind
+    // this one the next tile's staging may overwrite the window.
+    __syncthreads();
+  }
+    if (BY_DEMAND && tid0 == 0) {
+        // the last workgroup to leave: everybody else has drawn for the last time
+        unsigned* const done = p.tile_cnt + kDenseLabels * kDenseCntStride;
+        if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+#pragma unroll
+            for (int l = 0; l <= kDenseLabels; ++l) __hip_atomic_store(p.tile_cnt + l * kDenseCntStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -190,16 +260,34 @@ std::vector<uint16_t> pack_conv1_w_split(const float* w) {
     return out;
 }
 
-void launch_conv1_split(const ConvLaunch& c, const uint16_t* wp_sp, hipStream_t s) {
-    Conv1Args a{c.x, wp_sp, c.bias, c.bn_a, c.bn_b, c.out_lens_dev, c.y, c.y_sp, c.B, c.fi, c.fo, c.ti, c.to, c.xs, c.ys};
-    const dim3 grid(ceil_div(c.to, C1TT), ceil_div(c.fo, C1NF), c.B);
-    if (c.y_sp) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_LDS);
-        DSMI_LAUNCH(conv1_f16x3_kernel<true>, grid, dim3(C1NT), C1_LDS, s, c.ev, a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_f16x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_LDS);
-        DSMI_LAUNCH(conv1_f16x3_kernel<false>, grid, dim3(C1NT), C1_LDS, s, c.ev, a);
+namespace {
+// the kernel's 62 KB of LDS are above the default limit: raised once per process, instantiation and device, not at every launch
+template <auto KERN>
+void conv1_lds_once() {
+    static std::atomic<bool> done[kLdsOnceDevices];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kLdsOnceDevices || !done[dev].load(std::memory_order_acquire)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_LDS + 16);
+        if (dev >= 0 && dev < kLdsOnceDevices) done[dev].store(true, std::memory_order_release);
     }
+}
+}  // namespace
+
+int launch_conv1_split(const ConvLaunch& c, const uint16_t* wp_sp, hipStream_t s) {
+    Conv1Args a{c.x, wp_sp, c.bias, c.bn_a, c.bn_b, c.out_lens_dev, c.y, c.y_sp, c.B, c.fi, c.fo, c.ti, c.to, c.xs, c.ys,
+                c.n_cus > 0 ? c.tile_cnt : nullptr};
+    const ConvGrid g{ceil_div(c.to, C1TT), ceil_div(c.fo, C1NF), c.B};
+    if (a.tile_cnt) {      // tiles by demand: two workgroups per CU (the kernel's occupancy), each takes tile after tile
+        const dim3 gridd(std::min(conv_total(g), 2 * c.n_cus));
+        const size_t lds = C1_LDS + 16;      // ... and the ticket's word behind the window
+        if (c.y_sp) { conv1_lds_once<conv1_f16x3_kernel<true, true>>(); DSMI_LAUNCH((conv1_f16x3_kernel<true, true>), gridd, dim3(C1NT), lds, s, c.ev, a); }
+        else { conv1_lds_once<conv1_f16x3_kernel<false, true>>(); DSMI_LAUNCH((conv1_f16x3_kernel<false, true>), gridd, dim3(C1NT), lds, s, c.ev, a); }
+        return (int)gridd.x;
+    }
+    const dim3 grid(g.nt, g.nf, g.nz);
+    if (c.y_sp) { conv1_lds_once<conv1_f16x3_kernel<true>>(); DSMI_LAUNCH(conv1_f16x3_kernel<true>, grid, dim3(C1NT), C1_LDS, s, c.ev, a); }
+    else { conv1_lds_once<conv1_f16x3_kernel<false>>(); DSMI_LAUNCH(conv1_f16x3_kernel<false>, grid, dim3(C1NT), C1_LDS, s, c.ev, a); }
+    return g.nt * g.nf * g.nz;
 }
 
 }  // namespace dsmi

@@ -24,6 +24,8 @@
 // and the weight fragments of the tap after next are requested before the current one's MFMAs
 // (they come from L2: ~600 cycles).
 #include "common.h"
+#include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 namespace dsmi {
@@ -45,13 +47,16 @@ constexpr int ROWPLANE = WIN * PITCH;  // halfs per (row, plane)
 constexpr int RCHUNK = NPL * WIN * 4;               // 16-byte chunks of one staged input row (both planes): 592
 constexpr int CPR = (RCHUNK + 255) / 256;           // chunks per thread and row: 3
 constexpr int NSLOT = 2 * BNF;                      // staged rows held in LDS: two families of four (see the kernel)
+constexpr int kConvLds = NSLOT * NPL * ROWPLANE * 2;   // 75,776 B: two workgroups per CU (by demand: + 16 for the ticket's word)
 
 struct ConvSplitArgs {
     const uint16_t* x_sp; const uint16_t* wp_sp; const float* bias; const float* bn_a; const float* bn_b;
     const int32_t* out_lens; float* y; uint16_t* y_sp;
     int B, fi, fo, ti, to, ys;
-    int nco;        // 32-channel output tiles (1: 32 channels, 3: 96); blockIdx.z = b * nco + tile
+    int nco;        // 32-channel output tiles (1: 32 channels, 3: 96); a tile's z = b * nco + tile
+    unsigned* tile_cnt;     // tiles by demand (conv_rows.h, dense_tiles.h): kDenseCntWords words, zero between launches; null: one workgroup per tile
 };
+static_assert(SF % 2 == 0 && PF % 2 == 0, "a row's first real kernel row, max(0, PF - SF f), is even: its first tap takes weight-ring slot 0");
 
 // Shared epilogue piece: 4 consecutive channels of one (b, f, t) -> two 8-byte stores, channels-last split.
 __device__ __forceinline__ void store_split4(uint16_t* y_sp, size_t bf_index, int t_stride, int t, int c0, const float (&v)[4]) {
@@ -71,19 +76,60 @@ __device__ __forceinline__ void store_split4(uint16_t* y_sp, size_t bf_index, in
 // XPIPE: a tap's eight x fragments are read from LDS during the MFMAs of the tap before it (a second set of 32 registers), one read
 // per three MFMAs, instead of in front of their own MFMAs -- where each tap began with two exposed LDS round trips that only the
 // SIMD's other wave could cover.
-template <bool SPLIT_OUT, bool XPIPE = true>
+// SKIP: kernel rows that read only the frequency padding are not multiplied (conv_rows.h: a wave runs the taps of its own row's range,
+// the workgroup stages and meets at the barrier over the range of its live rows); false: every row, the form before, for timing
+// (experiments build).  BY_DEMAND: min(tiles, 2 x CUs) workgroups take tile after tile from their label's counter, then from the
+// others' (the scheme of gemm_f16x3_wide_kernel; the next ticket is asked for in front of a tile's stores and redeemed behind them).
+template <bool SPLIT_OUT, bool XPIPE = true, bool SKIP = true, bool BY_DEMAND = false>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char csm[];
     _Float16* Xs = reinterpret_cast<_Float16*>(csm);  // [2 families][4 slots][2 planes][WIN][PITCH]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int t0 = blockIdx.x * BTT, f0 = blockIdx.y * BNF;
-    const int b = blockIdx.z / p.nco, ct = blockIdx.z - b * p.nco;
+    const int tid0 = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    const int CO = 32 * p.nco;
+    const ConvGrid grid{(p.to + BTT - 1) / BTT, (p.fo + BNF - 1) / BNF, p.B * p.nco};
+    const int total = conv_total(grid);
+    const int label = blockIdx.x & 7;
+    // the linear index of the workgroup's tile (-1: none left); lane 0 writes it, everybody reads it behind a barrier
+    volatile int* const tk_lds = reinterpret_cast<volatile int*>(csm + kConvLds);
+    auto cnt_add = [&](int l) { return __hip_atomic_fetch_add(p.tile_cnt + l * kDenseCntStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto cnt_peek = [&](int l) { return __hip_atomic_load(p.tile_cnt + l * kDenseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    unsigned dead = 0;      // lane 0's: the labels this workgroup has found used up
+    if (BY_DEMAND) {
+        if (tid0 == 0) tk_lds[0] = dense_draw(total, label, dead, cnt_add, cnt_peek, grid.nf);
+        __syncthreads();
+    }
+  // Every barrier below is reached by all four waves of the workgroup, tile after tile: what depends on the wave (f < p.fo, its own
+  // kernel rows) guards multiplications and stores only, and what ends a tile early (a masked tile) is uniform over the workgroup.
+  for (;;) {
+    // (by demand: what a tile derives from the lane is derived per tile -- hoisted out of the tile loop it would stay in registers
+    // through the kernel rows)
+    int tid = tid0;
+    if (BY_DEMAND) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
+    ConvTile tile;
+    if (BY_DEMAND) {
+        const int idx = __builtin_amdgcn_readfirstlane(tk_lds[0]);
+        if (idx < 0) break;
+        tile = conv_tile_at(grid, idx);
+    } else {
+        tile = ConvTile{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
+    }
+    const int t0 = tile.tt * BTT, f0 = tile.ft * BNF;
+    const int b = tile.z / p.nco, ct = tile.z - b * p.nco;
     const int f = f0 + wv;
     const int olen = p.out_lens[b];
-    const int CO = 32 * p.nco;
+    // (by demand: the epilogue's per-channel constants are loaded per tile -- hoisted out of the tile loop they would stay in registers
+    // through the kernel rows)
+    const float *bias = p.bias, *bn_a = p.bn_a, *bn_b = p.bn_b;
+    if (BY_DEMAND) asm volatile("" : "+s"(bias), "+s"(bn_a), "+s"(bn_b));
+    // the next tile's ticket goes out in front of this tile's stores and is redeemed behind them
+    bool own_asked = false;
+    unsigned own_ticket = 0;
+    auto ask = [&] { if (BY_DEMAND && tid == 0 && !((dead >> label) & 1u)) { own_asked = true; own_ticket = cnt_add(label); } };
 
     if (t0 >= olen) {     // fully masked tile: zeros in the consumer's format
+        ask();
         if (SPLIT_OUT) {
             for (int idx = tid; idx < BNF * NPL * BTT * 4; idx += 256) {
                 const int part = idx & 3, tl = (idx >> 2) % BTT, pl = (idx / (4 * BTT)) % NPL, ff = idx / (4 * BTT * NPL);
@@ -96,8 +142,13 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
                 if (f0 + ff < p.fo && t0 + tl < p.to) p.y[(((size_t)b * CO + co) * p.fo + f0 + ff) * p.ys + t0 + tl] = 0.f;
             }
         }
-        return;
-    }
+        if (BY_DEMAND) __syncthreads();      // everybody has read this tile's ticket before lane 0 writes the next one
+    } else {
+    // the kernel rows the workgroup walks (k0 .. k1, k0 even) and the ones this wave multiplies (lo .. hi, lo even)
+    const ConvRows wgr = SKIP ? conv_rows_wg(f0, BNF, p.fo, p.fi, KF, PF, SF) : ConvRows{0, KF - 1};
+    const ConvRows myr = SKIP ? conv_rows_of(f, p.fi, KF, PF, SF) : ConvRows{0, KF - 1};
+    const int k0 = wgr.lo, k1 = wgr.hi;
+    const bool live = f < p.fo && myr.lo <= myr.hi;
 
     f32x4 acc[2][4];                      // [16-channel tile][16-step tile]
 #pragma unroll
@@ -152,8 +203,11 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
                 dst[c][pl] = __builtin_bit_cast(f16x8, wbase[((((size_t)q * p.nco + ct) * 2 + c) * NPL + pl) * 64]);
     };
     constexpr int NQ = KF * KT;
-    load_w(0, wq[0]);
-    load_w(1, wq[1]);
+    {   // primed at the wave's first real tap (lo is even and KT odd: tap lo * KT takes slot 0, as tap 0 did)
+        const int q0 = live ? myr.lo * KT : 0;
+        load_w(q0, wq[0]);
+        load_w(min(q0 + 1, NQ - 1), wq[1]);
+    }
     auto tap = [&](const _Float16* xrow, int kf, int kt, auto slot_c) {
         constexpr int slot = decltype(slot_c)::value;
         const int q = kf * KT + kt;
@@ -240,35 +294,37 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
     u32x4 stg[CPR];                       // the row in flight
     auto kernel_row = [&](int kf, auto first_slot) {
         const int fam = kf & 1, m0 = kf >> 1;
-        if (kf >= 1 && kf + 1 < KF) store_row(((kf - 1) & 1) * 4 + (((kf - 1) >> 1) & 3), stg);     // requested during kf - 1, for kf + 1
-        if (kf + 2 < KF) load_row(r0 + kf + 8, stg);
-        if (f < p.fo) taps(Xs + ((fam * 4 + ((m0 + wv) & 3)) * NPL) * ROWPLANE, kf, first_slot);
+        if (kf > k0 && kf + 1 <= k1) store_row(((kf - 1) & 1) * 4 + (((kf - 1) >> 1) & 3), stg);     // requested during kf - 1, for kf + 1
+        if (kf + 2 <= k1) load_row(r0 + kf + 8, stg);
+        if (live && kf >= myr.lo && kf <= myr.hi) taps(Xs + ((fam * 4 + ((m0 + wv) & 3)) * NPL) * ROWPLANE, kf, first_slot);
         __syncthreads();
     };
-    // prologue: the eight rows of kernel rows 0 and 1, four at a time
+    // prologue: the eight rows of kernel rows k0 and k0 + 1, four at a time
     {
         u32x4 pre[4][CPR];
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) load_row(r0 + half * 4 + j, pre[j]);
+            for (int j = 0; j < 4; ++j) load_row(r0 + k0 + half * 4 + j, pre[j]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int row = half * 4 + j;           // row r0 + row: family row & 1, m = row >> 1
-                store_row((row & 1) * 4 + (row >> 1), pre[j]);
+                const int row = half * 4 + j;           // row r0 + k0 + row: family row & 1 (k0 is even), m = (k0 >> 1) + (row >> 1)
+                store_row((row & 1) * 4 + (((k0 >> 1) + (row >> 1)) & 3), pre[j]);
             }
         }
     }
     __syncthreads();
-    static_assert(KF % 2 == 1, "the last kernel row is an even one");
+    // the rows are walked in pairs from the even k0; the workgroup's last row is an even one (a third copy of the body) or an odd one
+    int kf = k0;
 #pragma unroll 1
-    for (int kf = 0; kf + 1 < KF; kf += 2) {
+    for (; kf + 1 <= k1; kf += 2) {
         kernel_row(kf, std::integral_constant<int, 0>{});
         kernel_row(kf + 1, std::integral_constant<int, 1>{});
     }
-    kernel_row(KF - 1, std::integral_constant<int, 0>{});
+    if (kf == k1) kernel_row(kf, std::integral_constant<int, 0>{});
 
-    if (f >= p.fo) return;
+    ask();
+    if (f < p.fo) {
     // ---- epilogue: D[i][j] of a 16 x 16 tile: j = lane & 15 = time, i = 4 (lane >> 4) + register = output channel
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
@@ -280,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int co = ct * 32 + c * 16 + 4 * l4 + q;
-                float x = (acc[c][tt][q] * (1.f / kConvWScale) + p.bias[co]) * p.bn_a[co] + p.bn_b[co];
+                float x = (acc[c][tt][q] * (1.f / kConvWScale) + bias[co]) * bn_a[co] + bn_b[co];
                 x = fminf(fmaxf(x, 0.f), 20.f);
                 v[q] = t < olen ? x : 0.f;
             }
@@ -291,6 +347,26 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
                 for (int q = 0; q < 4; ++q)
                     p.y[(((size_t)b * CO + ct * 32 + c * 16 + 4 * l4 + q) * p.fo + f) * p.ys + t] = v[q];
             }
+        }
+    }
+    }      // f < p.fo
+    }      // not a masked tile
+    if (!BY_DEMAND) break;
+    if (tid == 0) {
+        int idx = own_asked ? dense_redeem(total, label, own_ticket, dead, grid.nf) : -1;
+        if (idx < 0) idx = dense_steal(total, dead, cnt_add, cnt_peek, grid.nf);
+        tk_lds[0] = idx;
+    }
+    // Every wave is past its last read of the staged rows (the barrier that closes the last kernel row) and of this tile's ticket
+    // (the barrier behind the prologue, or the masked tile's own): behind this one the next tile's staging may overwrite the rows.
+    __syncthreads();
+  }
+    if (BY_DEMAND && tid0 == 0) {
+        // the last workgroup to leave: everybody else has drawn for the last time
+        unsigned* const done = p.tile_cnt + kDenseLabels * kDenseCntStride;
+        if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+#pragma unroll
+            for (int l = 0; l <= kDenseLabels; ++l) __hip_atomic_store(p.tile_cnt + l * kDenseCntStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -324,24 +400,48 @@ std::vector<uint16_t> pack_conv_w_split(const float* w, int co_total) {
     return out;
 }
 
-void launch_conv_split(const ConvSplitLaunch& c, hipStream_t s) {
-    ConvSplitArgs a{c.x_sp, c.wp_sp, c.bias, c.bn_a, c.bn_b, c.out_lens_dev, c.y, c.y_sp, c.B, c.fi, c.fo, c.ti, c.to, c.ys, c.co / 32};
-    const dim3 grid(ceil_div(c.to, BTT), ceil_div(c.fo, BNF), c.B * a.nco);
-    const size_t lds = (size_t)NSLOT * NPL * ROWPLANE * 2;   // 75,776 B: two workgroups per CU
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_f16x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_f16x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#ifdef DSMI_EXPERIMENTS       // the form that reads a tap's fragments in front of its own MFMAs (rounds 3-5), for A/B runs
-    static const bool plain = [] { const char* e = exp_env("DSMI_DEBUG_CONV_XPIPE"); return e && std::atoi(e) == 0; }();
-    if (plain) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_f16x3_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_f16x3_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (c.y_sp) DSMI_LAUNCH((conv_f16x3_kernel<true, false>), grid, dim3(256), lds, s, c.ev, a);
-        else DSMI_LAUNCH((conv_f16x3_kernel<false, false>), grid, dim3(256), lds, s, c.ev, a);
-        return;
+namespace {
+// the kernel's 74 KB of LDS are above the default limit: raised once per process, instantiation and device, not at every launch (the
+// call runs on the enqueueing thread)
+template <auto KERN>
+void conv_lds_once() {
+    static std::atomic<bool> done[kLdsOnceDevices];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kLdsOnceDevices || !done[dev].load(std::memory_order_acquire)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, kConvLds + 16);
+        if (dev >= 0 && dev < kLdsOnceDevices) done[dev].store(true, std::memory_order_release);
     }
+}
+template <bool XPIPE, bool SKIP>
+int launch_conv_split_form(const ConvSplitLaunch& c, const ConvSplitArgs& a, hipStream_t s) {
+    const ConvGrid g{ceil_div(c.to, BTT), ceil_div(c.fo, BNF), c.B * a.nco};
+    if (a.tile_cnt) {      // tiles by demand: two workgroups per CU (the kernel's occupancy), each takes tile after tile
+        const dim3 gridd(std::min(conv_total(g), 2 * c.n_cus));
+        const size_t lds = kConvLds + 16;      // ... and the ticket's word behind the rows
+        if (c.y_sp) { conv_lds_once<conv_f16x3_kernel<true, XPIPE, SKIP, true>>(); DSMI_LAUNCH((conv_f16x3_kernel<true, XPIPE, SKIP, true>), gridd, dim3(256), lds, s, c.ev, a); }
+        else { conv_lds_once<conv_f16x3_kernel<false, XPIPE, SKIP, true>>(); DSMI_LAUNCH((conv_f16x3_kernel<false, XPIPE, SKIP, true>), gridd, dim3(256), lds, s, c.ev, a); }
+        return (int)gridd.x;
+    }
+    const dim3 grid(g.nt, g.nf, g.nz);
+    const size_t lds = kConvLds;
+    if (c.y_sp) { conv_lds_once<conv_f16x3_kernel<true, XPIPE, SKIP>>(); DSMI_LAUNCH((conv_f16x3_kernel<true, XPIPE, SKIP>), grid, dim3(256), lds, s, c.ev, a); }
+    else { conv_lds_once<conv_f16x3_kernel<false, XPIPE, SKIP>>(); DSMI_LAUNCH((conv_f16x3_kernel<false, XPIPE, SKIP>), grid, dim3(256), lds, s, c.ev, a); }
+    return g.nt * g.nf * g.nz;
+}
+}  // namespace
+
+int launch_conv_split(const ConvSplitLaunch& c, hipStream_t s) {
+    ConvSplitArgs a{c.x_sp, c.wp_sp, c.bias, c.bn_a, c.bn_b, c.out_lens_dev, c.y, c.y_sp, c.B, c.fi, c.fo, c.ti, c.to, c.ys, c.co / 32,
+                    c.n_cus > 0 ? c.tile_cnt : nullptr};
+#ifdef DSMI_EXPERIMENTS       // for A/B runs: the form that reads a tap's fragments in front of its own MFMAs (rounds 3-5), and the form
+                              // that multiplies the padding's kernel rows like real ones (the kernel before the skip; timing only)
+    static const bool plain = [] { const char* e = exp_env("DSMI_DEBUG_CONV_XPIPE"); return e && std::atoi(e) == 0; }();
+    static const bool noskip = [] { const char* e = exp_env("DSMI_DEBUG_CONV_SKIP"); return e && std::atoi(e) == 0; }();
+    if (plain && noskip) return launch_conv_split_form<false, false>(c, a, s);
+    if (plain) return launch_conv_split_form<false, true>(c, a, s);
+    if (noskip) return launch_conv_split_form<true, false>(c, a, s);
 #endif
-    if (c.y_sp) DSMI_LAUNCH((conv_f16x3_kernel<true>), grid, dim3(256), lds, s, c.ev, a);
-    else DSMI_LAUNCH((conv_f16x3_kernel<false>), grid, dim3(256), lds, s, c.ev, a);
+    return launch_conv_split_form<true, true>(c, a, s);
 }
 
 }  // namespace dsmi

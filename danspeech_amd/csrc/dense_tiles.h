@@ -27,11 +27,13 @@ struct DenseGrid { int mtiles, nunits, pn; };      // pn: units of a W panel (>=
 struct DenseTile { int mt, nu; };
 
 DSMI_TILES_HD inline int dense_total(const DenseGrid& g) { return g.mtiles * g.nunits; }
-DSMI_TILES_HD inline int dense_share(int total) { return (total + kDenseLabels - 1) / kDenseLabels; }
-DSMI_TILES_HD inline int dense_base(int total, int label) { return label * dense_share(total); }
+// (`unit`: tiles that stay together on one label -- a share is whole units; the conv kernels' f-neighbours, conv_rows.h.  `total` is a
+// multiple of it.)
+DSMI_TILES_HD inline int dense_share(int total, int unit = 1) { return (total / unit + kDenseLabels - 1) / kDenseLabels * unit; }
+DSMI_TILES_HD inline int dense_base(int total, int label, int unit = 1) { return label * dense_share(total, unit); }
 // tiles of `label`'s own share
-DSMI_TILES_HD inline int dense_count(int total, int label) {
-    const int share = dense_share(total), left = total - label * share;
+DSMI_TILES_HD inline int dense_count(int total, int label, int unit = 1) {
+    const int share = dense_share(total, unit), left = total - label * share;
     return left < 0 ? 0 : (left < share ? left : share);
 }
 
@@ -49,8 +51,8 @@ DSMI_TILES_HD inline DenseTile dense_tile_at(const DenseGrid& g, int idx) {
 DSMI_TILES_HD inline DenseTile tile_of(const DenseGrid& g, int label, int ticket) { return dense_tile_at(g, dense_base(dense_total(g), label) + ticket); }
 
 // A ticket that `label`'s counter gave: the linear index of its tile, or -1 with the label marked dead (its share is used up).
-DSMI_TILES_HD inline int dense_redeem(int total, int label, unsigned ticket, unsigned& dead) {
-    if (ticket < (unsigned)dense_count(total, label)) return dense_base(total, label) + (int)ticket;
+DSMI_TILES_HD inline int dense_redeem(int total, int label, unsigned ticket, unsigned& dead, int unit = 1) {
+    if (ticket < (unsigned)dense_count(total, label, unit)) return dense_base(total, label, unit) + (int)ticket;
     dead |= 1u << label;
     return -1;
 }
@@ -58,31 +60,31 @@ DSMI_TILES_HD inline int dense_redeem(int total, int label, unsigned ticket, uns
 // Draw from the other labels: the one with most left first (peek(l): the counter's value now, add(l): fetch-and-add 1).  -1: all used up.
 // At most eight failed adds per workgroup and kernel, so a counter never exceeds its share by more than the workgroups of the launch.
 template <class Add, class Peek>
-DSMI_TILES_HD inline int dense_steal(int total, unsigned& dead, Add add, Peek peek) {
+DSMI_TILES_HD inline int dense_steal(int total, unsigned& dead, Add add, Peek peek, int unit = 1) {
     for (;;) {
         int best = -1, best_left = 0;
         for (int l = 0; l < kDenseLabels; ++l) {
             if ((dead >> l) & 1u) continue;
-            const int cnt = dense_count(total, l);
+            const int cnt = dense_count(total, l, unit);
             const unsigned seen = peek(l);
             const int left = seen < (unsigned)cnt ? cnt - (int)seen : 0;
             if (left == 0) dead |= 1u << l;
             else if (left > best_left) { best = l; best_left = left; }
         }
         if (best < 0) return -1;
-        const int idx = dense_redeem(total, best, add(best), dead);
+        const int idx = dense_redeem(total, best, add(best), dead, unit);
         if (idx >= 0) return idx;
     }
 }
 
 // One draw of a workgroup of `label`: its own share first, then the others'.  `dead` is the workgroup's own word, 0 at its start.
 template <class Add, class Peek>
-DSMI_TILES_HD inline int dense_draw(int total, int label, unsigned& dead, Add add, Peek peek) {
+DSMI_TILES_HD inline int dense_draw(int total, int label, unsigned& dead, Add add, Peek peek, int unit = 1) {
     if (!((dead >> label) & 1u)) {
-        const int idx = dense_redeem(total, label, add(label), dead);
+        const int idx = dense_redeem(total, label, add(label), dead, unit);
         if (idx >= 0) return idx;
     }
-    return dense_steal(total, dead, add, peek);
+    return dense_steal(total, dead, add, peek, unit);
 }
 
 }  // namespace dsmi

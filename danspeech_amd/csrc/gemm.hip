@@ -673,6 +673,20 @@ bool dense_tiles_on(bool dense_token_on) {
     return on;
 }
 
+// The conv layers (conv_split.hip, conv1_split.hip): DSMI_CONV_TILES=0|1 decides for them alone (A/B runs, tests/test_gpu_conv_tiles.py);
+// without it a DSMI_DENSE_TILES that is SET decides for them as for the GEMM (0: the static order in both, otherwise by demand in
+// both).  Neither set: the static order, whether the dense token is on or off -- unlike the GEMM's rule, so no parameter: by demand
+// the convs are held bit-identical and within the float64 bound, but they did not meet the bar for a default
+// (profiles/conv_tiles.txt).  Read where DSMI_DENSE_TILES is: once per process, when its first model is made.
+bool conv_tiles_on() {
+    static const bool on = [] {
+        const char* e = std::getenv("DSMI_CONV_TILES");
+        if (!(e && *e)) e = std::getenv("DSMI_DENSE_TILES");
+        return e && *e && !(e[0] == '0' && e[1] == 0);
+    }();
+    return on;
+}
+
 #ifdef DSMI_EXPERIMENTS
 static std::mutex g_tile_stamp_mu;      // guards the two below: launches take slots on any thread, dsmi_debug_dense_stamps reads them
 static unsigned long long* g_tile_stamps = nullptr;

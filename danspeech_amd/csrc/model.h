@@ -76,6 +76,9 @@ struct dsmi_model {
     int last_xp_rows = 0, last_xp_cols = 0, last_xp_wgs = 0;      // dsmi_debug_xproj: what the last layer's GEMM wrote into xp, and with how many workgroups
     bool dense_tiles = false;       // the x-projection GEMM takes its tiles by demand (DSMI_DENSE_TILES, read when the model is made)
     unsigned* tile_cnt = nullptr;   // ... and its tile counters (dense_tiles.h): zeroed here, and by every launch behind itself
+    bool conv_tiles = false;        // the split-fp16 conv layers take their tiles by demand (DSMI_CONV_TILES over DSMI_DENSE_TILES)
+    unsigned* conv_tile_cnt[3] = {nullptr, nullptr, nullptr};   // ... each layer its own counters, zeroed like the GEMM's
+    int last_conv_wgs[3] = {0, 0, 0};                           // dsmi_debug_conv_workgroups: workgroups of each layer's last launch
     unsigned* pcnt = nullptr;     // persistent-kernel step counters [layers][D*ceil(B/32)][T]
     unsigned* perr = nullptr;     // persistent-kernel timeout word (device)
     // ---- a forward whose persistent kernel timed out is recomputed by dsmi_forward_status (api.hip: collect_oldest).  Forwards are

@@ -81,6 +81,12 @@ extern "C" int dsmi_debug_xproj(dsmi_model* m, float* xp_host, int64_t capacity,
     return DSMI_OK;
 }
 
+extern "C" int dsmi_debug_conv_workgroups(const dsmi_model* m, int32_t* workgroups, int32_t capacity) {
+    if (!m || !workgroups || capacity < m->desc.conv_layers) return DSMI_ERR_INVALID;
+    for (int l = 0; l < m->desc.conv_layers; ++l) workgroups[l] = m->last_conv_wgs[l];
+    return m->desc.conv_layers;
+}
+
 extern "C" int dsmi_set_profiling(dsmi_model* m, int level) {
     if (!m) return DSMI_ERR_INVALID;
     m->profiling = level < 0 ? 0 : (level > 2 ? 2 : level);

@@ -453,6 +453,10 @@ int dsmi_debug_last_rnn_plan(const dsmi_model* m, char* buf, int64_t capacity);
  * compare two forms of the GEMM bit for bit and must know that two forms ran.  DSMI_ERR_INVALID: null argument, no layer yet, or
  * capacity (in floats) below rows * cols. */
 int dsmi_debug_xproj(dsmi_model* m, float* xp_host, int64_t capacity, int32_t* rows, int32_t* cols, int32_t* workgroups);
+/* How many workgroups each conv layer's LAST launch on the handle had: workgroups[l] for layer l (one per tile in the static order;
+ * min(tiles, 2 x CUs) by demand; 0: the layer has not run, or ran on the fp32 kernel).  Host bookkeeping, no device call.  Returns
+ * the number of conv layers; DSMI_ERR_INVALID: null argument or capacity below it. */
+int dsmi_debug_conv_workgroups(const dsmi_model* m, int32_t* workgroups, int32_t capacity);
 /* Experiments build of the library, with DSMI_DEBUG_TILE_STAMPS=1: where the XCDs ended inside each of the process's first 4096
  * launches of the x-projection GEMM, 32 words per launch (csrc/gemm.hip: kTileStampWords; tools/exp/dense_tile_spread.py prints
  * them).  Returns the number of launches copied to stamps_host (at most n_words / 32); the product library records nothing: 0. */

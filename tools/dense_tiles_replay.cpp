@@ -4,7 +4,11 @@
 //
 //   dense_tiles_replay check            every grid x every draw order: each tile exactly once, nothing past the end; prints "ok ..."
 //   dense_tiles_replay map M N PN       the tiles of every label's own share, one "label ticket mt nu" per line (no stealing)
-#include "../danspeech_amd/csrc/dense_tiles.h"
+// and the conv kernels' side of it (danspeech_amd/csrc/conv_rows.h; tests/test_conv_tiles_host.py):
+//   dense_tiles_replay conv-rows        the real kernel rows of every output row and workgroup, fi = 1 .. 200, both geometries; "ok ..."
+//   dense_tiles_replay conv-check [R]   conv grids of 1-9 t-tiles x 1-14 f-tiles x 1-12 clip tiles, the same draw orders; "ok ..."
+//   dense_tiles_replay conv-map T F Z   the tiles of every label's own share, one "label ticket tt ft z" per line (no stealing)
+#include "../danspeech_amd/csrc/conv_rows.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -40,7 +44,8 @@ struct Sim {
     std::vector<char> left;             // workgroup has drawn -1 and gone
     std::vector<int> hits;              // per linear tile index
     long draws = 0, stolen = 0;
-    Sim(int total_, int nwg_) : total(total_), nwg(nwg_), cnt(kDenseCntWords, 0u), dead(nwg_, 0u), left(nwg_, 0), hits(total_, 0) {}
+    int unit = 1;                       // tiles that stay on one label (conv_rows.h: the f-tiles of a group)
+    Sim(int total_, int nwg_, int unit_ = 1) : total(total_), nwg(nwg_), cnt(kDenseCntWords, 0u), dead(nwg_, 0u), left(nwg_, 0), hits(total_, 0), unit(unit_) {}
     // One draw of workgroup w, as ONE indivisible step: the schedules interleave whole draws.  The kernel's lane 0 is finer grained
     // -- other workgroups draw between a steal's peeks and its add, and between the early add on the own counter and its redeem
     // behind the epilogue -- which this replay does not simulate.  What it asserts does not depend on that: a tile is handed out by
@@ -49,31 +54,31 @@ struct Sim {
         const int label = w & (kDenseLabels - 1);
         auto add = [&](int l) { REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l); return cnt[(size_t)l * kDenseCntStride]++; };
         auto peek = [&](int l) { REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l); return cnt[(size_t)l * kDenseCntStride]; };
-        const int idx = dense_draw(total, label, dead[w], add, peek);
+        const int idx = dense_draw(total, label, dead[w], add, peek, unit);
         ++draws;
         if (idx < 0) { left[w] = 1; return idx; }
         REQUIRE(idx < total, "index %d of %d handed out", idx, total);
         if (idx < total) {
             hits[idx] += 1;
-            if (idx < dense_base(total, label) || idx >= dense_base(total, label) + dense_count(total, label)) ++stolen;
+            if (idx < dense_base(total, label, unit) || idx >= dense_base(total, label, unit) + dense_count(total, label, unit)) ++stolen;
         }
         return idx;
     }
     void finish(const char* what) {
         for (int i = 0; i < total; ++i) REQUIRE(hits[i] == 1, "%s: total %d, tile %d handed out %d times", what, total, i, hits[i]);
         for (int l = 0; l < kDenseLabels; ++l)
-            REQUIRE(cnt[(size_t)l * kDenseCntStride] <= (unsigned)(dense_count(total, l) + nwg), "%s: counter %d ran to %u", what, l, cnt[(size_t)l * kDenseCntStride]);
+            REQUIRE(cnt[(size_t)l * kDenseCntStride] <= (unsigned)(dense_count(total, l, unit) + nwg), "%s: counter %d ran to %u", what, l, cnt[(size_t)l * kDenseCntStride]);
     }
 };
 
 // the workgroups of a launch: min(tiles, 2 x CUs)
 static int launch_wgs(int total, int n_cus) { return std::min(total, 2 * n_cus); }
 
-static long replay_orders(int total, int n_cus, int n_random) {
+static long replay_orders(int total, int n_cus, int n_random, int unit = 1) {
     const int nwg = launch_wgs(total, n_cus);
     long draws = 0;
     {   // labels take strict turns; inside a label its workgroups take turns
-        Sim s(total, nwg);
+        Sim s(total, nwg, unit);
         std::vector<int> next_of(kDenseLabels, 0);
         for (bool any = true; any;) {
             any = false;
@@ -92,18 +97,18 @@ static long replay_orders(int total, int n_cus, int n_random) {
         draws += s.draws;
     }
     for (int l = 0; l < kDenseLabels && l < nwg; ++l) {      // one label draws everything: every other share is stolen
-        Sim s(total, nwg);
+        Sim s(total, nwg, unit);
         for (bool any = true; any;) {
             any = false;
             for (int w = l; w < nwg; w += kDenseLabels)
                 if (!s.left[w]) { s.draw(w); any = true; }
         }
         s.finish("one label");
-        REQUIRE(s.stolen == total - dense_count(total, l), "one label: %ld stolen of %d", s.stolen, total);
+        REQUIRE(s.stolen == total - dense_count(total, l, unit), "one label: %ld stolen of %d", s.stolen, total);
         draws += s.draws;
     }
     for (int it = 0; it < n_random; ++it) {      // seeded random interleavings, some of them with a few workgroups far slower than the rest
-        Sim s(total, nwg);
+        Sim s(total, nwg, unit);
         Rng rng(1000003ull * (uint64_t)total + (uint64_t)it);
         std::vector<int> live(nwg);
         for (int w = 0; w < nwg; ++w) live[w] = w;
@@ -143,7 +148,106 @@ static void check_map(const DenseGrid& g) {
     REQUIRE(sum == total, "%d x %d: the shares add up to %d", g.mtiles, g.nunits, sum);
 }
 
+// ---- the conv kernels (conv_rows.h)
+// kf lies in a row's range exactly when the input row it reads is a real one; a workgroup's range is the union of its live rows'
+// ranges; a row's first real kernel row is even where the kernel's two-slot weight ring assumes it (sf and pf even: conv_split.hip)
+static long check_conv_rows(int KF, int PF, int SF, int nf_wg, bool lo_even) {
+    long n = 0;
+    for (int fi = 1; fi <= 200; ++fi) {
+        const int fo = (fi + 2 * PF - KF) / SF + 1;
+        REQUIRE(fo >= 1, "fi %d: fo %d", fi, fo);
+        for (int f = 0; f < fo; ++f) {
+            const ConvRows r = conv_rows_of(f, fi, KF, PF, SF);
+            for (int kf = 0; kf < KF; ++kf, ++n) {
+                const int row = SF * f - PF + kf;
+                REQUIRE((kf >= r.lo && kf <= r.hi) == (row >= 0 && row < fi), "KF %d fi %d f %d kf %d: range %d..%d, input row %d", KF, fi, f, kf, r.lo, r.hi, row);
+            }
+            REQUIRE(!conv_rows_empty(r), "KF %d fi %d f %d: no real row", KF, fi, f);
+            if (lo_even) REQUIRE(r.lo % 2 == 0, "KF %d fi %d f %d: first real kernel row %d is odd", KF, fi, f, r.lo);
+        }
+        for (int f0 = 0; f0 < fo; f0 += nf_wg) {
+            const ConvRows u = conv_rows_wg(f0, nf_wg, fo, fi, KF, PF, SF);
+            if (lo_even) REQUIRE(u.lo % 2 == 0, "KF %d fi %d f0 %d: the workgroup's first kernel row %d is odd", KF, fi, f0, u.lo);
+            for (int kf = 0; kf < KF; ++kf, ++n) {
+                bool any = false;
+                for (int w = 0; w < nf_wg && f0 + w < fo; ++w) {
+                    const ConvRows r = conv_rows_of(f0 + w, fi, KF, PF, SF);
+                    any = any || (kf >= r.lo && kf <= r.hi);
+                }
+                REQUIRE((kf >= u.lo && kf <= u.hi) == any, "KF %d fi %d f0 %d kf %d: workgroup range %d..%d", KF, fi, f0, kf, u.lo, u.hi);
+            }
+        }
+        // rows past fo and an empty workgroup: nothing
+        REQUIRE(conv_rows_empty(conv_rows_wg(fo, nf_wg, fo, fi, KF, PF, SF)), "KF %d fi %d: a workgroup past fo has rows", KF, fi);
+    }
+    return n;
+}
+
+// every linear index maps to a tile of the grid, no two to the same one; the shares are whole groups, add up, and inside a share the
+// f-tiles of one (z, t-tile) are consecutive tickets; with eight t-tiles a label's tickets are the workgroups the hardware gives its XCD
+// from the (t-tiles, f-tiles, z) grid of the static order (linear id x + 8 (y + nf z): XCD = x, in the order z, y)
+static void check_conv_map(const ConvGrid& g) {
+    const int total = conv_total(g);
+    std::vector<char> seen((size_t)total, 0);
+    int sum = 0;
+    for (int l = 0; l < kDenseLabels; ++l) {
+        const int n = dense_count(total, l, g.nf);
+        REQUIRE(n >= 0 && n % g.nf == 0 && n <= dense_share(total, g.nf), "share of label %d: %d", l, n);
+        REQUIRE(n == 0 || dense_base(total, l, g.nf) == sum, "label %d starts at %d, not %d", l, dense_base(total, l, g.nf), sum);
+        for (int t = 0; t < n; ++t) {
+            const ConvTile tl = conv_tile_of(g, l, t);
+            const bool inside = tl.tt >= 0 && tl.tt < g.nt && tl.ft >= 0 && tl.ft < g.nf && tl.z >= 0 && tl.z < g.nz;
+            REQUIRE(inside, "%d x %d x %d: label %d ticket %d -> (%d, %d, %d)", g.nt, g.nf, g.nz, l, t, tl.tt, tl.ft, tl.z);
+            if (!inside) continue;
+            char& c = seen[((size_t)tl.z * g.nt + tl.tt) * g.nf + tl.ft];
+            REQUIRE(!c, "%d x %d x %d: tile (%d, %d, %d) twice", g.nt, g.nf, g.nz, tl.tt, tl.ft, tl.z);
+            c = 1;
+            const ConvTile first = conv_tile_of(g, l, t - t % g.nf);
+            REQUIRE(tl.ft == t % g.nf && tl.tt == first.tt && tl.z == first.z, "%d x %d x %d: label %d ticket %d is no f-neighbour of ticket %d", g.nt, g.nf, g.nz, l, t, t - t % g.nf);
+            if (g.nt == kDenseLabels) REQUIRE(tl.tt == l && tl.z == t / g.nf, "%d x %d x %d: label %d ticket %d -> (%d, %d, %d), the grid's XCD order gives (%d, %d, %d)", g.nt, g.nf, g.nz, l, t, tl.tt, tl.ft, tl.z, l, t % g.nf, t / g.nf);
+        }
+        sum += n;
+    }
+    REQUIRE(sum == total, "%d x %d x %d: the shares add up to %d", g.nt, g.nf, g.nz, sum);
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !std::strcmp(argv[1], "conv-rows")) {
+        long n = check_conv_rows(41, 20, 2, 8, false);      // conv1_split.hip: 8 rows per workgroup, no parity assumed
+        n += check_conv_rows(21, 10, 2, 4, true);           // conv_split.hip: 4 rows per workgroup
+        if (g_fail) return 1;
+        std::printf("ok %ld kernel rows\n", n);
+        return 0;
+    }
+    if (argc >= 5 && !std::strcmp(argv[1], "conv-map")) {
+        const ConvGrid g{std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4])};
+        if (g.nt < 1 || g.nf < 1 || g.nz < 1) return 2;
+        const int total = conv_total(g);
+        for (int l = 0; l < kDenseLabels; ++l)
+            for (int t = 0; t < dense_count(total, l, g.nf); ++t) {
+                const ConvTile tl = conv_tile_of(g, l, t);
+                std::printf("%d %d %d %d %d\n", l, t, tl.tt, tl.ft, tl.z);
+            }
+        return 0;
+    }
+    if (argc >= 2 && !std::strcmp(argv[1], "conv-check")) {
+        const int n_random = argc >= 3 ? std::atoi(argv[2]) : 20;
+        long draws = 0;
+        int maps = 0;
+        for (int nt = 1; nt <= 9; ++nt)
+            for (int nf = 1; nf <= 14; ++nf)
+                for (int nz = 1; nz <= 12; ++nz) {
+                    const ConvGrid g{nt, nf, nz};
+                    check_conv_map(g);
+                    ++maps;
+                    // 256 CUs (most of these grids: one workgroup per tile), and a small device on which the workgroups loop
+                    draws += replay_orders(conv_total(g), 256, n_random, nf);
+                    draws += replay_orders(conv_total(g), 4, n_random, nf);
+                }
+        if (g_fail) return 1;
+        std::printf("ok %d maps %ld draws\n", maps, draws);
+        return 0;
+    }
     if (argc >= 5 && !std::strcmp(argv[1], "map")) {
         const DenseGrid g{std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4])};
         if (g.mtiles < 1 || g.nunits < 1 || g.pn < 1) return 2;
@@ -173,6 +277,6 @@ int main(int argc, char** argv) {
         std::printf("ok %d maps %ld draws\n", maps, draws);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s check [random-orders] | map M N PN\n", argv[0]);
+    std::fprintf(stderr, "usage: %s check [random-orders] | map M N PN | conv-rows | conv-check [random-orders] | conv-map T F Z\n", argv[0]);
     return 2;
 }
