@@ -45,7 +45,7 @@ static int run_conv(dsmi_model* m, const float* feat, int B, int T, int To, int 
             c.out_lens_dev = m->lens_dev; c.y = next_split ? nullptr : m->conv_buf[l & 1]; c.y_sp = next_split ? m->conv_buf_sp[l] : nullptr;
             c.B = B; c.co = sp.co; c.fi = m->conv_fi[l]; c.fo = m->conv_fo[l]; c.ti = ti; c.to = To; c.ys = ys;
             c.ev = timer_arm(m, KK_CONV1 + l, true, fl, by);
-            c.tile_cnt = m->conv_tiles ? m->conv_tile_cnt[l] : nullptr; c.n_cus = m->n_cus;
+            c.tile_cnt = m->conv_tiles ? m->tile_counters(dsmi_model::kTileCntConv0 + l) : nullptr; c.n_cus = m->n_cus;
             m->last_conv_wgs[l] = launch_conv_split(c, s);
             x = c.y; x_sp = c.y_sp;
         } else {
@@ -57,7 +57,7 @@ static int run_conv(dsmi_model* m, const float* feat, int B, int T, int To, int 
             c.y_sp = next_split ? m->conv_buf_sp[l] : nullptr;
             c.ev = timer_arm(m, KK_CONV1 + l, true, fl, by);
             // layer 0 on the split-fp16 MFMA (features are z-normalised log magnitudes: far inside fp16's range)
-            c.tile_cnt = m->conv_tiles ? m->conv_tile_cnt[l] : nullptr; c.n_cus = m->n_cus;
+            c.tile_cnt = m->conv_tiles ? m->tile_counters(dsmi_model::kTileCntConv0 + l) : nullptr; c.n_cus = m->n_cus;
             m->last_conv_wgs[l] = 0;      // (conv.hip, the fp32 statement: not reported)
             if (l == 0 && m->conv_mode == 1 && m->conv1_split) m->last_conv_wgs[l] = launch_conv1_split(c, m->conv[0].wp_sp, s);
             else launch_conv(c, s);
@@ -222,7 +222,7 @@ static GemmLaunch xproj_gemm(dsmi_model* m, int l, int B, int To) {
     const RnnW& r = m->rnn[l];
     gl.w = r.wih; gl.bias = r.bih; gl.c = m->xp;
     gl.w_sp = m->gemm_mode == 1 ? r.wih_sp : nullptr;
-    gl.a_sp = m->a_sp; gl.tile_cnt = m->dense_tiles ? m->tile_cnt : nullptr; gl.n_cus = m->n_cus;
+    gl.a_sp = m->a_sp; gl.tile_cnt = m->dense_tiles ? m->tile_counters(dsmi_model::kTileCntGemm) : nullptr; gl.n_cus = m->n_cus;
     gl.M = To * B; gl.N = m->geom.Np; gl.K = r.K; gl.ldw = r.ldw; gl.ldc = m->geom.Np;
     gl.B = B; gl.T = To;
     return gl;

@@ -21,7 +21,30 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kWave = 64;  // gfx950 wavefront
-constexpr int kLdsOnceDevices = 64;   // devices for which a kernel's raised LDS limit is remembered (conv_split.hip, conv1_split.hip); beyond: set per launch
+constexpr int kLdsOnceDevices = 64;   // devices for which a kernel's raised LDS limit is remembered (lds_once); beyond: set per launch
+
+// A kernel whose dynamic LDS is above the default limit: the limit is raised once per process, instantiation and device, not at every
+// launch (the call runs on the enqueueing thread).  For kernels that always ask for the same `bytes`.
+template <auto KERN>
+void lds_once(int bytes) {
+    static std::atomic<bool> done[kLdsOnceDevices];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kLdsOnceDevices || !done[dev].load(std::memory_order_acquire)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (dev >= 0 && dev < kLdsOnceDevices) done[dev].store(true, std::memory_order_release);
+    }
+}
+
+// The two fp16 terms of a split operand as the packers store them: hi = fp16(x), lo = fp16((x - hi) * lo_scale) (gemm.hip,
+// conv_split.hip: the lo term unscaled; conv1_split.hip: times 2^11).
+struct F16Pair { uint16_t hi, lo; };
+inline F16Pair f16_split_bits(float x, float lo_scale = 1.f) {
+    const _Float16 h[2] = {(_Float16)x, (_Float16)((x - (float)(_Float16)x) * lo_scale)};
+    F16Pair r;
+    __builtin_memcpy(&r.hi, &h[0], 2);
+    __builtin_memcpy(&r.lo, &h[1], 2);
+    return r;
+}
 
 // Optional per-dispatch timestamps: when both events are set the kernel is launched with
 // hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin/end times (the same
@@ -114,8 +137,6 @@ struct GemmLaunch {
     EvPair ev;
 };
 int launch_gemm(const GemmLaunch& p, hipStream_t s);      // returns the workgroups the GEMM kernel was launched with
-bool dense_tiles_on(bool dense_token_on);     // DSMI_DENSE_TILES, read once per process when the first model is made (gemm.hip)
-bool conv_tiles_on();                               // DSMI_CONV_TILES, else a DSMI_DENSE_TILES that is set, else the static order: the conv layers (gemm.hip)
 std::vector<uint16_t> pack_gemm_w_split(const float* w, int N, int K, int ldw);
 
 // rnn_step.hip: one time step of both directions of one recurrent layer.

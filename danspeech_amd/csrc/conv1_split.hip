@@ -43,10 +43,12 @@ struct Conv1Args {
 };
 
 // Kernel rows that read only the frequency padding are neither staged nor multiplied (conv_rows.h: a wave walks its own row's range;
-// the rows no live wave reads stay unwritten).  BY_DEMAND: min(tiles, 2 x CUs) workgroups take tile after tile from their label's
-// counter, then from the others' (the scheme of gemm_f16x3_wide_kernel and conv_f16x3_kernel).
+// the rows no live wave reads stay unwritten).  BY_DEMAND: the workgroups of a by-demand launch take tile after tile (TileTaker,
+// dense_tiles.h; a label's share is whole groups of f-neighbours, conv_rows.h); here: the ticket's word, the barriers around it, and
+// what is derived per tile so that it does not live through the kernel rows.
 // (Two workgroups per CU are sixteen waves: 128 registers each.  The static form takes 94; the by-demand form takes 128 / 126, exactly the
-// limit -- any addition to its tile loop can spill: check -Rpass-analysis=kernel-resource-usage after a change.)
+// limit -- any addition to its tile loop can spill: check -Rpass-analysis=kernel-resource-usage after a change.  How the compiler
+// orders the kernel-row loop of the by-demand form also moves with the locals declared behind it: profiles/tile_taker.txt.)
 template <bool SPLIT_OUT, bool BY_DEMAND = false>
 __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char c1sm[];
@@ -54,15 +56,13 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
     const int tid0 = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     const ConvGrid grid{(p.to + C1TT - 1) / C1TT, (p.fo + C1NF - 1) / C1NF, p.B};
-    const int total = conv_total(grid);
-    const int label = blockIdx.x & 7;
+    const int total = conv_total(grid), label = blockIdx.x & 7;
     // the linear index of the workgroup's tile (-1: none left); lane 0 writes it, everybody reads it behind a barrier
     volatile int* const tk_lds = reinterpret_cast<volatile int*>(c1sm + C1_LDS);
-    auto cnt_add = [&](int l) { return __hip_atomic_fetch_add(p.tile_cnt + l * kDenseCntStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto cnt_peek = [&](int l) { return __hip_atomic_load(p.tile_cnt + l * kDenseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    unsigned dead = 0;      // lane 0's: the labels this workgroup has found used up
+    const TileCounters cnt{p.tile_cnt};
+    unsigned dead = 0;      // lane 0's: the labels this workgroup has found used up (every tile's TileTaker works on it)
     if (BY_DEMAND) {
-        if (tid0 == 0) tk_lds[0] = dense_draw(total, label, dead, cnt_add, cnt_peek, grid.nf);
+        if (tid0 == 0) tk_lds[0] = TileTaker(total, label, grid.nf, dead).first(cnt);
         __syncthreads();
     }
   // Every barrier below is reached by all eight waves of the workgroup, tile after tile: f < p.fo guards multiplications and stores
@@ -89,9 +89,8 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
     const float *bias = p.bias, *bn_a = p.bn_a, *bn_b = p.bn_b;
     if (BY_DEMAND) asm volatile("" : "+s"(bias), "+s"(bn_a), "+s"(bn_b));
     // the next tile's ticket goes out in front of this tile's stores and is redeemed behind them
-    bool own_asked = false;
-    unsigned own_ticket = 0;
-    auto ask = [&] { if (BY_DEMAND && tid == 0 && !((dead >> label) & 1u)) { own_asked = true; own_ticket = cnt_add(label); } };
+    TileTaker taker(total, label, grid.nf, dead);
+    auto ask = [&] { if (BY_DEMAND && tid == 0) taker.ask(cnt); };
 
     if (t0 >= olen) {     // fully masked tile: zeros in the consumer's format
         ask();
@@ -214,30 +213,13 @@ __global__ __launch_bounds__(C1NT, 4) void conv1_f16x3_kernel(Conv1Args p) {
     }      // f < p.fo
     }      // not a masked tile
     if (!BY_DEMAND) break;
-    if (tid == 0) {
-        int idx = own_asked ? dense_redeem(total, label, own_ticket, dead, grid.nf) : -1;
-        if (idx < 0) idx = dense_steal(total, dead, cnt_add, cnt_peek, grid.nf);
-        tk_lds[0] = idx;
-    }
+    if (tid == 0) tk_lds[0] = taker.next(cnt);
     // Every live wave is past its last read of the window (its kernel-row loop has ended: the fragments are in registers before the
     // MFMAs that take them) and everybody past this tile's ticket (the barrier behind the staging, or the masked tile's own): behind
     // this one the next tile's staging may overwrite the window.
     __syncthreads();
   }
-    if (BY_DEMAND && tid0 == 0) {
-        // the last workgroup to leave: everybody else has drawn for the last time
-        unsigned* const done = p.tile_cnt + kDenseLabels * kDenseCntStride;
-        if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-#pragma unroll
-            for (int l = 0; l <= kDenseLabels; ++l) __hip_atomic_store(p.tile_cnt + l * kDenseCntStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-inline uint16_t c1_bits(_Float16 h) {
-    uint16_t u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
+    if (BY_DEMAND && tid0 == 0) tiles_leave(cnt);
 }
 
 }  // namespace
@@ -251,25 +233,19 @@ std::vector<uint16_t> pack_conv1_w_split(const float* w) {
             for (int e = 0; e < 8; ++e) {
                 const int co = lane & 31, kt = 8 * (lane >> 5) + e;
                 if (kt >= KT) continue;
-                const float x = w[((size_t)co * KF + kf) * KT + kt];
-                const _Float16 h1 = (_Float16)x;
-                const _Float16 h2 = (_Float16)((x - (float)h1) * kLoScale);
+                const F16Pair x = f16_split_bits(w[((size_t)co * KF + kf) * KT + kt], kLoScale);
                 const size_t base = (((size_t)kf * 2) * 64 + lane) * 8 + e;
-                out[base] = c1_bits(h1); out[base + 512] = c1_bits(h2);
+                out[base] = x.hi; out[base + 512] = x.lo;
             }
     return out;
 }
 
 namespace {
-// the kernel's 62 KB of LDS are above the default limit: raised once per process, instantiation and device, not at every launch
-template <auto KERN>
-void conv1_lds_once() {
-    static std::atomic<bool> done[kLdsOnceDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kLdsOnceDevices || !done[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_LDS + 16);
-        if (dev >= 0 && dev < kLdsOnceDevices) done[dev].store(true, std::memory_order_release);
-    }
+// the kernel's 62 KB of LDS (+ the ticket's word, in every form) are above the default limit
+template <bool SPLIT_OUT, bool BY_DEMAND>
+void launch_conv1_form(const Conv1Args& a, dim3 grid, size_t lds, EvPair ev, hipStream_t s) {
+    lds_once<conv1_f16x3_kernel<SPLIT_OUT, BY_DEMAND>>((int)C1_LDS + kTileTicketLds);
+    DSMI_LAUNCH((conv1_f16x3_kernel<SPLIT_OUT, BY_DEMAND>), grid, dim3(C1NT), lds, s, ev, a);
 }
 }  // namespace
 
@@ -277,16 +253,15 @@ int launch_conv1_split(const ConvLaunch& c, const uint16_t* wp_sp, hipStream_t s
     Conv1Args a{c.x, wp_sp, c.bias, c.bn_a, c.bn_b, c.out_lens_dev, c.y, c.y_sp, c.B, c.fi, c.fo, c.ti, c.to, c.xs, c.ys,
                 c.n_cus > 0 ? c.tile_cnt : nullptr};
     const ConvGrid g{ceil_div(c.to, C1TT), ceil_div(c.fo, C1NF), c.B};
-    if (a.tile_cnt) {      // tiles by demand: two workgroups per CU (the kernel's occupancy), each takes tile after tile
-        const dim3 gridd(std::min(conv_total(g), 2 * c.n_cus));
-        const size_t lds = C1_LDS + 16;      // ... and the ticket's word behind the window
-        if (c.y_sp) { conv1_lds_once<conv1_f16x3_kernel<true, true>>(); DSMI_LAUNCH((conv1_f16x3_kernel<true, true>), gridd, dim3(C1NT), lds, s, c.ev, a); }
-        else { conv1_lds_once<conv1_f16x3_kernel<false, true>>(); DSMI_LAUNCH((conv1_f16x3_kernel<false, true>), gridd, dim3(C1NT), lds, s, c.ev, a); }
+    if (a.tile_cnt) {      // tiles by demand
+        const dim3 gridd(tiles_workgroups(conv_total(g), c.n_cus));
+        if (c.y_sp) launch_conv1_form<true, true>(a, gridd, C1_LDS + kTileTicketLds, c.ev, s);
+        else launch_conv1_form<false, true>(a, gridd, C1_LDS + kTileTicketLds, c.ev, s);
         return (int)gridd.x;
     }
     const dim3 grid(g.nt, g.nf, g.nz);
-    if (c.y_sp) { conv1_lds_once<conv1_f16x3_kernel<true>>(); DSMI_LAUNCH(conv1_f16x3_kernel<true>, grid, dim3(C1NT), C1_LDS, s, c.ev, a); }
-    else { conv1_lds_once<conv1_f16x3_kernel<false>>(); DSMI_LAUNCH(conv1_f16x3_kernel<false>, grid, dim3(C1NT), C1_LDS, s, c.ev, a); }
+    if (c.y_sp) launch_conv1_form<true, false>(a, grid, C1_LDS, c.ev, s);
+    else launch_conv1_form<false, false>(a, grid, C1_LDS, c.ev, s);
     return g.nt * g.nf * g.nz;
 }
 

@@ -25,7 +25,6 @@
 // (they come from L2: ~600 cycles).
 #include "common.h"
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 namespace dsmi {
@@ -47,7 +46,7 @@ constexpr int ROWPLANE = WIN * PITCH;  // halfs per (row, plane)
 constexpr int RCHUNK = NPL * WIN * 4;               // 16-byte chunks of one staged input row (both planes): 592
 constexpr int CPR = (RCHUNK + 255) / 256;           // chunks per thread and row: 3
 constexpr int NSLOT = 2 * BNF;                      // staged rows held in LDS: two families of four (see the kernel)
-constexpr int kConvLds = NSLOT * NPL * ROWPLANE * 2;   // 75,776 B: two workgroups per CU (by demand: + 16 for the ticket's word)
+constexpr int kConvLds = NSLOT * NPL * ROWPLANE * 2;   // 75,776 B: two workgroups per CU (by demand: + kTileTicketLds)
 
 struct ConvSplitArgs {
     const uint16_t* x_sp; const uint16_t* wp_sp; const float* bias; const float* bn_a; const float* bn_b;
@@ -78,8 +77,9 @@ __device__ __forceinline__ void store_split4(uint16_t* y_sp, size_t bf_index, in
 // SIMD's other wave could cover.
 // SKIP: kernel rows that read only the frequency padding are not multiplied (conv_rows.h: a wave runs the taps of its own row's range,
 // the workgroup stages and meets at the barrier over the range of its live rows); false: every row, the form before, for timing
-// (experiments build).  BY_DEMAND: min(tiles, 2 x CUs) workgroups take tile after tile from their label's counter, then from the
-// others' (the scheme of gemm_f16x3_wide_kernel; the next ticket is asked for in front of a tile's stores and redeemed behind them).
+// (experiments build).  BY_DEMAND: the workgroups of a by-demand launch take tile after tile (TileTaker, dense_tiles.h; a label's share
+// is whole groups of f-neighbours, conv_rows.h); here: the ticket's word, the barriers around it, and what is derived per tile so
+// that it does not live through the kernel rows.
 template <bool SPLIT_OUT, bool XPIPE = true, bool SKIP = true, bool BY_DEMAND = false>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char csm[];
@@ -92,11 +92,10 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
     const int label = blockIdx.x & 7;
     // the linear index of the workgroup's tile (-1: none left); lane 0 writes it, everybody reads it behind a barrier
     volatile int* const tk_lds = reinterpret_cast<volatile int*>(csm + kConvLds);
-    auto cnt_add = [&](int l) { return __hip_atomic_fetch_add(p.tile_cnt + l * kDenseCntStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto cnt_peek = [&](int l) { return __hip_atomic_load(p.tile_cnt + l * kDenseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    unsigned dead = 0;      // lane 0's: the labels this workgroup has found used up
+    const TileCounters cnt{p.tile_cnt};
+    unsigned dead = 0;      // lane 0's: the labels this workgroup has found used up (every tile's TileTaker works on it)
     if (BY_DEMAND) {
-        if (tid0 == 0) tk_lds[0] = dense_draw(total, label, dead, cnt_add, cnt_peek, grid.nf);
+        if (tid0 == 0) tk_lds[0] = TileTaker(total, label, grid.nf, dead).first(cnt);
         __syncthreads();
     }
   // Every barrier below is reached by all four waves of the workgroup, tile after tile: what depends on the wave (f < p.fo, its own
@@ -124,9 +123,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
     const float *bias = p.bias, *bn_a = p.bn_a, *bn_b = p.bn_b;
     if (BY_DEMAND) asm volatile("" : "+s"(bias), "+s"(bn_a), "+s"(bn_b));
     // the next tile's ticket goes out in front of this tile's stores and is redeemed behind them
-    bool own_asked = false;
-    unsigned own_ticket = 0;
-    auto ask = [&] { if (BY_DEMAND && tid == 0 && !((dead >> label) & 1u)) { own_asked = true; own_ticket = cnt_add(label); } };
+    TileTaker taker(total, label, grid.nf, dead);
+    auto ask = [&] { if (BY_DEMAND && tid == 0) taker.ask(cnt); };
 
     if (t0 >= olen) {     // fully masked tile: zeros in the consumer's format
         ask();
@@ -352,29 +350,12 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(ConvSplitArgs p) {
     }      // f < p.fo
     }      // not a masked tile
     if (!BY_DEMAND) break;
-    if (tid == 0) {
-        int idx = own_asked ? dense_redeem(total, label, own_ticket, dead, grid.nf) : -1;
-        if (idx < 0) idx = dense_steal(total, dead, cnt_add, cnt_peek, grid.nf);
-        tk_lds[0] = idx;
-    }
+    if (tid == 0) tk_lds[0] = taker.next(cnt);
     // Every wave is past its last read of the staged rows (the barrier that closes the last kernel row) and of this tile's ticket
     // (the barrier behind the prologue, or the masked tile's own): behind this one the next tile's staging may overwrite the rows.
     __syncthreads();
   }
-    if (BY_DEMAND && tid0 == 0) {
-        // the last workgroup to leave: everybody else has drawn for the last time
-        unsigned* const done = p.tile_cnt + kDenseLabels * kDenseCntStride;
-        if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-#pragma unroll
-            for (int l = 0; l <= kDenseLabels; ++l) __hip_atomic_store(p.tile_cnt + l * kDenseCntStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-inline uint16_t c_f16_bits(_Float16 h) {
-    uint16_t u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
+    if (BY_DEMAND && tid0 == 0) tiles_leave(cnt);
 }
 
 }  // namespace
@@ -391,41 +372,32 @@ std::vector<uint16_t> pack_conv_w_split(const float* w, int co_total) {
                     for (int lane = 0; lane < 64; ++lane)
                         for (int e = 0; e < 8; ++e) {
                             const int co = ct * 32 + c * 16 + (lane & 15), ci = 8 * (lane >> 4) + e;
-                            const float x = w[(((size_t)co * CI + ci) * KF + kf) * KT + kt] * kConvWScale;
-                            const _Float16 h1 = (_Float16)x;
-                            const _Float16 h2 = (_Float16)(x - (float)h1);
+                            const F16Pair x = f16_split_bits(w[(((size_t)co * CI + ci) * KF + kf) * KT + kt] * kConvWScale);
                             const size_t base = ((((((size_t)kf * KT + kt) * nco + ct) * 2 + c) * NPL) * 64 + lane) * 8 + e;
-                            out[base] = c_f16_bits(h1); out[base + 512] = c_f16_bits(h2);
+                            out[base] = x.hi; out[base + 512] = x.lo;
                         }
     return out;
 }
 
 namespace {
-// the kernel's 74 KB of LDS are above the default limit: raised once per process, instantiation and device, not at every launch (the
-// call runs on the enqueueing thread)
-template <auto KERN>
-void conv_lds_once() {
-    static std::atomic<bool> done[kLdsOnceDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kLdsOnceDevices || !done[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, kConvLds + 16);
-        if (dev >= 0 && dev < kLdsOnceDevices) done[dev].store(true, std::memory_order_release);
-    }
+// the kernel's 74 KB of LDS (+ the ticket's word, in every form) are above the default limit
+template <bool SPLIT_OUT, bool XPIPE, bool SKIP, bool BY_DEMAND>
+void launch_conv_form(const ConvSplitArgs& a, dim3 grid, size_t lds, EvPair ev, hipStream_t s) {
+    lds_once<conv_f16x3_kernel<SPLIT_OUT, XPIPE, SKIP, BY_DEMAND>>(kConvLds + kTileTicketLds);
+    DSMI_LAUNCH((conv_f16x3_kernel<SPLIT_OUT, XPIPE, SKIP, BY_DEMAND>), grid, dim3(256), lds, s, ev, a);
 }
 template <bool XPIPE, bool SKIP>
 int launch_conv_split_form(const ConvSplitLaunch& c, const ConvSplitArgs& a, hipStream_t s) {
     const ConvGrid g{ceil_div(c.to, BTT), ceil_div(c.fo, BNF), c.B * a.nco};
-    if (a.tile_cnt) {      // tiles by demand: two workgroups per CU (the kernel's occupancy), each takes tile after tile
-        const dim3 gridd(std::min(conv_total(g), 2 * c.n_cus));
-        const size_t lds = kConvLds + 16;      // ... and the ticket's word behind the rows
-        if (c.y_sp) { conv_lds_once<conv_f16x3_kernel<true, XPIPE, SKIP, true>>(); DSMI_LAUNCH((conv_f16x3_kernel<true, XPIPE, SKIP, true>), gridd, dim3(256), lds, s, c.ev, a); }
-        else { conv_lds_once<conv_f16x3_kernel<false, XPIPE, SKIP, true>>(); DSMI_LAUNCH((conv_f16x3_kernel<false, XPIPE, SKIP, true>), gridd, dim3(256), lds, s, c.ev, a); }
+    if (a.tile_cnt) {      // tiles by demand
+        const dim3 gridd(tiles_workgroups(conv_total(g), c.n_cus));
+        if (c.y_sp) launch_conv_form<true, XPIPE, SKIP, true>(a, gridd, kConvLds + kTileTicketLds, c.ev, s);
+        else launch_conv_form<false, XPIPE, SKIP, true>(a, gridd, kConvLds + kTileTicketLds, c.ev, s);
         return (int)gridd.x;
     }
     const dim3 grid(g.nt, g.nf, g.nz);
-    const size_t lds = kConvLds;
-    if (c.y_sp) { conv_lds_once<conv_f16x3_kernel<true, XPIPE, SKIP>>(); DSMI_LAUNCH((conv_f16x3_kernel<true, XPIPE, SKIP>), grid, dim3(256), lds, s, c.ev, a); }
-    else { conv_lds_once<conv_f16x3_kernel<false, XPIPE, SKIP>>(); DSMI_LAUNCH((conv_f16x3_kernel<false, XPIPE, SKIP>), grid, dim3(256), lds, s, c.ev, a); }
+    if (c.y_sp) launch_conv_form<true, XPIPE, SKIP, false>(a, grid, kConvLds, c.ev, s);
+    else launch_conv_form<false, XPIPE, SKIP, false>(a, grid, kConvLds, c.ev, s);
     return g.nt * g.nf * g.nz;
 }
 }  // namespace

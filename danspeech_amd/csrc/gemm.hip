@@ -417,15 +417,13 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 3 : 2) void gemm_f16x3_kernel(Ge
 // 768 cycles the MFMAs take.  Here a wave's four A fragments (per plane) serve eight W tiles instead of four: 24 reads per 96 MFMAs
 // (-25 % per MFMA), 48 KB requested per k-tile for twice the products (-25 %), half the barriers per MFMA.  One LDS stage (48 KB)
 // and the registers as the second buffer, as before; 224 registers of fragments and accumulators: two workgroups per CU.
-// TILES_BY_DEMAND (dense_tiles.h): min(tiles, 2 x CUs) workgroups, each of which takes tile after tile from the counter of its label
-// (blockIdx.x & 7: the workgroups that share an XCD) in the static order, and from the other labels' counters once its own share is
-// used up.  Beside the other kernels of the pipeline the XCDs do not have the same CUs free -- measured: by demand they take 516 to
-// 674 tiles of a mean 597; NOT measured: by what (a 50-workgroup ring window would put 7 workgroups on two XCDs and 6 on the others,
-// and without the dense token the other lanes' dense kernels take CUs as well; nothing counts the ring workgroups per XCD) --, and
-// an equal share per XCD ends when the slowest one does; by demand the median launch's last XCD ends 1 % behind the mean.  One
-// lane draws, the ticket reaches the workgroup through a word of LDS behind the stage.  The draw for the next tile goes out between
-// the k-loop and the epilogue and is redeemed behind it, so its way to memory and back lies under the epilogue's stores.  The
-// workgroup that leaves last (the "done" word) zeroes the counters for the next launch on the stream.  Nobody waits for anybody.
+// TILES_BY_DEMAND: the workgroups of a by-demand launch take tile after tile (TileTaker, dense_tiles.h).  Beside the other kernels of
+// the pipeline the XCDs do not have the same CUs free -- measured: by demand they take 516 to 674 tiles of a mean 597; NOT measured:
+// by what (a 50-workgroup ring window would put 7 workgroups on two XCDs and 6 on the others, and without the dense token the other
+// lanes' dense kernels take CUs as well; nothing counts the ring workgroups per XCD) --, and an equal share per XCD ends when the
+// slowest one does; by demand the median launch's last XCD ends 1 % behind the mean.  Here: lane 0 runs the taker, its draw reaches
+// the workgroup through a word of LDS behind the stage, and the labels it has found used up wait in the word beside it while the
+// k-loop runs (no register to spare); the request goes out between the k-loop and the epilogue.
 constexpr int kWideStage = 49152;           // one stage: A and two W tiles, two 8-KiB planes each
 template <bool CONV_ROWS, int GAP = 6, bool TILES_BY_DEMAND = false>
 __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p, const uint16_t* a_sp) {
@@ -456,12 +454,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
         }
     };
 #endif
-    auto cnt_add = [&](int l) { return __hip_atomic_fetch_add(p.tile_cnt + l * kDenseCntStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto cnt_peek = [&](int l) { return __hip_atomic_load(p.tile_cnt + l * kDenseCntStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    const TileCounters cnt{p.tile_cnt};
     if (TILES_BY_DEMAND) {
         if (tid == 0) {
             unsigned dead = 0;
-            tk_lds[0] = dense_draw(total, label, dead, cnt_add, cnt_peek);
+            tk_lds[0] = TileTaker(total, label, 1, dead).first(cnt);
             tk_lds[1] = (int)dead;
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -547,13 +544,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");           // the next tile has landed, for everybody
     }
 
-    // the next tile's ticket is requested now and redeemed behind the epilogue
-    unsigned own_ticket = 0, dead = 0;
-    bool own_asked = false;
+    // the next tile's ticket is requested now and redeemed behind the epilogue; `dead` waits in LDS while the k-loop runs
+    unsigned dead = 0;
+    TileTaker taker(total, label, 1, dead);
     if (TILES_BY_DEMAND && tid == 0) {
         dead = (unsigned)tk_lds[1];
-        own_asked = !((dead >> label) & 1u);
-        if (own_asked) own_ticket = cnt_add(label);
+        taker.ask(cnt);
     }
 
     // ---- epilogue: as the 128 x 128 form's, once per n-tile of the pair
@@ -606,9 +602,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
 #endif
     if (!TILES_BY_DEMAND) break;
     if (tid == 0) {
-        int idx = own_asked ? dense_redeem(total, label, own_ticket, dead) : -1;
-        if (idx < 0) idx = dense_steal(total, dead, cnt_add, cnt_peek);
-        tk_lds[0] = idx;
+        tk_lds[0] = taker.next(cnt);
         tk_lds[1] = (int)dead;
     }
     // Every wave's last read of the turn buffer was retired by the lgkmcnt(0) that closes its epilogue, lane 0's ticket by this
@@ -618,20 +612,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_wide_kernel(GemmSplitArgs p
 #ifdef DSMI_EXPERIMENTS
     stamp_end();
 #endif
-    if (TILES_BY_DEMAND && tid == 0) {
-        // the last workgroup to leave: everybody else has drawn for the last time
-        unsigned* const done = p.tile_cnt + kDenseLabels * kDenseCntStride;
-        if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-#pragma unroll
-            for (int l = 0; l <= kDenseLabels; ++l) __hip_atomic_store(p.tile_cnt + l * kDenseCntStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-static inline uint16_t g_f16_bits(_Float16 h) {
-    uint16_t u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
+    if (TILES_BY_DEMAND && tid == 0) tiles_leave(cnt);
 }
 
 // W [N][ldw] fp32 (first K columns valid) -> [n-tile][k-tile][plane][128][32] fp16 terms (hi, lo) of W * kGemmWScale.
@@ -640,11 +621,9 @@ std::vector<uint16_t> pack_gemm_w_split(const float* w, int N, int K, int ldw) {
     std::vector<uint16_t> out((size_t)ntl * ktl * 2 * 128 * 32, 0);
     for (int n = 0; n < N; ++n)
         for (int k = 0; k < K; ++k) {
-            const float x = w[(size_t)n * ldw + k] * kGemmWScale;
-            const _Float16 h1 = (_Float16)x;
-            const _Float16 h2 = (_Float16)(x - (float)h1);
+            const F16Pair x = f16_split_bits(w[(size_t)n * ldw + k] * kGemmWScale);
             const size_t base = (((size_t)(n / BN) * ktl + k / BK) * 2) * 4096 + (size_t)(n % BN) * 32 + (k % BK);
-            out[base] = g_f16_bits(h1); out[base + 4096] = g_f16_bits(h2);
+            out[base] = x.hi; out[base + 4096] = x.lo;
         }
     return out;
 }
@@ -657,34 +636,6 @@ static int gemm_panel_width(int ktiles) {
     static const int forced = [] { const char* e = exp_env("DSMI_DEBUG_GEMM_PN"); return e ? std::atoi(e) : 0; }();
     (void)ktiles;
     return forced > 0 ? forced : 5;
-}
-
-// Tiles by demand in the 128 x 256 form (gemm_f16x3_wide_kernel)?  DSMI_DENSE_TILES=0: the static order, every XCD an equal share;
-// any other value: by demand (A/B runs, tests/test_gpu_dense_tiles.py).  Not set: by demand where the dense token is off, the static
-// order where it is on -- the gain is measured only with the token off (profiles/dense_tiles.txt); with it on a GEMM already has
-// the chip's free CUs to itself and the effect of 512 resident workgroups on the ring windows beside it is not measured.  Read once
-// per process, when its first model is made (model_build.hip keeps the answer in the handle), like DSMI_DENSE_TOKENS.
-bool dense_tiles_on(bool dense_token_on) {
-    static const bool on = [dense_token_on] {
-        const char* e = std::getenv("DSMI_DENSE_TILES");
-        if (e && *e) return !(e[0] == '0' && e[1] == 0);
-        return !dense_token_on;
-    }();
-    return on;
-}
-
-// The conv layers (conv_split.hip, conv1_split.hip): DSMI_CONV_TILES=0|1 decides for them alone (A/B runs, tests/test_gpu_conv_tiles.py);
-// without it a DSMI_DENSE_TILES that is SET decides for them as for the GEMM (0: the static order in both, otherwise by demand in
-// both).  Neither set: the static order, whether the dense token is on or off -- unlike the GEMM's rule, so no parameter: by demand
-// the convs are held bit-identical and within the float64 bound, but they did not meet the bar for a default
-// (profiles/conv_tiles.txt).  Read where DSMI_DENSE_TILES is: once per process, when its first model is made.
-bool conv_tiles_on() {
-    static const bool on = [] {
-        const char* e = std::getenv("DSMI_CONV_TILES");
-        if (!(e && *e)) e = std::getenv("DSMI_DENSE_TILES");
-        return e && *e && !(e[0] == '0' && e[1] == 0);
-    }();
-    return on;
 }
 
 #ifdef DSMI_EXPERIMENTS
@@ -763,9 +714,9 @@ int launch_gemm(const GemmLaunch& g, hipStream_t s) {
 #ifdef DSMI_EXPERIMENTS
             a.stamps = tile_stamp_slot();
 #endif
-            if (a.tile_cnt) {      // tiles by demand: two workgroups per CU (the kernel's occupancy), each takes tile after tile
-                const dim3 gridd(std::min(total, 2 * g.n_cus));
-                const size_t ldsd = kWideStage + 16;        // ... and the ticket's words behind the stage
+            if (a.tile_cnt) {      // tiles by demand
+                const dim3 gridd(tiles_workgroups(total, g.n_cus));
+                const size_t ldsd = kWideStage + kTileTicketLds;        // the ticket's words behind the stage
                 if (g.mode == GEMM_A_CONV) DSMI_LAUNCH((gemm_f16x3_wide_kernel<true, 6, true>), gridd, dim3(256), ldsd, s, g.ev, a, (const uint16_t*)g.a_sp);
                 else DSMI_LAUNCH((gemm_f16x3_wide_kernel<false, 6, true>), gridd, dim3(256), ldsd, s, g.ev, a, (const uint16_t*)g.a_sp);
                 return (int)gridd.x;
@@ -780,14 +731,8 @@ int launch_gemm(const GemmLaunch& g, hipStream_t s) {
         static const int stages = [] { const char* e = exp_env("DSMI_DEBUG_GEMM_STAGES"); return e && std::atoi(e) == 2 ? 2 : 1; }();
         if (stages == 2) {
             const size_t lds2 = 65536;                  // two stages
-            static bool attr = false;
-            if (!attr) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16x3_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16x3_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                attr = true;
-            }
-            if (g.mode == GEMM_A_CONV) DSMI_LAUNCH((gemm_f16x3_kernel<true, 2>), grid3, dim3(256), lds2, s, g.ev, a, (const uint16_t*)g.a_sp);
-            else DSMI_LAUNCH((gemm_f16x3_kernel<false, 2>), grid3, dim3(256), lds2, s, g.ev, a, (const uint16_t*)g.a_sp);
+            if (g.mode == GEMM_A_CONV) { lds_once<gemm_f16x3_kernel<true, 2>>((int)lds2); DSMI_LAUNCH((gemm_f16x3_kernel<true, 2>), grid3, dim3(256), lds2, s, g.ev, a, (const uint16_t*)g.a_sp); }
+            else { lds_once<gemm_f16x3_kernel<false, 2>>((int)lds2); DSMI_LAUNCH((gemm_f16x3_kernel<false, 2>), grid3, dim3(256), lds2, s, g.ev, a, (const uint16_t*)g.a_sp); }
             return (int)grid3.x;
         }
         const size_t lds3 = 32768;                      // one stage: four 8-KiB operand planes of a 32-deep k-tile

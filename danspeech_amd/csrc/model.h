@@ -74,10 +74,13 @@ struct dsmi_model {
     uint16_t* hpack16 = nullptr;   // packed split state of rnn_persist16.hip
     uint16_t* a_sp = nullptr;       // split A operand of the x-projection GEMM
     int last_xp_rows = 0, last_xp_cols = 0, last_xp_wgs = 0;      // dsmi_debug_xproj: what the last layer's GEMM wrote into xp, and with how many workgroups
-    bool dense_tiles = false;       // the x-projection GEMM takes its tiles by demand (DSMI_DENSE_TILES, read when the model is made)
-    unsigned* tile_cnt = nullptr;   // ... and its tile counters (dense_tiles.h): zeroed here, and by every launch behind itself
-    bool conv_tiles = false;        // the split-fp16 conv layers take their tiles by demand (DSMI_CONV_TILES over DSMI_DENSE_TILES)
-    unsigned* conv_tile_cnt[3] = {nullptr, nullptr, nullptr};   // ... each layer its own counters, zeroed like the GEMM's
+    bool dense_tiles = false;       // the x-projection GEMM takes its tiles by demand (tile_switches, dense_tiles.h; read when the model is made)
+    bool conv_tiles = false;        // the split-fp16 conv layers take theirs by demand
+    // the tile counters (dense_tiles.h) of the kernels that may run by demand, each its own kDenseCntWords words of one allocation:
+    // zeroed when it is made, and by every launch behind itself
+    enum TileCnt { kTileCntGemm = 0, kTileCntConv0 = 1, kTileCntBlocks = 4 };      // (kTileCntConv0 + l: conv layer l)
+    unsigned* tile_cnt = nullptr;
+    unsigned* tile_counters(int which) const { return tile_cnt + (size_t)which * dsmi::kDenseCntWords; }
     int last_conv_wgs[3] = {0, 0, 0};                           // dsmi_debug_conv_workgroups: workgroups of each layer's last launch
     unsigned* pcnt = nullptr;     // persistent-kernel step counters [layers][D*ceil(B/32)][T]
     unsigned* perr = nullptr;     // persistent-kernel timeout word (device)

@@ -51,8 +51,10 @@ extern "C" int dsmi_model_create(const dsmi_model_desc* d, int device, dsmi_mode
     {
         hipDeviceProp_t prop;
         m->n_cus = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 0;
-        m->dense_tiles = dense_tiles_on(dense_token_limit() > 0);
-        m->conv_tiles = conv_tiles_on();
+        // DSMI_DENSE_TILES / DSMI_CONV_TILES: read once per process, when its first model is made, like DSMI_DENSE_TOKENS
+        static const TileSwitches tiles = tile_switches(std::getenv("DSMI_DENSE_TILES"), std::getenv("DSMI_CONV_TILES"), dense_token_limit() > 0);
+        m->dense_tiles = tiles.gemm;
+        m->conv_tiles = tiles.convs;
         const char* mode = std::getenv("DSMI_RNN_MODE");      // "steps": one launch per time step; "persist8": first-generation persistent kernel
         m->rnn_mode = (mode && std::string(mode) == "steps") ? 0 : 1;
         m->persist_gen = (mode && std::string(mode) == "persist8") ? 1 : 2;
@@ -329,12 +331,9 @@ extern "C" int dsmi_reserve(dsmi_model* m, int max_B, int max_T) {
         const size_t mt = (size_t)max_B * ceil_div(std::max(To, 1), 128) + ceil_div((int)rows, 128) + 1;
         const size_t kt = (size_t)ceil_div(std::max(m->I0, m->Hs), 32);
         if ((rc = ws_alloc(m, &m->a_sp, mt * kt * 2 * 4096))) return rc;
-        if ((rc = ws_alloc(m, &m->tile_cnt, (size_t)kDenseCntWords))) return rc;
-        HIP_OK(m, hipMemset(m->tile_cnt, 0, kDenseCntWords * sizeof(unsigned)));
-        for (int l = 0; l < 3; ++l) {
-            if ((rc = ws_alloc(m, &m->conv_tile_cnt[l], (size_t)kDenseCntWords))) return rc;
-            HIP_OK(m, hipMemset(m->conv_tile_cnt[l], 0, kDenseCntWords * sizeof(unsigned)));
-        }
+        const size_t cnt_words = (size_t)dsmi_model::kTileCntBlocks * kDenseCntWords;
+        if ((rc = ws_alloc(m, &m->tile_cnt, cnt_words))) return rc;
+        HIP_OK(m, hipMemset(m->tile_cnt, 0, cnt_words * sizeof(unsigned)));
     }
     if (m->have16) {
         const size_t n = rnn_persist16_state_halfs(m->geom16, max_B);

@@ -9,8 +9,10 @@ fo; the first real kernel row of a row and of a workgroup is even in conv_split.
 every range in slot 0.
 
 Tiles (`conv-check`), for grids of 1-9 t-tiles x 1-14 f-tiles x 1-12 clip tiles, on 256 CUs and on 4, with the labels drawing in
-strict turns, one label drawing everything (all other shares stolen) and seeded random interleavings: every tile is handed out
-exactly once and nothing past the end; a label's share is whole groups and its own tickets reproduce the static map (`conv-map`,
+strict turns, one label drawing everything (all other shares stolen) and seeded random interleavings of the kernels' own steps
+(TileTaker: first, ask, next, leave; every other random order also interleaves inside a step), launch after launch over the same
+counter words: every tile is handed out exactly once and nothing past the end, every workgroup counts itself out once and the
+last one leaves the words zero; a label's share is whole groups and its own tickets reproduce the static map (`conv-map`,
 written out again below): the f-tiles of one (clip, t-tile) are consecutive tickets of one label, and with eight t-tiles label l
 gets t-tile l clip by clip -- the workgroups the hardware gives XCD l from the grid (t-tiles, f-tiles, clips) of the static order."""
 import os

@@ -4,7 +4,14 @@ stand-alone program, nothing is loaded into python.  Over the tile grids 1 x 1, 
 grids with a single n-unit, with every panel width, and with the labels drawing in strict turns, one label drawing everything
 (all other shares stolen) and 1000 seeded random interleavings per grid: every tile is handed out exactly once and nothing past
 the end.  Without stealing, a label's own tickets give the tiles of the static map the kernels had before (written out again
-below), in the same order."""
+below), in the same order.
+
+The replay drives the kernels' own TileTaker and tiles_leave (first, ask, next, leave) through plain counter words: the schedules
+interleave whole steps, so other workgroups draw between a workgroup's early request and its redeem, and every other random order
+also lets other workgroups step in front of any single add, peek or count of the stepping one (between a steal's peeks and its
+add).  Every workgroup counts itself out exactly once, the last one leaves all nine words zero, and every order of a grid is one
+more launch over the same words.  `switch` prints tile_switches, the rule of DSMI_DENSE_TILES / DSMI_CONV_TILES, held to a table
+here."""
 import os
 import shutil
 import subprocess
@@ -68,3 +75,51 @@ def test_own_share_is_the_static_map(exe, mtiles, nunits):
         assert got == ref, (mtiles, nunits, pn)
         assert order == sorted(ref), (mtiles, nunits, pn)          # tickets 0, 1, 2, ... of a label: its slots in order
         assert sorted(ref.values()) == [(m, n) for m in range(mtiles) for n in range(nunits)]
+
+
+def _switch_rule(dense, conv, token_on):
+    """The documented rule, written out again: an empty text counts as not set, "0" is the static order, any other text by demand."""
+    def is_set(t):
+        return t is not None and t != ""
+    gemm = (dense != "0") if is_set(dense) else not token_on
+    convs = (conv != "0") if is_set(conv) else (is_set(dense) and dense != "0")
+    return gemm, convs
+
+
+# (DSMI_DENSE_TILES, DSMI_CONV_TILES, dense token on) -> (the GEMM by demand, the convs by demand); None: not set
+SWITCH_TABLE = [
+    ((None, None, False), (True, False)),       # nothing set: the GEMM by demand only with the token off, the convs static
+    ((None, None, True), (False, False)),
+    (("", "", False), (True, False)),           # empty texts count as not set
+    (("", "", True), (False, False)),
+    (("0", None, False), (False, False)),       # DSMI_DENSE_TILES=0: the static order in both, whatever the token is
+    (("0", None, True), (False, False)),
+    (("1", None, False), (True, True)),         # any other text: by demand in both
+    (("1", None, True), (True, True)),
+    (("x", None, True), (True, True)),
+    (("00", None, True), (True, True)),         # only the text "0" means off
+    ((None, "1", True), (False, True)),         # DSMI_CONV_TILES decides for the convs alone
+    ((None, "1", False), (True, True)),
+    ((None, "0", False), (True, False)),
+    (("0", "1", False), (False, True)),
+    (("1", "0", True), (True, False)),
+    (("1", "", True), (True, True)),            # an empty DSMI_CONV_TILES leaves the convs to DSMI_DENSE_TILES
+    (("0", "00", True), (False, True)),
+    (("", "x", True), (False, True)),
+]
+
+
+def test_switch_table(exe):
+    texts = [None, "", "0", "1", "00", "x"]
+    cases = [(d, c, t) for d in texts for c in texts for t in (False, True)]
+    assert all(case in cases for case, _ in SWITCH_TABLE)
+    args = []
+    for d, c, t in cases:
+        args += ["-" if d is None else d, "-" if c is None else c, "1" if t else "0"]
+    lines = _run(exe, ["switch"] + args).splitlines()
+    assert len(lines) == len(cases)
+    got = {case: tuple(x == "1" for x in line.split()) for case, line in zip(cases, lines)}
+    for case, want in SWITCH_TABLE:
+        assert got[case] == want, (case, got[case], want)
+    for case in cases:
+        assert got[case] == _switch_rule(*case), (case, got[case])

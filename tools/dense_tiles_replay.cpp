@@ -1,8 +1,12 @@
 // Replays the dense kernels' tile hand-out (danspeech_amd/csrc/dense_tiles.h) on the CPU: the counters are plain words, a
-// "workgroup" is a label and a dead mask, and a schedule says which workgroup draws next.  tests/test_dense_tiles_host.py builds
-// this file with -fsanitize=address,undefined and runs it.
+// "workgroup" runs the kernels' own TileTaker and tiles_leave over them, and a schedule says which workgroup takes its next step.
+// tests/test_dense_tiles_host.py builds this file with -fsanitize=address,undefined and runs it.
 //
-//   dense_tiles_replay check            every grid x every draw order: each tile exactly once, nothing past the end; prints "ok ..."
+//   dense_tiles_replay check            every grid x every draw order, launch after launch over the same counters: each tile exactly
+//                                       once, nothing past the end, every workgroup counts itself out once, the last one leaves
+//                                       all nine words zero; prints "ok ..."
+//   dense_tiles_replay switch D C T ... tile_switches for the texts of DSMI_DENSE_TILES and DSMI_CONV_TILES ("-": not set) and the
+//                                       dense token (0 | 1), triple after triple: one "gemm convs" per line
 //   dense_tiles_replay map M N PN       the tiles of every label's own share, one "label ticket mt nu" per line (no stealing)
 // and the conv kernels' side of it (danspeech_amd/csrc/conv_rows.h; tests/test_conv_tiles_host.py):
 //   dense_tiles_replay conv-rows        the real kernel rows of every output row and workgroup, fi = 1 .. 200, both geometries; "ok ..."
@@ -37,48 +41,120 @@ struct Rng {      // xorshift64*: the same sequence everywhere
     int below(int n) { return (int)(next() % (uint64_t)n); }
 };
 
-struct Sim {
-    int total, nwg;
-    std::vector<unsigned> cnt;          // laid out as on the device: kDenseCntWords words
-    std::vector<unsigned> dead;         // per workgroup
-    std::vector<char> left;             // workgroup has drawn -1 and gone
+// One launch of a by-demand kernel over `cnt`, the counter words as they lie on the device.  A workgroup is a TileTaker (dense_tiles.h:
+// the very steps the kernels run) and a state: first -> (ask -> next)* -> leave.  A schedule says which workgroup takes its next
+// whole step; and with `nest` set, the counters may let other workgroups take whole steps in front of any single add, peek or done
+// of the stepping one (one level deep, seeded) -- which puts other draws between a steal's peeks and its add, inside a first draw,
+// and between the counts of two leaving workgroups.
+struct Launch;
+struct SimCounters {      // the counters policy of TileTaker / tiles_leave
+    Launch& s;
+    int w;                // the workgroup that is stepping
+    unsigned add(int l);
+    unsigned peek(int l);
+    unsigned done();
+    void zero(int l);
+    unsigned workgroups() const;
+};
+
+struct Launch {
+    enum State { kFirst, kHasTile, kAsked, kLeaving, kGone };
+    int total, nwg, unit;               // unit: tiles that stay on one label (conv_rows.h: the f-tiles of a group)
+    std::vector<unsigned>& cnt;         // kDenseCntWords words, zero before and behind the launch
+    std::vector<unsigned> dead;         // per workgroup: TileTaker::dead
+    std::vector<TileTaker> taker;       // per workgroup
+    std::vector<int> state, done_calls;
     std::vector<int> hits;              // per linear tile index
+    std::vector<int> live;              // workgroups that are not gone yet, in no particular order
     long draws = 0, stolen = 0;
-    int unit = 1;                       // tiles that stay on one label (conv_rows.h: the f-tiles of a group)
-    Sim(int total_, int nwg_, int unit_ = 1) : total(total_), nwg(nwg_), cnt(kDenseCntWords, 0u), dead(nwg_, 0u), left(nwg_, 0), hits(total_, 0), unit(unit_) {}
-    // One draw of workgroup w, as ONE indivisible step: the schedules interleave whole draws.  The kernel's lane 0 is finer grained
-    // -- other workgroups draw between a steal's peeks and its add, and between the early add on the own counter and its redeem
-    // behind the epilogue -- which this replay does not simulate.  What it asserts does not depend on that: a tile is handed out by
-    // the value a fetch-and-add returned, and every value is returned once, wherever the add falls; a peek only chooses the label.
-    int draw(int w) {
-        const int label = w & (kDenseLabels - 1);
-        auto add = [&](int l) { REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l); return cnt[(size_t)l * kDenseCntStride]++; };
-        auto peek = [&](int l) { REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l); return cnt[(size_t)l * kDenseCntStride]; };
-        const int idx = dense_draw(total, label, dead[w], add, peek, unit);
+    Rng* nest = nullptr;                // finer interleaving: see above
+    bool nested = false;
+
+    Launch(std::vector<unsigned>& cnt_, int total_, int nwg_, int unit_ = 1)
+        : total(total_), nwg(nwg_), unit(unit_), cnt(cnt_), dead(nwg_, 0u), state(nwg_, kFirst), done_calls(nwg_, 0), hits(total_, 0), live(nwg_) {
+        taker.reserve(nwg);
+        for (int w = 0; w < nwg; ++w) { taker.emplace_back(total, w & (kDenseLabels - 1), unit, dead[w]); live[w] = w; }
+        for (int l = 0; l <= kDenseLabels; ++l) REQUIRE(word(l) == 0u, "total %d: word %d is %u before the launch", total, l, word(l));
+    }
+    bool gone(int w) const { return state[w] == kGone; }
+    void got(int w, int idx) {
         ++draws;
-        if (idx < 0) { left[w] = 1; return idx; }
+        if (idx < 0) { state[w] = kLeaving; return; }
+        state[w] = kHasTile;
         REQUIRE(idx < total, "index %d of %d handed out", idx, total);
-        if (idx < total) {
-            hits[idx] += 1;
-            if (idx < dense_base(total, label, unit) || idx >= dense_base(total, label, unit) + dense_count(total, label, unit)) ++stolen;
+        if (idx >= total) return;
+        hits[idx] += 1;
+        const int label = w & (kDenseLabels - 1);
+        if (idx < dense_base(total, label, unit) || idx >= dense_base(total, label, unit) + dense_count(total, label, unit)) ++stolen;
+    }
+    // one whole step of workgroup w
+    void step(int w) {
+        SimCounters c{*this, w};
+        switch (state[w]) {
+            case kFirst: got(w, taker[w].first(c)); break;
+            case kHasTile: taker[w].ask(c); state[w] = kAsked; break;
+            case kAsked: got(w, taker[w].next(c)); break;
+            case kLeaving:
+                tiles_leave(c);
+                state[w] = kGone;
+                live.erase(std::find(live.begin(), live.end(), w));
+                break;
+            default: REQUIRE(false, "workgroup %d steps after it has left", w);
         }
-        return idx;
+    }
+    // in front of one access of workgroup w: maybe a few whole steps of others
+    void others(int w) {
+        if (!nest || nested || nest->below(4) != 0) return;
+        nested = true;
+        for (int n = 1 + nest->below(3); n > 0 && live.size() > 1; --n) {
+            const int v = live[nest->below((int)live.size())];
+            if (v != w) step(v);
+        }
+        nested = false;
+    }
+    unsigned& word(int l) {
+        REQUIRE(l >= 0 && l <= kDenseLabels, "word %d", l);
+        return cnt[(size_t)(l < 0 || l > kDenseLabels ? 0 : l) * kDenseCntStride];
     }
     void finish(const char* what) {
+        REQUIRE(live.empty(), "%s: total %d, %zu workgroups have not left", what, total, live.size());
         for (int i = 0; i < total; ++i) REQUIRE(hits[i] == 1, "%s: total %d, tile %d handed out %d times", what, total, i, hits[i]);
-        for (int l = 0; l < kDenseLabels; ++l)
-            REQUIRE(cnt[(size_t)l * kDenseCntStride] <= (unsigned)(dense_count(total, l, unit) + nwg), "%s: counter %d ran to %u", what, l, cnt[(size_t)l * kDenseCntStride]);
+        for (int w = 0; w < nwg; ++w) REQUIRE(done_calls[w] == 1, "%s: total %d, workgroup %d counted itself out %d times", what, total, w, done_calls[w]);
+        for (int l = 0; l <= kDenseLabels; ++l) REQUIRE(word(l) == 0u, "%s: total %d, word %d is %u behind the launch", what, total, l, word(l));
     }
 };
 
-// the workgroups of a launch: min(tiles, 2 x CUs)
-static int launch_wgs(int total, int n_cus) { return std::min(total, 2 * n_cus); }
+unsigned SimCounters::add(int l) {
+    REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l);
+    s.others(w);
+    const unsigned t = s.word(l)++;
+    REQUIRE(t < (unsigned)(dense_count(s.total, l, s.unit) + s.nwg), "total %d: counter %d ran to %u", s.total, l, t + 1);
+    return t;
+}
+unsigned SimCounters::peek(int l) {
+    REQUIRE(l >= 0 && l < kDenseLabels, "label %d", l);
+    s.others(w);
+    return s.word(l);
+}
+unsigned SimCounters::done() {
+    s.others(w);
+    s.done_calls[w] += 1;
+    return s.word(kDenseLabels)++;
+}
+void SimCounters::zero(int l) {
+    REQUIRE(s.live.size() == 1 && s.live[0] == w, "total %d: workgroup %d resets the counters with %zu workgroups still there", s.total, w, s.live.size());
+    s.word(l) = 0u;
+}
+unsigned SimCounters::workgroups() const { return (unsigned)s.nwg; }
 
+// Every draw order is one launch over the SAME counter words: each must find them zero and leave them zero, so the launches of a
+// grid relaunch each other, with a different schedule or seed each time.
 static long replay_orders(int total, int n_cus, int n_random, int unit = 1) {
-    const int nwg = launch_wgs(total, n_cus);
+    const int nwg = tiles_workgroups(total, n_cus);
+    std::vector<unsigned> cnt(kDenseCntWords, 0u);
     long draws = 0;
     {   // labels take strict turns; inside a label its workgroups take turns
-        Sim s(total, nwg, unit);
+        Launch s(cnt, total, nwg, unit);
         std::vector<int> next_of(kDenseLabels, 0);
         for (bool any = true; any;) {
             any = false;
@@ -86,8 +162,8 @@ static long replay_orders(int total, int n_cus, int n_random, int unit = 1) {
                 const int n_l = (nwg - l + kDenseLabels - 1) / kDenseLabels;      // workgroups with this label
                 for (int tries = 0; tries < n_l; ++tries) {
                     const int w = l + kDenseLabels * (next_of[l]++ % n_l);
-                    if (s.left[w]) continue;
-                    s.draw(w);
+                    if (s.gone(w)) continue;
+                    s.step(w);
                     any = true;
                     break;
                 }
@@ -96,33 +172,34 @@ static long replay_orders(int total, int n_cus, int n_random, int unit = 1) {
         s.finish("turns");
         draws += s.draws;
     }
-    for (int l = 0; l < kDenseLabels && l < nwg; ++l) {      // one label draws everything: every other share is stolen
-        Sim s(total, nwg, unit);
+    for (int l = 0; l < kDenseLabels && l < nwg; ++l) {      // one label draws everything: every other share is stolen; then the others come and go
+        Launch s(cnt, total, nwg, unit);
         for (bool any = true; any;) {
             any = false;
             for (int w = l; w < nwg; w += kDenseLabels)
-                if (!s.left[w]) { s.draw(w); any = true; }
+                if (s.state[w] != Launch::kLeaving && !s.gone(w)) { s.step(w); any = true; }
         }
-        s.finish("one label");
         REQUIRE(s.stolen == total - dense_count(total, l, unit), "one label: %ld stolen of %d", s.stolen, total);
+        for (int w = 0; w < nwg; ++w)
+            while (!s.gone(w)) s.step(w);
+        s.finish("one label");
+        REQUIRE(s.stolen == total - dense_count(total, l, unit), "one label: %ld stolen of %d behind the others", s.stolen, total);
         draws += s.draws;
     }
     for (int it = 0; it < n_random; ++it) {      // seeded random interleavings, some of them with a few workgroups far slower than the rest
-        Sim s(total, nwg, unit);
-        Rng rng(1000003ull * (uint64_t)total + (uint64_t)it);
-        std::vector<int> live(nwg);
-        for (int w = 0; w < nwg; ++w) live[w] = w;
-        const int slow = it % 3 == 0 ? rng.below(nwg) + 1 : 0;      // the first `slow` workgroups draw 16 times less often
-        while (!live.empty()) {
-            const int k = rng.below((int)live.size());
-            const int w = live[k];
+        Launch s(cnt, total, nwg, unit);
+        Rng rng(1000003ull * (uint64_t)total + (uint64_t)it), nest_rng(7919ull * (uint64_t)total + 31ull * (uint64_t)it + 1);
+        if (it % 2 == 1) s.nest = &nest_rng;      // every other one also interleaves inside the steps
+        const int slow = it % 3 == 0 ? rng.below(nwg) + 1 : 0;      // the first `slow` workgroups step 16 times less often
+        while (!s.live.empty()) {
+            const int w = s.live[rng.below((int)s.live.size())];
             if (w < slow && rng.below(16) != 0) continue;
-            s.draw(w);
-            if (s.left[w]) { live[k] = live.back(); live.pop_back(); }
+            s.step(w);
         }
         s.finish("random");
         draws += s.draws;
     }
+    for (size_t i = 0; i < cnt.size(); ++i) REQUIRE(cnt[i] == 0u, "total %d: word %zu is %u behind the last launch", total, i, cnt[i]);      // also between the nine
     return draws;
 }
 
@@ -277,6 +354,16 @@ int main(int argc, char** argv) {
         std::printf("ok %d maps %ld draws\n", maps, draws);
         return 0;
     }
-    std::fprintf(stderr, "usage: %s check [random-orders] | map M N PN | conv-rows | conv-check [random-orders] | conv-map T F Z\n", argv[0]);
+    if (argc >= 5 && !std::strcmp(argv[1], "switch")) {      // triples DENSE CONV TOKEN; a text of "-" stands for a variable that is not set
+        if ((argc - 2) % 3 != 0) return 2;
+        for (int i = 2; i + 2 < argc; i += 3) {
+            const char* d = std::strcmp(argv[i], "-") ? argv[i] : nullptr;
+            const char* c = std::strcmp(argv[i + 1], "-") ? argv[i + 1] : nullptr;
+            const TileSwitches s = tile_switches(d, c, std::atoi(argv[i + 2]) != 0);
+            std::printf("%d %d\n", s.gemm ? 1 : 0, s.convs ? 1 : 0);
+        }
+        return 0;
+    }
+    std::fprintf(stderr, "usage: %s check [random-orders] | map M N PN | conv-rows | conv-check [random-orders] | conv-map T F Z | switch DENSE CONV TOKEN ...\n", argv[0]);
     return 2;
 }
