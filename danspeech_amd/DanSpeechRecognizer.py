@@ -659,6 +659,52 @@ class DanSpeechRecognizer(object):
         """``find_phrases_batch`` of one recording: ``result[k]`` for ``phrases[k]``."""
         return self.find_phrases_batch([recording], phrases, max_hits, min_confidence)[0]
 
+    # ---- how probable are given transcripts (CTC transcript scoring) --------------------------------------------------
+    def score_batch(self, recordings, candidates):
+        """How probable is each of ``candidates[i]`` (a list of transcripts) as the transcript of ``recordings[i]``?
+        ``result[i][k]`` is ``None`` when the transcript cannot fit the recording's frames, else ``(text, logp, confidence,
+        share)``: the normalised transcript (``Decoder.normalise_transcript``), the natural log of the probability that the
+        model emits exactly it, summed over every alignment (``dsmi_score``, float64), its per-frame geometric mean
+        ``exp(logp / frames)``, and ``exp(logp)`` as a share of the sum over recording i's feasible candidates (the posterior
+        among them).  Every transcript is checked before any GPU work (``ValueError`` for characters that are not labels)."""
+        if self.model is None:
+            raise ModelNotInitialized("Trying to score without a DanSpeech model.")
+        if len(recordings) != len(candidates):
+            raise ValueError("score_batch: %d recordings and %d candidate lists" % (len(recordings), len(candidates)))
+        texts = [[self.decoder.normalise_transcript(t) for t in cands] for cands in candidates]
+        ids = [[self.decoder.transcript_ids(t) for t in cands] for cands in texts]
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        scored = self.decoder.score_ids(job.probs, [ids[i] for i in job.order], job.sizes)
+        frames = np.asarray(job.sizes).astype(np.int64)
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            lps = [lp for lp in scored[pos] if lp is not None]
+            total = float(np.logaddexp.reduce(lps)) if lps else 0.0
+            results[i] = [None if lp is None else (texts[i][k], lp, float(np.exp(lp / max(int(frames[pos]), 1))), float(np.exp(lp - total)))
+                          for k, lp in enumerate(scored[pos])]
+        return results
+
+    def score(self, recording, candidates):
+        """``score_batch`` of one recording: ``result[k]`` for ``candidates[k]``."""
+        return self.score_batch([recording], [candidates])[0]
+
+    def transcribe_scored_batch(self, recordings, n_best=1):
+        """``transcribe_batch`` with the exact likelihood of what was recognised: per recording ``[(text, logp), ...]``, the
+        decoder's first ``n_best`` hypotheses in its own order (a greedy decoder has one), ``logp`` the natural log of the
+        probability of the hypothesis' label sequence summed over every alignment (``dsmi_score``), or ``None`` if infeasible."""
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        strings, _, logps = self.decoder.decode_scored(job.probs, job.sizes, n_best)
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            results[i] = list(zip(strings[pos], logps[pos]))
+        return results
+
     # ---- long recordings and files ----------------------------------------------------------------------------------
     def transcribe_long(self, recording, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
                         max_batch=32, show_all=False, sample_rate=None, resample="polyphase"):

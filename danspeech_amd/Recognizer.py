@@ -67,6 +67,20 @@ class Recognizer(object):
         """``find_phrases`` for a list of clips in one batched pass over the GPU; ``result[i][k]`` for clip i and phrase k."""
         return self.danspeech_recognizer.find_phrases_batch(audio_list, phrases, max_hits, min_confidence)
 
+    def score(self, audio_data, candidates):
+        """How probable is each of ``candidates`` as the transcript of ``audio_data``: per candidate ``(text, logp, confidence,
+        share)``, or ``None`` when it cannot fit the audio (``DanSpeechRecognizer.score_batch``)."""
+        return self.danspeech_recognizer.score(audio_data, candidates)
+
+    def score_batch(self, audio_list, candidates):
+        """``score`` for a list of clips in one batched pass over the GPU; ``result[i][k]`` for clip i and ``candidates[i][k]``."""
+        return self.danspeech_recognizer.score_batch(audio_list, candidates)
+
+    def recognize_scored(self, audio_list, n_best=1):
+        """``recognize_batch`` with the exact likelihood of each recognised text: per clip ``[(text, logp), ...]``, the
+        decoder's first ``n_best`` hypotheses (``DanSpeechRecognizer.transcribe_scored_batch``)."""
+        return self.danspeech_recognizer.transcribe_scored_batch(audio_list, n_best=n_best)
+
     def recognize_batches(self, batches, show_all=False):
         """Generator: ``recognize_batch`` over a sequence of batches, with the upload of the next batch and the
         decoding of the previous one overlapped with the GPU's work on the current one."""

@@ -32,6 +32,7 @@ ALIGN_MAX_TOKENS = 4096         # the longest transcript dsmi_align takes (L_str
 SPOT_MAX_TOKENS = 128           # the longest phrase dsmi_spot takes (L_stride)
 SPOT_MAX_PHRASES = 4096         # phrases of one dsmi_spot call
 SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
+SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -176,6 +177,8 @@ _PROTOS = {
     "dsmi_align": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_spot_plan": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "dsmi_spot": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_score_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "dsmi_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1093,6 +1096,32 @@ class NativeDecoder(_Handle):
                                     _np_ptr(E) if tracks else None, _np_ptr(ST) if tracks else None, _stream(self.device)))
         return (hits, scores, counts, E, ST) if tracks else (hits, scores, counts)
 
+    def score(self, probs, sizes, cand_clip, targets, target_lens=None):
+        """CTC transcript scoring (``dsmi_score``): the exact float64 log likelihood of candidate transcripts, summed over
+        every alignment.  probs: CUDA [B,T,C]; sizes: [B] frames or None (= T); cand_clip: [N] the clip of each candidate;
+        targets: [N, L_stride] int array with ``target_lens`` [N], or a list of N id sequences (``target_lens`` None).
+        Returns numpy arrays (logp float64 [N], status int32 [N]: 1 = infeasible, logp = -inf)."""
+        B, T = probs.shape[0], probs.shape[1]
+        clip = np.ascontiguousarray(cand_clip, dtype=np.int32).reshape(-1)
+        N = len(clip)
+        if target_lens is None:
+            seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+            if len(seqs) != N:
+                raise ValueError("score: %d target sequences for %d candidates" % (len(seqs), N))
+            target_lens = np.array([len(t) for t in seqs], dtype=np.int32)
+            tg = np.zeros((N, int(target_lens.max()) if N else 0), dtype=np.int32)
+            for n, t in enumerate(seqs):
+                tg[n, :len(t)] = t
+        else:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(N, -1)
+            target_lens = np.ascontiguousarray(target_lens, dtype=np.int32)
+        tg = np.ascontiguousarray(tg)
+        lp = np.zeros(N, dtype=np.float64)
+        st = np.zeros(N, dtype=np.int32)
+        self._check(lib().dsmi_score(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(clip), _np_ptr(tg),
+                                     _np_ptr(target_lens), N, tg.shape[1], _np_ptr(lp), _np_ptr(st), _stream(self.device)))
+        return lp, st
+
 
 def spot_plan(phrase_lens):
     """dsmi_spot_plan (host only): (n_groups, group_of, first_state) of phrases with these token counts, as dsmi_spot packs them."""
@@ -1103,6 +1132,21 @@ def spot_plan(phrase_lens):
     if rc < 0:
         raise DsmiError(rc, "dsmi_spot_plan: 1 .. %d phrases of 1 .. %d tokens" % (SPOT_MAX_PHRASES, SPOT_MAX_TOKENS))
     return rc, group_of, first_state
+
+
+def score_plan(cand_clip, cand_frames, target_lens):
+    """dsmi_score_plan (host only): the order in which dsmi_score launches candidates with these clips, frames of their clips
+    and token counts -- order[i] = the candidate of workgroup i."""
+    clip = np.ascontiguousarray(cand_clip, dtype=np.int32).reshape(-1)
+    frames = np.ascontiguousarray(cand_frames, dtype=np.int32).reshape(-1)
+    lens = np.ascontiguousarray(target_lens, dtype=np.int32).reshape(-1)
+    if not (len(clip) == len(frames) == len(lens)):
+        raise ValueError("score_plan: one clip, frame count and token count per candidate")
+    order = np.zeros(len(clip), dtype=np.int32)
+    rc = lib().dsmi_score_plan(_np_ptr(clip), _np_ptr(frames), _np_ptr(lens), len(clip), _np_ptr(order))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_score_plan: at least one candidate, no negative entry")
+    return order
 
 
 class NativeBeamStream(_Handle):

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "align.h"
 #include "spot.h"
+#include "score.h"
 #include <cstring>
 #include <mutex>
 #include "lm.h"
@@ -67,6 +68,8 @@ struct dsmi_decoder {
     // dsmi_spot: inputs and hits of the launch (int32 words), the E and ST tracks 2 x [B][K][T_out] words
     int32_t* sp_io = nullptr; size_t sp_io_cap = 0;
     int32_t* sp_tr = nullptr; size_t sp_tr_cap = 0;
+    // dsmi_score: inputs of the launch (int32 words) and, behind them on 8 bytes, the results [N] doubles
+    int32_t* sc_io = nullptr; size_t sc_io_cap = 0;
 };
 
 // ONE stream per device for the device-to-host copies of every decoder handle's collect, made at the first collect and kept for
@@ -139,6 +142,7 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     if (d->al_bp) (void)hipFree(d->al_bp);
     if (d->sp_io) (void)hipFree(d->sp_io);
     if (d->sp_tr) (void)hipFree(d->sp_tr);
+    if (d->sc_io) (void)hipFree(d->sc_io);
     delete d;
 }
 
@@ -648,6 +652,89 @@ extern "C" int dsmi_spot(dsmi_decoder* d, const float* probs, const int32_t* siz
     return DSMI_OK;
 }
 
+
+// ---- CTC transcript scoring (the kernel: score.hip).  Every refusal comes before any launch or output write; a candidate that
+// cannot fit its clip's frames (one frame per token, one more between two equal tokens) is skipped and marked.
+extern "C" int dsmi_score_plan(const int32_t* cand_clip, const int32_t* cand_frames, const int32_t* target_lens, int N, int32_t* order) {
+    if (!cand_clip || !cand_frames || !target_lens || !order || N <= 0) return DSMI_ERR_INVALID;
+    for (int n = 0; n < N; ++n)
+        if (cand_clip[n] < 0 || cand_frames[n] < 0 || target_lens[n] < 0) return DSMI_ERR_INVALID;
+    return score_plan(cand_clip, cand_frames, target_lens, N, order);
+}
+
+extern "C" int dsmi_score(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* cand_clip,
+                          const int32_t* targets, const int32_t* target_lens, int N, int L_stride, double* logp, int32_t* status,
+                          void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !cand_clip || !target_lens || !logp || !status || (L_stride > 0 && !targets)) {
+        d->err = "bad score arguments"; return DSMI_ERR_INVALID;
+    }
+    if (B <= 0 || To <= 0 || N <= 0) { d->err = "score: B, T_out and N must be positive"; return DSMI_ERR_INVALID; }
+    if (L_stride < 0) { d->err = "score: negative L_stride"; return DSMI_ERR_INVALID; }
+    if (L_stride > DSMI_SCORE_MAX_TOKENS) {
+        d->err = "score: L_stride " + std::to_string(L_stride) + " exceeds DSMI_SCORE_MAX_TOKENS (" + std::to_string(DSMI_SCORE_MAX_TOKENS) + ")";
+        return DSMI_ERR_CAPACITY;
+    }
+    if ((uint64_t)N * (uint64_t)L_stride > ((uint64_t)1 << 24)) { d->err = "score: N * L_stride exceeds 2^24"; return DSMI_ERR_CAPACITY; }
+    std::vector<int32_t> sz(B), tl(N), frames(N), order(N);
+    for (int b = 0; b < B; ++b) {
+        sz[b] = sizes ? sizes[b] : To;
+        if (sz[b] < 0 || sz[b] > To) { d->err = "score: clip " + std::to_string(b) + ": size outside 0 .. T_out"; return DSMI_ERR_INVALID; }
+    }
+    int L_max = 0;
+    for (int n = 0; n < N; ++n) {
+        const int b = cand_clip[n], L = target_lens[n];
+        if (b < 0 || b >= B) { d->err = "score: candidate " + std::to_string(n) + ": clip outside 0 .. B-1"; return DSMI_ERR_INVALID; }
+        if (L < 0 || L > L_stride) { d->err = "score: candidate " + std::to_string(n) + ": target length outside 0 .. L_stride"; return DSMI_ERR_INVALID; }
+        const int32_t* tg = targets + (size_t)n * L_stride;
+        int repeats = 0;
+        for (int k = 0; k < L; ++k) {
+            if (tg[k] < 0 || tg[k] >= C || tg[k] == d->blank) {
+                d->err = "score: candidate " + std::to_string(n) + ": target id " + std::to_string(tg[k]) + " is the blank or not a label";
+                return DSMI_ERR_INVALID;
+            }
+            if (k > 0 && tg[k] == tg[k - 1]) ++repeats;
+        }
+        frames[n] = sz[b];
+        tl[n] = L + repeats > sz[b] ? -1 : L;        // -1: infeasible, the kernel skips the candidate
+        if (tl[n] > L_max) L_max = tl[n];
+    }
+    score_plan(cand_clip, frames.data(), target_lens, N, order.data());
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- the upload buffer, grown on demand: sizes [B], order [N], clips [N], lens [N], targets [N][L], then logp [N] doubles
+    const size_t NL = (size_t)N * L_stride, in_words = ((size_t)B + 3 * (size_t)N + NL + 1) & ~(size_t)1;
+    const size_t io_words = in_words + 2 * (size_t)N;
+    if (io_words > d->sc_io_cap) {
+        DEC_HIP(d, hipDeviceSynchronize());
+        if (d->sc_io) (void)hipFree(d->sc_io);
+        d->sc_io = nullptr; d->sc_io_cap = 0;
+        DEC_HIP(d, hipMalloc((void**)&d->sc_io, sizeof(int32_t) * io_words));
+        d->sc_io_cap = io_words;
+    }
+    int32_t* w_sz = d->sc_io; int32_t* w_or = w_sz + B; int32_t* w_cl = w_or + N; int32_t* w_tl = w_cl + N; int32_t* w_tg = w_tl + N;
+    double* w_lp = reinterpret_cast<double*>(d->sc_io + in_words);
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_or, order.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_cl, cand_clip, sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    if (NL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * NL, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_lp, 0, sizeof(double) * N, s));
+    ScoreArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w_sz; a.order = w_or; a.cand_clip = w_cl; a.tlen = w_tl; a.targets = w_tg; a.L_stride = L_stride;
+    a.S_max = 2 * L_max + 1; a.logp = w_lp;
+    DEC_HIP(d, launch_score(a, N, s));
+    std::vector<double> out(N);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_lp, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    for (int n = 0; n < N; ++n) {
+        status[n] = tl[n] < 0 ? 1 : 0;
+        logp[n] = tl[n] < 0 ? -INFINITY : out[n];
+    }
+    return DSMI_OK;
+}
 
 // ---- resumable search: one utterance's CTC prefix beam search carried across chunks (beam_kernel<..., RESUME = true>)
 struct dsmi_beam_stream {

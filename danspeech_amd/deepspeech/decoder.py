@@ -154,6 +154,38 @@ class Decoder(object):
         return [[[(int(hits[b, k, n, 0]), int(hits[b, k, n, 1]), float(scores[b, k, n])) for n in range(counts[b, k])]
                  for k in range(len(ids))] for b in range(hits.shape[0])]
 
+    # ---- CTC transcript scoring (dsmi_score): how probable is a transcript, over every alignment; no language model
+    def score(self, probs, candidates, sizes=None):
+        """The exact likelihood of candidate transcripts: ``candidates[b]`` is a list of transcripts for clip b (``probs``
+        [B,T,C], ``sizes`` frames per clip), each normalised with ``normalise_transcript``.  ``result[b][k]`` is ``None`` when
+        the transcript cannot fit the clip's frames, else the natural log (float64) of the probability that the model emits
+        exactly its label sequence, summed over every CTC alignment."""
+        ids = [[self.transcript_ids(self.normalise_transcript(t)) for t in cands] for cands in candidates]   # every check before any GPU work
+        return self.score_ids(probs, ids, sizes)
+
+    def score_ids(self, probs, ids, sizes=None):
+        """``score`` for label-id sequences as they are (no normalisation): ``ids[b]`` a list of id sequences for clip b."""
+        import torch
+        from .. import _native
+        if len(ids) != len(probs):
+            raise ValueError("score: candidate lists for %d clips and a batch of %d" % (len(ids), len(probs)))
+        flat = [t for cands in ids for t in cands]
+        longest = max([len(t) for t in flat] + [0])
+        if longest > _native.SCORE_MAX_TOKENS:
+            raise ValueError("candidate of %d labels is longer than %d" % (longest, _native.SCORE_MAX_TOKENS))
+        if not flat:
+            return [[] for _ in ids]
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        clip = [b for b, cands in enumerate(ids) for _ in cands]
+        lp, status = dec.score(probs, sz, clip, flat)
+        out, n = [], 0
+        for cands in ids:
+            out.append([None if status[n + k] else float(lp[n + k]) for k in range(len(cands))])
+            n += len(cands)
+        return out
+
 
 class GreedyDecoder(Decoder):
     """decoder.py:147-198: argmax per frame, collapse repeats, drop blanks; one path per utterance."""
@@ -170,6 +202,18 @@ class GreedyDecoder(Decoder):
         strings = [[self._to_string(ids)] for ids, _ in res]
         offsets = [[torch.from_numpy(off.astype(np.int32))] for _, off in res]
         return strings, offsets
+
+    def decode_scored(self, probs, sizes=None, n_best=None):
+        """``decode`` and, for each clip's one hypothesis, the exact likelihood of its label sequence over the same (still
+        resident) probabilities (``dsmi_score``): ``(strings, offsets, logps)`` with ``logps[b][0]`` the natural log."""
+        import torch
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        res = dec.greedy(probs, sz)
+        strings = [[self._to_string(ids)] for ids, _ in res]
+        offsets = [[torch.from_numpy(off.astype(np.int32))] for _, off in res]
+        return strings, offsets, self.score_ids(probs, [[ids] for ids, _ in res], sizes)
 
     # the same in two halves for the batch pipeline (DanSpeechRecognizer.transcribe_batches): the kernel and the copies of its
     # results are queued right behind the forward, on the forward's own stream (on_lane: no side stream), `slot` = one native
@@ -245,9 +289,26 @@ class BeamCTCDecoder(Decoder):
         return strings, offsets
 
     def decode_collect(self, ticket):
-        import torch
         tok, ts, ln, sc = ticket.beam_collect()
         self.last_scores = sc      # the reference drops ctcdecode's scores (decoder.py:140); kept for inspection
+        return self._beam_strings(tok, ts, ln)
+
+    def decode_scored(self, probs, sizes=None, n_best=None):
+        """``decode`` cut to the first ``n_best`` beams (None: all of them) and, for every hypothesis, the exact likelihood of
+        its label sequence over the same (still resident) probabilities, all of a clip's hypotheses in one ``dsmi_score``
+        call: ``(strings, offsets, logps)`` with ``logps[b][p]`` the natural log.  Unlike the search's own scores
+        (``last_scores``) these sum over every alignment, carry no language-model term and are not pruned."""
+        probs = self._on_gpu(probs)
+        tok, ts, ln, sc = self.decode_enqueue(probs, sizes).beam_collect()
+        self.last_scores = sc
+        W = tok.shape[1] if n_best is None else max(1, min(int(n_best), tok.shape[1]))
+        tok, ts, ln = tok[:, :W], ts[:, :W], ln[:, :W]
+        strings, offsets = self._beam_strings(tok, ts, ln)
+        ids = [[tok[b, p, :ln[b, p]] for p in range(W)] for b in range(tok.shape[0])]
+        return strings, offsets, self.score_ids(probs, ids, sizes)
+
+    def _beam_strings(self, tok, ts, ln):
+        import torch
         # label strings and emission offsets of every beam, built in bulk: the valid prefixes of all beams are gathered
         # once (a few hundred thousand ids instead of B x beam x T), turned into ONE string, and cut by length
         B, W = tok.shape[0], tok.shape[1]

@@ -597,6 +597,41 @@ int dsmi_spot(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host
               int32_t* hits_host, float* scores_host, int32_t* counts_host,
               float* track_scores_host, int32_t* track_starts_host, void* stream);
 
+/* ---- CTC transcript scoring (no reference counterpart): how probable is this transcript, summed over every alignment?  The
+ * natural log of the probability that the CTC model emits exactly a candidate's label sequence, through the probabilities
+ * dsmi_forward wrote.  Every frame's softmax sums to 1, so the likelihoods of all label sequences sum to 1 and exp(logp) is the
+ * acoustic model's posterior of the transcript.  The decoder's language model plays no part.
+ * probs_dev [B][T_out][n_labels]; sizes_host[B] frames per clip (NULL = T_out for all), as for dsmi_align.  N candidates over
+ * the B clips: candidate n belongs to clip cand_clip_host[n] (any order; a clip may have none or many) and its tokens are
+ * targets_host[n][0 .. target_lens_host[n]) of targets_host [N][L_stride] (never the blank; 0 tokens is legal).
+ * The recurrence (the contract).  The states are dsmi_align's: S = 2L + 1 (blank, t_1, blank, t_2, ..., blank), the same skip
+ * rule and the same alpha_0.  Everything is in float64, with lp(t, c) = log((double)fmaxf(p, FLT_MIN)):
+ *     alpha_0    = {lp(0, blank), lp(0, t_1), -inf, ...}
+ *     alpha_t(s) = logsumexp(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2) [only if s is a token state and
+ *                  label(s) != label(s-2)]) + lp(t, label(s))
+ *     logp       = logsumexp(alpha_{T-1}(S-1), alpha_{T-1}(S-2))
+ * A log-sum-exp whose arguments are all -inf is -inf, never NaN.  The result is specified as a value with a bound, not bit for
+ * bit: |logp - the recurrence evaluated exactly| <= 8 * T * 2^-52 * max(1, |logp|) (log-sum-exp is non-expansive, so the
+ * rounding errors of the frames add linearly, a few ulp of |alpha| per frame); how the log-sum-exp is formed is the
+ * library's choice.  Frames past sizes[b] are never read.  The scoring is deterministic and batch-invariant: a candidate's
+ * result is bit-identical whatever else is in the call.
+ * Outputs: logp_host [N] (natural log); status_host [N] = 0 scored, 1 infeasible (the rule of dsmi_align:
+ * L + #{k : t_k == t_{k+1}} > frames; then logp = -inf).  0 frames with 0 tokens gives logp = 0.
+ * Refused before any launch with nothing written: DSMI_ERR_INVALID for B, T_out or N <= 0, sizes[b] outside 0 .. T_out,
+ * cand_clip[n] outside 0 .. B-1, a length outside 0 .. L_stride, a token that is the blank or >= n_labels, NULL outputs;
+ * DSMI_ERR_CAPACITY for L_stride > DSMI_SCORE_MAX_TOKENS (LDS: two alpha rows of S doubles per candidate) or
+ * N * L_stride > 2^24 (the upload buffer, kept on the handle).  One kernel launch whatever N.  Synchronises `stream`.
+ *
+ * dsmi_score_plan (host only) is the launch order dsmi_score uses, one workgroup per candidate: order[i] is the candidate
+ * workgroup i scores, sorted by cand_frames (the frames of the candidate's clip) descending, so that the longest chains start
+ * first; then by clip ascending, so that the candidates of one clip run side by side and share the clip's probabilities in L2;
+ * then by token count descending; then by index ascending.  Returns N; < 0 for NULL arguments, N <= 0 or a negative entry. */
+#define DSMI_SCORE_MAX_TOKENS 2048
+int dsmi_score_plan(const int32_t* cand_clip, const int32_t* cand_frames, const int32_t* target_lens, int N, int32_t* order);
+int dsmi_score(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+               const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host, int N, int L_stride,
+               double* logp_host, int32_t* status_host, void* stream);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off

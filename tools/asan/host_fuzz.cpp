@@ -8,6 +8,8 @@
 //   host_fuzz rnnplan grid    the invariants over the grid of 29 315 520 inputs that the plan was compared on with the code it replaced
 //   host_fuzz gate SEED N     the device gate's admission (gate_plan.h): a table of launches with the masks written out by hand, then N
 //                             random sequences of planned launches of models of different widths, checked against the invariants below
+//   host_fuzz scoreplan SEED N  the launch order of CTC transcript scoring (score.h: score_plan) on N random candidate lists with many
+//                             ties: a permutation, every neighbouring pair in the documented order, nothing written past order[N)
 #define __host__
 #define __device__
 #include <cmath>
@@ -22,6 +24,7 @@
 #include "host_logic.h"
 #include "rnn_plan.h"
 #include "gate_plan.h"
+#include "score.h"
 
 using namespace dsmi;
 
@@ -358,11 +361,41 @@ static int run_gate(int argc, char** argv) {
     return 0;
 }
 
+// ---- scoreplan: frames descending, then clip ascending, then tokens descending, then index ascending --------------------------
+static int run_scoreplan(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    for (int rep = 0; rep < reps; ++rep) {
+        const int N = 1 + (int)(rng() % 300), B = 1 + (int)(rng() % 9), span = 1 + (int)(rng() % 6);
+        std::vector<int32_t> frames_of((size_t)B), clip((size_t)N), frames((size_t)N), lens((size_t)N), order((size_t)N + 1, -7);
+        for (auto& f : frames_of) f = (int32_t)(rng() % (unsigned)span);       // few distinct values: clips tie on frames
+        for (int n = 0; n < N; ++n) {
+            clip[(size_t)n] = (int32_t)(rng() % (unsigned)B);
+            frames[(size_t)n] = frames_of[(size_t)clip[(size_t)n]];
+            lens[(size_t)n] = (int32_t)(rng() % (unsigned)span);
+        }
+        if (score_plan(clip.data(), frames.data(), lens.data(), N, order.data()) != N || order[(size_t)N] != -7) return 9;
+        std::vector<int> seen((size_t)N, 0);
+        for (int i = 0; i < N; ++i) {
+            const int32_t x = order[(size_t)i];
+            if (x < 0 || x >= N || seen[(size_t)x]++) return 9;
+            if (i == 0) continue;
+            const int32_t w = order[(size_t)i - 1];
+            const long long kw[4] = {-(long long)frames[(size_t)w], clip[(size_t)w], -(long long)lens[(size_t)w], w};
+            const long long kx[4] = {-(long long)frames[(size_t)x], clip[(size_t)x], -(long long)lens[(size_t)x], x};
+            if (!std::lexicographical_compare(kw, kw + 4, kx, kx + 4)) return 9;
+        }
+    }
+    std::printf("%d score plans ok\n", reps);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "rnnplan")) return run_rnnplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "gate")) return run_gate(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]]\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]]\n");
     return 2;
 }
