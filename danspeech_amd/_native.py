@@ -1051,19 +1051,8 @@ class NativeDecoder(_Handle):
         int array with ``target_lens`` [B], or a list of B id sequences (``target_lens`` None).  Returns numpy arrays
         (spans int32 [B,L_stride,2], token_probs float32 [B,L_stride], path_logp float32 [B], status int32 [B]: 1 = infeasible)."""
         B, T = probs.shape[0], probs.shape[1]
-        if target_lens is None:
-            seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
-            if len(seqs) != B:
-                raise ValueError("align: %d target sequences for a batch of %d" % (len(seqs), B))
-            target_lens = np.array([len(t) for t in seqs], dtype=np.int32)
-            tg = np.zeros((B, int(target_lens.max()) if B else 0), dtype=np.int32)
-            for b, t in enumerate(seqs):
-                tg[b, :len(t)] = t
-        else:
-            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(B, -1)
-            target_lens = np.ascontiguousarray(target_lens, dtype=np.int32)
+        tg, target_lens = _padded_ids(targets, target_lens, B, 0, "align: %d target sequences for a batch of %d")
         Ls = tg.shape[1]
-        tg = np.ascontiguousarray(tg)
         spans = np.zeros((B, Ls, 2), dtype=np.int32)
         tp = np.zeros((B, Ls), dtype=np.float32)
         lp = np.zeros(B, dtype=np.float32)
@@ -1079,12 +1068,8 @@ class NativeDecoder(_Handle):
         float32 [B,K,max_hits] natural-log probabilities, counts int32 [B,K]; rows past the count are 0), best hit first; with
         ``tracks`` also the end scores float32 [B,K,T] and the start frames int32 [B,K,T] behind them."""
         B, T = probs.shape[0], probs.shape[1]
-        seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in phrases]
-        K, M = len(seqs), int(max_hits)
-        lens = np.array([len(t) for t in seqs], dtype=np.int32)
-        ph = np.zeros((K, max(1, int(lens.max()) if K else 1)), dtype=np.int32)
-        for k, t in enumerate(seqs):
-            ph[k, :len(t)] = t
+        ph, lens = _padded_ids(phrases, None, None, 1, None)
+        K, M = len(lens), int(max_hits)
         rows = max(M, 0)
         hits = np.zeros((B, K, rows, 2), dtype=np.int32)
         scores = np.zeros((B, K, rows), dtype=np.float32)
@@ -1104,23 +1089,31 @@ class NativeDecoder(_Handle):
         B, T = probs.shape[0], probs.shape[1]
         clip = np.ascontiguousarray(cand_clip, dtype=np.int32).reshape(-1)
         N = len(clip)
-        if target_lens is None:
-            seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
-            if len(seqs) != N:
-                raise ValueError("score: %d target sequences for %d candidates" % (len(seqs), N))
-            target_lens = np.array([len(t) for t in seqs], dtype=np.int32)
-            tg = np.zeros((N, int(target_lens.max()) if N else 0), dtype=np.int32)
-            for n, t in enumerate(seqs):
-                tg[n, :len(t)] = t
-        else:
-            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(N, -1)
-            target_lens = np.ascontiguousarray(target_lens, dtype=np.int32)
-        tg = np.ascontiguousarray(tg)
+        tg, target_lens = _padded_ids(targets, target_lens, N, 0, "score: %d target sequences for %d candidates")
         lp = np.zeros(N, dtype=np.float64)
         st = np.zeros(N, dtype=np.int32)
         self._check(lib().dsmi_score(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(clip), _np_ptr(tg),
                                      _np_ptr(target_lens), N, tg.shape[1], _np_ptr(lp), _np_ptr(st), _stream(self.device)))
         return lp, st
+
+
+def _padded_ids(rows, lens, count, min_width, mismatch):
+    """The token rows of dsmi_align / dsmi_spot / dsmi_score as a contiguous int32 [count, L_stride] array and its int32 lens:
+    from an array with ``lens``, or (``lens`` None) from a list of ``count`` id sequences (None: as many as there are),
+    zero-padded to the longest (at least ``min_width`` columns).  ``mismatch`` is the ValueError's text for another number of
+    sequences (% (given, count))."""
+    if lens is not None:
+        return (np.ascontiguousarray(rows, dtype=np.int32).reshape(count, -1), np.ascontiguousarray(lens, dtype=np.int32))
+    seqs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in rows]
+    if count is None:
+        count = len(seqs)
+    if len(seqs) != count:
+        raise ValueError(mismatch % (len(seqs), count))
+    lens = np.array([len(t) for t in seqs], dtype=np.int32)
+    ids = np.zeros((count, max(min_width, int(lens.max()) if count else 0)), dtype=np.int32)
+    for i, t in enumerate(seqs):
+        ids[i, :len(t)] = t
+    return ids, lens
 
 
 def spot_plan(phrase_lens):

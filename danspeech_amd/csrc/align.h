@@ -1,12 +1,11 @@
 // CTC forced alignment (align.hip): the Viterbi path of a fixed label sequence through the CTC trellis, one workgroup per
-// clip.  Launched by dsmi_align (decoder.hip), which checks every argument and the feasibility of every clip first.
+// clip.  Launched by dsmi_align (ctc_tools.hip), which checks every argument and the feasibility of every clip first.
 #pragma once
 #include "common.h"
 
 namespace dsmi {
 
 constexpr int kAlignThreads = 256;
-constexpr int kAlignChunk = 16;        // frames of probabilities per prefetch
 constexpr int kAlignTile = 64;          // frames per backtrace tile: 64 steps lower the state by at most 126
 constexpr int kAlignTileCols = 33;      // dwords per tile row: 132 bytes hold states s - 126 .. s from a 4-byte aligned start
 

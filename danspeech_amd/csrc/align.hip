@@ -10,17 +10,13 @@
 //
 // One workgroup per clip.  The two alpha rows live in LDS, double-buffered, so a frame costs one barrier; each thread owns the
 // states tid, tid + 256, ... and reads a state's three predecessors and its packed label / skip word at once.  The
-// probabilities travel in chunks of 16 frames, each loaded a whole chunk before it is needed and turned into lp in LDS behind
-// the last frame of the chunk before, so the chain from barrier to barrier is LDS work only (loading frame t+1 within frame t
-// left a global round trip on every frame's chain: profiles/align_time.txt).  Each (t, s) leaves a one-byte backpointer
-// (0, 1, 2: how far the state fell) in a device workspace [B][T_out][S_stride].  The backtrace stays on the GPU: going back
-// 64 frames lowers the state by at most 126, so the workgroup stages the backpointers of frames t-63..t and states s-126..s
-// (64 rows x 132 bytes) into LDS with one cooperative load and one lane walks the 64 steps from there -- one dependent global
-// round trip per 64 frames, not per frame.  lpc assumes at most 128 labels (dsmi_decoder_create's limit).
+// probabilities arrive as lp in LDS a chunk of frames ahead (CtcFeeder, ctc_trellis.h), so the chain from barrier to barrier is
+// LDS work only.  Each (t, s) leaves a one-byte backpointer (0, 1, 2: how far the state fell) in a device workspace
+// [B][T_out][S_stride].  The backtrace stays on the GPU: going back 64 frames lowers the state by at most 126, so the workgroup
+// stages the backpointers of frames t-63..t and states s-126..s (64 rows x 132 bytes) into LDS with one cooperative load and one
+// lane walks the 64 steps from there -- one dependent global round trip per 64 frames, not per frame.
 #include "align.h"
-
-#include <cfloat>
-#include <cmath>
+#include "ctc_trellis.h"
 
 namespace dsmi {
 
@@ -28,7 +24,8 @@ __global__ void __launch_bounds__(kAlignThreads) align_kernel(AlignArgs a) {
     // alpha rows [2][S_max + 2], each behind two -inf guards so that s-1 and s-2 are always readable (later: spans start[L] /
     // end[L]), then per state its label | (may skip from s-2) << 8 [S_max]
     extern __shared__ float carve[];
-    __shared__ float lpc[2][kAlignChunk * 128];   // lp of two chunks of kAlignChunk frames: chunk j in lpc[j & 1], [frame][label]
+    using Feeder = CtcFeeder<float, kAlignThreads>;
+    __shared__ float lpc[2][Feeder::kImage];      // chunk j in lpc[j & 1], [frame][label]
     __shared__ uint32_t tile[kAlignTile * kAlignTileCols];
     __shared__ int s_cur;
     constexpr int NT = kAlignThreads;
@@ -47,42 +44,18 @@ __global__ void __launch_bounds__(kAlignThreads) align_kernel(AlignArgs a) {
     unsigned char* BP = a.bp + (size_t)b * a.T_out * a.S_stride;
 
     const int32_t* tg = a.targets + (size_t)b * a.L_stride;
-    for (int s = tid; s < S; s += NT) {
-        const int j = s >> 1;
-        lsk[s] = (s & 1) ? tg[j] | (j >= 1 && tg[j - 1] != tg[j] ? 256 : 0) : a.blank;
-    }
-    if (tid < 2) al0[tid - 2] = al1[tid - 2] = -INFINITY;
-    // probabilities travel in chunks: chunk j + 1 is loaded into registers at the last frame of chunk j - 1 and turned into lp
-    // in LDS at the last frame of chunk j, a whole chunk of frames later -- no frame waits for a global load
-    constexpr int PER = kAlignChunk * 128 / NT;
-    const int CF = kAlignChunk * C;
-    float pr[PER];
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid + j * NT, f = chunk * kAlignChunk + i / C;
-            pr[j] = i < CF && f < T ? P[(size_t)chunk * CF + i] : 1.f;
-        }
-    };
-    auto store = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid + j * NT;
-            if (i < CF) lpc[chunk & 1][i] = logf(fmaxf(pr[j], FLT_MIN));
-        }
-    };
-    fetch(0);
-    store(0);
-    fetch(1);
+    ctc_blank_interleaved<float, NT>(tg, S, a.blank, tid, lsk, al0, al1);
+    Feeder feed(P, T, C, tid);
+    feed.prologue(lpc);
     __syncthreads();
     for (int s = tid; s < S; s += NT) al0[s] = s < 2 ? lpc[0][lsk[s] & 255] : -INFINITY;
     __syncthreads();
 
-    // ---- forward: alpha_t in al[t & 1], lp of frame t in lpc[(t / kAlignChunk) & 1][(t % kAlignChunk) * C + label]
+    // ---- forward: alpha_t in al[t & 1], lp of frame t in feed.frame(lpc, t)[label]
     for (int t = 1; t < T; ++t) {
         const float* prev = (t & 1) ? al0 : al1;
         float* cur = (t & 1) ? al1 : al0;
-        const float* lpt = lpc[(t / kAlignChunk) & 1] + (t % kAlignChunk) * C;
+        const float* lpt = feed.frame(lpc, t);
         unsigned char* row = BP + (size_t)t * a.S_stride;
         for (int s = tid; s < S; s += NT) {
             // every LDS read of the state at once, then lp of its label: two round trips, no branch
@@ -96,11 +69,7 @@ __global__ void __launch_bounds__(kAlignThreads) align_kernel(AlignArgs a) {
             cur[s] = best + l;
             row[s] = (unsigned char)k;
         }
-        if ((t + 1) % kAlignChunk == 0) {          // the last frame of a chunk: the next chunk's lp, then the one after it
-            const int next = (t + 1) / kAlignChunk;
-            store(next);
-            fetch(next + 1);
-        }
+        feed.end_of_frame(lpc, t);
         __syncthreads();
     }
 

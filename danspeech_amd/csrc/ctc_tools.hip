@@ -1,0 +1,163 @@
+// The three tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
+// (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip) and transcript scoring (dsmi_score; score.hip).
+// Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
+// before any output write), grows its workspaces, uploads, launches and copies the results back.  A clip or candidate whose
+// transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
+#include "decoder.h"
+#include "align.h"
+#include "spot.h"
+#include "score.h"
+
+#include <cmath>
+#include <cstring>
+
+using namespace dsmi;
+
+// The workspaces of one call: nothing happens when every capacity suffices; otherwise ONE device synchronise (a launch in flight
+// may still read a buffer that is about to be freed), then each buffer that is too small is replaced.
+static int reserve_all(dsmi_decoder* d, DevBuf& a, size_t a_bytes, DevBuf* b = nullptr, size_t b_bytes = 0) {
+    if (a.holds(a_bytes) && (!b || b->holds(b_bytes))) return DSMI_OK;
+    DEC_HIP(d, hipDeviceSynchronize());
+    DEC_HIP(d, a.reserve(a_bytes));
+    if (b) DEC_HIP(d, b->reserve(b_bytes));
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_align(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* targets,
+                          const int32_t* target_lens, int L_stride, int32_t* spans, float* token_probs, float* path_logp,
+                          int32_t* status, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !target_lens || !path_logp || !status || (L_stride > 0 && (!targets || !spans || !token_probs))) {
+        d->err = "bad align arguments"; return DSMI_ERR_INVALID;
+    }
+    std::vector<int32_t> sz, tl;
+    int L_max = 0;
+    if (int rc = align_check(sizes, B, To, targets, target_lens, L_stride, C, d->blank, sz, tl, &L_max, d->err)) return rc;
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces: io = sizes [B], lens [B], targets [B][L], spans [B][L][2], token probs [B][L], logp [B]
+    const int S_max = 2 * L_max + 1, S_stride = round_up(S_max, 4);
+    const size_t BL = (size_t)B * L_stride, io_words = 3 * (size_t)B + 4 * BL;
+    if (int rc = reserve_all(d, d->al_io, sizeof(int32_t) * io_words, &d->al_bp, (size_t)B * To * S_stride + kAlignBpSlack)) return rc;
+    int32_t* w_sz = d->al_io.as<int32_t>(); int32_t* w_tl = w_sz + B; int32_t* w_tg = w_tl + B;
+    int32_t* w_sp = w_tg + BL; float* w_tp = reinterpret_cast<float*>(w_sp + 2 * BL); float* w_lp = w_tp + BL;
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    if (BL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * BL, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_sp, 0, sizeof(int32_t) * (3 * BL + B), s));
+    AlignArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w_sz; a.tlen = w_tl; a.targets = w_tg; a.L_stride = L_stride; a.S_max = S_max;
+    a.bp = d->al_bp.as<unsigned char>(); a.S_stride = S_stride;
+    a.spans = w_sp; a.token_probs = w_tp; a.path_logp = w_lp;
+    DEC_HIP(d, launch_align(a, B, s));
+    if (BL) {
+        DEC_HIP(d, hipMemcpyAsync(spans, w_sp, sizeof(int32_t) * 2 * BL, hipMemcpyDeviceToHost, s));
+        DEC_HIP(d, hipMemcpyAsync(token_probs, w_tp, sizeof(float) * BL, hipMemcpyDeviceToHost, s));
+    }
+    DEC_HIP(d, hipMemcpyAsync(path_logp, w_lp, sizeof(float) * B, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+        status[b] = tl[b] < 0 ? 1 : 0;
+        if (tl[b] < 0) path_logp[b] = -INFINITY;
+    }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_spot_plan(const int32_t* phrase_lens, int K, int32_t* group_of, int32_t* first_state) {
+    if (!phrase_lens || !group_of || !first_state || K < 1 || K > DSMI_SPOT_MAX_PHRASES) return DSMI_ERR_INVALID;
+    for (int k = 0; k < K; ++k)
+        if (phrase_lens[k] < 1 || phrase_lens[k] > DSMI_SPOT_MAX_TOKENS) return DSMI_ERR_INVALID;
+    return spot_plan(phrase_lens, K, group_of, first_state);
+}
+
+extern "C" int dsmi_spot(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* phrases,
+                         const int32_t* phrase_lens, int K, int L_stride, int max_hits, float min_mean_logp, int32_t* hits,
+                         float* scores, int32_t* counts, float* track_scores, int32_t* track_starts, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !phrases || !phrase_lens || !hits || !scores || !counts) { d->err = "bad spot arguments"; return DSMI_ERR_INVALID; }
+    std::vector<int32_t> sz;
+    if (int rc = spot_check(sizes, B, To, phrases, phrase_lens, K, L_stride, max_hits, min_mean_logp, C, d->blank, sz, d->err)) return rc;
+    // ---- the packing: per state its label and flags, groups of kSpotThreads states
+    std::vector<int32_t> group_of(K), first_state(K);
+    const int n_groups = spot_plan(phrase_lens, K, group_of.data(), first_state.data());
+    std::vector<int32_t> words((size_t)n_groups * kSpotThreads, 0);
+    spot_pack(phrases, phrase_lens, K, L_stride, d->blank, group_of.data(), first_state.data(), words.data());
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces: io = sizes [B], words [n_groups][256], hits [B][K][M][2], scores [B][K][M], counts [B][K]
+    const size_t BK = (size_t)B * K, BKM = BK * max_hits, n_words = words.size(), n_tr = BK * To;
+    const size_t io_words = (size_t)B + n_words + 3 * BKM + BK;
+    if (int rc = reserve_all(d, d->sp_io, sizeof(int32_t) * io_words, &d->sp_tr, sizeof(int32_t) * 2 * n_tr)) return rc;
+    int32_t* w_sz = d->sp_io.as<int32_t>(); int32_t* w_wd = w_sz + B; int32_t* w_hit = w_wd + n_words;
+    float* w_sc = reinterpret_cast<float*>(w_hit + 2 * BKM); int32_t* w_cnt = w_hit + 3 * BKM;
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_wd, words.data(), sizeof(int32_t) * n_words, hipMemcpyHostToDevice, s));
+    SpotArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.K = K; a.n_groups = n_groups;
+    a.sizes = w_sz; a.words = w_wd;
+    a.E = d->sp_tr.as<float>(); a.ST = d->sp_tr.as<int32_t>() + n_tr;
+    a.max_hits = max_hits; a.min_mean_logp = min_mean_logp;
+    a.hits = w_hit; a.scores = w_sc; a.counts = w_cnt;
+    DEC_HIP(d, launch_spot(a, B, s));
+    // hits, scores and counts lie back to back: one copy into a host image, then the caller's three arrays
+    std::vector<int32_t> out(3 * BKM + BK);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_hit, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, s));
+    if (track_scores) DEC_HIP(d, hipMemcpyAsync(track_scores, a.E, sizeof(float) * n_tr, hipMemcpyDeviceToHost, s));
+    if (track_starts) DEC_HIP(d, hipMemcpyAsync(track_starts, a.ST, sizeof(int32_t) * n_tr, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    std::memcpy(hits, out.data(), sizeof(int32_t) * 2 * BKM);
+    std::memcpy(scores, out.data() + 2 * BKM, sizeof(float) * BKM);
+    std::memcpy(counts, out.data() + 3 * BKM, sizeof(int32_t) * BK);
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_score_plan(const int32_t* cand_clip, const int32_t* cand_frames, const int32_t* target_lens, int N, int32_t* order) {
+    if (!cand_clip || !cand_frames || !target_lens || !order || N <= 0) return DSMI_ERR_INVALID;
+    for (int n = 0; n < N; ++n)
+        if (cand_clip[n] < 0 || cand_frames[n] < 0 || target_lens[n] < 0) return DSMI_ERR_INVALID;
+    return score_plan(cand_clip, cand_frames, target_lens, N, order);
+}
+
+extern "C" int dsmi_score(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* cand_clip,
+                          const int32_t* targets, const int32_t* target_lens, int N, int L_stride, double* logp, int32_t* status,
+                          void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !cand_clip || !target_lens || !logp || !status || (L_stride > 0 && !targets)) {
+        d->err = "bad score arguments"; return DSMI_ERR_INVALID;
+    }
+    std::vector<int32_t> sz, tl, frames;
+    int L_max = 0;
+    if (int rc = score_check(sizes, B, To, cand_clip, targets, target_lens, N, L_stride, C, d->blank, sz, tl, frames, &L_max, d->err)) return rc;
+    std::vector<int32_t> order(N);
+    score_plan(cand_clip, frames.data(), target_lens, N, order.data());
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- the workspace: sizes [B], order [N], clips [N], lens [N], targets [N][L], then logp [N] doubles
+    const size_t NL = (size_t)N * L_stride, in_words = ((size_t)B + 3 * (size_t)N + NL + 1) & ~(size_t)1;
+    if (int rc = reserve_all(d, d->sc_io, sizeof(int32_t) * (in_words + 2 * (size_t)N))) return rc;
+    int32_t* w_sz = d->sc_io.as<int32_t>(); int32_t* w_or = w_sz + B; int32_t* w_cl = w_or + N; int32_t* w_tl = w_cl + N; int32_t* w_tg = w_tl + N;
+    double* w_lp = reinterpret_cast<double*>(w_sz + in_words);
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_or, order.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_cl, cand_clip, sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    if (NL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * NL, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_lp, 0, sizeof(double) * N, s));
+    ScoreArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w_sz; a.order = w_or; a.cand_clip = w_cl; a.tlen = w_tl; a.targets = w_tg; a.L_stride = L_stride;
+    a.S_max = 2 * L_max + 1; a.logp = w_lp;
+    DEC_HIP(d, launch_score(a, N, s));
+    std::vector<double> out(N);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_lp, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    for (int n = 0; n < N; ++n) {
+        status[n] = tl[n] < 0 ? 1 : 0;
+        logp[n] = tl[n] < 0 ? -INFINITY : out[n];
+    }
+    return DSMI_OK;
+}

@@ -8,13 +8,10 @@
 // until the final beams.  Algorithm and the deliberate float64 carry: oracle/beam.py restates ctcdecode's published
 // algorithm, oracle/beam_flat.py the kernel's own formulation of it (implicit prefix trie held on chip, edge tuples, one-pass
 // histogram selection); the parity tests compare with both.  DESIGN.md 4 "Beam search" describes the frame's six phases.
-#include "common.h"
-#include "align.h"
-#include "spot.h"
-#include "score.h"
+// The handle itself: decoder.h; the tools over the CTC trellis (align, spot, score) that share it: ctc_tools.hip.
+#include "decoder.h"
+#include "ctc_host.h"      // kCtcMaxLabels: the label limit the trellis kernels' LDS images are sized for
 #include <cstring>
-#include <mutex>
-#include "lm.h"
 #include "lm.cpp.inc"
 #include "lm_klm.cpp.inc"
 
@@ -26,51 +23,6 @@ using namespace dsmi;
 
 #define DSMI_WAIT_STORES() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #include "beam_kernel.inc"
-
-// ------------------------------------------------------------------------------------------------
-struct dsmi_decoder {
-    int device = 0;
-    std::vector<std::string> labels;
-    int blank = 0, space = -2;
-    std::string err;
-    // greedy scratch
-    size_t greedy_cap = 0;
-    int32_t *g_raw = nullptr, *g_ids = nullptr, *g_offs = nullptr, *g_nout = nullptr, *g_sizes = nullptr;
-    // dsmi_greedy_enqueue / _collect: pinned host images of the results and of the sizes, the event behind the last copy
-    int32_t* gh = nullptr; size_t gh_cap = 0; hipEvent_t g_done = nullptr; bool greedy_pending = false; int gp_B = 0, gp_T = 0;
-    // LM
-    bool has_lm = false;
-    HostLM lm;
-    double alpha = 0, beta = 0;
-    LmEntry* d_tab = nullptr; int32_t *d_next = nullptr, *d_word = nullptr;
-    unsigned char* d_klm = nullptr;      // device copy of a KenLM probing binary's search memory
-    // beam workspace
-    size_t ws_bytes = 0;
-    unsigned char* ws = nullptr;
-    // the beam search between dsmi_beam_enqueue and dsmi_beam_collect: geometry, pinned copies of its outputs, completion event
-    bool beam_pending = false;
-    int pb_B = 0, pb_To = 0, pb_beam = 0;
-    size_t pb_out = 0, pb_out_bytes = 0; hipStream_t pb_stream = nullptr;
-    int32_t stats[4] = {0, 0, 0, 0};      // of the last collected search: see dsmi_decoder_beam_stats
-    uint64_t stamps[64 * 8] = {0};
-    int32_t* pin_sz = nullptr; size_t pin_sz_cap = 0;
-    unsigned char* pin = nullptr; size_t pin_bytes = 0;
-    hipEvent_t beam_done = nullptr;
-    hipStream_t copy_stream = nullptr;      // the collect's device-to-host copies: the device's collect stream (collect_stream)
-    // resumable searches (dsmi_beam_stream): bumped by every dsmi_decoder_set_lm, so that a stream can tell that the scorer it was
-    // created with is gone; the launch table and result staging of dsmi_beam_stream_advance_many (not the offline workspace above)
-    uint64_t lm_gen = 0;
-    std::mutex bs_mu;
-    unsigned char *bs_dev = nullptr, *bs_pin = nullptr; size_t bs_dev_cap = 0, bs_pin_cap = 0;
-    // dsmi_align: inputs and outputs of the launch (int32 words), backpointers [B][T_out][S_stride] bytes
-    int32_t* al_io = nullptr; size_t al_io_cap = 0;
-    unsigned char* al_bp = nullptr; size_t al_bp_cap = 0;
-    // dsmi_spot: inputs and hits of the launch (int32 words), the E and ST tracks 2 x [B][K][T_out] words
-    int32_t* sp_io = nullptr; size_t sp_io_cap = 0;
-    int32_t* sp_tr = nullptr; size_t sp_tr_cap = 0;
-    // dsmi_score: inputs of the launch (int32 words) and, behind them on 8 bytes, the results [N] doubles
-    int32_t* sc_io = nullptr; size_t sc_io_cap = 0;
-};
 
 // ONE stream per device for the device-to-host copies of every decoder handle's collect, made at the first collect and kept for
 // the life of the process.  (It was a stream per handle: a pipeline with a beam search keeps six decoder handles, and the runtime
@@ -93,14 +45,8 @@ static hipStream_t collect_stream(int device) {
 
 static thread_local std::string g_dec_error;
 
-#define DEC_HIP(d, expr)                                                                  \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) { (d)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return DSMI_ERR_HIP; } \
-    } while (0)
-
 extern "C" int dsmi_decoder_create(int device, const char* const* labels, int n_labels, int blank, dsmi_decoder** out) {
-    if (!labels || !out || n_labels < 1 || n_labels > 128 || blank < 0 || blank >= n_labels) { g_dec_error = "bad decoder arguments"; return DSMI_ERR_INVALID; }
+    if (!labels || !out || n_labels < 1 || n_labels > kCtcMaxLabels || blank < 0 || blank >= n_labels) { g_dec_error = "bad decoder arguments"; return DSMI_ERR_INVALID; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_dec_error = "no such HIP device"; return DSMI_ERR_HIP; }
     dsmi_decoder* d = new dsmi_decoder();
@@ -138,11 +84,7 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     free_lm(d);
     if (d->bs_dev) (void)hipFree(d->bs_dev);
     if (d->bs_pin) (void)hipHostFree(d->bs_pin);
-    if (d->al_io) (void)hipFree(d->al_io);
-    if (d->al_bp) (void)hipFree(d->al_bp);
-    if (d->sp_io) (void)hipFree(d->sp_io);
-    if (d->sp_tr) (void)hipFree(d->sp_tr);
-    if (d->sc_io) (void)hipFree(d->sc_io);
+    for (DevBuf* b : {&d->al_io, &d->al_bp, &d->sp_io, &d->sp_tr, &d->sc_io}) b->release();
     delete d;
 }
 
@@ -462,278 +404,6 @@ extern "C" int dsmi_beam(dsmi_decoder* d, const float* probs, const int32_t* siz
     const int rc = dsmi_beam_enqueue(d, probs, sizes, B, To, beam, cutoff_top_n, cutoff_prob, stream);
     if (rc) return rc;
     return dsmi_beam_collect(d, tokens, tsteps, lens, scores);
-}
-
-// ---- CTC forced alignment of known transcripts (the kernel: align.hip).  Every refusal comes before any launch or output write;
-// a clip whose transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
-extern "C" int dsmi_align(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* targets,
-                          const int32_t* target_lens, int L_stride, int32_t* spans, float* token_probs, float* path_logp,
-                          int32_t* status, void* stream) {
-    if (!d) return DSMI_ERR_INVALID;
-    const int C = (int)d->labels.size();
-    if (!probs || !target_lens || !path_logp || !status || (L_stride > 0 && (!targets || !spans || !token_probs))) {
-        d->err = "bad align arguments"; return DSMI_ERR_INVALID;
-    }
-    if (B <= 0 || To <= 0) { d->err = "align: B and T_out must be positive"; return DSMI_ERR_INVALID; }
-    if (L_stride < 0) { d->err = "align: negative L_stride"; return DSMI_ERR_INVALID; }
-    if (L_stride > DSMI_ALIGN_MAX_TOKENS) {
-        d->err = "align: L_stride " + std::to_string(L_stride) + " exceeds DSMI_ALIGN_MAX_TOKENS (" + std::to_string(DSMI_ALIGN_MAX_TOKENS) + ")";
-        return DSMI_ERR_CAPACITY;
-    }
-    std::vector<int32_t> sz(B), tl(B);
-    int L_max = 0;
-    for (int b = 0; b < B; ++b) {
-        sz[b] = sizes ? sizes[b] : To;
-        if (sz[b] < 0 || sz[b] > To) { d->err = "align: clip " + std::to_string(b) + ": size outside 0 .. T_out"; return DSMI_ERR_INVALID; }
-        const int L = target_lens[b];
-        if (L < 0 || L > L_stride) { d->err = "align: clip " + std::to_string(b) + ": target length outside 0 .. L_stride"; return DSMI_ERR_INVALID; }
-        const int32_t* tg = targets + (size_t)b * L_stride;
-        int repeats = 0;
-        for (int k = 0; k < L; ++k) {
-            if (tg[k] < 0 || tg[k] >= C || tg[k] == d->blank) {
-                d->err = "align: clip " + std::to_string(b) + ": target id " + std::to_string(tg[k]) + " is the blank or not a label";
-                return DSMI_ERR_INVALID;
-            }
-            if (k > 0 && tg[k] == tg[k - 1]) ++repeats;
-        }
-        tl[b] = L + repeats > sz[b] ? -1 : L;        // -1: infeasible, the kernel skips the clip
-        if (tl[b] > L_max) L_max = tl[b];
-    }
-    DEC_HIP(d, hipSetDevice(d->device));
-    hipStream_t s = (hipStream_t)stream;
-    // ---- workspaces, grown on demand: io = sizes [B], lens [B], targets [B][L], spans [B][L][2], token probs [B][L], logp [B]
-    const int S_max = 2 * L_max + 1, S_stride = round_up(S_max, 4);
-    const size_t BL = (size_t)B * L_stride, io_words = 3 * (size_t)B + 4 * BL;
-    const size_t bp_bytes = (size_t)B * To * S_stride + kAlignBpSlack;
-    if (io_words > d->al_io_cap || bp_bytes > d->al_bp_cap) {
-        DEC_HIP(d, hipDeviceSynchronize());
-        if (io_words > d->al_io_cap) {
-            if (d->al_io) (void)hipFree(d->al_io);
-            d->al_io = nullptr; d->al_io_cap = 0;
-            DEC_HIP(d, hipMalloc((void**)&d->al_io, sizeof(int32_t) * io_words));
-            d->al_io_cap = io_words;
-        }
-        if (bp_bytes > d->al_bp_cap) {
-            if (d->al_bp) (void)hipFree(d->al_bp);
-            d->al_bp = nullptr; d->al_bp_cap = 0;
-            DEC_HIP(d, hipMalloc((void**)&d->al_bp, bp_bytes));
-            d->al_bp_cap = bp_bytes;
-        }
-    }
-    int32_t* w_sz = d->al_io; int32_t* w_tl = w_sz + B; int32_t* w_tg = w_tl + B;
-    int32_t* w_sp = w_tg + BL; float* w_tp = reinterpret_cast<float*>(w_sp + 2 * BL); float* w_lp = w_tp + BL;
-    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-    if (BL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * BL, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemsetAsync(w_sp, 0, sizeof(int32_t) * (3 * BL + B), s));
-    AlignArgs a{};
-    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
-    a.sizes = w_sz; a.tlen = w_tl; a.targets = w_tg; a.L_stride = L_stride; a.S_max = S_max;
-    a.bp = d->al_bp; a.S_stride = S_stride;
-    a.spans = w_sp; a.token_probs = w_tp; a.path_logp = w_lp;
-    DEC_HIP(d, launch_align(a, B, s));
-    if (BL) {
-        DEC_HIP(d, hipMemcpyAsync(spans, w_sp, sizeof(int32_t) * 2 * BL, hipMemcpyDeviceToHost, s));
-        DEC_HIP(d, hipMemcpyAsync(token_probs, w_tp, sizeof(float) * BL, hipMemcpyDeviceToHost, s));
-    }
-    DEC_HIP(d, hipMemcpyAsync(path_logp, w_lp, sizeof(float) * B, hipMemcpyDeviceToHost, s));
-    DEC_HIP(d, hipStreamSynchronize(s));
-    for (int b = 0; b < B; ++b) {
-        status[b] = tl[b] < 0 ? 1 : 0;
-        if (tl[b] < 0) path_logp[b] = -INFINITY;
-    }
-    return DSMI_OK;
-}
-
-
-// ---- CTC phrase search (the kernels: spot.hip).  Every refusal comes before any launch or output write.
-extern "C" int dsmi_spot_plan(const int32_t* phrase_lens, int K, int32_t* group_of, int32_t* first_state) {
-    if (!phrase_lens || !group_of || !first_state || K < 1 || K > DSMI_SPOT_MAX_PHRASES) return DSMI_ERR_INVALID;
-    for (int k = 0; k < K; ++k)
-        if (phrase_lens[k] < 1 || phrase_lens[k] > DSMI_SPOT_MAX_TOKENS) return DSMI_ERR_INVALID;
-    return spot_plan(phrase_lens, K, group_of, first_state);
-}
-
-extern "C" int dsmi_spot(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* phrases,
-                         const int32_t* phrase_lens, int K, int L_stride, int max_hits, float min_mean_logp, int32_t* hits,
-                         float* scores, int32_t* counts, float* track_scores, int32_t* track_starts, void* stream) {
-    if (!d) return DSMI_ERR_INVALID;
-    const int C = (int)d->labels.size();
-    if (!probs || !phrases || !phrase_lens || !hits || !scores || !counts) { d->err = "bad spot arguments"; return DSMI_ERR_INVALID; }
-    if (B <= 0 || To <= 0 || K <= 0) { d->err = "spot: B, T_out and K must be positive"; return DSMI_ERR_INVALID; }
-    if (max_hits < 1 || max_hits > DSMI_SPOT_MAX_HITS) {
-        d->err = "spot: max_hits outside 1 .. DSMI_SPOT_MAX_HITS (" + std::to_string(DSMI_SPOT_MAX_HITS) + ")"; return DSMI_ERR_INVALID;
-    }
-    if (std::isnan(min_mean_logp)) { d->err = "spot: min_mean_logp is not a number"; return DSMI_ERR_INVALID; }
-    if (L_stride > DSMI_SPOT_MAX_TOKENS) {
-        d->err = "spot: L_stride " + std::to_string(L_stride) + " exceeds DSMI_SPOT_MAX_TOKENS (" + std::to_string(DSMI_SPOT_MAX_TOKENS) + ")";
-        return DSMI_ERR_CAPACITY;
-    }
-    if (K > DSMI_SPOT_MAX_PHRASES) {
-        d->err = "spot: " + std::to_string(K) + " phrases exceed DSMI_SPOT_MAX_PHRASES (" + std::to_string(DSMI_SPOT_MAX_PHRASES) + ")";
-        return DSMI_ERR_CAPACITY;
-    }
-    constexpr uint64_t kTrackCap = (uint64_t)1 << 27;
-    if ((uint64_t)B * (uint64_t)K > kTrackCap || (uint64_t)B * (uint64_t)K * (uint64_t)To > kTrackCap) {
-        d->err = "spot: B * K * T_out exceeds 2^27 (the track workspace)"; return DSMI_ERR_CAPACITY;
-    }
-    std::vector<int32_t> sz(B);
-    for (int b = 0; b < B; ++b) {
-        sz[b] = sizes ? sizes[b] : To;
-        if (sz[b] < 0 || sz[b] > To) { d->err = "spot: clip " + std::to_string(b) + ": size outside 0 .. T_out"; return DSMI_ERR_INVALID; }
-    }
-    for (int k = 0; k < K; ++k) {
-        const int L = phrase_lens[k];
-        if (L < 1 || L > L_stride) { d->err = "spot: phrase " + std::to_string(k) + ": length outside 1 .. L_stride"; return DSMI_ERR_INVALID; }
-        const int32_t* ph = phrases + (size_t)k * L_stride;
-        for (int j = 0; j < L; ++j)
-            if (ph[j] < 0 || ph[j] >= C || ph[j] == d->blank) {
-                d->err = "spot: phrase " + std::to_string(k) + ": token id " + std::to_string(ph[j]) + " is the blank or not a label";
-                return DSMI_ERR_INVALID;
-            }
-    }
-    // ---- the packing: per state its label and flags, groups of kSpotThreads states
-    std::vector<int32_t> group_of(K), first_state(K);
-    const int n_groups = spot_plan(phrase_lens, K, group_of.data(), first_state.data());
-    std::vector<int32_t> words((size_t)n_groups * kSpotThreads, 0);
-    for (int k = 0; k < K; ++k) {
-        const int L = phrase_lens[k], S = 2 * L - 1;
-        const int32_t* ph = phrases + (size_t)k * L_stride;
-        int32_t* w = words.data() + (size_t)group_of[k] * kSpotThreads + first_state[k];
-        for (int s = 0; s < S; ++s) {
-            const int j = s >> 1;
-            int32_t q = kSpotLive | ((s & 1) ? d->blank : ph[j]);
-            if (!(s & 1) && j >= 1 && ph[j] != ph[j - 1]) q |= kSpotSkip;
-            if (s == 0) q |= kSpotFirst;
-            if (s == S - 1) q |= kSpotLast | (k << kSpotPhraseShift);
-            w[s] = q;
-        }
-    }
-    DEC_HIP(d, hipSetDevice(d->device));
-    hipStream_t s = (hipStream_t)stream;
-    // ---- workspaces, grown on demand: io = sizes [B], words [n_groups][256], hits [B][K][M][2], scores [B][K][M], counts [B][K]
-    const size_t BK = (size_t)B * K, BKM = BK * max_hits, n_words = words.size(), n_tr = BK * To;
-    const size_t io_words = (size_t)B + n_words + 3 * BKM + BK;
-    if (io_words > d->sp_io_cap || 2 * n_tr > d->sp_tr_cap) {
-        DEC_HIP(d, hipDeviceSynchronize());
-        if (io_words > d->sp_io_cap) {
-            if (d->sp_io) (void)hipFree(d->sp_io);
-            d->sp_io = nullptr; d->sp_io_cap = 0;
-            DEC_HIP(d, hipMalloc((void**)&d->sp_io, sizeof(int32_t) * io_words));
-            d->sp_io_cap = io_words;
-        }
-        if (2 * n_tr > d->sp_tr_cap) {
-            if (d->sp_tr) (void)hipFree(d->sp_tr);
-            d->sp_tr = nullptr; d->sp_tr_cap = 0;
-            DEC_HIP(d, hipMalloc((void**)&d->sp_tr, sizeof(int32_t) * 2 * n_tr));
-            d->sp_tr_cap = 2 * n_tr;
-        }
-    }
-    int32_t* w_sz = d->sp_io; int32_t* w_wd = w_sz + B; int32_t* w_hit = w_wd + n_words;
-    float* w_sc = reinterpret_cast<float*>(w_hit + 2 * BKM); int32_t* w_cnt = w_hit + 3 * BKM;
-    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemcpyAsync(w_wd, words.data(), sizeof(int32_t) * n_words, hipMemcpyHostToDevice, s));
-    SpotArgs a{};
-    a.probs = probs; a.T_out = To; a.C = C; a.K = K; a.n_groups = n_groups;
-    a.sizes = w_sz; a.words = w_wd;
-    a.E = reinterpret_cast<float*>(d->sp_tr); a.ST = d->sp_tr + n_tr;
-    a.max_hits = max_hits; a.min_mean_logp = min_mean_logp;
-    a.hits = w_hit; a.scores = w_sc; a.counts = w_cnt;
-    DEC_HIP(d, launch_spot(a, B, s));
-    // hits, scores and counts lie back to back: one copy into a host image, then the caller's three arrays
-    std::vector<int32_t> out(3 * BKM + BK);
-    DEC_HIP(d, hipMemcpyAsync(out.data(), w_hit, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, s));
-    if (track_scores) DEC_HIP(d, hipMemcpyAsync(track_scores, a.E, sizeof(float) * n_tr, hipMemcpyDeviceToHost, s));
-    if (track_starts) DEC_HIP(d, hipMemcpyAsync(track_starts, a.ST, sizeof(int32_t) * n_tr, hipMemcpyDeviceToHost, s));
-    DEC_HIP(d, hipStreamSynchronize(s));
-    std::memcpy(hits, out.data(), sizeof(int32_t) * 2 * BKM);
-    std::memcpy(scores, out.data() + 2 * BKM, sizeof(float) * BKM);
-    std::memcpy(counts, out.data() + 3 * BKM, sizeof(int32_t) * BK);
-    return DSMI_OK;
-}
-
-
-// ---- CTC transcript scoring (the kernel: score.hip).  Every refusal comes before any launch or output write; a candidate that
-// cannot fit its clip's frames (one frame per token, one more between two equal tokens) is skipped and marked.
-extern "C" int dsmi_score_plan(const int32_t* cand_clip, const int32_t* cand_frames, const int32_t* target_lens, int N, int32_t* order) {
-    if (!cand_clip || !cand_frames || !target_lens || !order || N <= 0) return DSMI_ERR_INVALID;
-    for (int n = 0; n < N; ++n)
-        if (cand_clip[n] < 0 || cand_frames[n] < 0 || target_lens[n] < 0) return DSMI_ERR_INVALID;
-    return score_plan(cand_clip, cand_frames, target_lens, N, order);
-}
-
-extern "C" int dsmi_score(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* cand_clip,
-                          const int32_t* targets, const int32_t* target_lens, int N, int L_stride, double* logp, int32_t* status,
-                          void* stream) {
-    if (!d) return DSMI_ERR_INVALID;
-    const int C = (int)d->labels.size();
-    if (!probs || !cand_clip || !target_lens || !logp || !status || (L_stride > 0 && !targets)) {
-        d->err = "bad score arguments"; return DSMI_ERR_INVALID;
-    }
-    if (B <= 0 || To <= 0 || N <= 0) { d->err = "score: B, T_out and N must be positive"; return DSMI_ERR_INVALID; }
-    if (L_stride < 0) { d->err = "score: negative L_stride"; return DSMI_ERR_INVALID; }
-    if (L_stride > DSMI_SCORE_MAX_TOKENS) {
-        d->err = "score: L_stride " + std::to_string(L_stride) + " exceeds DSMI_SCORE_MAX_TOKENS (" + std::to_string(DSMI_SCORE_MAX_TOKENS) + ")";
-        return DSMI_ERR_CAPACITY;
-    }
-    if ((uint64_t)N * (uint64_t)L_stride > ((uint64_t)1 << 24)) { d->err = "score: N * L_stride exceeds 2^24"; return DSMI_ERR_CAPACITY; }
-    std::vector<int32_t> sz(B), tl(N), frames(N), order(N);
-    for (int b = 0; b < B; ++b) {
-        sz[b] = sizes ? sizes[b] : To;
-        if (sz[b] < 0 || sz[b] > To) { d->err = "score: clip " + std::to_string(b) + ": size outside 0 .. T_out"; return DSMI_ERR_INVALID; }
-    }
-    int L_max = 0;
-    for (int n = 0; n < N; ++n) {
-        const int b = cand_clip[n], L = target_lens[n];
-        if (b < 0 || b >= B) { d->err = "score: candidate " + std::to_string(n) + ": clip outside 0 .. B-1"; return DSMI_ERR_INVALID; }
-        if (L < 0 || L > L_stride) { d->err = "score: candidate " + std::to_string(n) + ": target length outside 0 .. L_stride"; return DSMI_ERR_INVALID; }
-        const int32_t* tg = targets + (size_t)n * L_stride;
-        int repeats = 0;
-        for (int k = 0; k < L; ++k) {
-            if (tg[k] < 0 || tg[k] >= C || tg[k] == d->blank) {
-                d->err = "score: candidate " + std::to_string(n) + ": target id " + std::to_string(tg[k]) + " is the blank or not a label";
-                return DSMI_ERR_INVALID;
-            }
-            if (k > 0 && tg[k] == tg[k - 1]) ++repeats;
-        }
-        frames[n] = sz[b];
-        tl[n] = L + repeats > sz[b] ? -1 : L;        // -1: infeasible, the kernel skips the candidate
-        if (tl[n] > L_max) L_max = tl[n];
-    }
-    score_plan(cand_clip, frames.data(), target_lens, N, order.data());
-    DEC_HIP(d, hipSetDevice(d->device));
-    hipStream_t s = (hipStream_t)stream;
-    // ---- the upload buffer, grown on demand: sizes [B], order [N], clips [N], lens [N], targets [N][L], then logp [N] doubles
-    const size_t NL = (size_t)N * L_stride, in_words = ((size_t)B + 3 * (size_t)N + NL + 1) & ~(size_t)1;
-    const size_t io_words = in_words + 2 * (size_t)N;
-    if (io_words > d->sc_io_cap) {
-        DEC_HIP(d, hipDeviceSynchronize());
-        if (d->sc_io) (void)hipFree(d->sc_io);
-        d->sc_io = nullptr; d->sc_io_cap = 0;
-        DEC_HIP(d, hipMalloc((void**)&d->sc_io, sizeof(int32_t) * io_words));
-        d->sc_io_cap = io_words;
-    }
-    int32_t* w_sz = d->sc_io; int32_t* w_or = w_sz + B; int32_t* w_cl = w_or + N; int32_t* w_tl = w_cl + N; int32_t* w_tg = w_tl + N;
-    double* w_lp = reinterpret_cast<double*>(d->sc_io + in_words);
-    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemcpyAsync(w_or, order.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemcpyAsync(w_cl, cand_clip, sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
-    if (NL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * NL, hipMemcpyHostToDevice, s));
-    DEC_HIP(d, hipMemsetAsync(w_lp, 0, sizeof(double) * N, s));
-    ScoreArgs a{};
-    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
-    a.sizes = w_sz; a.order = w_or; a.cand_clip = w_cl; a.tlen = w_tl; a.targets = w_tg; a.L_stride = L_stride;
-    a.S_max = 2 * L_max + 1; a.logp = w_lp;
-    DEC_HIP(d, launch_score(a, N, s));
-    std::vector<double> out(N);
-    DEC_HIP(d, hipMemcpyAsync(out.data(), w_lp, sizeof(double) * N, hipMemcpyDeviceToHost, s));
-    DEC_HIP(d, hipStreamSynchronize(s));
-    for (int n = 0; n < N; ++n) {
-        status[n] = tl[n] < 0 ? 1 : 0;
-        logp[n] = tl[n] < 0 ? -INFINITY : out[n];
-    }
-    return DSMI_OK;
 }
 
 // ---- resumable search: one utterance's CTC prefix beam search carried across chunks (beam_kernel<..., RESUME = true>)

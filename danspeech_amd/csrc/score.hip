@@ -9,18 +9,15 @@
 // The log-sum-exp takes the largest argument m out, so that its term is exactly 1: m + log1p(exp(u - m) + exp(v - m)) for the
 // two others; all -inf gives -inf.
 //
-// One workgroup per candidate, in the order of score_plan (score.h).  The two alpha rows live in LDS, double-buffered, so a
-// frame costs one barrier; each thread owns the states tid, tid + 256, ...  The probabilities travel as in align.hip: chunks of
-// 16 frames, each loaded a whole chunk before it is needed and turned into float64 lp in LDS behind the last frame of the chunk
-// before, so the chain from barrier to barrier is LDS and ALU work only.  States on no complete path are not computed: state s
-// cannot be reached before frame (s - 1) / 2 (their alpha is still the -inf both rows start with), and a state below
-// S - 2 - 2 (T - 1 - t) cannot reach the end in the frames left (no later state reads it).  Both bounds depend on the
-// candidate's own S and T only, so a candidate's result is the same bits whatever else is in the launch.  lpc assumes at most
-// 128 labels (dsmi_decoder_create's limit).
+// One workgroup per candidate, in the order of score_plan (ctc_host.h).  The two alpha rows live in LDS, double-buffered, so a
+// frame costs one barrier; each thread owns the states tid, tid + 256, ...  The probabilities arrive as float64 lp in LDS a
+// chunk of frames ahead (CtcFeeder, ctc_trellis.h), so the chain from barrier to barrier is LDS and ALU work only.  States on
+// no complete path are not computed: state s cannot be reached before frame (s - 1) / 2 (their alpha is still the -inf both
+// rows start with), and a state below S - 2 - 2 (T - 1 - t) cannot reach the end in the frames left (no later state reads
+// it).  Both bounds depend on the candidate's own S and T only, so a candidate's result is the same bits whatever else is in
+// the launch.
 #include "score.h"
-
-#include <cfloat>
-#include <cmath>
+#include "ctc_trellis.h"
 
 namespace dsmi {
 
@@ -36,7 +33,8 @@ __global__ void __launch_bounds__(kScoreThreads) score_kernel(ScoreArgs a) {
     // alpha rows [2][S_max + 2], each behind two -inf guards so that s-1 and s-2 are always readable, then per state its
     // label | (may skip from s-2) << 8 [S_max]
     extern __shared__ double score_carve[];
-    __shared__ double lpc[2][kScoreChunk * 128];   // lp of two chunks of kScoreChunk frames: chunk j in lpc[j & 1], [frame][label]
+    using Feeder = CtcFeeder<double, kScoreThreads>;
+    __shared__ double lpc[2][Feeder::kImage];      // chunk j in lpc[j & 1], [frame][label]
     constexpr int NT = kScoreThreads;
     const int n = a.order[blockIdx.x], tid = threadIdx.x;
     const int L = a.tlen[n];
@@ -54,33 +52,9 @@ __global__ void __launch_bounds__(kScoreThreads) score_kernel(ScoreArgs a) {
     const float* P = a.probs + (size_t)b * a.T_out * C;
 
     const int32_t* tg = a.targets + (size_t)n * a.L_stride;
-    for (int s = tid; s < S; s += NT) {
-        const int j = s >> 1;
-        lsk[s] = (s & 1) ? tg[j] | (j >= 1 && tg[j - 1] != tg[j] ? 256 : 0) : a.blank;
-    }
-    if (tid < 2) al0[tid - 2] = al1[tid - 2] = -INFINITY;
-    // probabilities travel in chunks: chunk j + 1 is loaded into registers at the last frame of chunk j - 1 and turned into lp
-    // in LDS at the last frame of chunk j, a whole chunk of frames later -- no frame waits for a global load
-    constexpr int PER = kScoreChunk * 128 / NT;
-    const int CF = kScoreChunk * C;
-    float pr[PER];
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid + j * NT, f = chunk * kScoreChunk + i / C;
-            pr[j] = i < CF && f < T ? P[(size_t)chunk * CF + i] : 1.f;
-        }
-    };
-    auto store = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid + j * NT;
-            if (i < CF) lpc[chunk & 1][i] = log((double)fmaxf(pr[j], FLT_MIN));
-        }
-    };
-    fetch(0);
-    store(0);
-    fetch(1);
+    ctc_blank_interleaved<double, NT>(tg, S, a.blank, tid, lsk, al0, al1);
+    Feeder feed(P, T, C, tid);
+    feed.prologue(lpc);
     __syncthreads();
     for (int s = tid; s < S; s += NT) {
         al0[s] = s < 2 ? lpc[0][lsk[s] & 255] : -INFINITY;
@@ -88,11 +62,11 @@ __global__ void __launch_bounds__(kScoreThreads) score_kernel(ScoreArgs a) {
     }
     __syncthreads();
 
-    // ---- forward: alpha_t in al[t & 1], lp of frame t in lpc[(t / kScoreChunk) & 1][(t % kScoreChunk) * C + label]
+    // ---- forward: alpha_t in al[t & 1], lp of frame t in feed.frame(lpc, t)[label]
     for (int t = 1; t < T; ++t) {
         const double* prev = (t & 1) ? al0 : al1;
         double* cur = (t & 1) ? al1 : al0;
-        const double* lpt = lpc[(t / kScoreChunk) & 1] + (t % kScoreChunk) * C;
+        const double* lpt = feed.frame(lpc, t);
         // the states on a complete path: reachable by frame t, and able to reach S - 2 in the frames left
         const int hi = min(S - 1, 2 * t + 1), lo = max(0, S - 2 - 2 * (T - 1 - t));
         for (int s = tid + (max(lo - tid, 0) + NT - 1) / NT * NT; s <= hi; s += NT) {
@@ -101,11 +75,7 @@ __global__ void __launch_bounds__(kScoreThreads) score_kernel(ScoreArgs a) {
             const double l = lpt[q & 255];
             cur[s] = score_lse3(a0, a1, a2) + l;
         }
-        if ((t + 1) % kScoreChunk == 0) {          // the last frame of a chunk: the next chunk's lp, then the one after it
-            const int next = (t + 1) / kScoreChunk;
-            store(next);
-            fetch(next + 1);
-        }
+        feed.end_of_frame(lpc, t);
         __syncthreads();
     }
 

@@ -7,20 +7,17 @@
 // frame gives it a free end.  No backpointer matrix: the start frame travels with the score.
 //
 // spot_dp_kernel: one state per thread, one workgroup per (group of phrases, clip).  The host packs the phrases into groups of
-// at most 256 states (spot_plan); a per-state word holds the label, "may skip from s-2", "is a phrase's state 0" (which keeps
-// s-1 / s-2 from reading the neighbouring phrase) and "is a phrase's last state".  All phrases of a group share one lp chunk
-// per clip: the probabilities travel as in align.hip, in chunks of 16 frames fetched a whole chunk ahead and turned into lp in
-// LDS behind the previous chunk's last frame, so a frame's chain from barrier to barrier is LDS work only
-// (profiles/align_time.txt has the forms that were slower).  Two score rows and two start rows live in LDS, double-buffered:
+// at most 256 states (spot_plan, ctc_host.h); a per-state word holds the label, "may skip from s-2", "is a phrase's state 0"
+// (which keeps s-1 / s-2 from reading the neighbouring phrase) and "is a phrase's last state".  All phrases of a group share one lp chunk
+// per clip: the probabilities arrive as lp in LDS a chunk of frames ahead (CtcFeeder, ctc_trellis.h), so a frame's chain from
+// barrier to barrier is LDS work only.  Two score rows and two start rows live in LDS, double-buffered:
 // one barrier per frame.  The owner of a phrase's last state writes E[f] and ST[f] to the workspace [B][K][T_out].
 //
 // spot_pick_kernel: one workgroup per (phrase, clip).  Up to max_hits times: a workgroup-wide argmax over the frames that pass
 // the threshold and whose window [ST[f], f] meets no hit taken so far (largest E, then lowest f).  The hits so far sit in LDS;
 // nothing is marked in the tracks, so the caller may still read them.  It also fills the tracks past the clip's frames.
 #include "spot.h"
-
-#include <cfloat>
-#include <cmath>
+#include "ctc_trellis.h"
 
 namespace dsmi {
 
@@ -29,7 +26,8 @@ __global__ void __launch_bounds__(kSpotThreads) spot_dp_kernel(SpotArgs a) {
     // a state 0, thread 1 a state 0 or a state 1, and a state 1 never skips)
     __shared__ float al[2][kSpotThreads + 2];
     __shared__ int sf[2][kSpotThreads + 2];
-    __shared__ float lpc[2][kSpotChunk * 128];    // lp of two chunks: chunk j in lpc[j & 1], [frame][label]; at most 128 labels
+    using Feeder = CtcFeeder<float, kSpotThreads>;
+    __shared__ float lpc[2][Feeder::kImage];      // chunk j in lpc[j & 1], [frame][label]
     constexpr int NT = kSpotThreads;
     const int g = blockIdx.x % a.n_groups, b = blockIdx.x / a.n_groups, tid = threadIdx.x;
     const int T = a.sizes[b], C = a.C;
@@ -48,35 +46,15 @@ __global__ void __launch_bounds__(kSpotThreads) spot_dp_kernel(SpotArgs a) {
         al[0][tid] = al[1][tid] = -INFINITY;
         sf[0][tid] = sf[1][tid] = -1;
     }
-    // probabilities travel in chunks: chunk j + 1 is loaded into registers at the last frame of chunk j - 1 and turned into lp
-    // in LDS at the last frame of chunk j, a whole chunk of frames later -- no frame waits for a global load
-    constexpr int PER = kSpotChunk * 128 / NT;
-    const int CF = kSpotChunk * C;
-    float pr[PER];
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid + j * NT, f = chunk * kSpotChunk + i / C;
-            pr[j] = i < CF && f < T ? P[(size_t)chunk * CF + i] : 1.f;
-        }
-    };
-    auto store = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid + j * NT;
-            if (i < CF) lpc[chunk & 1][i] = logf(fmaxf(pr[j], FLT_MIN));
-        }
-    };
-    fetch(0);
-    store(0);
-    fetch(1);
+    Feeder feed(P, T, C, tid);
+    feed.prologue(lpc);
     __syncthreads();
 
-    // ---- frame f: scores and starts in row f & 1, from row (f + 1) & 1; lp of frame f in lpc[(f / chunk) & 1]
+    // ---- frame f: scores and starts in row f & 1, from row (f + 1) & 1; lp of frame f in feed.frame(lpc, f)
     for (int f = 0; f < T; ++f) {
         const float* pa = al[(f + 1) & 1] + tid;
         const int* ps = sf[(f + 1) & 1] + tid;
-        const float* lpt = lpc[(f / kSpotChunk) & 1] + (f % kSpotChunk) * C;
+        const float* lpt = feed.frame(lpc, f);
         if (live) {
             // every LDS read of the state at once, then no branch: predecessor s before s-1 before s-2, strict > to move
             const float a0 = pa[2], a1 = pa[1], a2 = pa[0];
@@ -92,11 +70,7 @@ __global__ void __launch_bounds__(kSpotThreads) spot_dp_kernel(SpotArgs a) {
             sf[f & 1][tid + 2] = from;
             if (last) { Ek[f] = v; Sk[f] = from; }
         }
-        if ((f + 1) % kSpotChunk == 0) {            // the last frame of a chunk: the next chunk's lp, then the one after it
-            const int next = (f + 1) / kSpotChunk;
-            store(next);
-            fetch(next + 1);
-        }
+        feed.end_of_frame(lpc, f);
         __syncthreads();
     }
 }

@@ -1,4 +1,4 @@
-"""Reference of CTC forced alignment (dsmi_align, csrc/align.hip) in numpy: the same lp = log(max(p, FLT_MIN)) in float32, the
+"""Reference of CTC forced alignment (dsmi_align: csrc/ctc_tools.hip, the kernel csrc/align.hip) in numpy: the same lp = log(max(p, FLT_MIN)) in float32, the
 same order of additions and the same tie rule (include/dsmi.h), so that its float32 results are the kernel's up to the last
 bits of log.  Also a float64 re-scorer of a given path and a brute-force enumeration of every CTC path for tiny cases.  A
 helper module of the tests (not collected)."""

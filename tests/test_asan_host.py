@@ -1,8 +1,9 @@
 """The host-only code of libdsmi.so under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not
 available on the pool): the ARPA and KenLM-binary readers against a few hundred damaged files, the shard plan and the phrase
 gate against their definitions, the device gate's admission of persistent launches (gate_plan.h) against a table written out by
-hand and its invariants.  `make -C danspeech_amd/csrc asan` builds tools/asan/host_fuzz.cpp with the product's own
-sources (lm.cpp.inc, lm_klm.cpp.inc, host_logic.h, rnn_plan.h, gate_plan.h).  A sanitizer report or a crash fails the test; a refused file is fine."""
+hand and its invariants, the argument checks and the phrase packing of the CTC tools (ctc_host.h).  `make -C danspeech_amd/csrc asan`
+builds tools/asan/host_fuzz.cpp with the product's own sources (lm.cpp.inc, lm_klm.cpp.inc, host_logic.h, rnn_plan.h, gate_plan.h,
+ctc_host.h).  A sanitizer report or a crash fails the test; a refused file is fine."""
 import os
 import shutil
 import subprocess
@@ -43,6 +44,14 @@ def test_device_gate_admission(exe):
     case where a ring launch waits for windows on slots that are not its own."""
     out = _run(exe, ["gate", "7", "400"]).split()
     assert out[1:3] == ["gate", "cases"] and out[4:7] == ["1200", "sequences", "ok,"] and int(out[0]) >= 16 and int(out[7]) > 0, out
+
+
+def test_ctc_argument_checks_and_phrase_packing(exe):
+    """What dsmi_align, dsmi_spot and dsmi_score check before any launch (csrc/ctc_host.h), on random calls held in exactly sized
+    heap arrays: sizes, token rows, the repeat count and the feasibility rule against their definitions, the refusals on the
+    numbers alone with no array at all, the phrase plan's groups within 256 states and every packed word's fields."""
+    out = _run(exe, ["ctccheck", "7", "400"]).split()
+    assert out[:4] == ["400", "ctc", "calls", "ok,"] and int(out[4]) > 300 and int(out[7]) > 100000, out
 
 
 def test_language_model_readers_on_damaged_files(exe, tmp_path):

@@ -1,4 +1,4 @@
-"""CTC forced alignment on the GPU (dsmi_align, csrc/align.hip) against the numpy reference of tests/_align_ref.py and a
+"""CTC forced alignment on the GPU (dsmi_align: csrc/ctc_tools.hip, the kernel csrc/align.hip) against the numpy reference of tests/_align_ref.py and a
 brute-force enumeration of every path, its refusals, and the recogniser surface end to end on a synthetic cfgA-shaped model."""
 import numpy as np
 import pytest
@@ -6,6 +6,7 @@ import pytest
 from danspeech_amd import synthetic as syn
 
 import _align_ref as ref
+import _ctc_edge_cases as edge
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -90,6 +91,23 @@ def test_reference_parity_ragged_batch(native, sharp, exact):
     for targets, same in ((greedy, exact), (randoms, False)):
         spans, tp, lp, status = dec.align(p_dev, sz, targets)
         _compare_with_reference(spans, tp, lp, status, probs, targets, same)
+    dec.close()
+
+
+@pytest.mark.parametrize("shape", edge.SHAPES + edge.LONG, ids=edge.name)
+def test_feeder_edges(native, shape):
+    """The shared feeder's chunk boundaries, image wrap and widths (tests/_ctc_edge_cases.py), under the tolerances of
+    _compare_with_reference.  No point is left out: the tests above have 33 labels only, and no batch of theirs pairs a clip of
+    these frame counts with a shorter one under the same T_out."""
+    T, C, L = shape
+    probs, rows = edge.case(T, C, L)
+    targets = [r[0] for r in rows]
+    dec = native.NativeDecoder(edge.labels(C), blank_index=0)
+    p_dev, sz = _padded(probs)
+    assert p_dev.shape[1] == T and sz[1] < T
+    spans, tp, lp, status = dec.align(p_dev, sz, targets)
+    assert status.tolist() == [0, 0]
+    _compare_with_reference(spans, tp, lp, status, probs, targets, False)
     dec.close()
 
 

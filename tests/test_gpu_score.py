@@ -8,6 +8,7 @@ import pytest
 from danspeech_amd import synthetic as syn
 
 import _align_ref as aref
+import _ctc_edge_cases as edge
 import _score_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +106,26 @@ def test_reference_parity_within_the_bound(native, parity):
         worst = max(worst, share)
     print("worst share of the bound: %.4f" % worst)
     assert float(want[[n for n, _, _ in cases].index("p = 0 on a needed label")]) < np.log(float(ref.FLT_MIN))
+    dec.close()
+
+
+@pytest.mark.parametrize("shape", edge.SHAPES + edge.LONG, ids=edge.name)
+def test_feeder_edges(native, shape):
+    """The shared feeder's chunk boundaries, image wrap and widths (tests/_ctc_edge_cases.py): every row of both clips within
+    the contract's bound of the float64 reference.  No point is left out: the parity cases above pass T = 15 .. 33 at 33 labels,
+    but one clip per T_out, never 3 or 128 labels and never a shorter clip beside it."""
+    T, C, L = shape
+    probs, rows = edge.case(T, C, L)
+    clip = [b for b, rs in enumerate(rows) for _ in rs]
+    targets = [r for rs in rows for r in rs]
+    dec = native.NativeDecoder(edge.labels(C), blank_index=0)
+    p_dev, sizes = _padded(probs)
+    assert p_dev.shape[1] == T and sizes[1] < T
+    lp, status = dec.score(p_dev, sizes, clip, targets)
+    assert not status.any()
+    for n, (b, t) in enumerate(zip(clip, targets)):
+        want = ref.forward(probs[b], t)
+        assert want is not None and _share_of_bound(lp[n], want, len(probs[b])) <= 1.0, (n, b, float(lp[n]), float(want))
     dec.close()
 
 

@@ -7,6 +7,7 @@ import pytest
 from danspeech_amd import synthetic as syn
 
 import _align_ref as aref
+import _ctc_edge_cases as edge
 import _spot_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +123,39 @@ def test_reference_parity_ragged_batch(native, sharp):
     # without the tracks: the same hits
     h3, s3, c3 = dec.spot(p_dev, sizes, phrases, 5, -np.inf)
     assert np.array_equal(h3, hits) and np.array_equal(s3, scores) and np.array_equal(c3, counts)
+    dec.close()
+
+
+@pytest.mark.parametrize("shape", edge.SHAPES, ids=edge.name)
+def test_feeder_edges(native, shape):
+    """The shared feeder's chunk boundaries, image wrap and widths (tests/_ctc_edge_cases.py), held as
+    test_reference_parity_ragged_batch holds its clips: the same frames finite, scores within 1e-3 of the float32 reference, a
+    start that differs only behind a float64 near tie, and the hits the documented picking of the kernel's own tracks.  No point
+    is left out: RAGGED has these frame counts at 33 labels, each under a T_out of 501, never 3 or 128 labels."""
+    T, C, _ = shape
+    probs, _ = edge.case(T, C)
+    phrases = edge.phrases(T, C)
+    assert all(aref.min_frames(ph) <= T for ph in phrases)
+    dec = native.NativeDecoder(edge.labels(C), blank_index=0)
+    p_dev, sizes = _padded(probs)
+    assert p_dev.shape[1] == T and sizes[1] < T
+    hits, scores, counts, E, ST = dec.spot(p_dev, sizes, phrases, 5, -np.inf, tracks=True)
+    assert counts[0].all()                                            # every phrase fits the first clip
+    for b, p in enumerate(probs):
+        for k, ph in enumerate(phrases):
+            n = len(p)
+            E32, S32 = ref.tracks(p, ph)
+            ok = E32 > -np.inf
+            assert ((E[b, k, :n] > -np.inf) == ok).all(), (b, k)
+            assert not ok.any() or float(np.abs(E[b, k, :n][ok] - E32[ok]).max()) < 1e-3, (b, k)
+            differ = np.nonzero(ST[b, k, :n] != S32)[0]
+            if len(differ):
+                E64, S64, MG = ref.tracks(p, ph, dtype=np.float64, margins=True)
+                for f in differ:
+                    assert ok[f] and MG[f] < 1e-4, (b, k, f, MG[f])
+                    r = aref.viterbi(p[ST[b, k, f]:f + 1], ph, dtype=np.float64)
+                    assert r is not None and abs(float(r["path_logp"]) - E64[f]) < 1e-3, (b, k, f)
+    _check_picking(hits, scores, counts, E, ST, sizes, 5, -np.inf)
     dec.close()
 
 

@@ -8,8 +8,11 @@
 //   host_fuzz rnnplan grid    the invariants over the grid of 29 315 520 inputs that the plan was compared on with the code it replaced
 //   host_fuzz gate SEED N     the device gate's admission (gate_plan.h): a table of launches with the masks written out by hand, then N
 //                             random sequences of planned launches of models of different widths, checked against the invariants below
-//   host_fuzz scoreplan SEED N  the launch order of CTC transcript scoring (score.h: score_plan) on N random candidate lists with many
+//   host_fuzz scoreplan SEED N  the launch order of CTC transcript scoring (ctc_host.h: score_plan) on N random candidate lists with many
 //                             ties: a permutation, every neighbouring pair in the documented order, nothing written past order[N)
+//   host_fuzz ctccheck SEED N   the argument checks and the phrase packing of dsmi_align / dsmi_spot / dsmi_score (ctc_host.h) on N random
+//                             calls held in exactly sized heap arrays, against the definitions written out below; what is refused
+//                             on the numbers alone is called with null arrays
 #define __host__
 #define __device__
 #include <cmath>
@@ -24,7 +27,7 @@
 #include "host_logic.h"
 #include "rnn_plan.h"
 #include "gate_plan.h"
-#include "score.h"
+#include "ctc_host.h"
 
 using namespace dsmi;
 
@@ -390,12 +393,191 @@ static int run_scoreplan(int argc, char** argv) {
     return 0;
 }
 
+// ---- ctccheck: every array is a heap block of exactly the size the call declares, so a read past it is a sanitizer report ----
+static std::vector<int32_t> exact(size_t n, int32_t v = 0) { std::vector<int32_t> a(n, v); a.shrink_to_fit(); return a; }
+static const int32_t* ptr_or_null(const std::vector<int32_t>& a) { return a.empty() ? nullptr : a.data(); }
+
+// The shortest frame labelling that emits the row: every token once, a blank between two equal tokens.
+static int min_frames(const int32_t* row, int L, int blank) {
+    std::vector<int32_t> path;
+    for (int k = 0; k < L; ++k) {
+        if (k && row[k] == row[k - 1]) path.push_back(blank);
+        path.push_back(row[k]);
+    }
+    return (int)path.size();
+}
+
+// A row of L ids of an alphabet of C labels; with `spoil` one of them is the blank, C or negative.  Returns the first bad id's index or -1.
+static int random_row(std::mt19937& rng, int32_t* row, int L, int C, int blank, bool spoil) {
+    for (int k = 0; k < L; ++k) {
+        do row[k] = (int32_t)(rng() % (unsigned)C); while (row[k] == blank);
+        if (k && C > 2 && rng() % 3 == 0) row[k] = row[k - 1];      // runs of equal tokens
+    }
+    if (!spoil || L == 0) return -1;
+    const int at = (int)(rng() % (unsigned)L);
+    const int32_t bad[3] = {(int32_t)blank, (int32_t)C, -1 - (int32_t)(rng() % 5)};
+    row[at] = bad[rng() % 3];
+    return at;
+}
+
+#define CTC_FAIL(what) do { std::fprintf(stderr, "ctccheck: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 10; } while (0)
+
+static int run_ctccheck(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long rows_checked = 0, words_checked = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        const int C = 2 + (int)(rng() % 127), blank = (int)(rng() % (unsigned)C);
+        const int B = 1 + (int)(rng() % 6), To = 1 + (int)(rng() % 40);
+        std::string err;
+        // ---- the clip sizes: inside 0 .. T_out, or one of them outside; no sizes = T_out frames each
+        {
+            std::vector<int32_t> sizes = exact((size_t)B), sz = exact((size_t)B, -7);
+            for (auto& v : sizes) v = (int32_t)(rng() % (unsigned)(To + 1));
+            const bool spoil = rng() % 3 == 0;
+            if (spoil) sizes[rng() % (unsigned)B] = rng() % 2 ? To + 1 + (int32_t)(rng() % 3) : -1 - (int32_t)(rng() % 3);
+            const int rc = ctc_check_sizes(kSpotRows, sizes.data(), B, To, sz.data(), err);
+            if (rc != (spoil ? DSMI_ERR_INVALID : DSMI_OK)) CTC_FAIL("sizes: wrong code");
+            if (spoil && err.find(": size outside 0 .. T_out") == std::string::npos) CTC_FAIL("sizes: wrong message");
+            if (!spoil && sz != sizes) CTC_FAIL("sizes: not copied");
+            if (ctc_check_sizes(kSpotRows, nullptr, B, To, sz.data(), err) != DSMI_OK || sz != exact((size_t)B, To)) CTC_FAIL("sizes: null is not T_out");
+        }
+        // ---- one token row of each tool: the length, the ids, the repeat count, the feasibility rule
+        for (const CtcRows* kind : {&kAlignRows, &kSpotRows, &kScoreRows}) {
+            const int L_stride = (int)(rng() % 20), L = (int)(rng() % 24) - 2;
+            int repeats = -7;
+            if (L < kind->min_len || L > L_stride) {      // refused on the length: the row is not read (there is none)
+                if (ctc_check_row(*kind, rep, nullptr, L, L_stride, C, blank, &repeats, err) != DSMI_ERR_INVALID || repeats != -7) CTC_FAIL("row: a bad length passed");
+                if (err.find(std::string(kind->length) + " outside " + std::to_string(kind->min_len) + " .. L_stride") == std::string::npos) CTC_FAIL("row: wrong message");
+                continue;
+            }
+            std::vector<int32_t> row = exact((size_t)L);
+            const int bad_at = random_row(rng, row.data(), L, C, blank, rng() % 3 == 0);
+            int first_bad = -1;
+            for (int k = L - 1; k >= 0; --k) if (row[(size_t)k] < 0 || row[(size_t)k] >= C || row[(size_t)k] == blank) first_bad = k;
+            if ((bad_at < 0) != (first_bad < 0)) CTC_FAIL("row: the test's own spoiling");
+            const int rc = ctc_check_row(*kind, rep, ptr_or_null(row), L, L_stride, C, blank, &repeats, err);
+            if (rc != (first_bad < 0 ? DSMI_OK : DSMI_ERR_INVALID)) CTC_FAIL("row: wrong code");
+            ++rows_checked;
+            if (first_bad >= 0) {
+                if (err.find(std::string(kind->id) + " " + std::to_string(row[(size_t)first_bad]) + " is the blank or not a label") == std::string::npos) CTC_FAIL("row: wrong id named");
+                continue;
+            }
+            int equal_pairs = 0;
+            for (int k = 1; k < L; ++k) equal_pairs += row[(size_t)k] == row[(size_t)k - 1];
+            const int need = min_frames(ptr_or_null(row), L, blank);
+            if (repeats != equal_pairs || L + repeats != need) CTC_FAIL("row: repeat count");
+            for (int frames : {need - 1, need, need + 1, 0, To})
+                if (frames >= 0 && ctc_feasible_len(L, repeats, frames) != (need <= frames ? L : -1)) CTC_FAIL("feasibility rule");
+        }
+        // ---- whole calls with nothing wrong: what the checks hand the launch
+        {
+            const int L_stride = (int)(rng() % 12), N = 1 + (int)(rng() % 9);
+            std::vector<int32_t> sizes = exact((size_t)B), clip = exact((size_t)N), lens = exact((size_t)N), tg = exact((size_t)N * L_stride);
+            for (auto& v : sizes) v = (int32_t)(rng() % (unsigned)(To + 1));
+            for (int n = 0; n < N; ++n) {
+                clip[(size_t)n] = (int32_t)(rng() % (unsigned)B);
+                lens[(size_t)n] = (int32_t)(rng() % (unsigned)(L_stride + 1));
+                random_row(rng, tg.data() + (size_t)n * L_stride, lens[(size_t)n], C, blank, false);
+            }
+            std::vector<int32_t> sz, tl, frames;
+            int L_max = -7;
+            if (score_check(sizes.data(), B, To, clip.data(), ptr_or_null(tg), lens.data(), N, L_stride, C, blank, sz, tl, frames, &L_max, err) != DSMI_OK) CTC_FAIL("score: a good call refused");
+            int want_max = 0;
+            for (int n = 0; n < N; ++n) {
+                const int T = sizes[(size_t)clip[(size_t)n]], L = lens[(size_t)n];
+                const int want = min_frames(tg.data() + (size_t)n * L_stride, L, blank) <= T ? L : -1;
+                if (frames[(size_t)n] != T || tl[(size_t)n] != want) CTC_FAIL("score: frames or feasibility");
+                want_max = std::max(want_max, want);
+            }
+            if (sz != sizes || L_max != want_max || (int)tl.size() != N) CTC_FAIL("score: sizes or the longest candidate");
+            // the same rows as one transcript per clip (the first B of them, N >= B or not)
+            const int Ba = std::min(B, N);
+            if (align_check(sizes.data(), Ba, To, ptr_or_null(tg), lens.data(), L_stride, C, blank, sz, tl, &L_max, err) != DSMI_OK) CTC_FAIL("align: a good call refused");
+            want_max = 0;
+            for (int b = 0; b < Ba; ++b) {
+                const int L = lens[(size_t)b], want = min_frames(tg.data() + (size_t)b * L_stride, L, blank) <= sizes[(size_t)b] ? L : -1;
+                if (tl[(size_t)b] != want) CTC_FAIL("align: feasibility");
+                want_max = std::max(want_max, want);
+            }
+            if (L_max != want_max || (int)sz.size() != Ba) CTC_FAIL("align: the longest transcript");
+            // one fault: a clip index outside the batch
+            clip[rng() % (unsigned)N] = rng() % 2 ? B : -1;
+            if (score_check(sizes.data(), B, To, clip.data(), ptr_or_null(tg), lens.data(), N, L_stride, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_INVALID ||
+                err.find("clip outside 0 .. B-1") == std::string::npos) CTC_FAIL("score: a clip outside the batch passed");
+        }
+        // ---- refused on the numbers alone: no array exists
+        {
+            std::vector<int32_t> sz, tl, frames;
+            int L_max = 0;
+            const int32_t* none = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            if (align_check(none, 0, To, none, none, 3, C, blank, sz, tl, &L_max, err) != DSMI_ERR_INVALID) CTC_FAIL("align: B = 0");
+            if (align_check(none, B, -big, none, none, 3, C, blank, sz, tl, &L_max, err) != DSMI_ERR_INVALID) CTC_FAIL("align: T_out < 0");
+            if (align_check(none, B, To, none, none, -big, C, blank, sz, tl, &L_max, err) != DSMI_ERR_INVALID) CTC_FAIL("align: L_stride < 0");
+            if (align_check(none, B, To, none, none, DSMI_ALIGN_MAX_TOKENS + big, C, blank, sz, tl, &L_max, err) != DSMI_ERR_CAPACITY) CTC_FAIL("align: L_stride over the limit");
+            if (score_check(none, B, To, none, none, none, 0, 3, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_INVALID) CTC_FAIL("score: N = 0");
+            if (score_check(none, B, To, none, none, none, big, -1, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_INVALID) CTC_FAIL("score: L_stride < 0");
+            if (score_check(none, B, To, none, none, none, big, DSMI_SCORE_MAX_TOKENS + big, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_CAPACITY) CTC_FAIL("score: L_stride over the limit");
+            if (score_check(none, B, To, none, none, none, (1 << 24) / 2048 + big, 2048, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_CAPACITY ||
+                err.find("2^24") == std::string::npos) CTC_FAIL("score: N * L_stride over 2^24");
+            const float floor_ = -1.f;
+            if (spot_check(none, B, To, none, none, 0, 3, 4, floor_, C, blank, sz, err) != DSMI_ERR_INVALID) CTC_FAIL("spot: K = 0");
+            if (spot_check(none, B, To, none, none, 2, 3, rng() % 2 ? 0 : DSMI_SPOT_MAX_HITS + big, floor_, C, blank, sz, err) != DSMI_ERR_INVALID) CTC_FAIL("spot: max_hits");
+            if (spot_check(none, B, To, none, none, 2, 3, 4, std::nanf(""), C, blank, sz, err) != DSMI_ERR_INVALID) CTC_FAIL("spot: NaN floor");
+            if (spot_check(none, B, To, none, none, 2, DSMI_SPOT_MAX_TOKENS + big, 4, floor_, C, blank, sz, err) != DSMI_ERR_CAPACITY) CTC_FAIL("spot: L_stride over the limit");
+            if (spot_check(none, B, To, none, none, DSMI_SPOT_MAX_PHRASES + big, 3, 4, floor_, C, blank, sz, err) != DSMI_ERR_CAPACITY) CTC_FAIL("spot: K over the limit");
+            if (spot_check(none, 1 << 14, 4 + big, none, none, 1 << 12, 3, 4, floor_, C, blank, sz, err) != DSMI_ERR_CAPACITY) CTC_FAIL("spot: the track cap");
+            if (spot_check(none, 1, 1 << 26, none, none, 2 + big, 3, 4, floor_, C, blank, sz, err) != DSMI_ERR_CAPACITY) CTC_FAIL("spot: the track cap by T_out");
+        }
+        // ---- phrase search: the check, the plan and every packed word
+        {
+            const int K = 1 + (int)(rng() % 40), L_stride = 1 + (int)(rng() % (rng() % 4 ? 12 : DSMI_SPOT_MAX_TOKENS));
+            std::vector<int32_t> sizes = exact((size_t)B, To), lens = exact((size_t)K), ph = exact((size_t)K * L_stride), sz;
+            for (int k = 0; k < K; ++k) {
+                lens[(size_t)k] = 1 + (int32_t)(rng() % (unsigned)L_stride);
+                random_row(rng, ph.data() + (size_t)k * L_stride, lens[(size_t)k], C, blank, false);
+            }
+            if (spot_check(sizes.data(), B, To, ph.data(), lens.data(), K, L_stride, 1 + (int)(rng() % DSMI_SPOT_MAX_HITS), -INFINITY, C, blank, sz, err) != DSMI_OK) CTC_FAIL("spot: a good call refused");
+            std::vector<int32_t> group_of = exact((size_t)K, -7), first = exact((size_t)K, -7);
+            const int n_groups = spot_plan(lens.data(), K, group_of.data(), first.data());
+            std::vector<int> used((size_t)n_groups, 0);
+            for (int k = 0; k < K; ++k) {      // in order, back to back, a group never beyond kSpotThreads states, a new group only when needed
+                const int g = group_of[(size_t)k], S = 2 * lens[(size_t)k] - 1;
+                if (g < 0 || g >= n_groups || (k && g != group_of[(size_t)k - 1] && (g != group_of[(size_t)k - 1] + 1 || used[(size_t)g - 1] + S <= kSpotThreads))) CTC_FAIL("plan: groups out of order");
+                if (first[(size_t)k] != used[(size_t)g]) CTC_FAIL("plan: a gap or an overlap");
+                used[(size_t)g] += S;
+                if (used[(size_t)g] > kSpotThreads) CTC_FAIL("plan: a group beyond 256 states");
+            }
+            if (group_of[(size_t)K - 1] != n_groups - 1) CTC_FAIL("plan: the number of groups");
+            std::vector<int32_t> words = exact((size_t)n_groups * kSpotThreads), want = exact((size_t)n_groups * kSpotThreads);
+            spot_pack(ph.data(), lens.data(), K, L_stride, blank, group_of.data(), first.data(), words.data());
+            for (int k = 0; k < K; ++k) {
+                std::vector<int32_t> ext;      // token, blank, token, ..., token
+                for (int j = 0; j < lens[(size_t)k]; ++j) { if (j) ext.push_back(blank); ext.push_back(ph[(size_t)k * L_stride + j]); }
+                for (size_t s = 0; s < ext.size(); ++s) {
+                    const int32_t w = words[(size_t)group_of[(size_t)k] * kSpotThreads + first[(size_t)k] + s];
+                    const bool skip = s % 2 == 0 && s >= 2 && ext[s] != ext[s - 2], last = s + 1 == ext.size();
+                    if ((w & 255) != ext[s] || !(w & kSpotLive) || !!(w & kSpotSkip) != skip || !!(w & kSpotFirst) != (s == 0) || !!(w & kSpotLast) != last ||
+                        (w >> kSpotPhraseShift) != (last ? k : 0) || (w & 0xf000)) CTC_FAIL("pack: a word's label, flags or phrase index");
+                    want[(size_t)group_of[(size_t)k] * kSpotThreads + first[(size_t)k] + s] = w;
+                    ++words_checked;
+                }
+            }
+            if (words != want) CTC_FAIL("pack: a word where no state sits");
+        }
+    }
+    std::printf("%d ctc calls ok, %ld rows and %ld packed words checked\n", reps, rows_checked, words_checked);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "rnnplan")) return run_rnnplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "gate")) return run_gate(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]]\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]]\n");
     return 2;
 }

@@ -3,7 +3,7 @@
 raw encodings, branch-target labels and objdump's "..." padding marks, and compares function by function.  A template
 parameter added with a default changes mangled names only: --strip removes such a fragment from the names of the second file.
 
-    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DDSMI_BUILD -fvisibility=hidden --cuda-device-only -c decoder.hip -o x.co
+    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DDSMI_BUILD -fvisibility=hidden --cuda-device-only -c score.hip -o x.co
     clang-offload-bundler --unbundle --type=o --input=x.co --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=x.elf
     python tools/same_isa.py before.elf after.elf --strip ELb0E:E
 """
