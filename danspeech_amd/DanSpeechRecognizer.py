@@ -171,6 +171,30 @@ def _words(text, spans, token_probs, frame_s):
     return words
 
 
+def _confidences(chars, ids, post, labels, blank):
+    """Characters ``chars`` with label ids ``ids`` and their slot posteriors ``post`` [L, C] (``Decoder.confidence_ids``) ->
+    ``(words, char_rows)``: ``char_rows[k] = (char, confidence, alternative, alternative_confidence)``, the alternative being
+    the most probable other label of the slot ('' for no character there), and ``words = [(word, confidence)]``, a word
+    being a maximal run of non-space characters and its confidence the least of its characters'."""
+    rows = []
+    for k, ch in enumerate(chars):
+        others = post[k].copy()
+        others[int(ids[k])] = -1.0
+        c = int(np.argmax(others))
+        rows.append((ch, float(post[k, int(ids[k])]), "" if c == blank else labels[c], float(post[k, c])))
+    words, k = [], 0
+    while k < len(chars):
+        if chars[k] == " ":
+            k += 1
+            continue
+        j = k
+        while j < len(chars) and chars[j] != " ":
+            j += 1
+        words.append(("".join(chars[k:j]), min(r[1] for r in rows[k:j])))
+        k = j
+    return words, rows
+
+
 def _packed_upload(chunks, device):
     """uint8 arrays -> (one uint8 tensor on ``device`` that holds them all, where each starts): one host buffer of at least 8
     bytes in which every chunk starts on 8 bytes, one copy to the device."""
@@ -703,6 +727,53 @@ class DanSpeechRecognizer(object):
         results = [None] * job.count
         for pos, i in enumerate(job.order):
             results[i] = list(zip(strings[pos], logps[pos]))
+        return results
+
+    # ---- how sure is the model of each character and word (CTC token confidence) --------------------------------------
+    def confidence_batch(self, recordings, transcripts):
+        """How sure is the model of each character and word of ``transcripts[i]`` as the transcript of ``recordings[i]``, and
+        what else might it have heard there?  Per recording ``None`` when the transcript cannot fit the recording's frames,
+        else ``(words, chars)``: ``chars = [(char, confidence, alternative, alternative_confidence), ...]`` for every
+        character of the normalised transcript (``Decoder.normalise_transcript``), spaces included -- ``confidence`` the
+        posterior of the character against every other label and against no character in its place, given the rest of the
+        transcript and summed over every alignment (``dsmi_alternatives``, float64), ``alternative`` the most probable other
+        label ('' for no character) -- and ``words = [(word, confidence), ...]``, a word's confidence the least of its
+        characters'.  Every transcript is checked before any GPU work (``ValueError`` for characters that are not labels)."""
+        if self.model is None:
+            raise ModelNotInitialized("Trying to compute confidences without a DanSpeech model.")
+        if len(recordings) != len(transcripts):
+            raise ValueError("confidence_batch: %d recordings and %d transcripts" % (len(recordings), len(transcripts)))
+        texts = [self.decoder.normalise_transcript(t) for t in transcripts]
+        ids = [self.decoder.transcript_ids(t) for t in texts]
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        conf = self.decoder.confidence_ids(job.probs, [ids[i] for i in job.order], job.sizes)
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            if conf[pos] is not None:
+                results[i] = _confidences(list(texts[i]), ids[i], conf[pos][1], self.decoder.labels, self.decoder.blank_index)
+        return results
+
+    def confidence(self, recording, transcript):
+        """``confidence_batch`` of one recording."""
+        return self.confidence_batch([recording], [transcript])[0]
+
+    def transcribe_confident_batch(self, recordings):
+        """``transcribe_batch`` with the confidence of what was recognised, from one forward: per recording ``(text, words,
+        chars)``, the decoder's first hypothesis and, for its label sequence as it is, ``words`` and ``chars`` as
+        ``confidence_batch`` returns them."""
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        strings, ids, conf = self.decoder.decode_confident(job.probs, job.sizes)
+        labels, blank = self.decoder.labels, self.decoder.blank_index
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            words, chars = _confidences([labels[int(c)] for c in ids[pos]], ids[pos], conf[pos][1], labels, blank)      # (what was decoded from the frames fits them)
+            results[i] = (strings[pos], words, chars)
         return results
 
     # ---- long recordings and files ----------------------------------------------------------------------------------

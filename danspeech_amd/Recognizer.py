@@ -81,6 +81,21 @@ class Recognizer(object):
         decoder's first ``n_best`` hypotheses (``DanSpeechRecognizer.transcribe_scored_batch``)."""
         return self.danspeech_recognizer.transcribe_scored_batch(audio_list, n_best=n_best)
 
+    def confidence(self, audio_data, transcript):
+        """How sure the model is of each word and character of a transcript of ``audio_data``: ``(words, chars)`` with
+        ``words = [(word, confidence), ...]`` and ``chars = [(char, confidence, alternative, alternative_confidence), ...]``,
+        or ``None`` when the transcript cannot fit the audio (``DanSpeechRecognizer.confidence_batch``)."""
+        return self.danspeech_recognizer.confidence(audio_data, transcript)
+
+    def confidence_batch(self, audio_list, transcripts):
+        """``confidence`` for a list of clips in one batched pass over the GPU; results in the caller's order."""
+        return self.danspeech_recognizer.confidence_batch(audio_list, transcripts)
+
+    def recognize_confident(self, audio_list):
+        """``recognize_batch`` with the confidence of each recognised text: per clip ``(text, words, chars)``
+        (``DanSpeechRecognizer.transcribe_confident_batch``)."""
+        return self.danspeech_recognizer.transcribe_confident_batch(audio_list)
+
     def recognize_batches(self, batches, show_all=False):
         """Generator: ``recognize_batch`` over a sequence of batches, with the upload of the next batch and the
         decoding of the previous one overlapped with the GPU's work on the current one."""

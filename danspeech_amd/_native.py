@@ -33,6 +33,7 @@ SPOT_MAX_TOKENS = 128           # the longest phrase dsmi_spot takes (L_stride)
 SPOT_MAX_PHRASES = 4096         # phrases of one dsmi_spot call
 SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
 SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
+ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes (L_stride)
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -179,6 +180,7 @@ _PROTOS = {
     "dsmi_spot": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_score_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "dsmi_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1095,6 +1097,23 @@ class NativeDecoder(_Handle):
         self._check(lib().dsmi_score(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(clip), _np_ptr(tg),
                                      _np_ptr(target_lens), N, tg.shape[1], _np_ptr(lp), _np_ptr(st), _stream(self.device)))
         return lp, st
+
+    def alternatives(self, probs, sizes, cand_clip, targets, target_lens=None):
+        """CTC token confidence (``dsmi_alternatives``): for every token of every candidate, the exact float64 log likelihood
+        of the candidate with that token replaced by each label, or deleted (the blank's column).  Arguments as ``score``.
+        Returns numpy arrays (logp float64 [N], alt float64 [N, L_stride, C], status int32 [N]: 1 = infeasible, all -inf);
+        rows past a candidate's length are -inf."""
+        B, T = probs.shape[0], probs.shape[1]
+        clip = np.ascontiguousarray(cand_clip, dtype=np.int32).reshape(-1)
+        N = len(clip)
+        tg, target_lens = _padded_ids(targets, target_lens, N, 0, "alternatives: %d target sequences for %d candidates")
+        lp = np.zeros(N, dtype=np.float64)
+        alt = np.zeros((N, tg.shape[1], probs.shape[2]), dtype=np.float64)
+        st = np.zeros(N, dtype=np.int32)
+        self._check(lib().dsmi_alternatives(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(clip), _np_ptr(tg),
+                                            _np_ptr(target_lens), N, tg.shape[1], _np_ptr(lp), _np_ptr(alt), _np_ptr(st),
+                                            _stream(self.device)))
+        return lp, alt, st
 
 
 def _padded_ids(rows, lens, count, min_width, mismatch):

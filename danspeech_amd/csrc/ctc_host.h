@@ -1,4 +1,4 @@
-// The host half of the three CTC trellis tools (dsmi_align, dsmi_spot, dsmi_score: ctc_tools.hip): the checks of everything a
+// The host half of the four CTC trellis tools (dsmi_align, dsmi_spot, dsmi_score, dsmi_alternatives: ctc_tools.hip): the checks of everything a
 // caller hands in, the packing of phrases into workgroups and the launch order of candidates.  No HIP: a plain C++ compiler
 // takes it, and tools/asan/host_fuzz.cpp (ctccheck, scoreplan) runs it under ASan + UBSan on exactly sized arrays.  A check
 // returns DSMI_OK or a DSMI_ERR_* code with the message in `err`; what the numbers alone refuse is refused before any array is read.
@@ -79,6 +79,7 @@ struct CtcRows { const char *tool, *unit, *length, *id, *limit_name; int min_len
 constexpr CtcRows kAlignRows{"align", "clip", "target length", "target id", "DSMI_ALIGN_MAX_TOKENS", 0, DSMI_ALIGN_MAX_TOKENS};
 constexpr CtcRows kSpotRows{"spot", "phrase", "length", "token id", "DSMI_SPOT_MAX_TOKENS", 1, DSMI_SPOT_MAX_TOKENS};
 constexpr CtcRows kScoreRows{"score", "candidate", "target length", "target id", "DSMI_SCORE_MAX_TOKENS", 0, DSMI_SCORE_MAX_TOKENS};
+constexpr CtcRows kAltRows{"alternatives", "candidate", "target length", "target id", "DSMI_ALT_MAX_TOKENS", 0, DSMI_ALT_MAX_TOKENS};
 
 inline int ctc_refuse(std::string& err, int code, const std::string& msg) { err = msg; return code; }
 // L_stride against the tool's limit (on the number alone)
@@ -173,6 +174,50 @@ inline int score_check(const int32_t* sizes, int B, int To, const int32_t* cand_
         tl[n] = ctc_feasible_len(target_lens[n], repeats, sz[b]);
         *L_max = std::max(*L_max, (int)tl[n]);
     }
+    return DSMI_OK;
+}
+
+// ---- token confidence: where each candidate's stored trellises lie.  A feasible candidate with T > 0 frames and L tokens takes
+// T * (2L + 1) elements from base[n], in the order of the candidates (every other candidate: base[n] = the running total, nothing
+// taken).  tl [N] as the checks leave it.  Returns the total.
+inline uint64_t alt_place(const int32_t* tl, const int32_t* frames, int N, int32_t* base) {
+    uint64_t total = 0;
+    for (int n = 0; n < N; ++n) {
+        if (base) base[n] = (int32_t)std::min<uint64_t>(total, INT32_MAX);
+        if (tl[n] >= 0) total += (uint64_t)frames[n] * (2 * (uint64_t)tl[n] + 1);
+    }
+    return total;
+}
+constexpr uint64_t kAltOutCap = (uint64_t)1 << 24;       // N * L_stride * n_labels: the results, on the handle and copied back
+constexpr uint64_t kAltTrellisCap = (uint64_t)1 << 25;   // elements of one stored trellis over all candidates of a call
+
+// sz [B], tl [N] (-1: infeasible), frames [N], base [N] (alt_place), *L_max = the longest feasible candidate, *trellis = alt_place's total
+inline int alt_check(const int32_t* sizes, int B, int To, const int32_t* cand_clip, const int32_t* targets, const int32_t* target_lens,
+                     int N, int L_stride, int C, int blank, std::vector<int32_t>& sz, std::vector<int32_t>& tl,
+                     std::vector<int32_t>& frames, std::vector<int32_t>& base, int* L_max, uint64_t* trellis, std::string& err) {
+    if (B <= 0 || To <= 0 || N <= 0) return ctc_refuse(err, DSMI_ERR_INVALID, "alternatives: B, T_out and N must be positive");
+    if (L_stride < 0) return ctc_refuse(err, DSMI_ERR_INVALID, "alternatives: negative L_stride");
+    if (int rc = ctc_check_stride(kAltRows, L_stride, err)) return rc;
+    if ((uint64_t)N * (uint64_t)L_stride * (uint64_t)C > kAltOutCap)
+        return ctc_refuse(err, DSMI_ERR_CAPACITY, "alternatives: N * L_stride * n_labels exceeds 2^24 (the results)");
+    if ((uint64_t)N * (uint64_t)L_stride > kAltOutCap) return ctc_refuse(err, DSMI_ERR_CAPACITY, "alternatives: N * L_stride exceeds 2^24");
+    sz.assign((size_t)B, 0); tl.assign((size_t)N, 0); frames.assign((size_t)N, 0);
+    if (int rc = ctc_check_sizes(kAltRows, sizes, B, To, sz.data(), err)) return rc;
+    *L_max = 0;
+    for (int n = 0; n < N; ++n) {
+        const int b = cand_clip[n];
+        if (b < 0 || b >= B) return ctc_refuse(err, DSMI_ERR_INVALID, "alternatives: candidate " + std::to_string(n) + ": clip outside 0 .. B-1");
+        int repeats = 0;
+        if (int rc = ctc_check_row(kAltRows, n, targets + (size_t)n * L_stride, target_lens[n], L_stride, C, blank, &repeats, err)) return rc;
+        frames[n] = sz[b];
+        tl[n] = ctc_feasible_len(target_lens[n], repeats, sz[b]);
+        *L_max = std::max(*L_max, (int)tl[n]);
+    }
+    *trellis = alt_place(tl.data(), frames.data(), N, nullptr);
+    if (*trellis > kAltTrellisCap)
+        return ctc_refuse(err, DSMI_ERR_CAPACITY, "alternatives: the stored trellises, the sum of frames * (2 * length + 1) over the candidates, exceed 2^25 elements (" + std::to_string(*trellis) + ")");
+    base.assign((size_t)N, 0);
+    alt_place(tl.data(), frames.data(), N, base.data());
     return DSMI_OK;
 }
 

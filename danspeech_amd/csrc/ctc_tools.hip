@@ -1,5 +1,6 @@
-// The three tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
-// (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip) and transcript scoring (dsmi_score; score.hip).
+// The four tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
+// (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip) and
+// token confidence (dsmi_alternatives; alt.hip).
 // Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
 // before any output write), grows its workspaces, uploads, launches and copies the results back.  A clip or candidate whose
 // transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
@@ -7,6 +8,7 @@
 #include "align.h"
 #include "spot.h"
 #include "score.h"
+#include "alt.h"
 
 #include <cmath>
 #include <cstring>
@@ -15,11 +17,13 @@ using namespace dsmi;
 
 // The workspaces of one call: nothing happens when every capacity suffices; otherwise ONE device synchronise (a launch in flight
 // may still read a buffer that is about to be freed), then each buffer that is too small is replaced.
-static int reserve_all(dsmi_decoder* d, DevBuf& a, size_t a_bytes, DevBuf* b = nullptr, size_t b_bytes = 0) {
-    if (a.holds(a_bytes) && (!b || b->holds(b_bytes))) return DSMI_OK;
+static int reserve_all(dsmi_decoder* d, DevBuf& a, size_t a_bytes, DevBuf* b = nullptr, size_t b_bytes = 0, DevBuf* c = nullptr,
+                       size_t c_bytes = 0) {
+    if (a.holds(a_bytes) && (!b || b->holds(b_bytes)) && (!c || c->holds(c_bytes))) return DSMI_OK;
     DEC_HIP(d, hipDeviceSynchronize());
     DEC_HIP(d, a.reserve(a_bytes));
     if (b) DEC_HIP(d, b->reserve(b_bytes));
+    if (c) DEC_HIP(d, c->reserve(c_bytes));
     return DSMI_OK;
 }
 
@@ -158,6 +162,60 @@ extern "C" int dsmi_score(dsmi_decoder* d, const float* probs, const int32_t* si
     for (int n = 0; n < N; ++n) {
         status[n] = tl[n] < 0 ? 1 : 0;
         logp[n] = tl[n] < 0 ? -INFINITY : out[n];
+    }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_alternatives(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* cand_clip,
+                                 const int32_t* targets, const int32_t* target_lens, int N, int L_stride, double* logp,
+                                 double* alt_logp, int32_t* status, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !cand_clip || !target_lens || !logp || !status || (L_stride > 0 && (!targets || !alt_logp))) {
+        d->err = "bad alternatives arguments"; return DSMI_ERR_INVALID;
+    }
+    std::vector<int32_t> sz, tl, frames, base;
+    int L_max = 0;
+    uint64_t trellis = 0;
+    if (int rc = alt_check(sizes, B, To, cand_clip, targets, target_lens, N, L_stride, C, d->blank, sz, tl, frames, base, &L_max, &trellis, d->err)) return rc;
+    std::vector<int32_t> order(N);
+    score_plan(cand_clip, frames.data(), target_lens, N, order.data());
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- the workspaces: sizes [B], order [N], clips [N], lens [N], bases [N], targets [N][L], then logp [N] doubles; the results
+    // [N][L][C]; the stored trellises: forward pairs and backward of `trellis` elements each, the backward pair sums of half as many
+    const size_t NL = (size_t)N * L_stride, NLC = NL * C, in_words = ((size_t)B + 4 * (size_t)N + NL + 1) & ~(size_t)1;
+    const size_t ws_elems = 2 * (size_t)trellis + (size_t)trellis / 2 + 1;
+    if (int rc = reserve_all(d, d->alt_io, sizeof(int32_t) * (in_words + 2 * (size_t)N), &d->alt_out, sizeof(double) * NLC, &d->alt_ws,
+                             sizeof(double) * ws_elems)) return rc;
+    int32_t* w_sz = d->alt_io.as<int32_t>(); int32_t* w_or = w_sz + B; int32_t* w_cl = w_or + N; int32_t* w_tl = w_cl + N;
+    int32_t* w_ba = w_tl + N; int32_t* w_tg = w_ba + N;
+    double* w_lp = reinterpret_cast<double*>(w_sz + in_words);
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_or, order.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_cl, cand_clip, sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_ba, base.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    if (NL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * NL, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_lp, 0, sizeof(double) * N, s));
+    AltArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w_sz; a.order = w_or; a.cand_clip = w_cl; a.tlen = w_tl; a.targets = w_tg; a.base = w_ba; a.L_stride = L_stride;
+    a.S_max = 2 * L_max + 1; a.n_blocks = (L_max * C + kAltThreads - 1) / kAltThreads;
+    a.fwd = d->alt_ws.as<double>(); a.bwd = a.fwd + trellis; a.bwd_pair = a.bwd + trellis;
+    a.logp = w_lp; a.alt = d->alt_out.as<double>();
+    DEC_HIP(d, launch_alt(a, N, s));
+    // the results come back into images of the call's own and reach the caller's arrays only when everything has succeeded
+    std::vector<double> out(N), rows(NLC);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_lp, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    if (NLC) DEC_HIP(d, hipMemcpyAsync(rows.data(), a.alt, sizeof(double) * NLC, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    for (int n = 0; n < N; ++n) {
+        status[n] = tl[n] < 0 ? 1 : 0;
+        logp[n] = tl[n] < 0 ? -INFINITY : out[n];
+        const size_t written = tl[n] < 0 ? 0 : (size_t)tl[n] * C, row = (size_t)L_stride * C;      // (the kernel writes rows k < length)
+        double* dst = alt_logp ? alt_logp + (size_t)n * row : nullptr;
+        for (size_t i = 0; i < row; ++i) dst[i] = i < written ? rows[(size_t)n * row + i] : -INFINITY;
     }
     return DSMI_OK;
 }

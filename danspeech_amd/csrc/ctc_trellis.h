@@ -63,6 +63,52 @@ struct CtcFeeder {
     }
 };
 
+// The same feeder for a kernel that walks the frames from T - 1 down to 0 (the backward pass of alt.hip): the chunks travel in
+// descending order, the last one first, and the chunk that is r chunks from the end sits in lpc[r & 1].  A struct of its own with
+// its own copies of P, T, C and tid, so that CtcFeeder and the three kernels built on it stay as they are.
+template <typename LP, int NT>
+struct CtcFeederDown {
+    static constexpr int kImage = kCtcChunk * kCtcMaxLabels;
+    static constexpr int PER = kImage / NT;
+    static_assert(kImage % NT == 0, "every thread moves the same number of values");
+    const float* P;
+    const int T, C, tid, CF, last;      // last = the chunk of frame T - 1
+    float pr[PER];
+
+    __device__ __forceinline__ CtcFeederDown(const float* clip_probs, int frames, int labels, int thread)
+        : P(clip_probs), T(frames), C(labels), tid(thread), CF(kCtcChunk * labels), last((frames - 1) / kCtcChunk) {}
+
+    __device__ __forceinline__ void fetch(int chunk) {           // (chunks before the first, frames past the clip's: p = 1, nothing is read)
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = tid + j * NT, f = chunk * kCtcChunk + i / C;
+            pr[j] = chunk >= 0 && i < CF && f < T ? P[(size_t)chunk * CF + i] : 1.f;
+        }
+    }
+    __device__ __forceinline__ void store(LP (*lpc)[kImage], int chunk) const {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = tid + j * NT;
+            if (i < CF) {
+                if constexpr (std::is_same_v<LP, double>) lpc[(last - chunk) & 1][i] = log((double)fmaxf(pr[j], FLT_MIN));
+                else lpc[(last - chunk) & 1][i] = logf(fmaxf(pr[j], FLT_MIN));
+            }
+        }
+    }
+    // before frame T - 1: the last chunk in LDS (behind the caller's next barrier), the one before it on its way
+    __device__ __forceinline__ void prologue(LP (*lpc)[kImage]) { fetch(last); store(lpc, last); fetch(last - 1); }
+    // lp of frame t, [label]
+    __device__ __forceinline__ const LP* frame(LP (*lpc)[kImage], int t) const { return lpc[(last - t / kCtcChunk) & 1] + (t % kCtcChunk) * C; }
+    // behind frame t's work, before its barrier: at the first frame of a chunk the lp of the chunk below, then the load of the one below that
+    __device__ __forceinline__ void end_of_frame(LP (*lpc)[kImage], int t) {
+        if (t % kCtcChunk == 0 && t > 0) {
+            const int next = t / kCtcChunk - 1;
+            store(lpc, next);
+            fetch(next - 1);
+        }
+    }
+};
+
 // The extended sequence of a transcript tg[0 .. L): S = 2L + 1 states, blank, t_1, blank, ..., blank.  lsk[s] = the state's label
 // | (a token state whose label differs from the token before: s-2 competes) << 8, and the two -inf guards in front of each alpha
 // row, so that s-1 and s-2 are always readable.  (tid by reference as in the feeder: by value the guards' code came out otherwise)

@@ -63,6 +63,9 @@ struct dsmi_decoder {
     DevBuf sp_io, sp_tr;
     // dsmi_score: inputs of the launch (int32 words) and, behind them on 8 bytes, the results [N] doubles
     DevBuf sc_io;
+    // dsmi_alternatives: inputs of the launch and logp [N] as dsmi_score's, the results [N][L_stride][n_labels] doubles, the
+    // stored trellises (doubles: forward pairs, backward, backward pair sums)
+    DevBuf alt_io, alt_out, alt_ws;
 };
 
 #define DEC_HIP(d, expr)                                                                  \

@@ -186,6 +186,47 @@ class Decoder(object):
             n += len(cands)
         return out
 
+    # ---- CTC token confidence (dsmi_alternatives): how sure is the model of each token, and what else might it have heard
+    def confidence(self, probs, transcripts, sizes=None):
+        """The posterior of every token of ``transcripts[b]`` (normalised with ``normalise_transcript``) against its
+        alternatives, over the probabilities of clip b (``probs`` [B,T,C], ``sizes`` frames per clip).  Per clip ``None`` when
+        the transcript cannot fit the clip's frames, else ``(logp, post)``: the natural log of the transcript's likelihood
+        summed over every alignment, and float64 [L, C] with ``post[k, c]`` the probability of label c in place of character
+        k given the rest of the transcript -- the blank's column is "no character here", ``post[k, ids[k]]`` the confidence
+        of the character itself, each row sums to 1."""
+        ids = [self.transcript_ids(self.normalise_transcript(t)) for t in transcripts]      # every check before any GPU work
+        return self.confidence_ids(probs, ids, sizes)
+
+    def confidence_ids(self, probs, ids, sizes=None):
+        """``confidence`` for label-id sequences as they are (no normalisation): ``ids[b]`` one id sequence for clip b."""
+        import torch
+        from .. import _native
+        if len(ids) != len(probs):
+            raise ValueError("confidence: transcripts for %d clips and a batch of %d" % (len(ids), len(probs)))
+        longest = max([len(t) for t in ids] + [0])
+        if longest > _native.ALT_MAX_TOKENS:
+            raise ValueError("transcript of %d labels is longer than %d" % (longest, _native.ALT_MAX_TOKENS))
+        if not len(ids):
+            return []
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        lp, alt, status = dec.alternatives(probs, sz, np.arange(len(ids)), ids)
+        out = []
+        for b, t in enumerate(ids):
+            if status[b]:
+                out.append(None)
+                continue
+            rows = alt[b, :len(t)]
+            out.append((float(lp[b]), np.exp(rows - np.logaddexp.reduce(rows, axis=1, keepdims=True))))
+        return out
+
+    def decode_confident(self, probs, sizes=None):
+        """``decode`` and the token confidences of each clip's first hypothesis over the same (still resident) probabilities:
+        ``(strings [B], ids [B], confidences [B])``, ``confidences[b]`` as ``confidence_ids`` returns it."""
+        strings, _, ids = self._decode_best_ids(probs, sizes)
+        return strings, ids, self.confidence_ids(probs, ids, sizes)
+
 
 class GreedyDecoder(Decoder):
     """decoder.py:147-198: argmax per frame, collapse repeats, drop blanks; one path per utterance."""
@@ -214,6 +255,15 @@ class GreedyDecoder(Decoder):
         strings = [[self._to_string(ids)] for ids, _ in res]
         offsets = [[torch.from_numpy(off.astype(np.int32))] for _, off in res]
         return strings, offsets, self.score_ids(probs, [[ids] for ids, _ in res], sizes)
+
+    def _decode_best_ids(self, probs, sizes=None):
+        """(the text of each clip, None, its label ids)"""
+        import torch
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        res = dec.greedy(probs, sz)
+        return [self._to_string(ids) for ids, _ in res], None, [np.asarray(ids, dtype=np.int32) for ids, _ in res]
 
     # the same in two halves for the batch pipeline (DanSpeechRecognizer.transcribe_batches): the kernel and the copies of its
     # results are queued right behind the forward, on the forward's own stream (on_lane: no side stream), `slot` = one native
@@ -306,6 +356,14 @@ class BeamCTCDecoder(Decoder):
         strings, offsets = self._beam_strings(tok, ts, ln)
         ids = [[tok[b, p, :ln[b, p]] for p in range(W)] for b in range(tok.shape[0])]
         return strings, offsets, self.score_ids(probs, ids, sizes)
+
+    def _decode_best_ids(self, probs, sizes=None):
+        """(the first beam's text of each clip, None, its label ids)"""
+        probs = self._on_gpu(probs)
+        tok, ts, ln, sc = self.decode_enqueue(probs, sizes).beam_collect()
+        self.last_scores = sc
+        strings, _ = self._beam_strings(tok[:, :1], ts[:, :1], ln[:, :1])
+        return [s[0] for s in strings], None, [np.asarray(tok[b, 0, :ln[b, 0]], dtype=np.int32) for b in range(tok.shape[0])]
 
     def _beam_strings(self, tok, ts, ln):
         import torch

@@ -632,6 +632,36 @@ int dsmi_score(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_hos
                const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host, int N, int L_stride,
                double* logp_host, int32_t* status_host, void* stream);
 
+/* ---- CTC token confidence (no reference counterpart): how sure is the model of THIS token, and what was the runner-up?  For
+ * every token of a candidate transcript, the likelihood of the transcript with that token replaced by each other label, or
+ * deleted -- all of them from one forward-backward pass, where dsmi_score would need one candidate per edit.
+ * probs_dev, sizes_host, cand_clip_host, targets_host, target_lens_host, N and L_stride are dsmi_score's.  Candidate n is a
+ * transcript y of L tokens on clip b with T frames.  It has L slots; slot k and label c define a variant transcript:
+ *     c != blank:  y with token k replaced by c (c = y_k: y itself);
+ *     c  = blank:  y with token k deleted.
+ * alt_logp[n][k][c] is the natural log of the probability that the model emits exactly the variant: what dsmi_score's
+ * recurrence defines for it (float64, lp = log((double)fmaxf(p, FLT_MIN)), the same states, skip rule and end rule), and -inf
+ * where the variant cannot fit the frames (dsmi_align's feasibility rule applied to the variant).  logp[n] is the same for y.
+ * exp(alt_logp[n][k][c] - logsumexp_c' alt_logp[n][k][c']) is the posterior of label c in slot k given the rest of y, the
+ * blank column being "no token here".  Insertions (a token y lacks) are not covered.
+ * The result is specified as a value with a bound, not bit for bit: |value - the recurrence evaluated exactly on the variant|
+ * <= 24 * T * 2^-52 * max(1, |value|), three times dsmi_score's, because a result passes through at most three chained float64
+ * recurrences of T steps (the forward pass, the backward pass, the slot's own chain), each non-expansive.  It is deterministic
+ * and batch-invariant: a candidate's logp and alt_logp rows are bit-identical whatever else is in the call.  Frames past
+ * sizes[b] are never read.
+ * Outputs: logp_host [N]; alt_logp_host [N][L_stride][n_labels], rows k >= target_lens[n] are -inf; status_host [N] = 0
+ * scored, 1 infeasible (then logp = -inf, every alt_logp row -inf, and nothing is computed for the candidate).  0 tokens is
+ * legal (no slots, logp as dsmi_score); with 0 frames the empty transcript has logp = 0 and every other candidate is infeasible.
+ * Refused before any launch with nothing written: DSMI_ERR_INVALID for everything dsmi_score refuses (alt_logp_host may be NULL
+ * only when L_stride == 0); DSMI_ERR_CAPACITY for L_stride > DSMI_ALT_MAX_TOKENS, N * L_stride * n_labels > 2^24 (the
+ * results), or a stored trellis -- the sum over the feasible candidates of frames * (2 * length + 1) -- above 2^25 elements
+ * (the workspace holds two and a half of them in float64, kept on the handle).  Two kernel launches whatever N.
+ * Synchronises `stream`. */
+#define DSMI_ALT_MAX_TOKENS 1024
+int dsmi_alternatives(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+                      const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host,
+                      int N, int L_stride, double* logp_host, double* alt_logp_host, int32_t* status_host, void* stream);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off

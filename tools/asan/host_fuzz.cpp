@@ -10,7 +10,7 @@
 //                             random sequences of planned launches of models of different widths, checked against the invariants below
 //   host_fuzz scoreplan SEED N  the launch order of CTC transcript scoring (ctc_host.h: score_plan) on N random candidate lists with many
 //                             ties: a permutation, every neighbouring pair in the documented order, nothing written past order[N)
-//   host_fuzz ctccheck SEED N   the argument checks and the phrase packing of dsmi_align / dsmi_spot / dsmi_score (ctc_host.h) on N random
+//   host_fuzz ctccheck SEED N   the argument checks and the phrase packing of dsmi_align / dsmi_spot / dsmi_score / dsmi_alternatives (ctc_host.h) on N random
 //                             calls held in exactly sized heap arrays, against the definitions written out below; what is refused
 //                             on the numbers alone is called with null arrays
 #define __host__
@@ -491,6 +491,20 @@ static int run_ctccheck(int argc, char** argv) {
                 want_max = std::max(want_max, want);
             }
             if (sz != sizes || L_max != want_max || (int)tl.size() != N) CTC_FAIL("score: sizes or the longest candidate");
+            // the same call through the token-confidence check: the same verdicts, and trellises placed back to back
+            {
+                std::vector<int32_t> sz2, tl2, frames2, base;
+                int L_max2 = -7;
+                uint64_t trellis = 7;
+                if (alt_check(sizes.data(), B, To, clip.data(), ptr_or_null(tg), lens.data(), N, L_stride, C, blank, sz2, tl2, frames2, base, &L_max2, &trellis, err) != DSMI_OK) CTC_FAIL("alternatives: a good call refused");
+                if (sz2 != sz || tl2 != tl || frames2 != frames || L_max2 != L_max || (int)base.size() != N) CTC_FAIL("alternatives: not score's verdicts");
+                uint64_t at = 0;
+                for (int n = 0; n < N; ++n) {
+                    if ((uint64_t)base[(size_t)n] != at) CTC_FAIL("alternatives: a trellis out of place");
+                    if (tl[(size_t)n] >= 0) at += (uint64_t)frames[(size_t)n] * (2 * (uint64_t)tl[(size_t)n] + 1);
+                }
+                if (trellis != at) CTC_FAIL("alternatives: the trellis total");
+            }
             // the same rows as one transcript per clip (the first B of them, N >= B or not)
             const int Ba = std::min(B, N);
             if (align_check(sizes.data(), Ba, To, ptr_or_null(tg), lens.data(), L_stride, C, blank, sz, tl, &L_max, err) != DSMI_OK) CTC_FAIL("align: a good call refused");
@@ -521,6 +535,16 @@ static int run_ctccheck(int argc, char** argv) {
             if (score_check(none, B, To, none, none, none, big, DSMI_SCORE_MAX_TOKENS + big, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_CAPACITY) CTC_FAIL("score: L_stride over the limit");
             if (score_check(none, B, To, none, none, none, (1 << 24) / 2048 + big, 2048, C, blank, sz, tl, frames, &L_max, err) != DSMI_ERR_CAPACITY ||
                 err.find("2^24") == std::string::npos) CTC_FAIL("score: N * L_stride over 2^24");
+            {
+                std::vector<int32_t> base;
+                uint64_t trellis = 0;
+                if (alt_check(none, B, To, none, none, none, 0, 3, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_INVALID) CTC_FAIL("alternatives: N = 0");
+                if (alt_check(none, B, To, none, none, none, big, -1, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_INVALID) CTC_FAIL("alternatives: L_stride < 0");
+                if (alt_check(none, B, To, none, none, none, big, DSMI_ALT_MAX_TOKENS + big, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_CAPACITY ||
+                    err.find("DSMI_ALT_MAX_TOKENS") == std::string::npos) CTC_FAIL("alternatives: L_stride over the limit");
+                if (alt_check(none, B, To, none, none, none, (1 << 24) / (1024 * C) + big, 1024, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_CAPACITY ||
+                    err.find("2^24") == std::string::npos) CTC_FAIL("alternatives: N * L_stride * n_labels over 2^24");
+            }
             const float floor_ = -1.f;
             if (spot_check(none, B, To, none, none, 0, 3, 4, floor_, C, blank, sz, err) != DSMI_ERR_INVALID) CTC_FAIL("spot: K = 0");
             if (spot_check(none, B, To, none, none, 2, 3, rng() % 2 ? 0 : DSMI_SPOT_MAX_HITS + big, floor_, C, blank, sz, err) != DSMI_ERR_INVALID) CTC_FAIL("spot: max_hits");
