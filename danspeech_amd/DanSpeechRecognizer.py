@@ -729,6 +729,40 @@ class DanSpeechRecognizer(object):
             results[i] = list(zip(strings[pos], logps[pos]))
         return results
 
+    # ---- the least expected error among the hypotheses, and the errors against known transcripts (batched edit distance) ----
+    def transcribe_min_risk_batch(self, recordings, n_best=8, unit="word"):
+        """``transcribe_scored_batch`` in minimum-Bayes-risk order: per recording ``[(text, risk, logp), ...]``, the decoder's
+        first ``n_best`` hypotheses by ascending ``risk``, the expected number of ``unit`` ("word" or "char") errors of the
+        hypothesis under the acoustic posteriors ``exp(logp)`` of the list (``Decoder.min_risk``; the language model has no
+        part in the weights).  The first text is the one to take when the error rate matters more than the exact text."""
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        strings, _, risks, logps = self.decoder.decode_min_risk(job.probs, job.sizes, n_best, unit)
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            results[i] = list(zip(strings[pos], risks[pos], logps[pos]))
+        return results
+
+    def evaluate_batch(self, recordings, transcripts):
+        """Recognise ``recordings`` and compare with their known ``transcripts`` (normalised with
+        ``Decoder.normalise_transcript``): a dict of ``texts``, the corpus rates ``wer`` and ``cer`` (summed distances over
+        summed reference lengths; ``None`` where the transcripts hold no token), ``word_counts`` / ``char_counts`` (int32
+        [N, 4]: distance, substitutions, deletions, insertions per recording) and ``word_ref_lens`` / ``char_ref_lens``.  One
+        recognition and two ``dsmi_edit_distance`` calls."""
+        if len(recordings) != len(transcripts):
+            raise ValueError("evaluate_batch: %d recordings and %d transcripts" % (len(recordings), len(transcripts)))
+        refs = [self.decoder.normalise_transcript(t) for t in transcripts]
+        texts = list(self.transcribe_batch(recordings)) if len(recordings) else []
+        out = {"texts": texts}
+        for unit, name in (("word", "wer"), ("char", "cer")):
+            counts, ref_lens = self.decoder.error_counts(refs, texts, unit)
+            total = int(ref_lens.sum())
+            out[name] = int(counts[:, 0].sum()) / total if total else None
+            out[unit + "_counts"], out[unit + "_ref_lens"] = counts, ref_lens
+        return out
+
     # ---- how sure is the model of each character and word (CTC token confidence) --------------------------------------
     def confidence_batch(self, recordings, transcripts):
         """How sure is the model of each character and word of ``transcripts[i]`` as the transcript of ``recordings[i]``, and

@@ -81,6 +81,18 @@ class Recognizer(object):
         decoder's first ``n_best`` hypotheses (``DanSpeechRecognizer.transcribe_scored_batch``)."""
         return self.danspeech_recognizer.transcribe_scored_batch(audio_list, n_best=n_best)
 
+    def recognize_min_risk(self, audio_list, n_best=8, unit="word"):
+        """``recognize_scored`` in minimum-Bayes-risk order: per clip ``[(text, risk, logp), ...]``, the decoder's first
+        ``n_best`` hypotheses by ascending expected ``unit`` ("word" or "char") errors under the acoustic posteriors of the
+        list (``DanSpeechRecognizer.transcribe_min_risk_batch``)."""
+        return self.danspeech_recognizer.transcribe_min_risk_batch(audio_list, n_best=n_best, unit=unit)
+
+    def evaluate(self, audio_list, transcripts):
+        """Recognise the clips and compare with their known transcripts: a dict of ``texts``, the corpus ``wer`` and ``cer``,
+        ``word_counts`` / ``char_counts`` (per clip: distance, substitutions, deletions, insertions) and ``word_ref_lens`` /
+        ``char_ref_lens`` (``DanSpeechRecognizer.evaluate_batch``)."""
+        return self.danspeech_recognizer.evaluate_batch(audio_list, transcripts)
+
     def confidence(self, audio_data, transcript):
         """How sure the model is of each word and character of a transcript of ``audio_data``: ``(words, chars)`` with
         ``words = [(word, confidence), ...]`` and ``chars = [(char, confidence, alternative, alternative_confidence), ...]``,

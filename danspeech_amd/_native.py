@@ -34,6 +34,7 @@ SPOT_MAX_PHRASES = 4096         # phrases of one dsmi_spot call
 SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
 SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
 ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes (L_stride)
+EDIT_MAX_TOKENS = 4096          # the longest sequence dsmi_edit_distance takes (L_stride)
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -181,6 +182,8 @@ _PROTOS = {
     "dsmi_score_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "dsmi_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "dsmi_edit_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "dsmi_edit_distance": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1115,6 +1118,22 @@ class NativeDecoder(_Handle):
                                             _stream(self.device)))
         return lp, alt, st
 
+    def edit_distance(self, seqs, pairs, seq_lens=None):
+        """Batched edit distance (``dsmi_edit_distance``).  seqs: the pool, an int array [M, L_stride] with ``seq_lens`` [M],
+        or a list of M id sequences (``seq_lens`` None); tokens are any int32.  pairs: int [N, 2], row n = (a, b) compares
+        pool sequence a (the reference) with pool sequence b (the hypothesis).  Returns int32 [N, 4]: distance,
+        substitutions, deletions, insertions of the minimum-distance alignment with the fewest substitutions."""
+        if seq_lens is not None and np.size(seqs) == 0:        # (a pool of empty sequences: no column to infer the rows from)
+            pool, seq_lens = np.zeros((len(seq_lens), 0), dtype=np.int32), np.ascontiguousarray(seq_lens, dtype=np.int32)
+        else:
+            pool, seq_lens = _padded_ids(seqs, seq_lens, None if seq_lens is None else len(seq_lens), 0, None)
+        pr =np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        counts = np.zeros((len(pr), 4), dtype=np.int32)
+        self._check(lib().dsmi_edit_distance(self._h, _np_ptr(pool) if pool.size else None, _np_ptr(seq_lens), pool.shape[0], pool.shape[1],
+                                             _np_ptr(pa), _np_ptr(pb), len(pr), _np_ptr(counts), _stream(self.device)))
+        return counts
+
 
 def _padded_ids(rows, lens, count, min_width, mismatch):
     """The token rows of dsmi_align / dsmi_spot / dsmi_score as a contiguous int32 [count, L_stride] array and its int32 lens:
@@ -1159,6 +1178,21 @@ def score_plan(cand_clip, cand_frames, target_lens):
     if rc < 0:
         raise DsmiError(rc, "dsmi_score_plan: at least one candidate, no negative entry")
     return order
+
+
+def edit_plan(len_a, len_b):
+    """dsmi_edit_plan (host only): (order, seg) for pairs of these token counts -- seg[n] the lane segment (16, 32 or 64) of
+    pair n, order the launch order of the pairs with both lengths > 0, as dsmi_edit_distance launches them."""
+    la = np.ascontiguousarray(len_a, dtype=np.int32).reshape(-1)
+    lb = np.ascontiguousarray(len_b, dtype=np.int32).reshape(-1)
+    if len(la) != len(lb):
+        raise ValueError("edit_plan: one length of a and one of b per pair")
+    order = np.zeros(len(la), dtype=np.int32)
+    seg = np.zeros(len(la), dtype=np.int32)
+    rc = lib().dsmi_edit_plan(_np_ptr(la), _np_ptr(lb), len(la), _np_ptr(order), _np_ptr(seg))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_edit_plan: at least one pair, no negative length")
+    return order[:rc].copy(), seg
 
 
 class NativeBeamStream(_Handle):

@@ -1,6 +1,7 @@
 // The four tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
 // (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip) and
-// token confidence (dsmi_alternatives; alt.hip).
+// token confidence (dsmi_alternatives; alt.hip) -- and, on the same handle and by the same conventions, the batched edit distance
+// of token sequences (dsmi_edit_distance; edit.hip), which needs no probabilities.
 // Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
 // before any output write), grows its workspaces, uploads, launches and copies the results back.  A clip or candidate whose
 // transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
@@ -9,6 +10,7 @@
 #include "spot.h"
 #include "score.h"
 #include "alt.h"
+#include "edit.h"
 
 #include <cmath>
 #include <cstring>
@@ -217,5 +219,40 @@ extern "C" int dsmi_alternatives(dsmi_decoder* d, const float* probs, const int3
         double* dst = alt_logp ? alt_logp + (size_t)n * row : nullptr;
         for (size_t i = 0; i < row; ++i) dst[i] = i < written ? rows[(size_t)n * row + i] : -INFINITY;
     }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_edit_plan(const int32_t* len_a, const int32_t* len_b, int N, int32_t* order, int32_t* seg) {
+    if (!len_a || !len_b || !order || !seg || N <= 0) return DSMI_ERR_INVALID;
+    for (int n = 0; n < N; ++n)
+        if (len_a[n] < 0 || len_b[n] < 0) return DSMI_ERR_INVALID;
+    return edit_plan(len_a, len_b, N, order, seg);
+}
+
+extern "C" int dsmi_edit_distance(dsmi_decoder* d, const int32_t* seqs, const int32_t* seq_lens, int M, int L_stride, const int32_t* pair_a,
+                                  const int32_t* pair_b, int N, int32_t* counts, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    if (!seq_lens || !pair_a || !pair_b || !counts || (L_stride > 0 && !seqs)) { d->err = "bad edit arguments"; return DSMI_ERR_INVALID; }
+    if (int rc = edit_check(seq_lens, M, L_stride, pair_a, pair_b, N, d->err)) return rc;
+    EditLaunch L;
+    edit_pack(seqs, seq_lens, M, L_stride, pair_a, pair_b, N, L);
+    std::vector<uint32_t> packed((size_t)L.n_launch);
+    if (L.n_launch) {
+        DEC_HIP(d, hipSetDevice(d->device));
+        hipStream_t s = (hipStream_t)stream;
+        // ---- the workspace: the upload (edit_pack: lens, pool, pairs in launch order, waves), then the packed results [n_launch]
+        const size_t in_words = L.words.size();
+        if (int rc = reserve_all(d, d->ed_io, sizeof(int32_t) * (in_words + (size_t)L.n_launch))) return rc;
+        int32_t* w = d->ed_io.as<int32_t>();
+        DEC_HIP(d, hipMemcpyAsync(w, L.words.data(), sizeof(int32_t) * in_words, hipMemcpyHostToDevice, s));
+        EditArgs a{};
+        a.lens = w; a.pool = w + L.off_pool; a.L_stride = L_stride; a.pair_a = w + L.off_a; a.pair_b = w + L.off_b;
+        a.waves = w + L.off_waves; a.n_waves = L.n_waves; a.col_words = L.col_words;
+        a.packed = reinterpret_cast<uint32_t*>(w + in_words);
+        DEC_HIP(d, launch_edit(a, s));
+        DEC_HIP(d, hipMemcpyAsync(packed.data(), a.packed, sizeof(uint32_t) * packed.size(), hipMemcpyDeviceToHost, s));
+        DEC_HIP(d, hipStreamSynchronize(s));
+    }
+    edit_unpack(L, packed.data(), seq_lens, pair_a, pair_b, N, counts);
     return DSMI_OK;
 }

@@ -227,6 +227,134 @@ class Decoder(object):
         strings, _, ids = self._decode_best_ids(probs, sizes)
         return strings, ids, self.confidence_ids(probs, ids, sizes)
 
+    # ---- batched edit distance (dsmi_edit_distance): WER / CER with their error counts, and minimum-risk choice among the
+    # hypotheses of an n-best list; the same on every decoder, a language model plays no part
+    def _edit_device(self):
+        """The native handle of the current CUDA device (no ``probs`` names one here)."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("the edit distance runs on the MI355X only (no CPU path) and no GPU is visible")
+        return self._dec(torch.cuda.current_device())
+
+    @staticmethod
+    def _edit_tokens(texts, unit, table):
+        """Id sequences of ``texts``: words (``s.split()``, as ``wer``) through the dictionary ``table``, which grows, or
+        characters without spaces (as ``cer``) by code point."""
+        if unit == "word":
+            return [np.array([table.setdefault(w, len(table)) for w in s.split()], dtype=np.int32) for s in texts]
+        if unit == "char":
+            return [np.array([ord(c) for c in s.replace(' ', '')], dtype=np.int32) for s in texts]
+        raise ValueError("unit must be 'word' or 'char', not %r" % (unit,))
+
+    @staticmethod
+    def _edit_limit(seqs):
+        from .. import _native
+        longest = max([len(t) for t in seqs] + [0])
+        if longest > _native.EDIT_MAX_TOKENS:
+            raise ValueError("sequence of %d tokens is longer than %d" % (longest, _native.EDIT_MAX_TOKENS))
+
+    def error_counts(self, references, hypotheses, unit="word"):
+        """The errors of ``hypotheses[n]`` against ``references[n]`` for N pairs of strings in one call: ``(counts, ref_lens)``
+        with ``counts`` int32 [N, 4] = distance, substitutions, deletions, insertions (of the minimum-distance alignment with
+        the fewest substitutions) and ``ref_lens`` int32 [N] the tokens of each reference.  ``unit="word"``: tokens are
+        ``s.split()`` words (``wer``'s tokenisation); ``"char"``: the characters without spaces (``cer``'s)."""
+        references, hypotheses = list(references), list(hypotheses)
+        if len(references) != len(hypotheses):
+            raise ValueError("error_counts: %d references and %d hypotheses" % (len(references), len(hypotheses)))
+        table = {}
+        seqs = self._edit_tokens(references, unit, table) + self._edit_tokens(hypotheses, unit, table)
+        self._edit_limit(seqs)                                                                # every check before any GPU work
+        N = len(references)
+        ref_lens = np.array([len(t) for t in seqs[:N]], dtype=np.int32)
+        if N == 0:
+            return np.zeros((0, 4), dtype=np.int32), ref_lens
+        pairs = np.stack([np.arange(N), np.arange(N, 2 * N)], axis=1)
+        return self._edit_device().edit_distance(seqs, pairs), ref_lens
+
+    def wer_batch(self, references, hypotheses):
+        """``[self.wer(r, h) for r, h in zip(references, hypotheses)]`` in one call, as a list of ints."""
+        return self.error_counts(references, hypotheses, "word")[0][:, 0].tolist()
+
+    def cer_batch(self, references, hypotheses):
+        """``[self.cer(r, h) for r, h in zip(references, hypotheses)]`` in one call, as a list of ints."""
+        return self.error_counts(references, hypotheses, "char")[0][:, 0].tolist()
+
+    def error_rate(self, references, hypotheses, unit="word"):
+        """The corpus error rate: the summed distances over the summed reference lengths (WER for ``"word"``, CER for
+        ``"char"``).  ``ValueError`` when the references hold no token."""
+        counts, ref_lens = self.error_counts(references, hypotheses, unit)
+        total = int(ref_lens.sum())
+        if total == 0:
+            raise ValueError("error_rate: the references hold no token")
+        return int(counts[:, 0].sum()) / total
+
+    def _risk_tokens(self, ids, unit, table):
+        """One hypothesis (label ids) as the tokens its risk is counted in: the words between space labels (empty words
+        dropped) through the dictionary ``table``, or the labels without the space label."""
+        ids = np.asarray(ids, dtype=np.int32).reshape(-1)
+        if unit == "char":
+            return ids[ids != self.space_index]
+        if unit != "word":
+            raise ValueError("unit must be 'word' or 'char', not %r" % (unit,))
+        words, out = np.split(ids, np.flatnonzero(ids == self.space_index)), []
+        for k, w in enumerate(words):
+            w = w[1:] if k else w                     # (every later piece begins with the space it was cut at)
+            if len(w):
+                out.append(table.setdefault(w.tobytes(), len(table)))
+        return np.array(out, dtype=np.int32)
+
+    def min_risk(self, ids, logps, unit="word"):
+        """Minimum-Bayes-risk order of n-best lists.  ``ids[b]``: clip b's K_b hypotheses as label-id sequences; ``logps[b]``:
+        their natural-log posteriors (``None`` = infeasible), as ``decode_scored`` returns them -- ``dsmi_score``'s, acoustic
+        only: the language model has no part in the weights.  Per clip ``(order, risks)``: ``risks[i]`` (float64) is the
+        expected number of word (``unit="word"``: the words between space labels) or character (``"char"``: the labels
+        without the space label) errors of hypothesis i, sum_j w_j * distance(i, j), under the weights w = softmax(logps[b])
+        (``None`` or -inf: 0; all ``None``: uniform); ``order`` is the stable ascending order of the risks, so ties keep
+        the decoder's order.  The pairs i < j of every clip go in ONE ``dsmi_edit_distance`` call."""
+        if len(ids) != len(logps):
+            raise ValueError("min_risk: hypotheses for %d clips and posteriors for %d" % (len(ids), len(logps)))
+        table, pool, base, pairs = {}, [], [], []
+        for hyps, lps in zip(ids, logps):
+            if len(hyps) != len(lps):
+                raise ValueError("min_risk: %d hypotheses and %d posteriors of one clip" % (len(hyps), len(lps)))
+            base.append(len(pool))
+            pool.extend(self._risk_tokens(t, unit, table) for t in hyps)
+            iu = np.triu_indices(len(hyps), 1)
+            pairs.append(np.stack([iu[0] + base[-1], iu[1] + base[-1]], axis=1))
+        self._edit_limit(pool)                                                                # every check before any GPU work
+        pairs = np.concatenate(pairs) if pairs else np.zeros((0, 2), dtype=np.int64)
+        dist = self._edit_device().edit_distance(pool, pairs)[:, 0] if len(pairs) else np.zeros(0, dtype=np.int32)
+        out, at = [], 0
+        for hyps, lps in zip(ids, logps):
+            K = len(hyps)
+            lp = np.array([-np.inf if v is None else float(v) for v in lps], dtype=np.float64)
+            if K and np.isfinite(lp.max()):
+                w = np.exp(lp - lp.max())
+                w /= w.sum()
+            else:
+                w = np.full(K, 1.0 / K if K else 0.0)
+            D = np.zeros((K, K), dtype=np.int32)
+            iu = np.triu_indices(K, 1)
+            D[iu] = dist[at:at + len(iu[0])]
+            at += len(iu[0])
+            D = D + D.T
+            risks = (D.astype(np.float64) * w[None, :]).sum(axis=1)
+            out.append((np.argsort(risks, kind="stable"), risks))
+        return out
+
+    def decode_min_risk(self, probs, sizes=None, n_best=None, unit="word"):
+        """``decode_scored``'s hypotheses in minimum-Bayes-risk order (``min_risk``): ``(strings, offsets, risks, logps)``,
+        each clip's lists reordered by ascending risk.  The first hypothesis is the one with the least expected ``unit``
+        errors under the acoustic posteriors, which need not be the most probable one."""
+        strings, offsets, logps, ids = self._decode_scored_ids(probs, sizes, n_best)
+        out_s, out_o, out_r, out_l = [], [], [], []
+        for b, (order, risks) in enumerate(self.min_risk(ids, logps, unit)):
+            out_s.append([strings[b][i] for i in order])
+            out_o.append([offsets[b][i] for i in order])
+            out_r.append([float(risks[i]) for i in order])
+            out_l.append([logps[b][i] for i in order])
+        return out_s, out_o, out_r, out_l
+
 
 class GreedyDecoder(Decoder):
     """decoder.py:147-198: argmax per frame, collapse repeats, drop blanks; one path per utterance."""
@@ -255,6 +383,12 @@ class GreedyDecoder(Decoder):
         strings = [[self._to_string(ids)] for ids, _ in res]
         offsets = [[torch.from_numpy(off.astype(np.int32))] for _, off in res]
         return strings, offsets, self.score_ids(probs, [[ids] for ids, _ in res], sizes)
+
+    def decode_min_risk(self, probs, sizes=None, n_best=None, unit="word"):
+        """``decode_scored`` with the risk of each clip's one hypothesis, which is 0 (nothing to choose among):
+        ``(strings, offsets, risks, logps)``."""
+        strings, offsets, logps = self.decode_scored(probs, sizes, n_best)
+        return strings, offsets, [[0.0] for _ in strings], logps
 
     def _decode_best_ids(self, probs, sizes=None):
         """(the text of each clip, None, its label ids)"""
@@ -348,6 +482,10 @@ class BeamCTCDecoder(Decoder):
         its label sequence over the same (still resident) probabilities, all of a clip's hypotheses in one ``dsmi_score``
         call: ``(strings, offsets, logps)`` with ``logps[b][p]`` the natural log.  Unlike the search's own scores
         (``last_scores``) these sum over every alignment, carry no language-model term and are not pruned."""
+        return self._decode_scored_ids(probs, sizes, n_best)[:3]
+
+    def _decode_scored_ids(self, probs, sizes=None, n_best=None):
+        """``decode_scored`` and the label ids of every hypothesis: (strings, offsets, logps, ids)."""
         probs = self._on_gpu(probs)
         tok, ts, ln, sc = self.decode_enqueue(probs, sizes).beam_collect()
         self.last_scores = sc
@@ -355,7 +493,7 @@ class BeamCTCDecoder(Decoder):
         tok, ts, ln = tok[:, :W], ts[:, :W], ln[:, :W]
         strings, offsets = self._beam_strings(tok, ts, ln)
         ids = [[tok[b, p, :ln[b, p]] for p in range(W)] for b in range(tok.shape[0])]
-        return strings, offsets, self.score_ids(probs, ids, sizes)
+        return strings, offsets, self.score_ids(probs, ids, sizes), ids
 
     def _decode_best_ids(self, probs, sizes=None):
         """(the first beam's text of each clip, None, its label ids)"""

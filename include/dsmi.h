@@ -662,6 +662,40 @@ int dsmi_alternatives(dsmi_decoder* d, const float* probs_dev, const int32_t* si
                       const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host,
                       int N, int L_stride, double* logp_host, double* alt_logp_host, int32_t* status_host, void* stream);
 
+/* ---- Batched edit distance (the reference calls Levenshtein.distance once per pair, on the host): how far is this text from
+ * that one, for many pairs at once -- WER / CER with their error counts, and the pairwise distances of n-best lists.
+ * A pool of M token sequences: seqs_host [M][L_stride] with seq_lens_host [M].  Tokens are any int32 and are compared for
+ * equality only (word ids or label ids; nothing is special about 0, negative values or the blank).  N pairs index the pool:
+ * pair n compares a = sequence pair_a_host[n] (the reference) with b = sequence pair_b_host[n] (the hypothesis).  A sequence
+ * may appear in any number of pairs, in either role, or paired with itself.
+ * Output: counts_host[n] = {distance, substitutions, deletions, insertions}.  A deletion is a token of a with no partner in b,
+ * an insertion a token of b with no partner in a.  The four numbers are those of the minimum-distance alignment with the
+ * FEWEST SUBSTITUTIONS: with H matches, H+S+D = La, H+S+I = Lb and S+D+I = d leave one degree of freedom given d, so "fewest
+ * substitutions" is also "most matches" and fixes all four uniquely.
+ * The recurrence (the contract).  Costs are unsigned 32-bit integers d << 16 | s.  A match adds 0, a substitution SUB = 0x10001,
+ * a deletion DEL or an insertion INS 0x10000:
+ *     D[i][0] = i << 16,  D[0][j] = j << 16,
+ *     D[i][j] = min3(D[i-1][j] + DEL, D[i][j-1] + INS, D[i-1][j-1] + (a_i == b_j ? 0 : SUB))
+ * The minimum of packed integers is the lexicographic minimum of (distance, substitutions).  With d, s = D[La][Lb]:
+ *     deletions = (d - s - (Lb - La)) / 2,  insertions = deletions + Lb - La.
+ * Lengths <= DSMI_EDIT_MAX_TOKENS keep both fields below 2^16.  Results are exact integers: deterministic and batch-invariant.
+ * Pairs with an empty side are answered by the host (all deletions or all insertions; 0 for both empty) and nothing is
+ * launched for them.  One kernel launch whatever N (none when every pair has an empty side).  Synchronises `stream`.
+ * Refused with nothing written and nothing launched: DSMI_ERR_INVALID for M or N <= 0, a length outside 0 .. L_stride, a pair
+ * index outside 0 .. M-1, a NULL array (seqs_host may be NULL only when L_stride == 0); DSMI_ERR_CAPACITY for
+ * L_stride > DSMI_EDIT_MAX_TOKENS, M * L_stride > 2^24 or N > 2^24 (the upload buffer, kept on the handle).
+ *
+ * dsmi_edit_plan (host only) is the launch plan dsmi_edit_distance uses for pairs of these lengths.  seg[n] is the lane
+ * segment pair n occupies: 16 if len_b <= 16, 32 if len_b <= 32, else 64 (written for every pair).  order[0 .. returned) is
+ * the launch order of the pairs that need the kernel (both lengths > 0): by seg ascending; then by work
+ * ceil(len_b / 64) * (len_a + seg) descending, so that wave-mates finish together and the longest chains start first; then by
+ * index ascending.  A wave takes 64 / seg consecutive pairs of one segment width.  Returns the number of pairs launched;
+ * < 0 for NULL arguments, N <= 0 or a negative length. */
+#define DSMI_EDIT_MAX_TOKENS 4096
+int dsmi_edit_plan(const int32_t* len_a, const int32_t* len_b, int N, int32_t* order, int32_t* seg);
+int dsmi_edit_distance(dsmi_decoder* d, const int32_t* seqs_host, const int32_t* seq_lens_host, int M, int L_stride,
+                       const int32_t* pair_a_host, const int32_t* pair_b_host, int N, int32_t* counts_host, void* stream);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off

@@ -13,6 +13,9 @@
 //   host_fuzz ctccheck SEED N   the argument checks and the phrase packing of dsmi_align / dsmi_spot / dsmi_score / dsmi_alternatives (ctc_host.h) on N random
 //                             calls held in exactly sized heap arrays, against the definitions written out below; what is refused
 //                             on the numbers alone is called with null arrays
+//   host_fuzz editcheck SEED N  the host half of dsmi_edit_distance (edit_host.h: edit_check, edit_plan, edit_pack, edit_unpack) on N random
+//                             calls held in exactly sized heap arrays, against the rules written out below; what is refused on the
+//                             numbers alone is called with null arrays
 #define __host__
 #define __device__
 #include <cmath>
@@ -28,6 +31,7 @@
 #include "rnn_plan.h"
 #include "gate_plan.h"
 #include "ctc_host.h"
+#include "edit_host.h"
 
 using namespace dsmi;
 
@@ -595,6 +599,133 @@ static int run_ctccheck(int argc, char** argv) {
     return 0;
 }
 
+// ---- editcheck: the rules of include/dsmi.h written out plainly, beside edit_host.h -------------------------------------------
+#define EDIT_FAIL(what) do { std::fprintf(stderr, "editcheck: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
+
+// D[la][lb] of the packed recurrence, by the full table
+static uint32_t edit_table(const int32_t* a, int la, const int32_t* b, int lb) {
+    std::vector<uint32_t> D((size_t)(la + 1) * (size_t)(lb + 1));
+    auto at = [&](int i, int j) -> uint32_t& { return D[(size_t)i * (size_t)(lb + 1) + (size_t)j]; };
+    for (int i = 0; i <= la; ++i) at(i, 0) = (uint32_t)i << 16;
+    for (int j = 0; j <= lb; ++j) at(0, j) = (uint32_t)j << 16;
+    for (int i = 1; i <= la; ++i)
+        for (int j = 1; j <= lb; ++j)
+            at(i, j) = std::min(std::min(at(i - 1, j) + 0x10000u, at(i, j - 1) + 0x10000u), at(i - 1, j - 1) + (a[i - 1] == b[j - 1] ? 0u : 0x10001u));
+    return at(la, lb);
+}
+
+static int run_editcheck(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long pairs_checked = 0, refused = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        std::string err;
+        const int32_t* none = nullptr;
+        // ---- refused on the numbers alone: no array is there to read
+        {
+            const int big = 1 + (int)(rng() % 1000);
+            if (edit_check(none, rng() % 2 ? 0 : -big, 4, none, none, 3, err) != DSMI_ERR_INVALID || err.empty()) EDIT_FAIL("M <= 0");
+            if (edit_check(none, 3, 4, none, none, rng() % 2 ? 0 : -big, err) != DSMI_ERR_INVALID) EDIT_FAIL("N <= 0");
+            if (edit_check(none, 3, -big, none, none, 3, err) != DSMI_ERR_INVALID) EDIT_FAIL("negative L_stride");
+            if (edit_check(none, 3, DSMI_EDIT_MAX_TOKENS + big, none, none, 3, err) != DSMI_ERR_CAPACITY || err.find("DSMI_EDIT_MAX_TOKENS") == std::string::npos) EDIT_FAIL("L_stride above the limit");
+            const int Ls = 1 + (int)(rng() % DSMI_EDIT_MAX_TOKENS);
+            if (edit_check(none, (int)(((int64_t)1 << 24) / Ls) + big, Ls, none, none, 3, err) != DSMI_ERR_CAPACITY) EDIT_FAIL("M * L_stride above 2^24");
+            if (edit_check(none, 3, 4, none, none, (1 << 24) + big, err) != DSMI_ERR_CAPACITY) EDIT_FAIL("N above 2^24");
+            if (edit_check(none, INT32_MAX, DSMI_EDIT_MAX_TOKENS, none, none, INT32_MAX, err) != DSMI_ERR_CAPACITY) EDIT_FAIL("the largest numbers");
+        }
+        // ---- a random call: a pool of few symbols, lengths around the segment and stripe edges, pairs that share rows
+        const int M = 1 + (int)(rng() % 12), N = 1 + (int)(rng() % 40);
+        const int edges[10] = {0, 1, 15, 16, 17, 32, 33, 64, 65, 130};
+        const int L_stride = rng() % 8 == 0 ? 0 : edges[rng() % 10] + (int)(rng() % 3);
+        std::vector<int32_t> seqs = exact((size_t)M * (size_t)L_stride), lens = exact((size_t)M), pa = exact((size_t)N), pb = exact((size_t)N);
+        const int symbols = 1 + (int)(rng() % 4);
+        for (auto& v : seqs) v = (int32_t)(rng() % (unsigned)symbols) - 1;
+        for (auto& v : lens) v = rng() % 4 == 0 ? 0 : (int32_t)(rng() % (unsigned)(L_stride + 1));
+        for (auto& v : pa) v = (int32_t)(rng() % (unsigned)M);
+        for (auto& v : pb) v = (int32_t)(rng() % (unsigned)M);
+        const int spoil = (int)(rng() % 6);
+        int want = DSMI_OK;
+        if (spoil == 1) { lens[rng() % (unsigned)M] = rng() % 2 ? L_stride + 1 + (int32_t)(rng() % 3) : -1 - (int32_t)(rng() % 3); want = DSMI_ERR_INVALID; }
+        if (spoil == 2) { (rng() % 2 ? pa : pb)[rng() % (unsigned)N] = rng() % 2 ? M + (int32_t)(rng() % 3) : -1 - (int32_t)(rng() % 3); want = DSMI_ERR_INVALID; }
+        const int rc = edit_check(lens.data(), M, L_stride, pa.data(), pb.data(), N, err);
+        if (rc != want) EDIT_FAIL("a call's verdict");
+        if (rc != DSMI_OK) {
+            if (err.empty()) EDIT_FAIL("a refusal without a message");
+            ++refused;
+            continue;
+        }
+        // ---- the plan: seg by len_b, the pairs with both sides non-empty, every neighbouring pair in the documented order
+        std::vector<int32_t> la = exact((size_t)N), lb = exact((size_t)N), order = exact((size_t)N + 1, -7), seg = exact((size_t)N + 1, -7);
+        for (int n = 0; n < N; ++n) { la[(size_t)n] = lens[(size_t)pa[(size_t)n]]; lb[(size_t)n] = lens[(size_t)pb[(size_t)n]]; }
+        const int n_launch = edit_plan(la.data(), lb.data(), N, order.data(), seg.data());
+        if (order[(size_t)N] != -7 || seg[(size_t)N] != -7) EDIT_FAIL("plan: a write past its arrays");
+        int want_launch = 0;
+        for (int n = 0; n < N; ++n) {
+            if (seg[(size_t)n] != (lb[(size_t)n] <= 16 ? 16 : lb[(size_t)n] <= 32 ? 32 : 64)) EDIT_FAIL("plan: seg");
+            want_launch += la[(size_t)n] > 0 && lb[(size_t)n] > 0;
+        }
+        if (n_launch != want_launch) EDIT_FAIL("plan: the number launched");
+        std::vector<int> seen((size_t)N, 0);
+        auto key = [&](int32_t x, long long* k) {
+            k[0] = seg[(size_t)x]; k[1] = -(long long)((lb[(size_t)x] + 63) / 64) * (la[(size_t)x] + seg[(size_t)x]); k[2] = x;
+        };
+        for (int i = 0; i < n_launch; ++i) {
+            const int32_t x = order[(size_t)i];
+            if (x < 0 || x >= N || seen[(size_t)x]++ || la[(size_t)x] == 0 || lb[(size_t)x] == 0) EDIT_FAIL("plan: not the pairs that need the kernel, once each");
+            if (i == 0) continue;
+            long long kw[3], kx[3];
+            key(order[(size_t)i - 1], kw); key(x, kx);
+            if (!std::lexicographical_compare(kw, kw + 3, kx, kx + 3)) EDIT_FAIL("plan: the order");
+        }
+        // ---- the packing: the upload's parts, every wave's word
+        EditLaunch L;
+        edit_pack(ptr_or_null(seqs), lens.data(), M, L_stride, pa.data(), pb.data(), N, L);
+        if (L.n_launch != n_launch || !std::equal(L.order.begin(), L.order.end(), order.begin())) EDIT_FAIL("pack: another plan");
+        if (n_launch == 0) {
+            if (!L.words.empty() || L.n_waves) EDIT_FAIL("pack: an upload for nothing");
+        } else {
+            const size_t pool = (size_t)M * (size_t)L_stride;
+            if (L.words.size() != (size_t)M + pool + 2 * (size_t)n_launch + (size_t)L.n_waves) EDIT_FAIL("pack: the upload's size");
+            if (!std::equal(lens.begin(), lens.end(), L.words.begin()) || !std::equal(seqs.begin(), seqs.end(), L.words.begin() + (ptrdiff_t)L.off_pool)) EDIT_FAIL("pack: lens or pool");
+            int next = 0, col = 0;
+            for (int w = 0; w < L.n_waves; ++w) {
+                const uint32_t word = (uint32_t)L.words[L.off_waves + (size_t)w];
+                const int first = (int)(word & 0xffffffu), s = 16 << ((word >> kEditSegShift) & 3), cnt = (int)(word >> kEditCountShift) & 7;
+                if (first != next || cnt < 1 || cnt > 64 / s || first + cnt > n_launch) EDIT_FAIL("pack: a wave's pairs");
+                for (int q = 0; q < cnt; ++q) {
+                    const int32_t n = order[(size_t)(first + q)];
+                    if (seg[(size_t)n] != s) EDIT_FAIL("pack: a wave of two segment widths");
+                    if (L.words[L.off_a + (size_t)(first + q)] != pa[(size_t)n] || L.words[L.off_b + (size_t)(first + q)] != pb[(size_t)n]) EDIT_FAIL("pack: a pair's rows");
+                    if (lb[(size_t)n] > 64) col = std::max(col, (int)la[(size_t)n] + 1);
+                }
+                // a wave is full unless the segment width ends behind it
+                if (cnt < 64 / s && first + cnt < n_launch && seg[(size_t)order[(size_t)(first + cnt)]] == s) EDIT_FAIL("pack: a wave with room left");
+                next = first + cnt;
+            }
+            if (next != n_launch || col != L.col_words) EDIT_FAIL("pack: the waves do not cover the launch, or the boundary column's size");
+        }
+        // ---- the unpacking: what the kernel would return (the recurrence, by the full table), against the counts' identities
+        std::vector<uint32_t> packed((size_t)n_launch);
+        for (int i = 0; i < n_launch; ++i) {
+            const int32_t n = order[(size_t)i];
+            packed[(size_t)i] = edit_table(seqs.data() + (size_t)pa[(size_t)n] * (size_t)L_stride, la[(size_t)n], seqs.data() + (size_t)pb[(size_t)n] * (size_t)L_stride, lb[(size_t)n]);
+        }
+        std::vector<int32_t> counts = exact(4 * (size_t)N + 1, -7);
+        edit_unpack(L, packed.data(), lens.data(), pa.data(), pb.data(), N, counts.data());
+        if (counts[4 * (size_t)N] != -7) EDIT_FAIL("unpack: a write past counts");
+        for (int n = 0; n < N; ++n) {
+            const int32_t* c = counts.data() + 4 * (size_t)n;
+            const int a_ = la[(size_t)n], b_ = lb[(size_t)n];
+            if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[3] < 0 || c[1] + c[2] + c[3] != c[0] || c[3] - c[2] != b_ - a_ || c[1] + c[2] > a_ || c[1] + c[3] > b_) EDIT_FAIL("unpack: the identities");
+            if ((a_ == 0 || b_ == 0) && (c[0] != a_ + b_ || c[1] != 0 || c[2] != a_ || c[3] != b_)) EDIT_FAIL("unpack: a pair with an empty side");
+            if (pa[(size_t)n] == pb[(size_t)n] && c[0] != 0) EDIT_FAIL("unpack: a sequence against itself");
+            ++pairs_checked;
+        }
+    }
+    std::printf("%d edit calls ok, %ld refused, %ld pairs checked\n", reps, refused, pairs_checked);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
@@ -602,6 +733,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "gate")) return run_gate(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]]\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]]\n");
     return 2;
 }
