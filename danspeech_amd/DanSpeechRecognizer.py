@@ -745,6 +745,41 @@ class DanSpeechRecognizer(object):
             results[i] = list(zip(strings[pos], risks[pos], logps[pos]))
         return results
 
+    # ---- the language model over finished n-best lists (LM sentence scoring): rescoring, and tuning alpha / beta --------------
+    def _lm_decoder(self, what):
+        if not hasattr(self.decoder, "rescore") or not getattr(self.decoder, "lm_path", None):
+            raise ValueError("%s needs a beam-search decoder with a language model" % what)
+        return self.decoder
+
+    def transcribe_rescored_batch(self, recordings, n_best=8, alpha=None, beta=None):
+        """``transcribe_scored_batch`` rescored with the language model: per recording ``[(text, total, logp), ...]``, the
+        decoder's first ``n_best`` hypotheses by descending ``total = logp + alpha * lm + beta * n_words`` (``logp`` the exact
+        acoustic ``dsmi_score`` likelihood, ``lm`` the ``dsmi_lm_score`` sentence score; ``alpha`` / ``beta`` None: the
+        decoder's own).  ``ValueError`` without a beam-search decoder that has a language model."""
+        dec = self._lm_decoder("transcribe_rescored_batch")
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        strings, _, totals, logps = dec.decode_rescored(job.probs, job.sizes, n_best, alpha, beta)
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            results[i] = list(zip(strings[pos], totals[pos], logps[pos]))
+        return results
+
+    def tune_lm_batch(self, recordings, transcripts, alphas, betas, n_best=8, unit="word"):
+        """``BeamCTCDecoder.tune_lm_weights`` on ``recordings`` with their known ``transcripts``: one forward, one n-best
+        search at the decoder's current weights, one ``dsmi_lm_score`` and one ``dsmi_edit_distance`` call, then the whole
+        alpha x beta grid on the host.  It tunes a rescoring of that search's n-best lists, not the search's own pruning."""
+        dec = self._lm_decoder("tune_lm_batch")
+        if len(recordings) != len(transcripts):
+            raise ValueError("tune_lm_batch: %d recordings and %d transcripts" % (len(recordings), len(transcripts)))
+        if len(recordings) == 0:
+            raise ValueError("tune_lm_batch: no recording")
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        return dec.tune_lm_weights(job.probs, job.sizes, [transcripts[i] for i in job.order], alphas, betas, n_best, unit)
+
     def evaluate_batch(self, recordings, transcripts):
         """Recognise ``recordings`` and compare with their known ``transcripts`` (normalised with
         ``Decoder.normalise_transcript``): a dict of ``texts``, the corpus rates ``wer`` and ``cer`` (summed distances over

@@ -87,6 +87,17 @@ class Recognizer(object):
         list (``DanSpeechRecognizer.transcribe_min_risk_batch``)."""
         return self.danspeech_recognizer.transcribe_min_risk_batch(audio_list, n_best=n_best, unit=unit)
 
+    def recognize_rescored(self, audio_list, n_best=8, alpha=None, beta=None):
+        """``recognize_scored`` rescored with the language model: per clip ``[(text, total, logp), ...]``, the decoder's first
+        ``n_best`` hypotheses by descending ``total = logp + alpha * lm + beta * n_words`` (``alpha`` / ``beta`` None: the
+        decoder's own; ``DanSpeechRecognizer.transcribe_rescored_batch``)."""
+        return self.danspeech_recognizer.transcribe_rescored_batch(audio_list, n_best=n_best, alpha=alpha, beta=beta)
+
+    def tune_lm(self, audio_list, transcripts, alphas, betas, n_best=8, unit="word"):
+        """Tune the language-model weights on clips with known transcripts: the errors of every (alpha, beta) of the grid when
+        the n-best lists of ONE search are rescored with it, and the best pair (``BeamCTCDecoder.tune_lm_weights``)."""
+        return self.danspeech_recognizer.tune_lm_batch(audio_list, transcripts, alphas, betas, n_best=n_best, unit=unit)
+
     def evaluate(self, audio_list, transcripts):
         """Recognise the clips and compare with their known transcripts: a dict of ``texts``, the corpus ``wer`` and ``cer``,
         ``word_counts`` / ``char_counts`` (per clip: distance, substitutions, deletions, insertions) and ``word_ref_lens`` /

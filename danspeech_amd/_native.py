@@ -35,6 +35,7 @@ SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
 SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
 ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes (L_stride)
 EDIT_MAX_TOKENS = 4096          # the longest sequence dsmi_edit_distance takes (L_stride)
+LM_SCORE_MAX_TOKENS = 4096      # the longest sequence dsmi_lm_score takes (L_stride)
 
 DSMI_ERR_INVALID = -1
 DSMI_ERR_CONV = -2
@@ -184,6 +185,9 @@ _PROTOS = {
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "dsmi_edit_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_edit_distance": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
+    "dsmi_lm_score_plan": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
+    "dsmi_lm_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "dsmi_lm_sentence_ln": (C.c_double, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "dsmi_model_info": (C.c_int, [_vp, C.POINTER(ModelDesc), C.POINTER(C.c_int)]),
     "dsmi_frontend_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dsmi_decoder_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1134,6 +1138,44 @@ class NativeDecoder(_Handle):
                                              _np_ptr(pa), _np_ptr(pb), len(pr), _np_ptr(counts), _stream(self.device)))
         return counts
 
+    def lm_score(self, ids, lens=None, want_terms=False):
+        """LM sentence scoring (``dsmi_lm_score``) with the language model of ``set_lm``.  ids: the pool, an int array
+        [M, L_stride] of label ids with ``lens`` [M], or a list of M id sequences (``lens`` None).  Returns numpy arrays
+        (lm_ln float64 [M] natural log, n_words int32 [M], n_oov int32 [M]) and, with ``want_terms``, a list of M float64
+        arrays: the n_words + 1 window terms of each sentence (2 for no words), whose sum in order is lm_ln."""
+        if lens is not None and np.size(ids) == 0:             # (a pool of empty sequences: no column to infer the rows from)
+            pool, lens = np.zeros((len(lens), 0), dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int32)
+        else:
+            pool, lens = _padded_ids(ids, lens, None if lens is None else len(lens), 0, None)
+        M = pool.shape[0]
+        W = pool.shape[1] // 2 + 2 if want_terms else 0       # words are at least a space apart: n_terms <= L_stride // 2 + 2
+        lm_ln = np.zeros(M, dtype=np.float64)
+        n_words, n_oov, n_terms = (np.zeros(M, dtype=np.int32) for _ in range(3))
+        terms = np.zeros((M, W), dtype=np.float64) if want_terms else None
+        self._check(lib().dsmi_lm_score(self._h, _np_ptr(pool) if pool.size else None, _np_ptr(lens), M, pool.shape[1], _np_ptr(lm_ln),
+                                        _np_ptr(n_words), _np_ptr(n_oov), _np_ptr(n_terms), _np_ptr(terms) if want_terms else None, W,
+                                        _stream(self.device)))
+        if want_terms:
+            return lm_ln, n_words, n_oov, [terms[m, :n_terms[m]].copy() for m in range(M)]
+        return lm_ln, n_words, n_oov
+
+
+def lm_score_plan(ids, lens=None, space=-2):
+    """dsmi_lm_score_plan (host only): the words dsmi_lm_score finds in rows of label ids -- (n_words int32 [M], word_first
+    int32 [M, W], word_len int32 [M, W]) with ``space`` the space label's id and W the largest n_words."""
+    if lens is not None and np.size(ids) == 0:
+        pool, lens = np.zeros((len(lens), 0), dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int32)
+    else:
+        pool, lens = _padded_ids(ids, lens, None if lens is None else len(lens), 0, None)
+    M, W = pool.shape[0], (pool.shape[1] + 1) // 2
+    n_words = np.zeros(M, dtype=np.int32)
+    first, length = np.zeros((M, W), dtype=np.int32), np.zeros((M, W), dtype=np.int32)
+    rc = lib().dsmi_lm_score_plan(_np_ptr(pool) if pool.size else None, _np_ptr(lens), M, pool.shape[1], int(space), _np_ptr(n_words),
+                                  _np_ptr(first) if W else None, _np_ptr(length) if W else None, W)
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_lm_score_plan: at least one row, every length within 0 .. L_stride")
+    return n_words, first[:, :rc].copy(), length[:, :rc].copy()
+
 
 def _padded_ids(rows, lens, count, min_width, mismatch):
     """The token rows of dsmi_align / dsmi_spot / dsmi_score as a contiguous int32 [count, L_stride] array and its int32 lens:
@@ -1286,6 +1328,13 @@ class NativeLM(_Handle):
     def cond_log10(self, ids):
         a = np.ascontiguousarray(ids, dtype=np.int32)
         return float(lib().dsmi_lm_cond_log10(self._h, _np_ptr(a), len(a)))
+
+    def sentence_ln(self, word_ids):
+        """(natural-log sentence score, its window terms float64 [n + 1], or [2] for no words) of a sentence of the file's own
+        word ids, -1 = out of vocabulary (``dsmi_lm_sentence_ln``: ctcdecode ``Scorer.get_sent_log_prob``)."""
+        a = np.ascontiguousarray(word_ids, dtype=np.int32).reshape(-1)
+        terms = np.zeros(max(len(a) + 1, 2), dtype=np.float64)
+        return float(lib().dsmi_lm_sentence_ln(self._h, _np_ptr(a) if len(a) else None, len(a), _np_ptr(terms), len(terms))), terms
 
 
 def plan_shards(n_samples, world):

@@ -1,7 +1,8 @@
 // The four tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
 // (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip) and
 // token confidence (dsmi_alternatives; alt.hip) -- and, on the same handle and by the same conventions, the batched edit distance
-// of token sequences (dsmi_edit_distance; edit.hip), which needs no probabilities.
+// of token sequences (dsmi_edit_distance; edit.hip) and the language-model score of known sentences (dsmi_lm_score; lmscore.hip),
+// which need no probabilities.
 // Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
 // before any output write), grows its workspaces, uploads, launches and copies the results back.  A clip or candidate whose
 // transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
@@ -11,6 +12,7 @@
 #include "score.h"
 #include "alt.h"
 #include "edit.h"
+#include "lmscore.h"
 
 #include <cmath>
 #include <cstring>
@@ -254,5 +256,46 @@ extern "C" int dsmi_edit_distance(dsmi_decoder* d, const int32_t* seqs, const in
         DEC_HIP(d, hipStreamSynchronize(s));
     }
     edit_unpack(L, packed.data(), seq_lens, pair_a, pair_b, N, counts);
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_lm_score_plan(const int32_t* seqs, const int32_t* seq_lens, int M, int L_stride, int space, int32_t* n_words,
+                                  int32_t* word_first, int32_t* word_len, int W_stride) {
+    if (!seq_lens || !n_words || M <= 0 || L_stride < 0 || W_stride < 0 || (L_stride > 0 && !seqs) || (W_stride > 0 && (!word_first || !word_len)))
+        return DSMI_ERR_INVALID;
+    return lm_score_plan(seqs, seq_lens, M, L_stride, space, n_words, word_first, word_len, W_stride);
+}
+
+extern "C" int dsmi_lm_score(dsmi_decoder* d, const int32_t* seqs, const int32_t* seq_lens, int M, int L_stride, double* lm_ln, int32_t* n_words,
+                             int32_t* n_oov, int32_t* n_terms, double* terms, int W_stride, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    if (!seq_lens || !lm_ln || !n_words || !n_oov || !n_terms || (L_stride > 0 && !seqs)) { d->err = "bad lm_score arguments"; return DSMI_ERR_INVALID; }
+    const int C = (int)d->labels.size();
+    if (int rc = lm_score_check(d->has_lm, seqs, seq_lens, M, L_stride, C, d->blank, d->space, terms != nullptr, W_stride, d->err)) return rc;
+    LmScoreLaunch L;
+    lm_score_pack(seqs, seq_lens, M, L_stride, d->space, L);
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- the workspace: the upload (lm_score_pack), then on 8 bytes lm_ln [M] doubles, terms [n_slots] doubles (when wanted),
+    // n_oov [M] words: one copy up, one launch, one copy down
+    const size_t in_words = (L.words.size() + 1) & ~(size_t)1, n_terms_out = terms ? L.n_slots : 0;
+    const size_t out_bytes = sizeof(double) * ((size_t)M + n_terms_out) + sizeof(int32_t) * (size_t)M;
+    if (int rc = reserve_all(d, d->lm_io, sizeof(int32_t) * in_words + out_bytes)) return rc;
+    int32_t* w = d->lm_io.as<int32_t>();
+    DEC_HIP(d, hipMemcpyAsync(w, L.words.data(), sizeof(int32_t) * L.words.size(), hipMemcpyHostToDevice, s));
+    LmScoreArgs a{};
+    a.lm = d->lm.view(); a.lm.tab = d->d_tab; a.lm.klm.base = d->d_klm; a.trie_next = d->d_next; a.trie_word = d->d_word;
+    a.C = C; a.order = d->lm.order; a.unk = d->lm.unk; a.bos = d->lm.bos; a.eos = d->lm.eos;
+    a.tok = w; a.slot_first = w + L.off_first; a.slot_len = w + L.off_len; a.slot_sent = w + L.off_sent;
+    a.sent_slot = w + L.off_sent_slot; a.pack_sent = w + L.off_pack;
+    a.lm_ln = reinterpret_cast<double*>(w + in_words); a.terms = terms ? a.lm_ln + M : nullptr;
+    a.n_oov = reinterpret_cast<int32_t*>(a.lm_ln + M + n_terms_out);
+    DEC_HIP(d, launch_lm_score(a, L.n_packs, s));
+    // the results come back into an image of the call's own and reach the caller's arrays only when everything has succeeded
+    std::vector<double> out(out_bytes / sizeof(double) + 1);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), a.lm_ln, out_bytes, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    lm_score_unpack(L, M, out.data(), out.data() + M, reinterpret_cast<const int32_t*>(out.data() + M + n_terms_out), lm_ln, n_words, n_oov,
+                    n_terms, terms, W_stride);
     return DSMI_OK;
 }

@@ -1,5 +1,5 @@
 // The handle behind dsmi_decoder*, shared by decoder.hip (its life, greedy, beam search, the LM) and ctc_tools.hip (forced
-// alignment, phrase search, transcript scoring, token confidence, edit distance).
+// alignment, phrase search, transcript scoring, token confidence, edit distance, LM sentence scoring).
 #pragma once
 #include "common.h"
 #include "lm.h"
@@ -68,6 +68,8 @@ struct dsmi_decoder {
     DevBuf alt_io, alt_out, alt_ws;
     // dsmi_edit_distance: the upload of the launch (int32 words: lens, pool, pairs, waves) and, behind it, the packed results
     DevBuf ed_io;
+    // dsmi_lm_score: the upload of the launch (int32 words: lm_score_pack) and, behind it on 8 bytes, the results
+    DevBuf lm_io;
 };
 
 #define DEC_HIP(d, expr)                                                                  \

@@ -11,6 +11,7 @@
 // The handle itself: decoder.h; the tools over the CTC trellis (align, spot, score) that share it: ctc_tools.hip.
 #include "decoder.h"
 #include "ctc_host.h"      // kCtcMaxLabels: the label limit the trellis kernels' LDS images are sized for
+#include "lmscore.h"       // lm_sentence_ln: dsmi_lm_sentence_ln
 #include <cstring>
 #include "lm.cpp.inc"
 #include "lm_klm.cpp.inc"
@@ -84,7 +85,7 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     free_lm(d);
     if (d->bs_dev) (void)hipFree(d->bs_dev);
     if (d->bs_pin) (void)hipHostFree(d->bs_pin);
-    for (DevBuf* b : {&d->al_io, &d->al_bp, &d->sp_io, &d->sp_tr, &d->sc_io, &d->alt_io, &d->alt_out, &d->alt_ws, &d->ed_io}) b->release();
+    for (DevBuf* b : {&d->al_io, &d->al_bp, &d->sp_io, &d->sp_tr, &d->sc_io, &d->alt_io, &d->alt_out, &d->alt_ws, &d->ed_io, &d->lm_io}) b->release();
     delete d;
 }
 
@@ -707,4 +708,10 @@ extern "C" int dsmi_lm_lookup(const dsmi_lm* h, const int32_t* ids, int n, float
 extern "C" double dsmi_lm_cond_log10(const dsmi_lm* h, const int32_t* ids, int n) {
     if (!h || !ids || n < 1 || n > h->lm.order) return 0.0 / 0.0;
     return (double)dsmi::lm_cond_log10(h->lm.view(), ids, n - 1, ids[n - 1], h->lm.unk);
+}
+extern "C" double dsmi_lm_sentence_ln(const dsmi_lm* h, const int32_t* word_ids, int n, double* terms, int capacity) {
+    if (!h || n < 0 || (n > 0 && !word_ids) || (terms && capacity < lm_score_terms(n))) return 0.0 / 0.0;
+    std::vector<int32_t> ids(word_ids, word_ids + n);
+    for (int32_t& w : ids) if (w < 0 || w >= (int32_t)h->lm.vocab.size()) w = -1;      // (anything outside the file's ids is out of vocabulary)
+    return dsmi::lm_sentence_ln(h->lm, ids.data(), n, terms);
 }

@@ -306,7 +306,8 @@ class Decoder(object):
     def min_risk(self, ids, logps, unit="word"):
         """Minimum-Bayes-risk order of n-best lists.  ``ids[b]``: clip b's K_b hypotheses as label-id sequences; ``logps[b]``:
         their natural-log posteriors (``None`` = infeasible), as ``decode_scored`` returns them -- ``dsmi_score``'s, acoustic
-        only: the language model has no part in the weights.  Per clip ``(order, risks)``: ``risks[i]`` (float64) is the
+        only: the language model has no part in the weights (``BeamCTCDecoder.rescore``'s totals are valid ``logps`` too, and
+        bring it in).  Per clip ``(order, risks)``: ``risks[i]`` (float64) is the
         expected number of word (``unit="word"``: the words between space labels) or character (``"char"``: the labels
         without the space label) errors of hypothesis i, sum_j w_j * distance(i, j), under the weights w = softmax(logps[b])
         (``None`` or -inf: 0; all ``None``: uniform); ``order`` is the stable ascending order of the risks, so ties keep
@@ -494,6 +495,112 @@ class BeamCTCDecoder(Decoder):
         strings, offsets = self._beam_strings(tok, ts, ln)
         ids = [[tok[b, p, :ln[b, p]] for p in range(W)] for b in range(tok.shape[0])]
         return strings, offsets, self.score_ids(probs, ids, sizes), ids
+
+    # ---- LM sentence scoring (dsmi_lm_score): the language model's score of known sentences, n-best rescoring, weight tuning
+    def lm_score_ids(self, ids, terms=False):
+        """The language model's score of sentences given as label-id sequences (no normalisation), all in ONE
+        ``dsmi_lm_score`` call: numpy arrays ``(lm_ln, n_words, n_oov)`` -- the natural-log sentence score as ctcdecode's
+        ``Scorer.get_sent_log_prob`` gives it (``</s>`` included, -1000 for every window that holds an out-of-vocabulary word),
+        the words between space labels, and how many of them the dictionary does not know -- and, with ``terms``, a list of
+        float64 arrays: each sentence's n_words + 1 window terms (2 for no words), which sum to its lm_ln.  ``DsmiError`` when
+        the decoder has no language model."""
+        from .. import _native
+        ids = [np.asarray(t, dtype=np.int32).reshape(-1) for t in ids]
+        longest = max([len(t) for t in ids] + [0])
+        if longest > _native.LM_SCORE_MAX_TOKENS:
+            raise ValueError("sentence of %d labels is longer than %d" % (longest, _native.LM_SCORE_MAX_TOKENS))
+        if not ids:
+            empty = (np.zeros(0), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
+            return empty + ([],) if terms else empty
+        return self._edit_device().lm_score(ids, want_terms=terms)
+
+    def lm_score(self, texts, terms=False):
+        """``lm_score_ids`` of texts, each normalised with ``normalise_transcript``; ``ValueError`` for characters that are
+        not labels.  ``-lm_ln.sum() / (n_words.sum() + len(texts))`` is the natural log of the model's perplexity on them."""
+        return self.lm_score_ids([self.transcript_ids(self.normalise_transcript(t)) for t in texts], terms)     # every check before any GPU work
+
+    def rescore(self, ids, logps, alpha=None, beta=None, eos=True):
+        """Rescore n-best lists with the language model.  ``ids[b]``: clip b's K_b hypotheses as label-id sequences;
+        ``logps[b]``: their natural-log acoustic scores (``None`` = infeasible: -inf), as ``decode_scored`` returns them.
+        Per clip ``(order, totals)`` with ``totals[i] = logp + alpha * lm + beta * n_words`` in float64, in that order of
+        operations -- ``lm`` the hypothesis' ``lm_score_ids`` score, or, with ``eos=False``, that score less its last window's
+        term (the ``</s>`` one): the sum the beam search itself accumulates, which never sees ``</s>`` -- and ``order`` the
+        stable descending order of the totals, so ties keep the incoming order.  ``alpha`` and ``beta`` default to the
+        decoder's own; the language model may be scored for a greedy decoder's list, or with other weights than the search
+        ran with.  All hypotheses of all clips go in ONE ``dsmi_lm_score`` call.  The totals are natural-log scores of the
+        hypotheses and therefore valid ``logps`` for ``min_risk``: its weights then include the language model."""
+        if len(ids) != len(logps):
+            raise ValueError("rescore: hypotheses for %d clips and scores for %d" % (len(ids), len(logps)))
+        for hyps, lps in zip(ids, logps):
+            if len(hyps) != len(lps):
+                raise ValueError("rescore: %d hypotheses and %d scores of one clip" % (len(hyps), len(lps)))
+        alpha = float(self.alpha if alpha is None else alpha)
+        beta = float(self.beta if beta is None else beta)
+        lm, n_words = self._lm_terms([t for hyps in ids for t in hyps], eos)
+        out, at = [], 0
+        for hyps, lps in zip(ids, logps):
+            K = len(hyps)
+            lp = np.array([-np.inf if v is None else float(v) for v in lps], dtype=np.float64)
+            totals = lp + alpha * lm[at:at + K] + beta * n_words[at:at + K].astype(np.float64)
+            out.append((np.argsort(-totals, kind="stable"), totals))
+            at += K
+        return out
+
+    def _lm_terms(self, flat, eos):
+        """(lm float64 [N], n_words int32 [N]) of N hypotheses: ``rescore``'s ``lm``."""
+        if eos:
+            lm, n_words, _ = self.lm_score_ids(flat)
+            return lm, n_words
+        lm, n_words, _, terms = self.lm_score_ids(flat, terms=True)
+        return lm - np.array([t[-1] for t in terms], dtype=np.float64).reshape(len(flat)), n_words
+
+    def decode_rescored(self, probs, sizes=None, n_best=None, alpha=None, beta=None):
+        """``decode_scored``'s hypotheses (exact acoustic ``dsmi_score`` likelihoods) in the order of ``rescore``:
+        ``(strings, offsets, totals, logps)``, each clip's lists by descending ``logp + alpha * lm + beta * n_words``."""
+        strings, offsets, logps, ids = self._decode_scored_ids(probs, sizes, n_best)
+        out_s, out_o, out_t, out_l = [], [], [], []
+        for b, (order, totals) in enumerate(self.rescore(ids, logps, alpha, beta)):
+            out_s.append([strings[b][i] for i in order])
+            out_o.append([offsets[b][i] for i in order])
+            out_t.append([float(totals[i]) for i in order])
+            out_l.append([logps[b][i] for i in order])
+        return out_s, out_o, out_t, out_l
+
+    def tune_lm_weights(self, probs, sizes, references, alphas, betas, n_best=8, unit="word", eos=True):
+        """Tune alpha and beta on clips with known transcripts.  ONE n-best search at the decoder's current weights
+        (``decode_scored``: exact acoustic scores), ONE ``dsmi_lm_score`` call over every hypothesis, ONE
+        ``dsmi_edit_distance`` call of every hypothesis against its clip's reference (normalised with
+        ``normalise_transcript``; ``unit`` "word" or "char"), then the grid in numpy: at each (alpha, beta) every clip takes
+        the hypothesis of the largest ``rescore`` total (the first of equals) and its errors are summed.  Returns a dict:
+        ``errors`` and ``ref_tokens`` int64 [len(alphas), len(betas)], ``best_index`` (i, j) -- the fewest errors, then the
+        lowest alpha index, then the lowest beta index -- ``best`` (alphas[i], betas[j]) and ``error_rate`` there (None when
+        the references hold no token).  It tunes a RESCORING of the current search's n-best lists, not the search's own
+        pruning: a hypothesis the search at its current weights dropped cannot win at any grid point."""
+        references = [self.normalise_transcript(t) for t in references]
+        if len(references) != len(probs):
+            raise ValueError("tune_lm_weights: %d references and a batch of %d" % (len(references), len(probs)))
+        alphas = np.asarray(alphas, dtype=np.float64).reshape(-1)
+        betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+        strings, _, logps, ids = self._decode_scored_ids(probs, sizes, n_best)
+        flat = [t for hyps in ids for t in hyps]
+        clip = np.array([b for b, hyps in enumerate(ids) for _ in hyps], dtype=np.int64)
+        lm, n_words = self._lm_terms(flat, eos)
+        counts, ref_lens = self.error_counts([references[b] for b in clip], [s for row in strings for s in row], unit)
+        dist = counts[:, 0].astype(np.int64)
+        lp = np.array([-np.inf if v is None else float(v) for row in logps for v in row], dtype=np.float64)
+        starts = np.concatenate(([0], np.cumsum([len(hyps) for hyps in ids])))
+        errors = np.zeros((len(alphas), len(betas)), dtype=np.int64)
+        nw = n_words.astype(np.float64)
+        for i, a in enumerate(alphas):
+            for j, bt in enumerate(betas):
+                totals = lp + a * lm + bt * nw
+                errors[i, j] = sum(int(dist[s + int(np.argmax(totals[s:e]))]) for s, e in zip(starts[:-1], starts[1:]) if e > s)
+        total_ref = int(sum(int(ref_lens[s]) for s, e in zip(starts[:-1], starts[1:]) if e > s))
+        best = np.unravel_index(int(np.argmin(errors)), errors.shape) if errors.size else (0, 0)
+        i, j = int(best[0]), int(best[1])
+        return {"errors": errors, "ref_tokens": np.full(errors.shape, total_ref, dtype=np.int64), "best_index": (i, j),
+                "best": (float(alphas[i]), float(betas[j])) if errors.size else None,
+                "error_rate": int(errors[i, j]) / total_ref if errors.size and total_ref else None}
 
     def _decode_best_ids(self, probs, sizes=None):
         """(the first beam's text of each clip, None, its label ids)"""

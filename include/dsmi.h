@@ -696,12 +696,51 @@ int dsmi_edit_plan(const int32_t* len_a, const int32_t* len_b, int N, int32_t* o
 int dsmi_edit_distance(dsmi_decoder* d, const int32_t* seqs_host, const int32_t* seq_lens_host, int M, int L_stride,
                        const int32_t* pair_a_host, const int32_t* pair_b_host, int N, int32_t* counts_host, void* stream);
 
+/* ---- LM sentence scoring: the n-gram score of known sentences with the tables dsmi_decoder_set_lm left on the device -- to
+ * rescore an n-best list, to score arbitrary texts, and to tune alpha and beta on the n-best lists of one search.
+ * A pool of M label-id sequences: seqs_host [M][L_stride] with seq_lens_host [M], the layout of dsmi_score's candidates and of
+ * dsmi_edit_distance's pool; the ids are the decoder's labels.  Nothing past seq_lens_host[m] in a row is read as a token.
+ * Words.  A word is a maximal run of tokens other than the space label: leading, trailing and doubled spaces make no empty
+ * words.  A decoder whose labels have no space treats every sequence as one word.  A word's id is what the dictionary trie
+ * gives for its labels, or -1 (out of vocabulary) if an arc is missing or no word ends at its node; n_oov_host[m] counts the
+ * words with id -1, n_words_host[m] all of them.
+ * Terms (the contract: ctcdecode Scorer::get_sent_log_prob, window for window).  With s = [<s>] * (order - 1) + words + [</s>],
+ * or [<s>] * order + [</s>] for no words, term i is the window s[i .. i + order): -1000 (OOV_SCORE) if any member is out of
+ * vocabulary or <unk>, else (double)log10 p(last | the others) / (double)0.4342944819f, the log10 by back-off in float32 as
+ * dsmi_lm_cond_log10 gives it.  n_terms_host[m] = n_words + 1, or 2 for no words.  terms_host[m][0 .. n_terms) holds them
+ * ([M][W_stride]; entries behind are left alone); terms_host may be NULL, and then W_stride is ignored.  lm_ln_host[m] is their
+ * sum in float64, in window order, from 0.0.
+ * Every result is exact: the bits dsmi_lm_sentence_ln gives on the host, whatever else is in the call (batch-invariant,
+ * deterministic).  One kernel launch whatever M.  Synchronises `stream`.
+ * Refused with nothing written and nothing launched: DSMI_ERR_INVALID for a decoder without a language model, M <= 0, a NULL
+ * array other than terms_host (seqs_host may be NULL only when L_stride == 0), a length outside 0 .. L_stride, a token outside
+ * 0 .. n_labels-1 or equal to the blank; DSMI_ERR_CAPACITY for L_stride > DSMI_LM_SCORE_MAX_TOKENS, M * L_stride > 2^24, or
+ * terms_host given with W_stride below the largest n_terms.
+ *
+ * dsmi_lm_score_plan (host only) is the word segmentation dsmi_lm_score uses, with `space` the space label's id (any value no
+ * token has: one word per non-empty row): n_words[m], and the first token and the length of each word in word_first /
+ * word_len [M][W_stride].  Returns the largest n_words; < 0 with nothing written for NULL arguments (seqs_host may be NULL
+ * only when L_stride == 0, the word arrays only when W_stride == 0), M <= 0, a negative L_stride or W_stride, a length outside
+ * 0 .. L_stride, or a row of more than W_stride words.
+ *
+ * dsmi_lm_sentence_ln (host only, on a dsmi_lm handle) is Scorer::get_sent_log_prob with its terms exposed: the sum for the n
+ * words word_ids (the file's own ids; anything outside them, such as -1, is out of vocabulary), and the n + 1 terms (2 for
+ * n = 0) in terms[0 .. capacity) unless terms is NULL.  NaN for a NULL handle, n < 0, NULL word_ids with n > 0, or a capacity
+ * below the number of terms. */
+#define DSMI_LM_SCORE_MAX_TOKENS 4096
+typedef struct dsmi_lm dsmi_lm;      /* (the host-only handle: below) */
+int dsmi_lm_score_plan(const int32_t* seqs_host, const int32_t* seq_lens_host, int M, int L_stride, int space,
+                       int32_t* n_words, int32_t* word_first, int32_t* word_len, int W_stride);
+int dsmi_lm_score(dsmi_decoder* d, const int32_t* seqs_host, const int32_t* seq_lens_host, int M, int L_stride,
+                  double* lm_ln_host, int32_t* n_words_host, int32_t* n_oov_host,
+                  int32_t* n_terms_host, double* terms_host, int W_stride, void* stream);
+double dsmi_lm_sentence_ln(const dsmi_lm* lm, const int32_t* word_ids, int n, double* terms, int capacity);
+
 /* ---- Host-only view of a language model file (no GPU involved): what dsmi_decoder_set_lm would load.
  * kind: 0 ARPA text, 1 KenLM probing binary, 2 KenLM trie binary.  Word ids are the file's own (KenLM's WordIndex for
  * binaries, <unk> = 0).  dsmi_lm_lookup: 1 = the n-gram ids[0..n) is in the model (its log10 probability and back-off
  * weight are returned), 0 = absent.  dsmi_lm_cond_log10 = log10 p(ids[n-1] | ids[0..n-1)) by back-off, the quantity the
  * beam search's scorer adds (ctcdecode Scorer::get_log_cond_prob / KenLM BaseScore). */
-typedef struct dsmi_lm dsmi_lm;
 int dsmi_lm_open(const char* path, dsmi_lm** out);
 void dsmi_lm_close(dsmi_lm* lm);
 const char* dsmi_lm_last_error(const dsmi_lm* lm);

@@ -16,6 +16,9 @@
 //   host_fuzz editcheck SEED N  the host half of dsmi_edit_distance (edit_host.h: edit_check, edit_plan, edit_pack, edit_unpack) on N random
 //                             calls held in exactly sized heap arrays, against the rules written out below; what is refused on the
 //                             numbers alone is called with null arrays
+//   host_fuzz lmscore SEED N    the host half of dsmi_lm_score (lm_score_host.h: lm_score_check, lm_score_plan, lm_score_pack, lm_score_unpack)
+//                             on N random calls held in exactly sized heap arrays, against the rules written out below; what is
+//                             refused on the numbers alone is called with null arrays
 #define __host__
 #define __device__
 #include <cmath>
@@ -32,6 +35,7 @@
 #include "gate_plan.h"
 #include "ctc_host.h"
 #include "edit_host.h"
+#include "lm_score_host.h"
 
 using namespace dsmi;
 
@@ -726,6 +730,161 @@ static int run_editcheck(int argc, char** argv) {
     return 0;
 }
 
+// ---- lmscore: the rules of include/dsmi.h written out plainly, beside lm_score_host.h -----------------------------------------
+#define LMS_FAIL(what) do { std::fprintf(stderr, "lmscore: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 12; } while (0)
+
+static int run_lmscore(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long slots_checked = 0, refused = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        std::string err;
+        const int32_t* none = nullptr;
+        const int C = 5, blank = 0, space = rng() % 8 == 0 ? -2 : 4;
+        // ---- refused on the numbers alone: no array is there to read
+        {
+            const int big = 1 + (int)(rng() % 1000);
+            if (lm_score_check(false, none, none, 3, 4, C, blank, space, false, 0, err) != DSMI_ERR_INVALID || err.empty()) LMS_FAIL("no language model");
+            if (lm_score_check(true, none, none, rng() % 2 ? 0 : -big, 4, C, blank, space, false, 0, err) != DSMI_ERR_INVALID) LMS_FAIL("M <= 0");
+            if (lm_score_check(true, none, none, 3, -big, C, blank, space, false, 0, err) != DSMI_ERR_INVALID) LMS_FAIL("negative L_stride");
+            if (lm_score_check(true, none, none, 3, DSMI_LM_SCORE_MAX_TOKENS + big, C, blank, space, true, 0, err) != DSMI_ERR_CAPACITY || err.find("DSMI_LM_SCORE_MAX_TOKENS") == std::string::npos) LMS_FAIL("L_stride above the limit");
+            const int Ls = 1 + (int)(rng() % DSMI_LM_SCORE_MAX_TOKENS);
+            if (lm_score_check(true, none, none, (int)(((int64_t)1 << 24) / Ls) + big, Ls, C, blank, space, false, 0, err) != DSMI_ERR_CAPACITY) LMS_FAIL("M * L_stride above 2^24");
+            if (lm_score_check(true, none, none, INT32_MAX, DSMI_LM_SCORE_MAX_TOKENS, C, blank, space, true, -1, err) != DSMI_ERR_CAPACITY) LMS_FAIL("the largest numbers");
+        }
+        // ---- a random call: few labels, many spaces, rows around the pack size, garbage behind every length
+        const int M = 1 + (int)(rng() % 40);
+        const int edges[8] = {0, 1, 2, 7, 24, 60, 520, 1100};
+        const int L_stride = edges[rng() % 8] + (int)(rng() % 3);
+        std::vector<int32_t> seqs = exact((size_t)M * (size_t)L_stride), lens = exact((size_t)M);
+        const unsigned space_in = 2 + rng() % 3;
+        for (auto& v : seqs) v = rng() % space_in == 0 ? 4 : 1 + (int32_t)(rng() % 3);
+        for (auto& v : lens) v = rng() % 5 == 0 ? 0 : (int32_t)(rng() % (unsigned)(L_stride + 1));
+        // the words by the definition: one begins at every token that is no space and has a space, or nothing, in front of it
+        std::vector<std::vector<std::pair<int, int>>> words((size_t)M);
+        int most = 0;
+        for (int m = 0; m < M; ++m) {
+            const int32_t* row = seqs.data() + (size_t)m * (size_t)L_stride;
+            for (int k = 0; k < lens[(size_t)m]; ++k) {
+                if (row[k] == space) continue;
+                if (k == 0 || row[k - 1] == space) words[(size_t)m].push_back({k, 0});
+                ++words[(size_t)m].back().second;
+            }
+            most = std::max(most, (int)words[(size_t)m].size());
+        }
+        const int most_terms = most > 0 ? most + 1 : 2;
+        const bool terms = rng() % 2 == 0;
+        const int W_stride = terms ? most_terms - 1 + (int)(rng() % 3) : (rng() % 2 ? 0 : -5);
+        const int spoil = (int)(rng() % 7);
+        int want = terms && W_stride < most_terms ? DSMI_ERR_CAPACITY : DSMI_OK;
+        if (spoil == 1) { lens[rng() % (unsigned)M] = rng() % 2 ? L_stride + 1 + (int32_t)(rng() % 3) : -1 - (int32_t)(rng() % 3); want = DSMI_ERR_INVALID; }
+        if (spoil == 2) {
+            std::vector<int> rows;
+            for (int m = 0; m < M; ++m) if (lens[(size_t)m] > 0) rows.push_back(m);
+            if (!rows.empty()) {
+                const int m = rows[rng() % rows.size()];
+                const int32_t bad[4] = {blank, C, -1, C + 7};
+                seqs[(size_t)m * (size_t)L_stride + rng() % (unsigned)lens[(size_t)m]] = bad[rng() % 4];
+                want = DSMI_ERR_INVALID;
+            }
+        }
+        const int rc = lm_score_check(true, ptr_or_null(seqs), lens.data(), M, L_stride, C, blank, space, terms, W_stride, err);
+        if (rc != want) LMS_FAIL("a call's verdict");
+        if (rc != DSMI_OK) {
+            if (err.empty()) LMS_FAIL("a refusal without a message");
+            ++refused;
+            continue;
+        }
+        // ---- the plan: the words by the definition; nothing written past a row's count, past the arrays, or on a refusal
+        {
+            const int Ws = most + (int)(rng() % 2);
+            std::vector<int32_t> nw = exact((size_t)M + 1, -7), wf = exact((size_t)M * (size_t)Ws + 1, -7), wl = exact((size_t)M * (size_t)Ws + 1, -7);
+            if (lm_score_plan(ptr_or_null(seqs), lens.data(), M, L_stride, space, nw.data(), wf.data(), wl.data(), Ws) != most) LMS_FAIL("plan: the largest n_words");
+            if (nw[(size_t)M] != -7 || wf[(size_t)M * (size_t)Ws] != -7 || wl[(size_t)M * (size_t)Ws] != -7) LMS_FAIL("plan: a write past its arrays");
+            for (int m = 0; m < M; ++m) {
+                const auto& w = words[(size_t)m];
+                if (nw[(size_t)m] != (int)w.size()) LMS_FAIL("plan: n_words");
+                for (int k = 0; k < Ws; ++k) {
+                    const int32_t f = wf[(size_t)m * (size_t)Ws + (size_t)k], l = wl[(size_t)m * (size_t)Ws + (size_t)k];
+                    if (k < (int)w.size() ? (f != w[(size_t)k].first || l != w[(size_t)k].second) : (f != -7 || l != -7)) LMS_FAIL("plan: a word's span");
+                }
+            }
+            if (most > 0) {
+                std::vector<int32_t> nw2 = exact((size_t)M, -7), wf2 = exact((size_t)M * (size_t)(most - 1), -7), wl2 = wf2;
+                if (lm_score_plan(ptr_or_null(seqs), lens.data(), M, L_stride, space, nw2.data(), wf2.data(), wl2.data(), most - 1) >= 0) LMS_FAIL("plan: a W_stride too small");
+                for (int32_t v : nw2) if (v != -7) LMS_FAIL("plan: a refusal that wrote");
+                for (int32_t v : wf2) if (v != -7) LMS_FAIL("plan: a refusal that wrote");
+            }
+        }
+        // ---- the packing
+        LmScoreLaunch L;
+        lm_score_pack(ptr_or_null(seqs), lens.data(), M, L_stride, space, L);
+        size_t n_tok = 0, n_slots = 0;
+        for (int m = 0; m < M; ++m) {
+            for (const auto& w : words[(size_t)m]) n_tok += (size_t)w.second;
+            n_slots += words[(size_t)m].empty() ? 2 : words[(size_t)m].size() + 1;
+        }
+        if (L.n_tok != n_tok || L.n_slots != n_slots || (int)L.order.size() != M) LMS_FAIL("pack: the totals");
+        if (L.words.size() != n_tok + 3 * n_slots + (size_t)M + 1 + (size_t)L.n_packs + 1) LMS_FAIL("pack: the upload's size");
+        const int32_t* tok = L.words.data();
+        const int32_t *s_first = tok + L.off_first, *s_len = tok + L.off_len, *s_sent = tok + L.off_sent, *sent_slot = tok + L.off_sent_slot, *pack_sent = tok + L.off_pack;
+        std::vector<int> seen((size_t)M, 0);
+        size_t slot = 0, at_tok = 0;
+        for (int s = 0; s < M; ++s) {
+            const int m = L.order[(size_t)s];
+            if (m < 0 || m >= M || seen[(size_t)m]++) LMS_FAIL("pack: the order is no permutation");
+            const auto& w = words[(size_t)m];
+            if (L.n_words[(size_t)m] != (int)w.size()) LMS_FAIL("pack: n_words");
+            if (s > 0) {
+                const int p = L.order[(size_t)s - 1];
+                if (words[(size_t)p].size() < w.size() || (words[(size_t)p].size() == w.size() && p > m)) LMS_FAIL("pack: not by n_words descending, then index");
+            }
+            if (sent_slot[s] != (int32_t)slot) LMS_FAIL("pack: a sentence's first slot");
+            const int32_t* row = seqs.data() + (size_t)m * (size_t)L_stride;
+            for (const auto& sp : w) {
+                if (s_sent[slot] != s || s_len[slot] != sp.second || s_first[slot] != (int32_t)at_tok) LMS_FAIL("pack: a word's slot");
+                if (!std::equal(row + sp.first, row + sp.first + sp.second, tok + at_tok)) LMS_FAIL("pack: a word's tokens");
+                at_tok += (size_t)sp.second; ++slot;
+            }
+            if (w.empty()) { if (s_sent[slot] != s || s_len[slot] != kLmSlotBos) LMS_FAIL("pack: the <s> slot of an empty sentence"); ++slot; }
+            if (s_sent[slot] != s || s_len[slot] != kLmSlotEos) LMS_FAIL("pack: the </s> slot");
+            ++slot;
+        }
+        if (sent_slot[M] != (int32_t)n_slots || slot != n_slots || at_tok != n_tok) LMS_FAIL("pack: the slots do not cover the call");
+        if (L.n_packs < 1 || pack_sent[0] != 0 || pack_sent[L.n_packs] != M) LMS_FAIL("pack: the packs do not cover the sentences");
+        for (int p = 0; p < L.n_packs; ++p) {
+            const int s0 = pack_sent[p], s1 = pack_sent[p + 1];
+            if (s1 <= s0) LMS_FAIL("pack: an empty pack");
+            const int n = sent_slot[s1] - sent_slot[s0];
+            if (n > kLmScoreMaxSlots || (n > kLmScoreThreads && s1 - s0 != 1)) LMS_FAIL("pack: too many slots");
+            // a pack is full: the next sentence would not have fitted
+            if (s1 < M && n + (sent_slot[s1 + 1] - sent_slot[s1]) <= kLmScoreThreads) LMS_FAIL("pack: a pack with room left");
+        }
+        // ---- the unpacking: results coded by sentence and slot come back under the caller's indices, nothing else is written
+        std::vector<double> d_ln((size_t)M), d_terms(n_slots);
+        std::vector<int32_t> d_oov = exact((size_t)M);
+        for (int s = 0; s < M; ++s) { d_ln[(size_t)s] = 1000.0 + L.order[(size_t)s]; d_oov[(size_t)s] = 7 * L.order[(size_t)s]; }
+        for (size_t g = 0; g < n_slots; ++g) d_terms[g] = 0.5 + (double)g;
+        const size_t Wt = terms ? (size_t)W_stride : 0;
+        std::vector<double> ln((size_t)M + 1, -7.0), tm((size_t)M * Wt + 1, -7.0);
+        std::vector<int32_t> nw = exact((size_t)M + 1, -7), no = exact((size_t)M + 1, -7), nt = exact((size_t)M + 1, -7);
+        ln.shrink_to_fit(); tm.shrink_to_fit();
+        lm_score_unpack(L, M, d_ln.data(), d_terms.data(), d_oov.data(), ln.data(), nw.data(), no.data(), nt.data(), terms ? tm.data() : nullptr, W_stride);
+        if (ln[(size_t)M] != -7.0 || tm[(size_t)M * Wt] != -7.0 || nw[(size_t)M] != -7 || no[(size_t)M] != -7 || nt[(size_t)M] != -7) LMS_FAIL("unpack: a write past an array");
+        for (int s = 0; s < M; ++s) {
+            const int m = L.order[(size_t)s], n = (int)words[(size_t)m].size(), want_terms = n > 0 ? n + 1 : 2;
+            if (ln[(size_t)m] != 1000.0 + m || no[(size_t)m] != 7 * m || nw[(size_t)m] != n || nt[(size_t)m] != want_terms) LMS_FAIL("unpack: a sentence's results");
+            for (size_t t = 0; t < Wt; ++t) {
+                const double v = tm[(size_t)m * Wt + t];
+                if ((int)t < want_terms ? v != 0.5 + (double)(sent_slot[s] + (int)t) : v != -7.0) LMS_FAIL("unpack: a sentence's terms");
+            }
+            slots_checked += want_terms;
+        }
+    }
+    std::printf("%d lmscore calls ok, %ld refused, %ld slots checked\n", reps, refused, slots_checked);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
@@ -734,6 +893,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]]\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]]\n");
     return 2;
 }
