@@ -41,12 +41,18 @@ class _StreamingSession(object):
     model gives the final text, the spectrograms of every part.  With ``lm_partials`` also the utterance's beam search,
     carried from part to part (a ``NativeBeamStream`` of ``beam_decoder``), and its best text after the last part.  A session
     whose source has another rate than the model's owns a ``NativeResampler`` (``resampler``; ``source`` = (rate, method)); the
-    converted samples that a pass did not take wait in ``pending`` (a float64 CUDA tensor)."""
+    converted samples that a pass did not take wait in ``pending`` (a float64 CUDA tensor).  With ``watching`` (a phrase watch,
+    ``enable_streaming(watch=...)``) also the utterance's phrase search, carried from part to part (``spot``, a
+    ``NativeSpotStream``), the detections nobody has taken yet and the ordinal of the utterance under way."""
 
-    def __init__(self, secondary_model, string_parts, lm_partials=False):
+    def __init__(self, secondary_model, string_parts, lm_partials=False, watching=False):
         self.secondary_model = secondary_model
         self.string_parts = string_parts
         self.lm_partials = lm_partials
+        self.watching = watching
+        self.spot = None
+        self.detections = []
+        self.utterance = 0
         self.beam = None
         self.beam_decoder = None
         self.resampler = None
@@ -61,8 +67,16 @@ class _StreamingSession(object):
         self.pending = None
         if self.beam is not None:
             self.beam.reset()
+        if self.spot is not None:
+            self.spot.reset()
         if self.resampler is not None:
             self.resampler.reset()
+
+    def take_detections(self):
+        """The phrase watch's detections since the last call, in firing order: ``(utterance_ordinal, phrase, start_s, end_s,
+        confidence, logp)``, seconds from the utterance's first output frame."""
+        found, self.detections = self.detections, []
+        return found
 
     def set_source(self, parser, sample_rate, resample):
         """The rate of the parts to come (None, or the model's own rate: they are taken as they are) and how to convert;
@@ -85,6 +99,9 @@ class _StreamingSession(object):
         if self.beam is not None:
             self.beam.close()
             self.beam = None
+        if self.spot is not None:
+            self.spot.close()
+            self.spot = None
         if self.resampler is not None:
             self.resampler.close()
             self.resampler = None
@@ -105,6 +122,9 @@ class LiveSessionHandle:
     def __init__(self, endpointer, resampler, passes, session, dtype):
         self.endpointer, self.resampler, self.passes, self.session, self.dtype = endpointer, resampler, passes, session, dtype
 
+    def take_detections(self):
+        return self.session.take_detections()
+
     def close(self):
         self.endpointer.close()
         if self.resampler is not None:
@@ -122,6 +142,9 @@ class StreamingSessionHandle(object):
         self.state = state
 
     text = property(lambda self: self.state.text)
+
+    def take_detections(self):
+        return self.state.take_detections()
 
     def close(self):
         self.stream.close()
@@ -225,6 +248,7 @@ class DanSpeechRecognizer(object):
         self.alpha, self.beta, self.beam_width = alpha, beta, beam_width
         self.model = self.model_name = self.labels = self.audio_config = self.audio_parser = None
         self._session = None
+        self._watch_spec = self._watch = None      # enable_streaming(watch=...): (phrases, ids, confidence, settle frames), its NativeSpotWatch
         self._side_streams = {}
         self._replicas = []
         if model_name:
@@ -915,7 +939,8 @@ class DanSpeechRecognizer(object):
         return res
 
     # ---- utterances that arrive in parts ----------------------------------------------------------------------------
-    def enable_streaming(self, secondary_model=None, return_string_parts=True, lm_partials=False, sample_rate=None, resample="polyphase"):
+    def enable_streaming(self, secondary_model=None, return_string_parts=True, lm_partials=False, sample_rate=None, resample="polyphase",
+                         watch=None, watch_confidence=0.5, watch_settle_s=0.5):
         """Streaming mode.  ``sample_rate``: the rate of the parts ``streaming_transcribe`` will be given when it is not the
         model's (telephony's 8 kHz, a sound card's 44.1 or 48 kHz): each part is then converted on the GPU as it arrives
         (``resample``: "polyphase" or "ratecv"), with the state carried from part to part, so that the converted parts are bit
@@ -923,15 +948,33 @@ class DanSpeechRecognizer(object):
         from part to part: every middle part then returns the best beam's text of the WHOLE utterance so far -- language-model
         hypotheses revise earlier words, so ``return_string_parts`` does not apply to them -- and the final text, when no
         secondary model gives it, comes from the carried search (equal to the full decode it replaces).  The running greedy
-        text and the final-text rules are those of ``lm_partials=False``, which is the reference's behaviour."""
+        text and the final-text rules are those of ``lm_partials=False``, which is the reference's behaviour.
+        ``watch``: a list of phrases to listen for in every session (``Decoder.watch``: normalised and checked as
+        ``find_phrases`` does it, ``ValueError`` before any GPU work).  Every session then carries a phrase search of its own on
+        the one shared watch; all due sessions' searches advance in one launch after the model pass, over exactly the rows the
+        pass produced.  A window counts when its per-frame geometric mean probability is at least ``watch_confidence`` and is
+        reported ``watch_settle_s`` seconds after its end (unless a better window that meets it has come up by then, or the
+        utterance ends first).  Detections wait on the session for ``take_detections()``: ``(utterance_ordinal, phrase, start_s,
+        end_s, confidence, logp)`` in seconds from the utterance's first output frame, ``confidence = exp(logp / frames)`` as
+        ``find_phrases`` reports it.  What the streaming calls return is the same with and without a watch."""
         if lm_partials and not isinstance(self.decoder, BeamCTCDecoder):
             raise ValueError("lm_partials needs a language-model decoder (update_decoder(lm=...)); this recogniser decodes greedily")
+        spec = None
+        if watch is not None:
+            phrases = [self.decoder.normalise_transcript(p) for p in watch]
+            ids = [self.decoder.phrase_ids(p) for p in watch]
+            if not ids:
+                raise ValueError("watch: at least one phrase")
+            if not watch_settle_s > 0:
+                raise ValueError("watch_settle_s must be positive")
+            spec = (phrases, ids, float(watch_confidence), max(1, int(round(watch_settle_s / self.frame_seconds()))))
+        self._watch_spec, self._watch = spec, None
         if secondary_model:
             secondary_model = secondary_model.to(self.device)
             secondary_model.eval()
         if self._session:
             self._session.close()
-        self._session = _StreamingSession(secondary_model or None, bool(return_string_parts), bool(lm_partials))
+        self._session = _StreamingSession(secondary_model or None, bool(return_string_parts), bool(lm_partials), spec is not None)
         self.greedy_decoder = GreedyDecoder(labels=self.labels, blank_index=self.labels.index('_'))
         self.audio_parser = InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index())
         self.set_streaming_source(sample_rate, resample)
@@ -947,6 +990,7 @@ class DanSpeechRecognizer(object):
         if self._session:
             self._session.close()
         self._session = _StreamingSession(kept, False)
+        self._watch_spec = self._watch = None
 
     def reset_streaming_params(self):
         if self._session:
@@ -989,7 +1033,7 @@ class DanSpeechRecognizer(object):
         native = getattr(self.model, "_native", None)
         if native is None:
             raise RuntimeError("the streaming model runs only on an MI355X: call model.to('cuda') first (no CPU path)")
-        state = _StreamingSession(self._session.secondary_model, self._session.string_parts, self._session.lm_partials)
+        state = _StreamingSession(self._session.secondary_model, self._session.string_parts, self._session.lm_partials, self._session.watching)
         # the resamplers of all sessions belong to ONE frontend (the engine's streaming parser's): one push_many serves them all
         state.set_source(self.audio_parser, sample_rate, resample)
         return StreamingSessionHandle(InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index()),
@@ -1145,6 +1189,37 @@ class DanSpeechRecognizer(object):
         for (ses, _), s in zip(items, strings):
             ses.beam_text = s[0]
 
+    def take_detections(self):
+        """The phrase watch's detections of ``streaming_transcribe``'s own session since the last call (``enable_streaming``)."""
+        return self._session.take_detections() if self._session else []
+
+    def _advance_watch(self, items):
+        """The phrase watch: advance the carried searches of several sessions in ONE launch, [(session state, the rows the pass
+        appended to its outputs or None, is_last)], and queue what fired on each session.  The last part flushes the search and
+        resets it for the session's next utterance."""
+        from . import _native
+        if not items:
+            return
+        phrases, ids, confidence, settle = self._watch_spec
+        if self._watch is None:
+            self._watch = self.greedy_decoder.watch_ids(ids, confidence, settle, self._device_index())
+        for ses, _, _ in items:
+            if ses.spot is None or ses.spot.watch is not self._watch:
+                if ses.spot is not None:
+                    ses.spot.close()
+                ses.spot = _native.NativeSpotStream(self._watch)
+        found, counts = _native.NativeSpotStream.advance_many_counts([ses.spot for ses, _, _ in items], [rows for _, rows, _ in items],
+                                                                     [last for _, _, last in items], _native.SPOT_MAX_HITS)
+        frame_s = self.frame_seconds()
+        for (ses, _, last), events, count in zip(items, found, counts):
+            for k, a, e, lp, _ in events:
+                ses.detections.append((ses.utterance, phrases[k], a * frame_s, e * frame_s, float(np.exp(lp / (e - a))), lp))
+            if int(count.max()) > _native.SPOT_MAX_HITS:
+                warnings.warn("phrase watch: more than %d detections of one phrase in one part; the later ones were dropped" % _native.SPOT_MAX_HITS)
+            if last:
+                ses.spot.reset()
+                ses.utterance += 1
+
     def streaming_transcribe_many(self, sessions, recordings, is_last, is_first, take=None, flush=None):
         """``streaming_transcribe`` for several sessions (``new_streaming_session``) at once, each on its next part of its own
         utterance; the parts' spectrograms and the model pass run batched over all sessions.  -> one string per session, each
@@ -1183,6 +1258,8 @@ class DanSpeechRecognizer(object):
             if ses.lm_partials and (k in probs or is_last[k]):
                 lm_items.append((ses, probs.get(k)))
         self._advance_lm_partials(lm_items)          # every due session's search in one launch, last parts included
+        self._advance_watch([(sessions[k].state, probs[k] if k in probs and not is_first[k] else None, is_last[k]) for k in range(n)
+                             if sessions[k].state.watching and ((k in probs and not is_first[k]) or is_last[k])])
         said = []
         for k in range(n):
             ses = sessions[k].state
@@ -1211,6 +1288,8 @@ class DanSpeechRecognizer(object):
             spect = spect.view(1, 1, spect.size(0), spect.size(1)).to(self.device)
             probs = self.model(spect, is_first, is_last)
             if is_first:
+                if ses.watching and is_last:
+                    self._advance_watch([(ses, None, True)])
                 return ""
             ses.outputs.append(probs)
             piece = ses.extend_text(self.greedy_decoder.decode(probs)[0][0][0])
@@ -1219,6 +1298,8 @@ class DanSpeechRecognizer(object):
             self._advance_lm_partials([(ses, probs)])
             if len(spect) != 0 and ses.beam_text is not None:
                 said = ses.beam_text
+        if ses.watching and (probs is not None or is_last):
+            self._advance_watch([(ses, probs, is_last)])
         if not is_last:
             return said
         return self._final_text(ses) if len(ses.text) > 1 else ""

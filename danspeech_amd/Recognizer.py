@@ -137,13 +137,18 @@ class Recognizer(object):
         return parallel.recognize_sharded(eng, audio_list, dist.get_rank(), dist.get_world_size(), dev)
 
     # ---- real-time streaming (Recognizer.py:499-720) without the microphone -----------------------------
-    def enable_real_time_streaming(self, streaming_model, secondary_model=None, string_parts=True, lm_partials=False):
+    def enable_real_time_streaming(self, streaming_model, secondary_model=None, string_parts=True, lm_partials=False, watch=None,
+                                   watch_confidence=0.5, watch_settle_s=0.5):
         """Recognizer.py:499-533: switch to a unidirectional streaming model (e.g.
         ``pretrained_models.GPUStreamingRNN``), optionally with a secondary model for the final text.  ``lm_partials``
         (needs a language model): every middle output is the language-model decoder's best text of the whole utterance so
-        far, from a beam search carried from part to part (``DanSpeechRecognizer.enable_streaming``)."""
+        far, from a beam search carried from part to part (``DanSpeechRecognizer.enable_streaming``).  ``watch``: phrases to
+        listen for in every stream -- a name, a command, a wake word; ``stream_recording``, ``stream_recordings`` and
+        ``stream_live`` then report each occurrence to their ``on_detection`` callback ``watch_settle_s`` seconds after it was
+        said, when its per-frame confidence is at least ``watch_confidence`` (``DanSpeechRecognizer.enable_streaming``)."""
         self.update_model(streaming_model)
-        self.danspeech_recognizer.enable_streaming(secondary_model, string_parts, lm_partials)
+        self.danspeech_recognizer.enable_streaming(secondary_model, string_parts, lm_partials, watch=watch, watch_confidence=watch_confidence,
+                                                   watch_settle_s=watch_settle_s)
         self.stream = True
 
     def disable_real_time_streaming(self, keep_secondary_model_loaded=False):
@@ -154,7 +159,14 @@ class Recognizer(object):
         else:
             print("No stream is running for the Recognizer")
 
-    def stream_recording(self, audio_data, chunk_samples=None, sample_rate=None, resample="polyphase"):
+    @staticmethod
+    def _report(on_detection, index, session):
+        """Hand the detections that wait on ``session`` to the callback (without one they are dropped)."""
+        for ordinal, phrase, start_s, end_s, confidence, logp in session.take_detections():
+            if on_detection is not None:
+                on_detection(index, ordinal, phrase, start_s, end_s, confidence, logp)
+
+    def stream_recording(self, audio_data, chunk_samples=None, sample_rate=None, resample="polyphase", on_detection=None):
         """The body of ``real_time_streaming`` (Recognizer.py:560-710) driven by an array instead of the
         microphone thread: the utterance is cut with the reference's sample requirements (first pass
         ``general + 15 * samples_pr_10ms``, later passes ``general``, :598-612; ``chunk_samples`` is the size
@@ -164,7 +176,10 @@ class Recognizer(object):
         ``sample_rate``: the recording's rate when it is not the model's.  It is converted on the GPU as it streams
         (``resample``: "polyphase" or "ratecv"): the passes are cut over the converted length (``chunk_samples`` counts
         model-rate samples) and the source is fed just far enough for each pass (``stream_plan.resample_feed_plan``), so that
-        the yields equal ``stream_recording(audio.resample(audio_data, sample_rate, method=resample), chunk_samples)``."""
+        the yields equal ``stream_recording(audio.resample(audio_data, sample_rate, method=resample), chunk_samples)``.
+        ``on_detection``: with a phrase watch (``enable_real_time_streaming(watch=...)``), called as ``on_detection(index,
+        utterance_ordinal, phrase, start_s, end_s, confidence, logp)`` for every occurrence, before the part's text is yielded
+        (``index`` is 0 here); what is yielded is the same with and without it."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
@@ -172,6 +187,7 @@ class Recognizer(object):
             audio_data = np.asarray(audio_data, dtype=np.float64)
             for lo, hi, is_first, is_last in self._cut_plan(len(audio_data), chunk_samples):
                 output = rec.streaming_transcribe(audio_data[lo:hi], is_last=is_last, is_first=is_first)
+                self._report(on_detection, 0, rec)
                 if output:
                     yield is_last, output
             return
@@ -182,12 +198,13 @@ class Recognizer(object):
         try:
             for (lo, hi, is_first, is_last), (a, b, flush) in zip(plan, feed):
                 output = rec.streaming_transcribe(audio_data[a:b], is_last=is_last, is_first=is_first, take=hi - lo, flush=flush)
+                self._report(on_detection, 0, rec)
                 if output:
                     yield is_last, output
         finally:
             rec.set_streaming_source(*(before or (None, "polyphase")))
 
-    def stream_recordings(self, audio_list, chunk_samples=None, sample_rate=None, resample="polyphase"):
+    def stream_recordings(self, audio_list, chunk_samples=None, sample_rate=None, resample="polyphase", on_detection=None):
         """``stream_recording`` for many recordings at once, one streaming session each: every recording is cut as
         ``stream_recording`` cuts it, and in each round every session that has a part due advances in ONE batched pass
         (``DanSpeechRecognizer.streaming_transcribe_many``).  Yields ``(index, is_last, text)``; for every index the
@@ -195,7 +212,9 @@ class Recognizer(object):
         after ``enable_real_time_streaming`` (every session starts with a fresh parser).  Requires
         ``enable_real_time_streaming``.
         ``sample_rate``: the recordings' rate, or a list with one rate per recording (None among them: the model's); the
-        sessions of other rates are converted together, one launch per round and method (``stream_recording``)."""
+        sessions of other rates are converted together, one launch per round and method (``stream_recording``).
+        ``on_detection``: as ``stream_recording``'s, ``index`` the recording's; a round's detections are reported before the
+        round's texts are yielded."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
@@ -222,6 +241,8 @@ class Recognizer(object):
                 texts = rec.streaming_transcribe_many([sessions[k] for k, _ in due], [audio[k][feeds[k][r][0]:feeds[k][r][1]] for k, _ in due],
                                                       [c[3] for _, c in due], [c[2] for _, c in due],
                                                       take=[c[1] - c[0] for _, c in due], flush=[feeds[k][r][2] for k, _ in due])
+                for k, _ in due:
+                    self._report(on_detection, k, sessions[k])
                 for (k, c), text in zip(due, texts):
                     if text:
                         yield k, c[3], text
@@ -229,7 +250,7 @@ class Recognizer(object):
             for ses in sessions.values():
                 ses.close()
 
-    def stream_live(self, sources, chunk=1024, sample_rate=None, resample="polyphase"):
+    def stream_live(self, sources, chunk=1024, sample_rate=None, resample="polyphase", on_detection=None):
         """Continuous audio from many sources -> per-utterance texts: ``real_time_streaming`` (Recognizer.py:560-715) for every
         source at once, with the listener's gate (``listen_stream``, :218-324), the conversion to the model's rate and the
         model passes all on the GPU.  ``sources``: a list of iterables of sample arrays of any lengths (int16 -- ``[n, 2]``
@@ -238,7 +259,9 @@ class Recognizer(object):
         every source is exhausted.  ``chunk``: the gate's buffer; ``sample_rate``: the sources' rate, or one per source, when it
         is not the model's (``resample`` must be "polyphase").  The gate's parameters are this recognizer's
         ``energy_threshold``, ``pause_threshold``, ``phrase_threshold`` and ``non_speaking_duration`` as they are when a source
-        delivers its first array.  Requires ``enable_real_time_streaming``."""
+        delivers its first array.  Requires ``enable_real_time_streaming``.  ``on_detection``: as ``stream_recording``'s, ``index``
+        the source's and ``utterance_ordinal`` counting the utterances the gate has found in it; a round's detections are
+        reported before the round's texts are yielded."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         if resample != "polyphase":
@@ -269,7 +292,10 @@ class Recognizer(object):
                     ks.append(k); parts.append(part); eos.append(False)
                 if not ks:
                     continue
-                for k, said in zip(ks, rec.streaming_listen_many([sessions[k] for k in ks], parts, eos)):
+                heard = rec.streaming_listen_many([sessions[k] for k in ks], parts, eos)
+                for k in ks:
+                    self._report(on_detection, k, sessions[k])
+                for k, said in zip(ks, heard):
                     for is_last, text in said:
                         yield k, is_last, text
         finally:

@@ -32,6 +32,7 @@ ALIGN_MAX_TOKENS = 4096         # the longest transcript dsmi_align takes (L_str
 SPOT_MAX_TOKENS = 128           # the longest phrase dsmi_spot takes (L_stride)
 SPOT_MAX_PHRASES = 4096         # phrases of one dsmi_spot call
 SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
+SPOT_STREAM_MANY_MAX = 4096     # streams of one dsmi_spot_stream_advance_many launch
 SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
 ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes (L_stride)
 EDIT_MAX_TOKENS = 4096          # the longest sequence dsmi_edit_distance takes (L_stride)
@@ -180,6 +181,17 @@ _PROTOS = {
     "dsmi_align": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_spot_plan": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "dsmi_spot": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_spot_watch_create": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(_vp)]),
+    "dsmi_spot_watch_destroy": (None, [_vp]),
+    "dsmi_spot_watch_last_error": (C.c_char_p, [_vp]),
+    "dsmi_spot_watch_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dsmi_spot_stream_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "dsmi_spot_stream_destroy": (None, [_vp]),
+    "dsmi_spot_stream_last_error": (C.c_char_p, [_vp]),
+    "dsmi_spot_stream_reset": (C.c_int, [_vp]),
+    "dsmi_spot_stream_frames": (C.c_int, [_vp, _i64p]),
+    "dsmi_spot_stream_advance_many": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "dsmi_spot_watch_pick": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "dsmi_score_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "dsmi_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
@@ -1300,6 +1312,135 @@ class NativeBeamStream(_Handle):
     def reset(self):
         if lib().dsmi_beam_stream_reset(self._h) != 0:
             raise DsmiError(DSMI_ERR_INVALID, "closed beam stream")
+
+
+class SpotPickState(C.Structure):
+    """dsmi_spot_pick_state: the online picking rule's state of one (stream, phrase); ``SpotPickState.fresh()`` starts an utterance."""
+    _fields_ = [("pending", C.c_int32), ("ps", C.c_int32), ("pe", C.c_int32), ("last_end", C.c_int32), ("pv", C.c_float)]
+
+    @classmethod
+    def fresh(cls):
+        return cls(0, 0, 0, -1, 0.0)
+
+
+def spot_watch_pick(E, ST, t0, flush, min_mean_logp, settle_frames, state, max_events=SPOT_MAX_HITS):
+    """dsmi_spot_watch_pick (host only): the online picking rule of the streaming phrase watch over the tracks of one phrase,
+    frames t0 .. t0 + len(E) - 1; ``state`` (a ``SpotPickState``) is carried from call to call, ``flush`` ends the utterance.
+    -> (count, [(start, end, logp, fired), ...] the first min(count, max_events) events, frames [start, end))."""
+    E = np.ascontiguousarray(E, dtype=np.float32).reshape(-1)
+    ST = np.ascontiguousarray(ST, dtype=np.int32).reshape(-1)
+    if len(E) != len(ST):
+        raise ValueError("spot_watch_pick: one start frame per end score")
+    M = int(max_events)
+    hits = np.zeros((max(M, 0), 2), dtype=np.int32)
+    scores = np.zeros(max(M, 0), dtype=np.float32)
+    fired = np.zeros(max(M, 0), dtype=np.int32)
+    rc = lib().dsmi_spot_watch_pick(_np_ptr(E) if len(E) else None, _np_ptr(ST) if len(E) else None, len(E), int(t0), int(bool(flush)),
+                                    float(min_mean_logp), int(settle_frames), C.byref(state), M, _np_ptr(hits) if M > 0 else None,
+                                    _np_ptr(scores) if M > 0 else None, _np_ptr(fired) if M > 0 else None)
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_spot_watch_pick: frames from t0 >= 0 within 2^31 - 1, settle_frames >= 1, max_events >= 0, no NaN floor")
+    return rc, [(int(hits[i, 0]), int(hits[i, 1]), float(scores[i]), int(fired[i])) for i in range(min(rc, M))]
+
+
+class NativeSpotWatch(_Handle):
+    """Owns one dsmi_spot_watch handle: a phrase list (label-id sequences) packed and uploaded once for ``decoder`` (a
+    ``NativeDecoder``, kept alive by the watch), with the picking parameters of the streaming phrase watch."""
+    _destroy, _last_error = "dsmi_spot_watch_destroy", "dsmi_spot_watch_last_error"
+
+    def __init__(self, decoder, phrases, min_mean_logp, settle_frames):
+        self.decoder = decoder
+        ph, lens = _padded_ids(phrases, None, None, 1, None)
+        self.min_mean_logp, self.settle_frames = float(min_mean_logp), int(settle_frames)
+        self._create("dsmi_spot_watch_create", decoder._h, _np_ptr(ph), _np_ptr(lens) if len(lens) else None, len(lens), ph.shape[1],
+                     self.min_mean_logp, self.settle_frames)
+        K, G, S = C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().dsmi_spot_watch_info(self._h, C.byref(K), C.byref(G), C.byref(S)))
+        self.K, self.n_groups = K.value, G.value
+        assert S.value == self.settle_frames
+
+
+class NativeSpotStream(_Handle):
+    """Owns one dsmi_spot_stream handle: one live utterance's phrase search over ``watch`` (a ``NativeSpotWatch``, kept alive by
+    the stream), carried from chunk to chunk."""
+    _destroy, _last_error = "dsmi_spot_stream_destroy", "dsmi_spot_stream_last_error"
+
+    def __init__(self, watch):
+        self.watch = watch
+        self._create("dsmi_spot_stream_create", watch._h)
+
+    def close(self):
+        if getattr(self.watch, "_h", None):      # (the handle points into its watch: after the watch has gone there is nothing to free safely)
+            super().close()
+        self._h = None
+
+    def frames(self):
+        f = C.c_int64()
+        if lib().dsmi_spot_stream_frames(self._h, C.byref(f)) != 0:
+            raise DsmiError(DSMI_ERR_INVALID, "closed spot stream")
+        return int(f.value)
+
+    def reset(self):
+        if lib().dsmi_spot_stream_reset(self._h) != 0:
+            raise DsmiError(DSMI_ERR_INVALID, "closed spot stream")
+
+    @staticmethod
+    def advance_many(streams, probs_list, flush, max_events=4, tracks=False):
+        """dsmi_spot_stream_advance_many: advance distinct ``NativeSpotStream`` of one watch in one launch, stream i by the
+        frames of ``probs_list[i]`` (CUDA float32 [T,C] or [1,T,C]; None or T = 0: no frames); ``flush[i]``: its utterance ends
+        with them.  -> per stream the events fired in this call, ``(phrase_index, start, end, logp, fired)`` with frames
+        [start, end) counted from the utterance's first frame, sorted by (fired, phrase_index); with ``tracks`` a tuple
+        (events, E float32 [K,T], ST int32 [K,T]) of this call's frames.  A (stream, phrase) that fired more than
+        ``max_events`` events in one call raises ``DsmiError`` (DSMI_ERR_CAPACITY) after every stream has advanced: use
+        ``advance_many_counts`` to be told instead.  Longer lists than SPOT_STREAM_MANY_MAX run as several launches."""
+        outs, counts = NativeSpotStream.advance_many_counts(streams, probs_list, flush, max_events, tracks)
+        for i, c in enumerate(counts):
+            if c.max(initial=0) > int(max_events):
+                raise DsmiError(DSMI_ERR_CAPACITY, "spot stream %d: %d events of one phrase in one call, max_events = %d" % (i, int(c.max()), int(max_events)))
+        return outs
+
+    @staticmethod
+    def advance_many_counts(streams, probs_list, flush, max_events=4, tracks=False):
+        """``advance_many`` with, per stream, the int32 [K] counts of the events fired beside what was stored (the first
+        ``max_events`` of each phrase): -> (outs, counts)."""
+        import torch
+        if not (len(probs_list) == len(flush) == len(streams)):
+            raise ValueError("streams, probs_list and flush must have one entry per stream")
+        probs, new = [], []
+        for p in probs_list:
+            t = 0
+            if p is not None:
+                t = p.shape[-2]
+                p = p.reshape(t, p.shape[-1]).contiguous()
+                assert p.is_cuda and p.dtype == torch.float32
+            probs.append(p if t > 0 else None)
+            new.append(t)
+        outs, all_counts = [], []
+        M = int(max_events)
+        for ss, ps, ts, fl in _cut(SPOT_STREAM_MANY_MAX, streams, probs, new, list(flush)):
+            n, K = len(ss), ss[0].watch.K
+            fr = np.array(ts, dtype=np.int32)
+            F = max(ts) if tracks else 0
+            rows = max(M, 0)
+            hits = np.zeros((n, K, rows, 2), dtype=np.int32)
+            scores = np.zeros((n, K, rows), dtype=np.float32)
+            fired = np.zeros((n, K, rows), dtype=np.int32)
+            counts = np.zeros((n, K), dtype=np.int32)
+            E = np.zeros((n, K, F), dtype=np.float32) if tracks else None
+            ST = np.zeros((n, K, F), dtype=np.int32) if tracks else None
+            NativeSpotStream._check_thread(lib().dsmi_spot_stream_advance_many(
+                _handle_array(ss), n, _ptr_array(ps), _np_ptr(fr), _np_ptr(_flag_array(fl)), M, _np_ptr(hits), _np_ptr(scores), _np_ptr(fired),
+                _np_ptr(counts), _np_ptr(E) if tracks else None, _np_ptr(ST) if tracks else None, F, _stream(ss[0].watch.decoder.device)))
+            for i in range(n):
+                ev = [(k, int(hits[i, k, e, 0]), int(hits[i, k, e, 1]), float(scores[i, k, e]), int(fired[i, k, e]))
+                      for k in range(K) for e in range(min(int(counts[i, k]), M))]
+                ev.sort(key=lambda h: (h[4], h[0]))
+                outs.append((ev, E[i, :, :ts[i]].copy(), ST[i, :, :ts[i]].copy()) if tracks else ev)
+                all_counts.append(counts[i].copy())
+        return outs, all_counts
+
+    def advance(self, probs, flush=False, max_events=4, tracks=False):
+        return NativeSpotStream.advance_many([self], [probs], [flush], max_events, tracks)[0]
 
 
 class NativeLM(_Handle):

@@ -154,6 +154,62 @@ inline int spot_check(const int32_t* sizes, int B, int To, const int32_t* phrase
     return DSMI_OK;
 }
 
+// ---- streaming phrase watch (dsmi_spot_watch_*, dsmi_spot_stream_*: spot_watch.hip)
+constexpr CtcRows kWatchRows{"spot watch", "phrase", "length", "token id", "DSMI_SPOT_MAX_TOKENS", 1, DSMI_SPOT_MAX_TOKENS};
+constexpr uint64_t kWatchEventCap = (uint64_t)1 << 24;      // n * K * max_events: the events of one call, on the watch and copied back
+constexpr uint64_t kWatchTrackCap = (uint64_t)1 << 27;      // n * K * F_stride: the tracks of one call, when asked for
+
+// a watch's phrase list and picking parameters
+inline int spot_watch_check(const int32_t* phrases, const int32_t* phrase_lens, int K, int L_stride, float min_mean_logp, int settle_frames,
+                            int C, int blank, std::string& err) {
+    if (K <= 0) return ctc_refuse(err, DSMI_ERR_INVALID, "spot watch: K must be positive");
+    if (settle_frames < 1) return ctc_refuse(err, DSMI_ERR_INVALID, "spot watch: settle_frames must be at least 1");
+    if (std::isnan(min_mean_logp)) return ctc_refuse(err, DSMI_ERR_INVALID, "spot watch: min_mean_logp is not a number");
+    if (int rc = ctc_check_stride(kWatchRows, L_stride, err)) return rc;
+    if (K > DSMI_SPOT_MAX_PHRASES)
+        return ctc_refuse(err, DSMI_ERR_CAPACITY, "spot watch: " + std::to_string(K) + " phrases exceed DSMI_SPOT_MAX_PHRASES (" + std::to_string(DSMI_SPOT_MAX_PHRASES) + ")");
+    for (int k = 0; k < K; ++k) {
+        int repeats = 0;
+        if (int rc = ctc_check_row(kWatchRows, k, phrases + (size_t)k * L_stride, phrase_lens[k], L_stride, C, blank, &repeats, err)) return rc;
+    }
+    return DSMI_OK;
+}
+
+// One dsmi_spot_stream_advance_many, behind its null-pointer checks: handles [n] (each non-null), watch_of [n] = the watch of each,
+// consumed [n] = the frames each has taken, probs [n] (may be null itself when no stream has frames), frames [n].  What the
+// numbers alone refuse is refused before any array is read.
+inline int spot_stream_check(const void* const* handles, const void* const* watch_of, const int64_t* consumed, int n, const float* const* probs,
+                             const int32_t* frames, int K, int max_events, bool tracks, int F_stride, std::string& err) {
+    if (n < 1 || n > DSMI_SPOT_STREAM_MANY_MAX)
+        return ctc_refuse(err, DSMI_ERR_INVALID, "spot stream: n outside 1 .. DSMI_SPOT_STREAM_MANY_MAX (" + std::to_string(DSMI_SPOT_STREAM_MANY_MAX) + ")");
+    if (max_events < 1 || max_events > DSMI_SPOT_MAX_HITS)
+        return ctc_refuse(err, DSMI_ERR_INVALID, "spot stream: max_events outside 1 .. DSMI_SPOT_MAX_HITS (" + std::to_string(DSMI_SPOT_MAX_HITS) + ")");
+    if (tracks && F_stride < 0) return ctc_refuse(err, DSMI_ERR_INVALID, "spot stream: negative F_stride");
+    if ((uint64_t)n * (uint64_t)K * (uint64_t)max_events > kWatchEventCap)
+        return ctc_refuse(err, DSMI_ERR_CAPACITY, "spot stream: n * K * max_events exceeds 2^24 (the events)");
+    if (tracks && (uint64_t)n * (uint64_t)K * (uint64_t)F_stride > kWatchTrackCap)
+        return ctc_refuse(err, DSMI_ERR_CAPACITY, "spot stream: n * K * F_stride exceeds 2^27 (the tracks)");
+    auto at = [](int i) { return "spot stream " + std::to_string(i) + ": "; };
+    {
+        std::vector<const void*> sorted(handles, handles + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+        if (twice != sorted.end()) {
+            int i = n - 1;
+            while (handles[i] != *twice) --i;      // (the later of the two)
+            return ctc_refuse(err, DSMI_ERR_INVALID, at(i) + "the same handle appears twice in one call");
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        if (watch_of[i] != watch_of[0]) return ctc_refuse(err, DSMI_ERR_INVALID, at(i) + "the streams of one call must belong to one watch");
+        if (frames[i] < 0) return ctc_refuse(err, DSMI_ERR_INVALID, at(i) + "negative frame count");
+        if (frames[i] > 0 && (!probs || !probs[i])) return ctc_refuse(err, DSMI_ERR_INVALID, at(i) + "no probabilities for " + std::to_string(frames[i]) + " frames");
+        if (tracks && frames[i] > F_stride) return ctc_refuse(err, DSMI_ERR_INVALID, at(i) + "F_stride is below the frame count");
+        if (consumed[i] + (int64_t)frames[i] > (int64_t)INT32_MAX) return ctc_refuse(err, DSMI_ERR_CAPACITY, at(i) + "the utterance would pass 2^31 - 1 frames");
+    }
+    return DSMI_OK;
+}
+
 // sz [B], tl [N] (-1: infeasible), frames [N] = the frames of each candidate's clip, *L_max = the longest feasible candidate
 inline int score_check(const int32_t* sizes, int B, int To, const int32_t* cand_clip, const int32_t* targets, const int32_t* target_lens,
                        int N, int L_stride, int C, int blank, std::vector<int32_t>& sz, std::vector<int32_t>& tl,

@@ -154,6 +154,26 @@ class Decoder(object):
         return [[[(int(hits[b, k, n, 0]), int(hits[b, k, n, 1]), float(scores[b, k, n])) for n in range(counts[b, k])]
                  for k in range(len(ids))] for b in range(hits.shape[0])]
 
+    # ---- streaming phrase watch (dsmi_spot_watch / dsmi_spot_stream): the same phrases, searched in live sessions chunk by chunk
+    def watch(self, phrases, min_confidence=0.5, settle_frames=25, device_index=0):
+        """A phrase list for live sessions (``NativeSpotWatch``): ``phrases`` normalised and checked exactly as ``spot`` does it
+        (the same ``ValueError``s, before any GPU work).  A window counts as an occurrence when its per-frame geometric mean
+        probability is at least ``min_confidence`` (0: every window), and is reported ``settle_frames`` frames after its last
+        frame unless a better window that meets it has come up by then (``dsmi_spot_stream_advance_many``).  One
+        ``NativeSpotStream(watch)`` per live utterance carries the search; ``NativeSpotStream.advance_many`` advances many."""
+        ids = [self.phrase_ids(p) for p in phrases]                                          # every check before any GPU work
+        return self.watch_ids(ids, min_confidence, settle_frames, device_index)
+
+    def watch_ids(self, ids, min_confidence=0.5, settle_frames=25, device_index=0):
+        """``watch`` for label-id sequences as they are (no normalisation)."""
+        from .. import _native
+        if len(ids) == 0:
+            raise ValueError("watch: at least one phrase")
+        if int(settle_frames) < 1:
+            raise ValueError("watch: settle_frames must be at least 1")
+        floor = float(np.log(min_confidence)) if min_confidence > 0 else -np.inf
+        return _native.NativeSpotWatch(self._dec(device_index), ids, floor, int(settle_frames))
+
     # ---- CTC transcript scoring (dsmi_score): how probable is a transcript, over every alignment; no language model
     def score(self, probs, candidates, sizes=None):
         """The exact likelihood of candidate transcripts: ``candidates[b]`` is a list of transcripts for clip b (``probs``

@@ -597,6 +597,83 @@ int dsmi_spot(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host
               int32_t* hits_host, float* scores_host, int32_t* counts_host,
               float* track_scores_host, int32_t* track_starts_host, void* stream);
 
+/* ---- Streaming phrase watch (no reference counterpart): dsmi_spot's search carried from one chunk of a live session's
+ * probabilities to the next, so that a streaming caller pays for each frame once and hears of a phrase settle_frames frames
+ * after it was said.  The recurrence needs one score and one start frame per state from the frame before, nothing else.
+ * A dsmi_spot_watch is a phrase list bound to one dsmi_decoder: K phrases as label ids with dsmi_spot's limits (1 <= length <=
+ * L_stride <= DSMI_SPOT_MAX_TOKENS, K <= DSMI_SPOT_MAX_PHRASES, never the blank), packed once into dsmi_spot_plan's groups and
+ * uploaded once, with the two picking parameters min_mean_logp (as dsmi_spot's; not NaN) and settle_frames >= 1.
+ * dsmi_spot_watch_info tells K, the number of groups and settle_frames (each pointer may be NULL).
+ * A dsmi_spot_stream is one live utterance's carried search over one watch: a device block of its own with, per state of every
+ * group, the float32 score and the int32 start frame of the last frame processed and, per phrase, the picker's state below.
+ * dsmi_spot_stream_reset starts a new utterance; dsmi_spot_stream_frames tells the frames consumed since.  A watch serves any
+ * number of streams; destroy every stream of a watch before the watch, and every watch before its decoder.
+ *
+ * dsmi_spot_stream_advance_many advances n distinct streams of one watch in ONE launch whatever n and K (1 <= n <=
+ * DSMI_SPOT_STREAM_MANY_MAX): stream i by frames[i] >= 0 rows of probs_dev[i] (device, [frames[i]][n_labels] float32, the
+ * softmax output; may be NULL when frames[i] = 0).  flush[i] != 0: the utterance ends with this chunk (a flush with 0 frames is
+ * legal).  Frames are counted from the utterance's first frame: this call's frame f of stream i is frame t0 + f, t0 = the
+ * frames consumed before.  A call that would take a stream past 2^31 - 1 frames is refused.
+ * Tracks (the contract).  E and ST of stream i over all its chunks laid end to end are exactly dsmi_spot's E / ST tracks of the
+ * concatenated probabilities -- the same recurrence, tie rule and float32 accumulation in frame order, so they are equal bit
+ * for bit however the utterance was cut.  track_scores_host / track_starts_host [n][K][F_stride] are optional (each is copied
+ * back only when not NULL; with either, F_stride >= every frames[i]): this call's frames, -inf / -1 past frames[i].
+ * The online picking rule (the contract).  Per (stream, phrase): a pending candidate (pv, ps, pe) or none, and last_end
+ * (-1 at the utterance's start).  For each frame f in order:
+ *   1. a pending candidate with f - pe >= settle_frames fires: the event [ps, pe + 1) with score pv and fired = f;
+ *      last_end = pe, and nothing is pending.
+ *   2. f is a candidate iff E[f] > -inf, E[f] >= min_mean_logp * (float)(f - ST[f] + 1) (dsmi_spot's float32 multiply) and
+ *      ST[f] > last_end.
+ *   3. with none pending the candidate becomes pending, (pv, ps, pe) = (E[f], ST[f], f); with one pending and ST[f] <= pe
+ *      (the windows meet) it replaces the pending one only if E[f] > pv (strict: the earlier one wins a tie); with one
+ *      pending and ST[f] > pe the pending one fires (fired = f, last_end = pe) and f becomes pending.
+ * After the last frame of a flushed call the pending candidate fires with fired = the utterance's frame count.  The events of a
+ * (stream, phrase) are pairwise disjoint and come out in time order, at most one per frame and phrase.  The rule is a
+ * function of the tracks alone: it does not depend on how the utterance was cut into calls.
+ * Outputs: hits_host [n][K][max_events][2] frames [start, end), scores_host and fired_host [n][K][max_events], counts_host
+ * [n][K] = the events fired in this call; the first min(count, max_events) are stored in firing order and rows past that are
+ * 0.  count > max_events: the later ones were dropped -- the stream's state advances all the same.  1 <= max_events <=
+ * DSMI_SPOT_MAX_HITS.
+ * Either every stream advances or the call is refused before any launch, with no stream's state changed and nothing written;
+ * the error text (dsmi_spot_stream_last_error(NULL)) names the stream index.  DSMI_ERR_INVALID: NULL arguments or handles, n
+ * outside its range, a handle listed twice, streams of different watches, frames[i] < 0, probabilities missing for frames[i] >
+ * 0, max_events outside its range, F_stride below a frames[i] when tracks are asked for.  DSMI_ERR_CAPACITY: n * K * max_events
+ * > 2^24 (the events), n * K * F_stride > 2^27 (the tracks), a stream past 2^31 - 1 frames.  Synchronises `stream`.
+ *
+ * dsmi_spot_watch_pick (host only, no GPU) is the rule itself over caller-supplied tracks of ONE phrase, chunk by chunk:
+ * E / ST [frames] are the frames t0 .. t0 + frames - 1, *state is carried from call to call ({0, 0, 0, -1, 0} starts an
+ * utterance), flush != 0 ends it.  hits [max_events][2], scores and fired [max_events] take the first min(count, max_events)
+ * events (nothing past them is written); returns the count, or DSMI_ERR_INVALID for a NULL state, frames < 0, t0 < 0, t0 +
+ * frames > 2^31 - 1, arrays missing for frames > 0, max_events < 0 or outputs missing for max_events > 0, settle_frames < 1,
+ * a NaN min_mean_logp.  The kernel runs the same inline function. */
+typedef struct dsmi_spot_watch dsmi_spot_watch;
+typedef struct dsmi_spot_stream dsmi_spot_stream;
+typedef struct {
+    int32_t pending;
+    int32_t ps;
+    int32_t pe;
+    int32_t last_end;
+    float pv;
+} dsmi_spot_pick_state;
+#define DSMI_SPOT_STREAM_MANY_MAX 4096
+int dsmi_spot_watch_create(dsmi_decoder* d, const int32_t* phrases_host, const int32_t* phrase_lens_host, int K, int L_stride,
+                           float min_mean_logp, int settle_frames, dsmi_spot_watch** out);
+void dsmi_spot_watch_destroy(dsmi_spot_watch* w);
+const char* dsmi_spot_watch_last_error(const dsmi_spot_watch* w);
+int dsmi_spot_watch_info(const dsmi_spot_watch* w, int* K, int* n_groups, int* settle_frames);
+int dsmi_spot_stream_create(dsmi_spot_watch* w, dsmi_spot_stream** out);
+void dsmi_spot_stream_destroy(dsmi_spot_stream* s);
+const char* dsmi_spot_stream_last_error(const dsmi_spot_stream* s);
+int dsmi_spot_stream_reset(dsmi_spot_stream* s);
+int dsmi_spot_stream_frames(const dsmi_spot_stream* s, int64_t* frames);
+int dsmi_spot_stream_advance_many(dsmi_spot_stream* const* streams, int n, const float* const* probs_dev, const int32_t* frames,
+                                  const int32_t* flush, int max_events, int32_t* hits_host, float* scores_host,
+                                  int32_t* fired_host, int32_t* counts_host, float* track_scores_host,
+                                  int32_t* track_starts_host, int F_stride, void* stream);
+int dsmi_spot_watch_pick(const float* E, const int32_t* ST, int frames, int t0, int flush, float min_mean_logp,
+                         int settle_frames, dsmi_spot_pick_state* state, int max_events, int32_t* hits, float* scores,
+                         int32_t* fired);
+
 /* ---- CTC transcript scoring (no reference counterpart): how probable is this transcript, summed over every alignment?  The
  * natural log of the probability that the CTC model emits exactly a candidate's label sequence, through the probabilities
  * dsmi_forward wrote.  Every frame's softmax sums to 1, so the likelihoods of all label sequences sum to 1 and exp(logp) is the

@@ -19,6 +19,10 @@
 //   host_fuzz lmscore SEED N    the host half of dsmi_lm_score (lm_score_host.h: lm_score_check, lm_score_plan, lm_score_pack, lm_score_unpack)
 //                             on N random calls held in exactly sized heap arrays, against the rules written out below; what is
 //                             refused on the numbers alone is called with null arrays
+//   host_fuzz spotwatch SEED N  the host half of the streaming phrase watch (ctc_host.h: spot_watch_check, spot_stream_check; spot_pick.h: the
+//                             online picking rule) on N random calls held in exactly sized heap arrays: the checks against the rules written
+//                             out below, the rule over random tracks cut into random chunks against the rule written out plainly, nothing
+//                             written past max_events
 #define __host__
 #define __device__
 #include <cmath>
@@ -36,6 +40,7 @@
 #include "ctc_host.h"
 #include "edit_host.h"
 #include "lm_score_host.h"
+#include "spot_pick.h"
 
 using namespace dsmi;
 
@@ -885,6 +890,148 @@ static int run_lmscore(int argc, char** argv) {
     return 0;
 }
 
+// ---- spotwatch: the rule of include/dsmi.h written out plainly, beside spot_pick.h ---------------------------------------------
+#define SW_FAIL(what) do { std::fprintf(stderr, "spotwatch: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 13; } while (0)
+
+struct PlainEvent { int s, e; float v; int at; };
+static std::vector<PlainEvent> plain_pick(const std::vector<float>& E, const std::vector<int32_t>& ST, float floor_, int settle, bool flush) {
+    std::vector<PlainEvent> out;
+    bool pending = false;
+    float pv = 0; int ps = 0, pe = 0, last_end = -1;
+    const int T = (int)E.size();
+    for (int f = 0; f < T; ++f) {
+        if (pending && (long long)f - pe >= settle) { out.push_back({ps, pe + 1, pv, f}); last_end = pe; pending = false; }
+        if (!(E[(size_t)f] > -INFINITY) || !(E[(size_t)f] >= floor_ * (float)(f - ST[(size_t)f] + 1)) || !(ST[(size_t)f] > last_end)) continue;
+        if (pending && ST[(size_t)f] <= pe) { if (E[(size_t)f] > pv) { pv = E[(size_t)f]; ps = ST[(size_t)f]; pe = f; } continue; }
+        if (pending) { out.push_back({ps, pe + 1, pv, f}); last_end = pe; }
+        pending = true; pv = E[(size_t)f]; ps = ST[(size_t)f]; pe = f;
+    }
+    if (flush && pending) out.push_back({ps, pe + 1, pv, T});
+    return out;
+}
+
+static int run_spotwatch(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long events = 0, refused = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        std::string err;
+        // ---- the rule: random tracks with few distinct scores (ties), cut into random chunks with empty ones, exactly sized arrays
+        {
+            const int T = (int)(rng() % 120), settle = rng() % 4 ? 1 + (int)(rng() % 30) : INT32_MAX;
+            const float floors[4] = {-INFINITY, -1.f, -0.5f, -2.f};
+            const float floor_ = floors[rng() % 4];
+            std::vector<float> E((size_t)T); std::vector<int32_t> ST((size_t)T);
+            for (int f = 0; f < T; ++f) {
+                const bool dead = rng() % 4 == 0;
+                ST[(size_t)f] = dead ? -1 : f - (int)(rng() % (unsigned)(std::min(f, 6) + 1));
+                E[(size_t)f] = dead ? -INFINITY : -(float)(1 + rng() % 5);
+            }
+            const bool flush = rng() % 4 != 0;
+            const std::vector<PlainEvent> want = plain_pick(E, ST, floor_, settle, flush);
+            SpotPick p = spot_pick_fresh();
+            std::vector<PlainEvent> got;
+            for (int at = 0, last = 0; !last;) {
+                const int c = std::min(T - at, (int)(rng() % 3 ? rng() % 34 : 0));
+                last = at + c == T && rng() % 2;
+                const int M = (int)(rng() % 6);
+                std::vector<float> e(E.begin() + at, E.begin() + at + c); e.shrink_to_fit();
+                std::vector<int32_t> st(ST.begin() + at, ST.begin() + at + c); st.shrink_to_fit();
+                std::vector<int32_t> hits = exact(2 * (size_t)M + 1, -7), fired = exact((size_t)M + 1, -7);
+                std::vector<float> sc((size_t)M + 1, -7.f); sc.shrink_to_fit();
+                // the events of this chunk, all of them, from a copy of the state; then the call under test with M slots
+                SpotPick q = p;
+                std::vector<int32_t> ah = exact(2 * (size_t)c + 2), af = exact((size_t)c + 1);
+                std::vector<float> as((size_t)c + 1);
+                const int all = spot_pick_chunk(q, e.data(), st.data(), c, at, last && flush, floor_, settle, c + 1, ah.data(), as.data(), af.data());
+                const int n = spot_pick_chunk(p, e.data(), st.data(), c, at, last && flush, floor_, settle, M, hits.data(), sc.data(), fired.data());
+                if (n != all || n > c + 1 || std::memcmp(&p, &q, sizeof p)) SW_FAIL("the count or the state depends on max_events");
+                if (hits[2 * (size_t)M] != -7 || fired[(size_t)M] != -7 || sc[(size_t)M] != -7.f) SW_FAIL("a write past max_events");
+                for (int i = 0; i < M; ++i) {
+                    if (i < n ? hits[2 * (size_t)i] != ah[2 * (size_t)i] || hits[2 * (size_t)i + 1] != ah[2 * (size_t)i + 1] || sc[(size_t)i] != as[(size_t)i] || fired[(size_t)i] != af[(size_t)i]
+                              : hits[2 * (size_t)i] != -7 || fired[(size_t)i] != -7) SW_FAIL("the stored events are not the first");
+                }
+                for (int i = 0; i < all; ++i) got.push_back({ah[2 * (size_t)i], ah[2 * (size_t)i + 1], as[(size_t)i], af[(size_t)i]});
+                at += c;
+            }
+            if (got.size() != want.size()) SW_FAIL("the number of events");
+            for (size_t i = 0; i < want.size(); ++i) {
+                if (got[i].s != want[i].s || got[i].e != want[i].e || got[i].v != want[i].v || got[i].at != want[i].at) SW_FAIL("an event differs from the rule");
+                if (got[i].s >= got[i].e || (i && (got[i - 1].e > got[i].s || got[i - 1].at > got[i].at))) SW_FAIL("events overlap or are out of order");
+            }
+            events += (long)want.size();
+        }
+        // ---- the watch's check: a good list, then one fault
+        {
+            const int C = 2 + (int)(rng() % 127), blank = (int)(rng() % (unsigned)C);
+            const int K = 1 + (int)(rng() % 20), L_stride = 1 + (int)(rng() % 12);
+            std::vector<int32_t> lens = exact((size_t)K), ph = exact((size_t)K * L_stride);
+            for (int k = 0; k < K; ++k) {
+                lens[(size_t)k] = 1 + (int32_t)(rng() % (unsigned)L_stride);
+                random_row(rng, ph.data() + (size_t)k * L_stride, lens[(size_t)k], C, blank, false);
+            }
+            if (spot_watch_check(ph.data(), lens.data(), K, L_stride, -1.f, 1 + (int)(rng() % 50), C, blank, err) != DSMI_OK) SW_FAIL("watch: a good list refused");
+            const int32_t* none = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            if (spot_watch_check(none, none, rng() % 2 ? 0 : -big, 3, -1.f, 5, C, blank, err) != DSMI_ERR_INVALID) SW_FAIL("watch: K <= 0");
+            if (spot_watch_check(none, none, K, 3, -1.f, rng() % 2 ? 0 : -big, C, blank, err) != DSMI_ERR_INVALID) SW_FAIL("watch: settle_frames < 1");
+            if (spot_watch_check(none, none, K, 3, std::nanf(""), 5, C, blank, err) != DSMI_ERR_INVALID) SW_FAIL("watch: NaN floor");
+            if (spot_watch_check(none, none, K, DSMI_SPOT_MAX_TOKENS + big, -1.f, 5, C, blank, err) != DSMI_ERR_CAPACITY) SW_FAIL("watch: L_stride over the limit");
+            if (spot_watch_check(none, none, DSMI_SPOT_MAX_PHRASES + big, 3, -1.f, 5, C, blank, err) != DSMI_ERR_CAPACITY) SW_FAIL("watch: K over the limit");
+            const int k = (int)(rng() % (unsigned)K);
+            if (rng() % 2) lens[(size_t)k] = rng() % 2 ? 0 : L_stride + 1;
+            else random_row(rng, ph.data() + (size_t)k * L_stride, lens[(size_t)k], C, blank, true);
+            if (spot_watch_check(ph.data(), lens.data(), K, L_stride, -1.f, 5, C, blank, err) != DSMI_ERR_INVALID ||
+                err.find("spot watch: phrase " + std::to_string(k) + ": ") != 0) SW_FAIL("watch: a spoilt phrase passed or another one was named");
+            refused += 6;
+        }
+        // ---- one advance: a good call, then one fault, the stream named
+        {
+            const int n = 1 + (int)(rng() % 12), K = 1 + (int)(rng() % 9), M = 1 + (int)(rng() % DSMI_SPOT_MAX_HITS), F = (int)(rng() % 40);
+            std::vector<char> objects((size_t)n + 2), watches(2);
+            std::vector<const void*> handles((size_t)n), watch_of((size_t)n);
+            std::vector<int64_t> consumed((size_t)n);
+            std::vector<int32_t> frames = exact((size_t)n);
+            std::vector<const float*> probs((size_t)n);
+            static const float some = 0.f;
+            for (int i = 0; i < n; ++i) {
+                handles[(size_t)i] = &objects[(size_t)i]; watch_of[(size_t)i] = &watches[0];
+                consumed[(size_t)i] = rng() % 3 ? (int64_t)(rng() % 1000) : (int64_t)INT32_MAX - F - (int64_t)(rng() % 3);
+                frames[(size_t)i] = (int32_t)(rng() % (unsigned)(F + 1));
+                probs[(size_t)i] = frames[(size_t)i] ? &some : nullptr;
+            }
+            handles.shrink_to_fit(); watch_of.shrink_to_fit(); consumed.shrink_to_fit(); probs.shrink_to_fit();
+            auto check = [&](bool tracks) { return spot_stream_check(handles.data(), watch_of.data(), consumed.data(), n, probs.data(), frames.data(), K, M, tracks, F, err); };
+            if (check(true) != DSMI_OK || check(false) != DSMI_OK) SW_FAIL("advance: a good call refused");
+            const void* const* no_h = nullptr; const int64_t* no_c = nullptr; const float* const* no_p = nullptr; const int32_t* no_f = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            if (spot_stream_check(no_h, no_h, no_c, rng() % 2 ? 0 : DSMI_SPOT_STREAM_MANY_MAX + big, no_p, no_f, K, M, true, F, err) != DSMI_ERR_INVALID) SW_FAIL("advance: n out of range");
+            if (spot_stream_check(no_h, no_h, no_c, n, no_p, no_f, K, rng() % 2 ? 0 : DSMI_SPOT_MAX_HITS + big, true, F, err) != DSMI_ERR_INVALID) SW_FAIL("advance: max_events out of range");
+            if (spot_stream_check(no_h, no_h, no_c, n, no_p, no_f, K, M, true, -big, err) != DSMI_ERR_INVALID) SW_FAIL("advance: negative F_stride");
+            if (spot_stream_check(no_h, no_h, no_c, DSMI_SPOT_STREAM_MANY_MAX, no_p, no_f, DSMI_SPOT_MAX_PHRASES, DSMI_SPOT_MAX_HITS, false, F, err) != DSMI_ERR_CAPACITY) SW_FAIL("advance: the event cap");
+            if (spot_stream_check(no_h, no_h, no_c, n, no_p, no_f, K, M, true, (1 << 27) / (n * K) + big, err) != DSMI_ERR_CAPACITY) SW_FAIL("advance: the track cap");
+            const int i = (int)(rng() % (unsigned)n);
+            const std::string named = "spot stream " + std::to_string(i) + ": ";
+            int want = DSMI_ERR_INVALID;
+            bool tracks = true;
+            switch (rng() % 6) {
+                case 0: if (n < 2) continue; handles[(size_t)i] = handles[(size_t)(i ? i - 1 : n - 1)]; if (!i) { std::swap(handles[0], handles[(size_t)n - 1]); } break;
+                case 1: if (i == 0) continue; watch_of[(size_t)i] = &watches[1]; break;
+                case 2: frames[(size_t)i] = -1 - (int32_t)(rng() % 5); break;
+                case 3: frames[(size_t)i] = 1 + (int32_t)(rng() % (unsigned)(F + 1)); probs[(size_t)i] = nullptr; tracks = false; consumed[(size_t)i] = 0; break;
+                case 4: frames[(size_t)i] = F + 1; probs[(size_t)i] = &some; consumed[(size_t)i] = 0; break;
+                default: consumed[(size_t)i] = (int64_t)INT32_MAX - frames[(size_t)i] + 1; want = DSMI_ERR_CAPACITY; break;
+            }
+            const int rc = check(tracks);
+            if (rc != want) SW_FAIL("advance: a fault passed or got the wrong code");
+            if (err.find(named) != 0 && !(n >= 2 && err.find("the same handle appears twice") != std::string::npos)) SW_FAIL("advance: another stream was named");
+            refused += 6;
+        }
+    }
+    std::printf("%d spotwatch calls ok, %ld events checked, %ld refusals\n", reps, events, refused);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
@@ -894,6 +1041,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]]\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]]\n");
     return 2;
 }
