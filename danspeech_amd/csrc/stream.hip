@@ -110,6 +110,22 @@ extern "C" int dsmi_stream_reset(dsmi_stream* st) {
 
 static int conv_t1(int tin) { return (tin + 2 * 5 - 11) / 2 + 1; }     // conv1: k_t 11, stride 2, pad 5 (model.py:455)
 
+// Rows LookaheadStream keeps of a chunk of Tc rows: x[-(context-1):] (model.py:263).  With context 1 that slice is x[-0:], the
+// WHOLE chunk, which the next pass then yields a second time: the reference's behaviour, kept.
+static int la_keep(int Tc, int ctx) { return ctx == 1 ? Tc : std::min(Tc, ctx - 1); }
+
+// What dsmi_debug_last_rnn_plan reports of a streaming pass: the launch of the recurrent layer that ran last.  persist8: the
+// carried-state launch of stream_persist_layer (direction 0, one direction, every lane slot of the gate, one CU per workgroup);
+// steps: rnn_step_kernel per step -- not eligible, DSMI_RNN_MODE=steps, refused, or the recomputation of a timed-out pass.
+static void record_stream_plan(dsmi_model* m, bool persisted) {
+    RnnLaunch l;
+    if (persisted) {
+        l.kernel = RNN_PERSIST8; l.at = 0; l.n = 1;
+        l.gate = GATE_LANES; l.slot0 = 0; l.nslots = kMaxLanes; l.cus = m->geom.nwg;
+    }
+    m->last_plan_x16 = false; m->last_plan_n = 1; m->last_plan[0] = l;
+}
+
 static int ensure(dsmi_stream* st, int T) {
     if (T <= st->cap_T) return DSMI_OK;
     dsmi_model* m = st->m;
@@ -202,6 +218,7 @@ extern "C" int dsmi_stream_forward(dsmi_stream* st, const float* feat, int T, in
         sl.xp = st->xp; sl.lens_dev = st->lens_dev + 2; sl.B = 1; sl.T = Tc; sl.hpack = st->hpack[l];
         sl.hcarry = st->has_hidden ? st->hcarry[l] : nullptr; sl.pbase = st->pbase[l];
         for (int step = 0; step < Tc; ++step) { sl.step = step; launch_rnn_step(sl, s); }
+        record_stream_plan(m, false);
         S_HIP(st, hipMemcpyAsync(st->hcarry[l], out + (size_t)(Tc - 1) * m->Hs, sizeof(float) * m->Hs, hipMemcpyDeviceToDevice, s));
         st->pbase[l] = (Tc + st->pbase[l]) & 1;
     }
@@ -239,7 +256,7 @@ extern "C" int dsmi_stream_forward(dsmi_stream* st, const float* feat, int T, in
     }
     S_HIP(st, hipMemcpyAsync(st->cat, st->la_buf, sizeof(float) * (size_t)st->la_rows * Hs, hipMemcpyDeviceToDevice, s));
     S_HIP(st, hipMemcpyAsync(st->cat + (size_t)st->la_rows * Hs, x, sizeof(float) * (size_t)Tc * Hs, hipMemcpyDeviceToDevice, s));
-    const int keep = std::min(Tc, ctx - 1);      // x[-(context-1):]
+    const int keep = la_keep(Tc, ctx);
     if ((rc = grow_la(keep))) return rc;
     S_HIP(st, hipMemcpyAsync(st->la_buf, x + (size_t)(Tc - keep) * Hs, sizeof(float) * (size_t)keep * Hs, hipMemcpyDeviceToDevice, s));
     st->la_rows = keep;
@@ -467,7 +484,7 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
         SessDev& S = sd[i];
         S.feat = feat[i]; S.left[0] = st->left[0]; S.left[1] = st->left[1]; S.la_buf = st->la_buf;
         S.T = T[i]; S.ctxl = ctxl; S.padl = padl; S.is_last = last; S.seed = st->has_hidden; S.buffering = buffering;
-        S.la_rows = buffering ? 0 : st->la_rows; S.ncat = buffering ? 0 : ncat; S.keep = std::min(to2, ctx - 1);
+        S.la_rows = buffering ? 0 : st->la_rows; S.ncat = buffering ? 0 : ncat; S.keep = la_keep(to2, ctx);
         S.tin[0] = tin1; S.tin[1] = tin2; S.to[0] = to1; S.to[1] = to2;
         nout[i] = no;
         tin1max = std::max(tin1max, tin1); tin2max = std::max(tin2max, tin2);
@@ -587,6 +604,7 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
                 sl.hcarry = h0; sl.pbase = 0;
                 for (int step = 0; step < tcmax; ++step) { sl.step = step; launch_rnn_step(sl, s); }
             }
+            record_stream_plan(m, done);
         }
         if (any_out) {
             const float* x = b.hb + (size_t)(L - 1) * tcmax * n * Hs;

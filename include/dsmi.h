@@ -445,6 +445,9 @@ int dsmi_debug_step_stamps(dsmi_model* m, int layer, int B, int T_out, int step,
  * launch "kernel at n nwin gate slot0 nslots cus ticket part;" with kernel one of steps, persist8, p16w8, p16w4, duo, ring8, ring4
  * (csrc/rnn_plan.h: RnnLaunch; the format of tools/asan/host_fuzz.cpp rnnplan).  Returns the number of launches the layer made (0
  * and an empty string before the first layer); the text holds the first eight of them.  Recording allocates nothing.
+ * dsmi_stream_forward and dsmi_stream_forward_many record their recurrent layers here too, one launch per layer: "persist8 0 1 1 lane
+ * 0 4 <workgroups> 0 1;" for the batched pass's carried-state launch, "steps ..." otherwise (a shape the persistent kernel does not
+ * take, DSMI_RNN_MODE=steps, every single-session call, and the recomputation of a timed-out pass).
  * DSMI_ERR_INVALID: null argument or a buffer too small (1400 bytes hold any answer). */
 int dsmi_debug_last_rnn_plan(const dsmi_model* m, char* buf, int64_t capacity);
 /* The x-projection the handle's LAST recurrent layer ran on (the GEMM's output, bias included, in the column order the layer's

@@ -30,6 +30,9 @@ them is called):
   symmetric window; the real DFT; ``log1p(hypot(re, im))``; with ``normalize`` minus the mean, over the unbiased standard deviation,
   of the clip's own ``n_freq x frames`` values.  Nothing is rounded to float32 anywhere.
 * ``stream_norm``: the running statistics of the streaming parser after a chunk, and the mean / std that normalise the chunk.
+
+The chunked unidirectional inference (oracle/streaming.py documents it, reference model.py:156-283 and 517-537; nothing of it is
+called): ``stream_model``, at the end of this file.
 """
 import numpy as np
 
@@ -258,3 +261,124 @@ def stream_norm(stats, state3):
         mean = input_mean * alpha + (1 - alpha) * DATASET_MEAN
         std = input_std * alpha + (1 - alpha) * DATASET_STD
     return np.array([input_mean, input_std, alpha]), mean, std
+
+
+# ---- chunked unidirectional inference ----------------------------------------------------------------------------------------------
+class stream_model(object):
+    """MaskConvStream, BatchRNNStream, LookaheadStream and streaming_forward in float64: the state of B sessions that advance in
+    lock step (the same chunk length and flags; a lone session is B = 1) and their forward.
+
+    * conv, per layer: ``is_first`` puts five zero frames in front of the chunk, otherwise ``is_last`` puts five behind it; unless
+      ``is_first`` the ten frames kept from the pass before are glued in front; unless ``is_last`` the last ten frames of the glued
+      input are kept; then the layer's own convolution with its zero padding (5 in time) ON THE GLUED INPUT, BatchNorm2d affine,
+      clip to [0, 20].  Nothing is masked.
+    * recurrent layers: from the carried (h, c), zero where there is none; ``is_last`` drops the carried state, and nothing else
+      does -- an ``is_first`` that no ``is_last`` preceded restarts the conv context and the lookahead buffer, not h / c.
+    * lookahead: without a buffer, or at ``is_first``, the whole chunk is buffered and the pass yields nothing (None).  Otherwise
+      the buffer and the chunk are concatenated, the chunk's ``x[-(context - 1):]`` kept (context 1: ``x[-0:]``, the WHOLE chunk,
+      which the next pass then emits a second time -- the reference's slice, kept as it is), ``is_last`` pads ``context - 1`` zero
+      rows behind and drops the buffer; ``y[t] = clip(sum_k w[:, k] x[t + k], 0, 20)`` wherever all taps exist.
+    * ``head`` on what the lookahead yields.
+
+    ``hooks`` (tests/test_stream_accuracy_sensitivity.py's mutants; the reference itself uses none), each optional:
+      carry(l, hs, cs, run_on) -> (h, c)   the state layer l hands to the next chunk.  hs, cs: [T + 1, B, H], the state before the
+                                           chunk and after each of its steps; run_on(n): (h, c) after n more steps on zero rows
+      tail(li, x) -> [..., 10]             the frames conv layer li keeps of its glued input x
+      keep(x, context) -> rows             the rows the lookahead keeps of the chunk x
+      route(l, B) -> index [B]             session i receives the carried state of session index[i]
+      rpad(li) -> frames                   the right padding of ``is_last`` (5)
+      first_clears_state                   True: ``is_first`` also drops h / c"""
+
+    def __init__(self, sd, cfg, hooks=None):
+        assert cfg["conv_layers"] == 2 and not cfg["bidirectional"]
+        self.sd, self.cfg, self.hooks = sd, cfg, dict(hooks or {})
+        self.w = [layer_weights(sd, l, False) for l in range(cfg["rnn_layers"])]
+        self.reset()
+
+    def reset(self):
+        self.left = [None, None]
+        self.hidden = [None] * self.cfg["rnn_layers"]
+        self.la_buf = None
+
+    def conv(self, x, is_first, is_last):
+        from danspeech_amd.synthetic import CONV_SPECS
+        sd, hk = self.sd, self.hooks
+        for li, (_, co, _, _, sf, st, pf, pt) in enumerate(CONV_SPECS[:2]):
+            if is_first:
+                x = np.concatenate([np.zeros(x.shape[:3] + (5,)), x], axis=3)
+            elif is_last:
+                x = np.concatenate([x, np.zeros(x.shape[:3] + (hk["rpad"](li) if "rpad" in hk else 5,))], axis=3)
+            if not is_first:
+                x = np.concatenate([self.left[li], x], axis=3)
+            if not is_last:
+                self.left[li] = (hk["tail"](li, x) if "tail" in hk else x[:, :, :, -10:]).copy()
+            y = correlate(x, _f64(sd["conv.seq_module.%d.weight" % (3 * li)]), (sf, st), (pf, pt))
+            a, b = bn2d_affine(sd, li)
+            y = (y + _f64(sd["conv.seq_module.%d.bias" % (3 * li)]).reshape(1, co, 1, 1)) * a.reshape(1, co, 1, 1) + b.reshape(1, co, 1, 1)
+            x = np.clip(y, 0.0, 20.0)
+        return x
+
+    def rnn(self, l, x, is_last):
+        kind, hk = self.cfg["rnn_type"], self.hooks
+        zero_row = np.zeros(x.shape[2])
+        if l > 0:
+            a, b = bn_affine(self.sd, l)
+            x, zero_row = x * a + b, b
+        w_ih, w_hh, b_ih, b_hh = self.w[l]
+        T, B, _ = x.shape
+        H = w_hh.shape[1]
+        whh_t = np.ascontiguousarray(w_hh.T)
+        if self.hidden[l] is None:
+            h, c = np.zeros((B, H)), np.zeros((B, H))
+        else:
+            h, c = self.hidden[l]
+            if "route" in hk:
+                idx = hk["route"](l, B)
+                h, c = h[idx], c[idx]
+        gi = (x.reshape(T * B, -1) @ w_ih.T + b_ih).reshape(T, B, -1)
+        hs, cs = np.empty((T + 1, B, H)), np.empty((T + 1, B, H))
+        hs[0], cs[0] = h, c
+        for t in range(T):
+            h, c = cell(kind, gi[t], h @ whh_t + b_hh, h, c)
+            hs[t + 1], cs[t + 1] = h, c
+
+        def run_on(n):
+            h1, c1, g0 = hs[T], cs[T], np.broadcast_to(zero_row @ w_ih.T + b_ih, (B, gi.shape[2]))
+            for _ in range(n):
+                h1, c1 = cell(kind, g0, h1 @ whh_t + b_hh, h1, c1)
+            return h1, c1
+
+        state = hk["carry"](l, hs, cs, run_on) if "carry" in hk else (hs[T], cs[T])
+        self.hidden[l] = None if is_last else state
+        return hs[1:]
+
+    def lookahead(self, x, is_first, is_last):
+        ctx, hk = self.cfg["context"], self.hooks
+        if self.la_buf is None or is_first:
+            self.la_buf = x
+            return None
+        out = np.concatenate([self.la_buf, x], axis=0)
+        self.la_buf = hk["keep"](x, ctx) if "keep" in hk else x[-(ctx - 1):]
+        n_out = out.shape[0] if is_last else out.shape[0] - (ctx - 1)
+        assert n_out >= 1, "fewer buffered frames than the context (torch raises here)"
+        if is_last:
+            out = np.concatenate([out, np.zeros((ctx - 1,) + out.shape[1:])], axis=0)
+            self.la_buf = None
+        w = _f64(self.sd["lookahead.0.conv.weight"])[:, 0, :]
+        y = np.zeros((n_out,) + out.shape[1:])
+        for k in range(ctx):
+            y += out[k:k + n_out] * w[:, k]
+        self.la_pre = y              # before the clip: what the case table's claim about the two clamps reads
+        return np.clip(y, 0.0, 20.0)
+
+    def forward(self, x, is_first, is_last):
+        """x [B, 1, F, T] float32 (widened exactly) -> probabilities [B, T_out, C] float64, or None while the lookahead buffers."""
+        if is_first and self.hooks.get("first_clears_state"):
+            self.hidden = [None] * self.cfg["rnn_layers"]
+        y = self.conv(_f64(x), is_first, is_last)
+        B, C, F, T = y.shape
+        y = np.ascontiguousarray(y.reshape(B, C * F, T).transpose(2, 0, 1))
+        for l in range(self.cfg["rnn_layers"]):
+            y = self.rnn(l, y, is_last)
+        y = self.lookahead(y, is_first, is_last)
+        return None if y is None else head(self.sd, y)

@@ -12,7 +12,11 @@ float32 kernels): 6.5e-8 .. 3.8e-7, held to the 2e-6 tests/test_oracle_golden.py
 The dense stages: against oracle/model.py's conv_stack, lookahead and the fc + softmax part of its forward, one tiny case per conv
 depth.  Conv outputs are sums of up to 7392 float32 products of magnitude 1 and below, clipped to [0, 20]: measured 1.1e-6 (depth
 1) .. 3e-7, held to 4e-6; a semantic difference (padding, stride, a mask, the BatchNorm's epsilon, the clip) is 1e-3 or more.
-Probabilities are at most 1: measured 4e-7, held to 2e-6."""
+Probabilities are at most 1: measured 4e-7, held to 2e-6.
+
+The streaming model (``stream_model``): against oracle/streaming.py on one tiny case per kind -- two utterances on one model, an
+is_first with no is_last before it, chunks of 5 / 1 / 1 frames, two sessions in one batch -- held to the probabilities' 2e-6; and
+against the reference's own run (tests/golden/g8_streaming.npz) at the 2e-6 tests/test_oracle_streaming.py holds the oracle to."""
 import numpy as np
 import pytest
 
@@ -128,3 +132,55 @@ def test_head_against_the_fp32_oracle(C, H):
     err = float(np.abs(o32 - ref).max())
     print("C %d H %d: max |fp32 oracle - f64| = %.3g" % (C, H, err))
     assert err <= 2e-6
+
+
+STREAM_SCHEDULE = [(5, True, False), (1, False, False), (1, False, True),                       # the shortest chunks there are
+                   (30, True, False), (17, False, False), (12, True, False), (9, False, False), (7, False, True)]      # is_first, no is_last before it
+
+
+@pytest.mark.parametrize("context", [1, 3])
+@pytest.mark.parametrize("kind", ["gru", "lstm", "rnn"])
+def test_stream_model_against_the_fp32_oracle(kind, context):
+    from oracle import streaming as ost
+    H, L = 24, 2
+    sd = syn.make_state_dict(2, kind, H, L, bidirectional=False, context=context, seed=68, fc_gain=4.0, sample_rate=100, window_size=0.02)
+    cfg = dict(conv_layers=2, rnn_type=kind, rnn_hidden_size=H, rnn_layers=L, bidirectional=False, context=context)
+    m64, m32 = f64.stream_model(sd, cfg), ost.StreamingModel(sd, cfg)
+    worst, frames = 0.0, []
+    for k, (T, first, last) in enumerate(STREAM_SCHEDULE):
+        x = syn.make_features(2, T, n_freq=2, seed=690 + k)
+        y64, y32 = m64.forward(x, first, last), m32.forward(x, first, last)
+        assert (y64 is None) == (y32 is None) == first                   # the first pass of an utterance yields nothing
+        frames.append(0 if y64 is None else y64.shape[1])
+        if y64 is not None:
+            assert y64.dtype == np.float64 and y64.shape == y32.shape and y64.shape[0] == 2
+            assert np.abs(y64.sum(axis=-1) - 1).max() < 1e-12
+            worst = max(worst, float(np.abs(y32 - y64).max()))
+        assert (m64.hidden[0] is None) == last and (m64.la_buf is None) == last
+    # context 1 keeps x[-0:], the whole chunk, and yields it again: 10 + 16, 16 + 23 frames; context 3: 10 + 16 - 2, 2 + 23
+    assert frames[:3] == ([0, 26, 39] if context == 1 else [0, 24, 25])
+    print("%s context %d: max |fp32 oracle - f64| = %.3g" % (kind, context, worst))
+    assert worst <= 2e-6
+
+
+@pytest.mark.parametrize("kind", ["gru", "lstm", "rnn"])
+def test_stream_model_against_the_reference_golden(golden, kind):
+    """tests/test_oracle_streaming.py's case: the reference's own streaming model, two utterances on one model."""
+    g = golden("g8_streaming")
+    tag = "%s_c2" % kind
+    chunks = [int(v) for v in g["chunks_" + tag]]
+    H, L, ctx = 32, 3, 6
+    sd = syn.make_state_dict(2, kind, H, L, bidirectional=False, context=ctx, seed=81, fc_gain=4.0)
+    m = f64.stream_model(sd, dict(conv_layers=2, rnn_type=kind, rnn_hidden_size=H, rnn_layers=L, bidirectional=False, context=ctx))
+    worst = 0.0
+    for utt in range(2):
+        for ci, T in enumerate(chunks):
+            y = m.forward(syn.make_features(1, T, seed=8100 + 100 * utt + ci), ci == 0, ci == len(chunks) - 1)
+            ref = g["probs_%s_u%d_k%d" % (tag, utt, ci)]
+            if ci == 0:
+                assert y is None and ref.size == 0
+            else:
+                assert y.shape[1:] == ref.shape
+                worst = max(worst, float(np.abs(y[0] - ref).max()))
+    print("%s: max |f64 - golden| = %.3g" % (tag, worst))
+    assert worst <= 2e-6
