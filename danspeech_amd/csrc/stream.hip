@@ -15,6 +15,7 @@
 // Only 2-conv models: the reference's streaming_init sizes the first RNN layer for two conv layers
 // whatever conv_layers says (model.py:476-484) and builds a non-streaming MaskConv for one.
 #include "model.h"
+#include "stream_host.h"
 
 #include <algorithm>
 #include <cstring>
@@ -26,15 +27,13 @@ struct dsmi_stream {
     dsmi_model* m = nullptr;
     std::string err;
     // carried state
+    StreamFlags f;                           // which of the buffers below hold something (stream_host.h)
     float* left[2] = {nullptr, nullptr};     // [ci*fi][10] per conv layer
-    bool has_left = false;
     std::vector<float*> hpack;               // per layer [2][nq][64][4]
     std::vector<float*> hcarry, ccarry;      // per layer [Hs]
     std::vector<int> pbase;
-    bool has_hidden = false;
     float* la_buf = nullptr;                 // [la_cap][Hs]
-    int la_rows = 0, la_cap = 0;
-    bool la_init = false;
+    int la_cap = 0;
     int32_t* lens_dev = nullptr;             // [2]: full-length masks of the two conv launches; [2] = INT_MAX for the RNN
     // per-call workspaces (grow only)
     int cap_T = 0;
@@ -45,10 +44,11 @@ struct dsmi_stream {
 
 static thread_local std::string g_stream_error;
 
-#define S_HIP(st, expr)                                                                   \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) { (st)->err = std::string(#expr) + ": " + hipGetErrorString(e_); return DSMI_ERR_HIP; } \
+// `err`: where the message goes, a handle's err (the single call) or g_stream_error (the batched call)
+#define S_HIP(err, expr)                                                                                          \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess) { (err) = std::string(#expr) + ": " + hipGetErrorString(e_); return DSMI_ERR_HIP; } \
     } while (0)
 
 static int sfail(dsmi_stream* st, int code, const char* msg) { st->err = msg; return code; }
@@ -103,16 +103,10 @@ extern "C" const char* dsmi_stream_last_error(const dsmi_stream* st) { return st
 // What is_last does to every module (model.py:234-236, 279-281; MaskConvStream simply stops storing).
 extern "C" int dsmi_stream_reset(dsmi_stream* st) {
     if (!st) return DSMI_ERR_INVALID;
-    st->has_left = false; st->has_hidden = false; st->la_init = false; st->la_rows = 0;
+    st->f = StreamFlags();
     std::fill(st->pbase.begin(), st->pbase.end(), 0);
     return DSMI_OK;
 }
-
-static int conv_t1(int tin) { return (tin + 2 * 5 - 11) / 2 + 1; }     // conv1: k_t 11, stride 2, pad 5 (model.py:455)
-
-// Rows LookaheadStream keeps of a chunk of Tc rows: x[-(context-1):] (model.py:263).  With context 1 that slice is x[-0:], the
-// WHOLE chunk, which the next pass then yields a second time: the reference's behaviour, kept.
-static int la_keep(int Tc, int ctx) { return ctx == 1 ? Tc : std::min(Tc, ctx - 1); }
 
 // What dsmi_debug_last_rnn_plan reports of a streaming pass: the launch of the recurrent layer that ran last.  persist8: the
 // carried-state launch of stream_persist_layer (direction 0, one direction, every lane slot of the gate, one CU per workgroup);
@@ -129,17 +123,17 @@ static void record_stream_plan(dsmi_model* m, bool persisted) {
 static int ensure(dsmi_stream* st, int T) {
     if (T <= st->cap_T) return DSMI_OK;
     dsmi_model* m = st->m;
-    S_HIP(st, hipDeviceSynchronize());
+    S_HIP(st->err, hipDeviceSynchronize());
     for (float** p : {&st->xin1, &st->y1, &st->xin2, &st->y2, &st->xp, &st->hb[0], &st->hb[1]}) free_p(*p);
     const int cap = std::max(T, 64) * 2;
     const int tin1 = cap + 15, to1 = conv_t1(tin1), tin2 = to1 + 15, to2 = tin2;
     const size_t f = m->n_freq;
-    S_HIP(st, hipMalloc((void**)&st->xin1, sizeof(float) * f * tin1));
-    S_HIP(st, hipMalloc((void**)&st->y1, sizeof(float) * 32 * m->conv_fo[0] * round_up(to1, 4)));
-    S_HIP(st, hipMalloc((void**)&st->xin2, sizeof(float) * 32 * m->conv_fo[0] * tin2));
-    S_HIP(st, hipMalloc((void**)&st->y2, sizeof(float) * 32 * m->conv_fo[1] * round_up(to2, 4)));
-    S_HIP(st, hipMalloc((void**)&st->xp, sizeof(float) * (size_t)to2 * m->geom.Np));
-    for (int i = 0; i < 2; ++i) S_HIP(st, hipMalloc((void**)&st->hb[i], sizeof(float) * (size_t)to2 * m->Hs));
+    S_HIP(st->err, hipMalloc((void**)&st->xin1, sizeof(float) * f * tin1));
+    S_HIP(st->err, hipMalloc((void**)&st->y1, sizeof(float) * 32 * m->conv_fo[0] * round_up(to1, 4)));
+    S_HIP(st->err, hipMalloc((void**)&st->xin2, sizeof(float) * 32 * m->conv_fo[0] * tin2));
+    S_HIP(st->err, hipMalloc((void**)&st->y2, sizeof(float) * 32 * m->conv_fo[1] * round_up(to2, 4)));
+    S_HIP(st->err, hipMalloc((void**)&st->xp, sizeof(float) * (size_t)to2 * m->geom.Np));
+    for (int i = 0; i < 2; ++i) S_HIP(st->err, hipMalloc((void**)&st->hb[i], sizeof(float) * (size_t)to2 * m->Hs));
     st->cap_T = cap;
     return DSMI_OK;
 }
@@ -151,126 +145,138 @@ static hipError_t copy2d(float* dst, int dst_stride, const float* src, int src_s
                             hipMemcpyDeviceToDevice, s);
 }
 
+// Room for `rows` rows in the handle's lookahead buffer; the rows it holds are kept.  Allocation only.  `err` as for S_HIP.
+static int grow_la(dsmi_stream* st, int rows, hipStream_t s, std::string& err) {
+    if (rows <= st->la_cap) return DSMI_OK;
+    const int Hs = st->m->Hs;
+    float* nb = nullptr;
+    S_HIP(err, hipMalloc((void**)&nb, sizeof(float) * (size_t)rows * 2 * Hs));
+    if (st->la_buf) {
+        S_HIP(err, hipMemcpyAsync(nb, st->la_buf, sizeof(float) * (size_t)st->f.la_rows * Hs, hipMemcpyDeviceToDevice, s));
+        S_HIP(err, hipStreamSynchronize(s));
+        (void)hipFree(st->la_buf);
+    }
+    st->la_buf = nb; st->la_cap = rows * 2;
+    return DSMI_OK;
+}
+
+// ---- the launches both executors make, from the model, the layer and what differs between them: the batch, the frames, the buffers
+static ConvLaunch conv_launch(const dsmi_model* m, int l, int B, const float* x, float* y, const int32_t* lens, int ti, int to,
+                              int ys) {
+    const ConvSpec& sp = kConvSpecs[l];
+    ConvLaunch c;
+    c.x = x; c.y = y; c.wp = m->conv[l].wp; c.bias = m->conv[l].bias; c.bn_a = m->conv[l].bn_a; c.bn_b = m->conv[l].bn_b;
+    c.out_lens_dev = lens;
+    c.B = B; c.ci = sp.ci; c.co = sp.co; c.fi = m->conv_fi[l]; c.fo = m->conv_fo[l];
+    c.ti = ti; c.to = to; c.xs = ti; c.ys = ys; c.layer = l; c.y_sp = nullptr;
+    return c;
+}
+
+// layer l's x-projection of T frames of B sessions into xp; a: conv2's output (time stride ys) for layer 0, else layer l - 1's output
+static GemmLaunch xproj_launch(const dsmi_model* m, int l, int B, int T, const float* a, int ys, float* xp) {
+    const RnnW& r = m->rnn[l];
+    GemmLaunch gl{};
+    gl.w = r.wih; gl.bias = r.bih; gl.c = xp; gl.w_sp = nullptr; gl.a_sp = nullptr; gl.a = a;
+    gl.M = T * B; gl.N = m->geom.Np; gl.K = r.K; gl.ldw = r.ldw; gl.ldc = m->geom.Np; gl.B = B; gl.T = T;
+    if (l == 0) { gl.mode = GEMM_A_CONV; gl.ys = ys; }
+    else { gl.mode = GEMM_A_SUM_BN; gl.a2 = nullptr; gl.alpha = r.bn_a; gl.beta = r.bn_b; gl.lda = m->Hs; }
+    return gl;
+}
+
+// layer l per step from the carried state (hcarry null: zero); the caller sets .step
+static RnnStepLaunch step_launch(const dsmi_model* m, int l, int B, int T, const float* xp, const int32_t* lens, float* out,
+                                 float* cstate, float* hpack, const float* hcarry, int pbase) {
+    const RnnW& r = m->rnn[l];
+    RnnStepLaunch sl;
+    sl.g = m->geom;
+    sl.whh_packed[0] = r.whh[0]; sl.whh_packed[1] = nullptr; sl.bhh[0] = r.bhh[0]; sl.bhh[1] = nullptr;
+    sl.out[0] = out; sl.out[1] = nullptr; sl.cstate[0] = cstate; sl.cstate[1] = nullptr;
+    sl.xp = xp; sl.lens_dev = lens; sl.B = B; sl.T = T; sl.hpack = hpack; sl.hcarry = hcarry; sl.pbase = pbase;
+    return sl;
+}
+
+// fc + softmax (model.py:531-536) of T rows of B sessions of the lookahead's output
+static HeadLaunch head_launch(const dsmi_model* m, int B, int T, const float* x, float* probs) {
+    HeadLaunch h;
+    h.bn_a = m->fc_a; h.bn_b = m->fc_b; h.w_packed = m->fc_wp; h.H = m->desc.rnn_hidden_size; h.C = m->desc.n_labels;
+    h.T = T; h.B = B; h.probs = probs; h.x1 = x; h.x2 = nullptr;
+    return h;
+}
+
+// The pass is planned (stream_host.h) before anything is allocated or enqueued: a refused call changes nothing.  The handle's flags and
+// parities are committed once, where the whole pass, a buffering one included, has been enqueued without error.  After a HIP error
+// mid-pass they are as before while the device buffers may be partly overwritten: the carried state is undefined until dsmi_stream_reset.
 extern "C" int dsmi_stream_forward(dsmi_stream* st, const float* feat, int T, int is_first, int is_last, float* probs,
                                    int T_out_cap, int32_t* T_out, void* stream) {
     if (!st) return DSMI_ERR_INVALID;
     if (!feat || !T_out || T < 1) return sfail(st, DSMI_ERR_INVALID, "bad stream arguments");
     dsmi_model* m = st->m;
     const dsmi_model_desc& d = m->desc;
-    S_HIP(st, hipSetDevice(m->device));
+    S_HIP(st->err, hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
     *T_out = 0;
-    if (!is_first && !st->has_left)
-        return sfail(st, DSMI_ERR_INVALID, "the first chunk of an utterance must be passed with is_first (MaskConvStream has no left context)");
-    int rc = ensure(st, T);
-    if (rc) return rc;
+    StreamPass p;
+    const char* why = nullptr;
+    int rc = stream_pass_plan(st->f, T, is_first != 0, is_last != 0, d.context, probs != nullptr, T_out_cap, &p, &why);
+    if (rc) return sfail(st, rc, why);
+    if ((rc = ensure(st, T))) return rc;
 
     // ---- MaskConvStream (model.py:171-201): per conv layer, pad / glue the left context, remember the tail
-    const int padl = is_first ? 5 : 0, padr = (!is_first && is_last) ? 5 : 0, ctxl = is_first ? 0 : 10;
-    const int tin1 = ctxl + padl + T + padr, to1 = conv_t1(tin1);
-    const int tin2 = ctxl + padl + to1 + padr, to2 = tin2;
-    if ((!is_last && (tin1 < 10 || tin2 < 10)) || to1 < 1) return sfail(st, DSMI_ERR_INVALID, "chunk too short for the conv context");
-    const int ys1 = round_up(to1, 4), ys2 = round_up(to2, 4);
-    // everything that can be refused is refused here, before any carried state changes
-    const bool buffering = !st->la_init || is_first;
-    const int ncat = st->la_rows + to2;
-    const int nout = buffering ? 0 : (is_last ? ncat : ncat - (d.context - 1));
-    if (!buffering && nout < 1) return sfail(st, DSMI_ERR_INVALID, "lookahead: fewer buffered frames than the context (torch raises here too)");
-    if (!buffering && (!probs || T_out_cap < nout)) return sfail(st, DSMI_ERR_CAPACITY, "probs buffer smaller than the frames this pass yields");
-    const int32_t lens_host[4] = {to1, to2, 0x7fffffff, 0};
-    S_HIP(st, hipMemcpyAsync(st->lens_dev, lens_host, sizeof(lens_host), hipMemcpyHostToDevice, s));
+    const int Tc = p.to[1], ys[2] = {round_up(p.to[0], 4), round_up(Tc, 4)};
+    const int32_t lens_host[4] = {p.to[0], Tc, 0x7fffffff, 0};
+    S_HIP(st->err, hipMemcpyAsync(st->lens_dev, lens_host, sizeof(lens_host), hipMemcpyHostToDevice, s));
     const float* src[2] = {feat, st->y1};
-    const int src_stride[2] = {T, ys1}, src_w[2] = {T, to1}, tin[2] = {tin1, tin2}, tout[2] = {to1, to2}, ysv[2] = {ys1, ys2};
+    const int src_stride[2] = {T, ys[0]}, src_w[2] = {T, p.to[0]};
     float* xin[2] = {st->xin1, st->xin2};
     float* yv[2] = {st->y1, st->y2};
     for (int l = 0; l < 2; ++l) {
-        const ConvSpec& sp = kConvSpecs[l];
-        const int rows = sp.ci * m->conv_fi[l];
-        if (padl || padr) S_HIP(st, hipMemsetAsync(xin[l], 0, sizeof(float) * (size_t)rows * tin[l], s));
-        if (ctxl) S_HIP(st, copy2d(xin[l], tin[l], st->left[l], 10, rows, 10, s));
-        S_HIP(st, copy2d(xin[l] + ctxl + padl, tin[l], src[l], src_stride[l], rows, src_w[l], s));
-        if (!is_last) S_HIP(st, copy2d(st->left[l], 10, xin[l] + tin[l] - 10, tin[l], rows, 10, s));
-        ConvLaunch c;
-        c.x = xin[l]; c.y = yv[l]; c.wp = m->conv[l].wp; c.bias = m->conv[l].bias; c.bn_a = m->conv[l].bn_a; c.bn_b = m->conv[l].bn_b;
-        c.out_lens_dev = st->lens_dev + l;
-        c.B = 1; c.ci = sp.ci; c.co = sp.co; c.fi = m->conv_fi[l]; c.fo = m->conv_fo[l];
-        c.ti = tin[l]; c.to = tout[l]; c.xs = tin[l]; c.ys = ysv[l]; c.layer = l; c.y_sp = nullptr;
-        launch_conv(c, s);
+        const int rows = kConvSpecs[l].ci * m->conv_fi[l], tin = p.tin[l];
+        if (p.padl || p.padr) S_HIP(st->err, hipMemsetAsync(xin[l], 0, sizeof(float) * (size_t)rows * tin, s));
+        if (p.ctxl) S_HIP(st->err, copy2d(xin[l], tin, st->left[l], 10, rows, 10, s));
+        S_HIP(st->err, copy2d(xin[l] + p.ctxl + p.padl, tin, src[l], src_stride[l], rows, src_w[l], s));
+        if (!is_last) S_HIP(st->err, copy2d(st->left[l], 10, xin[l] + tin - 10, tin, rows, 10, s));
+        launch_conv(conv_launch(m, l, 1, xin[l], yv[l], st->lens_dev + l, tin, p.to[l], ys[l]), s);
     }
-    st->has_left = !is_last;
 
     // ---- BatchRNNStream x layers (model.py:219-238): x-projection of the chunk, then Tc steps from the carried state
-    const int Tc = to2;
+    const int Hs = m->Hs;
     for (int l = 0; l < d.rnn_layers; ++l) {
-        const RnnW& r = m->rnn[l];
-        GemmLaunch gl{};
-        gl.w = r.wih; gl.bias = r.bih; gl.c = st->xp; gl.w_sp = nullptr; gl.a_sp = nullptr;
-        gl.M = Tc; gl.N = m->geom.Np; gl.K = r.K; gl.ldw = r.ldw; gl.ldc = m->geom.Np; gl.B = 1; gl.T = Tc;
-        if (l == 0) { gl.mode = GEMM_A_CONV; gl.a = st->y2; gl.ys = ys2; }
-        else { gl.mode = GEMM_A_SUM_BN; gl.a = st->hb[(l - 1) & 1]; gl.a2 = nullptr; gl.alpha = r.bn_a; gl.beta = r.bn_b; gl.lda = m->Hs; }
-        launch_gemm(gl, s);
+        launch_gemm(xproj_launch(m, l, 1, Tc, l == 0 ? st->y2 : st->hb[(l - 1) & 1], ys[1], st->xp), s);
         float* out = st->hb[l & 1];
-        if (m->Hs != d.rnn_hidden_size) S_HIP(st, hipMemsetAsync(out, 0, sizeof(float) * (size_t)Tc * m->Hs, s));
-        RnnStepLaunch sl;
-        sl.g = m->geom;
-        sl.whh_packed[0] = r.whh[0]; sl.whh_packed[1] = nullptr; sl.bhh[0] = r.bhh[0]; sl.bhh[1] = nullptr;
-        sl.out[0] = out; sl.out[1] = nullptr; sl.cstate[0] = st->ccarry[l]; sl.cstate[1] = nullptr;
-        sl.xp = st->xp; sl.lens_dev = st->lens_dev + 2; sl.B = 1; sl.T = Tc; sl.hpack = st->hpack[l];
-        sl.hcarry = st->has_hidden ? st->hcarry[l] : nullptr; sl.pbase = st->pbase[l];
+        if (Hs != d.rnn_hidden_size) S_HIP(st->err, hipMemsetAsync(out, 0, sizeof(float) * (size_t)Tc * Hs, s));
+        RnnStepLaunch sl = step_launch(m, l, 1, Tc, st->xp, st->lens_dev + 2, out, st->ccarry[l], st->hpack[l],
+                                       st->f.has_hidden ? st->hcarry[l] : nullptr, st->pbase[l]);
         for (int step = 0; step < Tc; ++step) { sl.step = step; launch_rnn_step(sl, s); }
         record_stream_plan(m, false);
-        S_HIP(st, hipMemcpyAsync(st->hcarry[l], out + (size_t)(Tc - 1) * m->Hs, sizeof(float) * m->Hs, hipMemcpyDeviceToDevice, s));
-        st->pbase[l] = (Tc + st->pbase[l]) & 1;
+        S_HIP(st->err, hipMemcpyAsync(st->hcarry[l], out + (size_t)(Tc - 1) * Hs, sizeof(float) * Hs, hipMemcpyDeviceToDevice, s));
     }
-    st->has_hidden = !is_last;
-    if (is_last) std::fill(st->pbase.begin(), st->pbase.end(), 0);
     const float* x = st->hb[(d.rnn_layers - 1) & 1];
 
-    // ---- LookaheadStream (model.py:256-283)
-    const int ctx = d.context, Hs = m->Hs;
-    auto grow_la = [&](int rows) -> int {
-        if (rows <= st->la_cap) return DSMI_OK;
-        float* nb = nullptr;
-        S_HIP(st, hipMalloc((void**)&nb, sizeof(float) * (size_t)rows * 2 * Hs));
-        if (st->la_buf) {
-            S_HIP(st, hipMemcpyAsync(nb, st->la_buf, sizeof(float) * (size_t)st->la_rows * Hs, hipMemcpyDeviceToDevice, s));
-            S_HIP(st, hipStreamSynchronize(s));
-            (void)hipFree(st->la_buf);
+    // ---- LookaheadStream (model.py:256-283), then fc + softmax
+    const int la_rows = st->f.la_rows;
+    if (p.buffering) {                           // buffer the whole first chunk, no output yet
+        if ((rc = grow_la(st, Tc, s, st->err))) return rc;
+        S_HIP(st->err, hipMemcpyAsync(st->la_buf, x, sizeof(float) * (size_t)Tc * Hs, hipMemcpyDeviceToDevice, s));
+    } else {
+        if (p.ncat > st->cat_cap) {
+            S_HIP(st->err, hipStreamSynchronize(s));
+            free_p(st->cat); free_p(st->la_out);
+            st->cat_cap = p.ncat * 2;
+            S_HIP(st->err, hipMalloc((void**)&st->cat, sizeof(float) * (size_t)st->cat_cap * Hs));
+            S_HIP(st->err, hipMalloc((void**)&st->la_out, sizeof(float) * (size_t)st->cat_cap * Hs));
         }
-        st->la_buf = nb; st->la_cap = rows * 2;
-        return DSMI_OK;
-    };
-    if (buffering) {                             // buffer the whole first chunk, no output yet
-        if ((rc = grow_la(Tc))) return rc;
-        S_HIP(st, hipMemcpyAsync(st->la_buf, x, sizeof(float) * (size_t)Tc * Hs, hipMemcpyDeviceToDevice, s));
-        st->la_rows = Tc; st->la_init = true;
-        S_HIP(st, hipGetLastError());
-        return DSMI_OK;
+        S_HIP(st->err, hipMemcpyAsync(st->cat, st->la_buf, sizeof(float) * (size_t)la_rows * Hs, hipMemcpyDeviceToDevice, s));
+        S_HIP(st->err, hipMemcpyAsync(st->cat + (size_t)la_rows * Hs, x, sizeof(float) * (size_t)Tc * Hs, hipMemcpyDeviceToDevice, s));
+        if ((rc = grow_la(st, p.keep, s, st->err))) return rc;
+        S_HIP(st->err, hipMemcpyAsync(st->la_buf, x + (size_t)(Tc - p.keep) * Hs, sizeof(float) * (size_t)p.keep * Hs,
+                                      hipMemcpyDeviceToDevice, s));
+        // rows past ncat count as zeros in the kernel: the is_last right padding; otherwise only the first nout rows are kept
+        launch_lookahead(st->cat, m->look_w, st->la_out, p.ncat, 1, d.rnn_hidden_size, d.context, s);
+        launch_head(head_launch(m, 1, p.nout, st->la_out, probs), s);
     }
-    if (ncat > st->cat_cap) {
-        S_HIP(st, hipStreamSynchronize(s));
-        free_p(st->cat); free_p(st->la_out);
-        st->cat_cap = ncat * 2;
-        S_HIP(st, hipMalloc((void**)&st->cat, sizeof(float) * (size_t)st->cat_cap * Hs));
-        S_HIP(st, hipMalloc((void**)&st->la_out, sizeof(float) * (size_t)st->cat_cap * Hs));
-    }
-    S_HIP(st, hipMemcpyAsync(st->cat, st->la_buf, sizeof(float) * (size_t)st->la_rows * Hs, hipMemcpyDeviceToDevice, s));
-    S_HIP(st, hipMemcpyAsync(st->cat + (size_t)st->la_rows * Hs, x, sizeof(float) * (size_t)Tc * Hs, hipMemcpyDeviceToDevice, s));
-    const int keep = la_keep(Tc, ctx);
-    if ((rc = grow_la(keep))) return rc;
-    S_HIP(st, hipMemcpyAsync(st->la_buf, x + (size_t)(Tc - keep) * Hs, sizeof(float) * (size_t)keep * Hs, hipMemcpyDeviceToDevice, s));
-    st->la_rows = keep;
-    // rows past ncat count as zeros in the kernel: the is_last right padding; otherwise only the first nout rows are kept
-    launch_lookahead(st->cat, m->look_w, st->la_out, ncat, 1, d.rnn_hidden_size, ctx, s);
-    if (is_last) { st->la_init = false; st->la_rows = 0; }
-
-    // ---- fc + softmax (model.py:531-536)
-    HeadLaunch h;
-    h.bn_a = m->fc_a; h.bn_b = m->fc_b; h.w_packed = m->fc_wp; h.H = d.rnn_hidden_size; h.C = d.n_labels;
-    h.T = nout; h.B = 1; h.probs = probs; h.x1 = st->la_out; h.x2 = nullptr;
-    launch_head(h, s);
-    S_HIP(st, hipGetLastError());
-    *T_out = nout;
+    S_HIP(st->err, hipGetLastError());
+    stream_pass_commit(st->f, st->pbase.data(), d.rnn_layers, p, is_last != 0);
+    *T_out = p.nout;
     return DSMI_OK;
 }
 
@@ -426,26 +432,6 @@ __global__ __launch_bounds__(256) void stream_commit_kernel(const SessDev* sd, c
 
 static int many_fail(int code, const std::string& msg) { g_stream_error = msg; return code; }
 
-#define M_HIP(expr)                                                                                              \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return many_fail(DSMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-static int grow_la_rows(dsmi_stream* st, int rows, hipStream_t s) {
-    if (rows <= st->la_cap) return DSMI_OK;
-    const int Hs = st->m->Hs;
-    float* nb = nullptr;
-    M_HIP(hipMalloc((void**)&nb, sizeof(float) * (size_t)rows * 2 * Hs));
-    if (st->la_buf) {
-        M_HIP(hipMemcpyAsync(nb, st->la_buf, sizeof(float) * (size_t)st->la_rows * Hs, hipMemcpyDeviceToDevice, s));
-        M_HIP(hipStreamSynchronize(s));
-        (void)hipFree(st->la_buf);
-    }
-    st->la_buf = nb; st->la_cap = rows * 2;
-    return DSMI_OK;
-}
-
 extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, const float* const* feat, const int* T, const int* is_first,
                                         const int* is_last, float* probs, int T_out_cap, int32_t* T_out, void* stream) {
     // ---- refusals: arguments, then every session's protocol and capacity, before any device work or state change
@@ -464,35 +450,29 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
     const dsmi_model_desc& d = m->desc;
     const int L = d.rnn_layers, Hs = m->Hs, ctx = d.context, C = d.n_labels;
     std::vector<SessDev> sd(n);
-    std::vector<int> nout(n, 0);
-    int tin1max = 1, tin2max = 1, ncatmax = 0, noutmax = 0;
+    std::vector<StreamPass> pass(n);
+    int tin1max = 1, to1max = 1, tin2max = 1, ncatmax = 0, noutmax = 0;
     bool any_out = false;
     for (int i = 0; i < n; ++i) {
         const dsmi_stream* st = streams[i];
-        const bool first = is_first[i] != 0, last = is_last[i] != 0;
-        if (!first && !st->has_left)
-            return sess_fail(DSMI_ERR_INVALID, i, "the first chunk of an utterance must be passed with is_first (MaskConvStream has no left context)");
-        const int padl = first ? 5 : 0, padr = (!first && last) ? 5 : 0, ctxl = first ? 0 : 10;
-        const int tin1 = ctxl + padl + T[i] + padr, to1 = conv_t1(tin1);
-        const int tin2 = ctxl + padl + to1 + padr, to2 = tin2;
-        if ((!last && (tin1 < 10 || tin2 < 10)) || to1 < 1) return sess_fail(DSMI_ERR_INVALID, i, "chunk too short for the conv context");
-        const bool buffering = !st->la_init || first;
-        const int ncat = st->la_rows + to2;
-        const int no = buffering ? 0 : (last ? ncat : ncat - (ctx - 1));
-        if (!buffering && no < 1) return sess_fail(DSMI_ERR_INVALID, i, "lookahead: fewer buffered frames than the context (torch raises here too)");
-        if (!buffering && (!probs || T_out_cap < no)) return sess_fail(DSMI_ERR_CAPACITY, i, "probs slot smaller than the frames this pass yields");
+        const bool last = is_last[i] != 0;
+        StreamPass& p = pass[i];
+        const char* why = nullptr;
+        const int rc = stream_pass_plan(st->f, T[i], is_first[i] != 0, last, ctx, probs != nullptr, T_out_cap, &p, &why);
+        if (rc) return sess_fail(rc, i, why);
         SessDev& S = sd[i];
         S.feat = feat[i]; S.left[0] = st->left[0]; S.left[1] = st->left[1]; S.la_buf = st->la_buf;
-        S.T = T[i]; S.ctxl = ctxl; S.padl = padl; S.is_last = last; S.seed = st->has_hidden; S.buffering = buffering;
-        S.la_rows = buffering ? 0 : st->la_rows; S.ncat = buffering ? 0 : ncat; S.keep = la_keep(to2, ctx);
-        S.tin[0] = tin1; S.tin[1] = tin2; S.to[0] = to1; S.to[1] = to2;
-        nout[i] = no;
-        tin1max = std::max(tin1max, tin1); tin2max = std::max(tin2max, tin2);
-        if (!buffering) { any_out = true; ncatmax = std::max(ncatmax, ncat); noutmax = std::max(noutmax, no); }
+        S.T = T[i]; S.ctxl = p.ctxl; S.padl = p.padl; S.is_last = last; S.seed = st->f.has_hidden; S.buffering = p.buffering;
+        S.la_rows = p.buffering ? 0 : st->f.la_rows; S.ncat = p.buffering ? 0 : p.ncat; S.keep = p.keep;
+        for (int l = 0; l < 2; ++l) { S.tin[l] = p.tin[l]; S.to[l] = p.to[l]; }
+        tin1max = std::max(tin1max, p.tin[0]);
+        to1max = std::max(to1max, p.to[0]);
+        tin2max = std::max(tin2max, p.tin[1]);
+        if (!p.buffering) { any_out = true; ncatmax = std::max(ncatmax, p.ncat); noutmax = std::max(noutmax, p.nout); }
     }
     for (int i = 0; i < n; ++i) T_out[i] = 0;
 
-    M_HIP(hipSetDevice(m->device));
+    S_HIP(g_stream_error, hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
     {
         static std::mutex create_mu;          // two threads' first batched calls on one model
@@ -503,19 +483,18 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
     std::lock_guard<std::mutex> lk(b.mu);
     // ---- capacity (allocation only; no session's state is touched)
     for (int i = 0; i < n; ++i) {
-        int rc = grow_la_rows(streams[i], sd[i].buffering ? sd[i].to[1] : sd[i].keep, s);
-        if (rc) return rc;
+        if (int rc = grow_la(streams[i], pass[i].buffering ? pass[i].to[1] : pass[i].keep, s, g_stream_error)) return rc;
         sd[i].la_buf = streams[i]->la_buf;
     }
     const int rows0 = kConvSpecs[0].ci * m->conv_fi[0], rows1 = kConvSpecs[1].ci * m->conv_fi[1];
-    const int to1max = conv_t1(tin1max), ys1 = round_up(to1max, 4), tcmax = tin2max, ys2 = round_up(tcmax, 4);
+    const int ys1 = round_up(to1max, 4), tcmax = tin2max, ys2 = round_up(tcmax, 4);
     const int nz = ceil_div(n, 32), nq = m->geom.nq, npair = ceil_div(nq, 2);
     const size_t tab_bytes = sizeof(SessDev) * n + sizeof(LayerDev) * (size_t)L * n + sizeof(int32_t) * 2 * n + 64;
     if (tab_bytes > b.tab_host_cap) {
-        M_HIP(hipStreamSynchronize(s));
+        S_HIP(g_stream_error, hipStreamSynchronize(s));
         if (b.tab_host) (void)hipHostFree(b.tab_host);
         b.tab_host = nullptr; b.tab_host_cap = 0;
-        M_HIP(hipHostMalloc((void**)&b.tab_host, tab_bytes * 2, hipHostMallocDefault));
+        S_HIP(g_stream_error, hipHostMalloc((void**)&b.tab_host, tab_bytes * 2, hipHostMallocDefault));
         b.tab_host_cap = tab_bytes * 2;
     }
     bool ok = grow_dev(b.tab, b.cap[0], tab_bytes) &&
@@ -551,24 +530,18 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
     const SessDev* sd_dev = reinterpret_cast<const SessDev*>(tdev);
     const LayerDev* ld_dev = reinterpret_cast<const LayerDev*>(tdev + sizeof(SessDev) * n);
     const int32_t* lens_dev = reinterpret_cast<const int32_t*>(tdev + sizeof(SessDev) * n + sizeof(LayerDev) * (size_t)L * n);
-    M_HIP(hipMemcpyAsync(tdev, th, tab_bytes - 64, hipMemcpyHostToDevice, s));
+    S_HIP(g_stream_error, hipMemcpyAsync(tdev, th, tab_bytes - 64, hipMemcpyHostToDevice, s));
 
     // ---- MaskConvStream for all sessions
     const int tinl[2] = {tin1max, tin2max}, toutl[2] = {to1max, tcmax}, ysl[2] = {ys1, ys2}, rowsl[2] = {rows0, rows1};
     for (int l = 0; l < 2; ++l) {
-        const ConvSpec& sp = kConvSpecs[l];
         const int blocks = std::min(ceil_div(rowsl[l] * tinl[l], 256), 256);
         hipLaunchKernelGGL(stream_conv_in_kernel, dim3(blocks, n), dim3(256), 0, s, sd_dev, l, (const float*)b.y[0], ys1, rowsl[l], tinl[l], b.xin[l]);
-        ConvLaunch c;
-        c.x = b.xin[l]; c.y = b.y[l]; c.wp = m->conv[l].wp; c.bias = m->conv[l].bias; c.bn_a = m->conv[l].bn_a; c.bn_b = m->conv[l].bn_b;
-        c.out_lens_dev = lens_dev + l * n;
-        c.B = n; c.ci = sp.ci; c.co = sp.co; c.fi = m->conv_fi[l]; c.fo = m->conv_fo[l];
-        c.ti = tinl[l]; c.to = toutl[l]; c.xs = tinl[l]; c.ys = ysl[l]; c.layer = l; c.y_sp = nullptr;
-        launch_conv(c, s);
+        launch_conv(conv_launch(m, l, n, b.xin[l], b.y[l], lens_dev + l * n, tinl[l], toutl[l], ysl[l]), s);
     }
 
     // ---- recurrent layers (attempt 0 may use the persistent kernel; attempt 1 recomputes a timed-out pass per step), lookahead, head
-    M_HIP(hipMemsetAsync(b.err, 0, sizeof(unsigned), s));
+    S_HIP(g_stream_error, hipMemsetAsync(b.err, 0, sizeof(unsigned), s));
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool persisted = false;
         const int sblocks = std::min(ceil_div(nz * 32 * Hs, 256), 512);
@@ -576,13 +549,8 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
         for (int l = 0; l < L; ++l) {
             const RnnW& r = m->rnn[l];
             float* out = b.hb + (size_t)l * tcmax * n * Hs;
-            GemmLaunch gl{};
-            gl.w = r.wih; gl.bias = r.bih; gl.c = b.xp; gl.w_sp = nullptr; gl.a_sp = nullptr;
-            gl.M = tcmax * n; gl.N = m->geom.Np; gl.K = r.K; gl.ldw = r.ldw; gl.ldc = m->geom.Np; gl.B = n; gl.T = tcmax;
-            if (l == 0) { gl.mode = GEMM_A_CONV; gl.a = b.y[1]; gl.ys = ys2; }
-            else { gl.mode = GEMM_A_SUM_BN; gl.a = out - (size_t)tcmax * n * Hs; gl.a2 = nullptr; gl.alpha = r.bn_a; gl.beta = r.bn_b; gl.lda = Hs; }
-            launch_gemm(gl, s);
-            if (Hs != d.rnn_hidden_size) M_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)tcmax * n * Hs, s));
+            launch_gemm(xproj_launch(m, l, n, tcmax, l == 0 ? b.y[1] : out - (size_t)tcmax * n * Hs, ys2, b.xp), s);
+            if (Hs != d.rnn_hidden_size) S_HIP(g_stream_error, hipMemsetAsync(out, 0, sizeof(float) * (size_t)tcmax * n * Hs, s));
             float* h0 = b.hseed + (size_t)l * n * Hs;
             float* cw = b.cwork + (size_t)l * n * Hs;
             bool done = false;
@@ -591,17 +559,13 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
                 pl.whh_sp[1] = nullptr; pl.bhh[1] = nullptr; pl.out[0] = out; pl.out[1] = nullptr;
                 pl.xp = b.xp; pl.lens_dev = lens_dev + n; pl.hpack_sp = b.hpack_sp; pl.counters = b.cnt; pl.err = b.err;
                 pl.h0 = h0; pl.cst = cw;
-                M_HIP(hipMemsetAsync(b.cnt, 0, sizeof(unsigned) * (size_t)nz * (tcmax + 1), s));
+                S_HIP(g_stream_error, hipMemsetAsync(b.cnt, 0, sizeof(unsigned) * (size_t)nz * (tcmax + 1), s));
                 done = stream_persist_layer(m, pl, s);
                 persisted = persisted || done;
             }
             if (!done) {
-                RnnStepLaunch sl;
-                sl.g = m->geom;
-                sl.whh_packed[0] = r.whh[0]; sl.whh_packed[1] = nullptr; sl.bhh[0] = r.bhh[0]; sl.bhh[1] = nullptr;
-                sl.out[0] = out; sl.out[1] = nullptr; sl.cstate[0] = cw; sl.cstate[1] = nullptr;
-                sl.xp = b.xp; sl.lens_dev = lens_dev + n; sl.B = n; sl.T = tcmax; sl.hpack = b.hpack + (size_t)l * 2 * nz * nq * 256;
-                sl.hcarry = h0; sl.pbase = 0;
+                float* hp = b.hpack + (size_t)l * 2 * nz * nq * 256;
+                RnnStepLaunch sl = step_launch(m, l, n, tcmax, b.xp, lens_dev + n, out, cw, hp, h0, 0);
                 for (int step = 0; step < tcmax; ++step) { sl.step = step; launch_rnn_step(sl, s); }
             }
             record_stream_plan(m, done);
@@ -612,45 +576,32 @@ extern "C" int dsmi_stream_forward_many(dsmi_stream* const* streams, int n, cons
             hipLaunchKernelGGL(stream_cat_kernel, dim3((unsigned)std::min<size_t>((items + 255) / 256, 2048)), dim3(256), 0, s,
                                sd_dev, x, n, Hs, ncatmax, b.cat);
             launch_lookahead(b.cat, m->look_w, b.la_out, ncatmax, n, d.rnn_hidden_size, ctx, s);
-            HeadLaunch h;
-            h.bn_a = m->fc_a; h.bn_b = m->fc_b; h.w_packed = m->fc_wp; h.H = d.rnn_hidden_size; h.C = C;
-            h.T = noutmax; h.B = n; h.probs = b.probs; h.x1 = b.la_out; h.x2 = nullptr;
-            launch_head(h, s);
+            launch_head(head_launch(m, n, noutmax, b.la_out, b.probs), s);
         }
-        M_HIP(hipGetLastError());
+        S_HIP(g_stream_error, hipGetLastError());
         if (!persisted) break;
         unsigned e = 0;
-        M_HIP(hipMemcpyAsync(&e, b.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        M_HIP(hipStreamSynchronize(s));
+        S_HIP(g_stream_error, hipMemcpyAsync(&e, b.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        S_HIP(g_stream_error, hipStreamSynchronize(s));
         if (!e) break;
         // a hand-off wait timed out: the pass is recomputed on the per-step path from the same seeded state, and this model
         // stays there (as dsmi_rnn_layer does)
-        M_HIP(hipMemsetAsync(b.err, 0, sizeof(unsigned), s));
+        S_HIP(g_stream_error, hipMemsetAsync(b.err, 0, sizeof(unsigned), s));
         m->rnn_mode = 0;
         m->recomputed += 1;
     }
     if (any_out)
-        M_HIP(hipMemcpy2DAsync(probs, sizeof(float) * (size_t)T_out_cap * C, b.probs, sizeof(float) * (size_t)noutmax * C,
+        S_HIP(g_stream_error, hipMemcpy2DAsync(probs, sizeof(float) * (size_t)T_out_cap * C, b.probs, sizeof(float) * (size_t)noutmax * C,
                                sizeof(float) * (size_t)noutmax * C, n, hipMemcpyDeviceToDevice, s));
 
     // ---- commit every session's new state
     hipLaunchKernelGGL(stream_commit_kernel, dim3(16, n), dim3(256), 0, s, sd_dev, ld_dev, n, L, Hs, nq, (const float*)b.xin[0], rows0,
                        tin1max, (const float*)b.xin[1], rows1, tin2max, (const float*)b.hb, tcmax, (const float*)b.cwork);
-    M_HIP(hipGetLastError());
-    M_HIP(hipStreamSynchronize(s));
+    S_HIP(g_stream_error, hipGetLastError());
+    S_HIP(g_stream_error, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i) {
-        dsmi_stream* st = streams[i];
-        const bool last = is_last[i] != 0;
-        const int Tc = sd[i].to[1];
-        st->has_left = !last;
-        for (int l = 0; l < L; ++l) st->pbase[l] = last ? 0 : (Tc + st->pbase[l]) & 1;
-        st->has_hidden = !last;
-        if (sd[i].buffering) { st->la_rows = Tc; st->la_init = true; }
-        else {
-            st->la_rows = sd[i].keep;
-            if (last) { st->la_init = false; st->la_rows = 0; }
-        }
-        T_out[i] = nout[i];
+        stream_pass_commit(streams[i]->f, streams[i]->pbase.data(), L, pass[i], is_last[i] != 0);
+        T_out[i] = pass[i].nout;
     }
     return DSMI_OK;
 }

@@ -309,7 +309,8 @@ int dsmi_features_stream_many(dsmi_frontend* f, const void* pcm_dev, int pcm_dty
  * number of streams.  feat_dev [n_freq][T] float32 (one chunk of the streaming parser's output);
  * probs_dev [T_out_cap][n_labels].  *T_out = frames written: 0 on the first pass (is_first), when the
  * lookahead only buffers (streaming_forward returns None, :529-530).  is_last flushes the lookahead with its
- * right padding and clears all carried state.  Asynchronous on `stream`. */
+ * right padding and clears all carried state.  Asynchronous on `stream`.  A refused call (DSMI_ERR_INVALID, DSMI_ERR_CAPACITY)
+ * changes nothing; after DSMI_ERR_HIP the handle's carried state is undefined until dsmi_stream_reset. */
 typedef struct dsmi_stream dsmi_stream;
 int dsmi_stream_create(dsmi_model* m, dsmi_stream** out);
 void dsmi_stream_destroy(dsmi_stream* s);

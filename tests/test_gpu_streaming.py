@@ -76,6 +76,59 @@ def test_stream_forward_vs_oracle_wide_model_many_chunks(native):
     m.close()
 
 
+@pytest.mark.parametrize("ctx", [8, 27])
+def test_refusals_change_nothing(native, ctx):
+    """dsmi_stream_forward's counterpart of tests/test_gpu_stream_sessions.py::test_refusals_change_nothing: two handles are fed the
+    same chunks, A also one call of every refusable kind between them; every refused call reports its code and sentence and
+    leaves T_out 0, and every later pass of A equals B's bit for bit.  A lookahead with too few frames needs a context of 27 or
+    more (the shortest buffered chunk has 10 rows, the shortest chunk after it 16: tests/test_stream_pass_host.py), so context 8
+    has the other three kinds and context 27 all four."""
+    import _stream_cases as sc
+    c = sc._case("refusals", "gru", 64, 1, [sc.SHORT], context=ctx)
+    cfg, sd, ac = sc.make_case(c)
+    m = native.NativeModel(cfg, sd, audio_conf=ac)
+    a, b = native.NativeStream(m), native.NativeStream(m)
+    x = lambda T, seed: torch.from_numpy(syn.make_features(1, T, n_freq=2, seed=8700 + seed)).cuda()
+
+    def refused(T, first, last, cap, code, text):
+        feat = x(T, 99).reshape(2, T).contiguous()
+        probs = torch.empty((max(cap, 1), m.n_labels), dtype=torch.float32, device="cuda")
+        tout = np.full(1, 7, dtype=np.int32)
+        rc = native.lib().dsmi_stream_forward(a._h, feat.data_ptr(), T, int(first), int(last), probs.data_ptr(), cap, native._np_ptr(tout),
+                                              native._stream(m.device))
+        assert rc == code and tout[0] == 0
+        with pytest.raises(native.DsmiError, match=text) as e:
+            a._check(rc)
+        assert e.value.code == code
+
+    def both(T, seed, first, last):
+        xa = x(T, seed)
+        ya, yb = a.forward(xa, first, last), b.forward(xa, first, last)
+        assert (ya is None) == (yb is None)
+        if ya is not None:
+            assert ya.shape == yb.shape and torch.equal(ya, yb)
+        return yb
+
+    I, big = native.DSMI_ERR_INVALID, 4096
+    refused(40, False, False, big, I, "must be passed with is_first")               # no is_first on a fresh handle
+    assert both(40, 0, True, False) is None
+    refused(1, True, False, big, I, "chunk too short")                               # a 1-frame first chunk that is not the last
+    n1 = both(39, 1, False, False).shape[1]
+    yb = b.forward(x(41, 2), False, False)                                           # B first: the frames the pass yields
+    refused(41, False, False, yb.shape[1] - 1, native.DSMI_ERR_CAPACITY, "probs slot smaller")      # room for one frame less
+    ya = a.forward(x(41, 2), False, False)
+    assert n1 >= 1 and ya.shape == yb.shape and torch.equal(ya, yb)
+    assert both(17, 3, False, True) is not None
+    refused(39, False, False, big, I, "must be passed with is_first")               # ... and on a finished one
+    # the next utterance on the same handles: the shortest first chunk, after which a 1-frame chunk has 26 rows to emit from
+    assert both(5, 4, True, False) is None
+    if ctx >= 27:
+        refused(1, False, False, big, I, "fewer buffered frames than the context")
+    assert both(40, 5, False, False) is not None
+    assert both(20, 6, False, True) is not None
+    a.close(); b.close(); m.close()
+
+
 def test_features_stream_vs_oracle(native):
     from oracle import streaming as ost
     fe = native.NativeFrontend()

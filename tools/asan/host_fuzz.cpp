@@ -23,6 +23,9 @@
 //                             online picking rule) on N random calls held in exactly sized heap arrays: the checks against the rules written
 //                             out below, the rule over random tracks cut into random chunks against the rule written out plainly, nothing
 //                             written past max_events
+//   host_fuzz streampass FILE   the streaming pass plan (stream_host.h: stream_pass_plan, stream_pass_commit) of every line of FILE, each one
+//                             session's schedule from a fresh handle: "context T_out_cap have_probs | T first last | T first last | ...";
+//                             per pass the code, every StreamPass field and the flags after it; a refusal must have written nothing
 #define __host__
 #define __device__
 #include <cmath>
@@ -41,6 +44,7 @@
 #include "edit_host.h"
 #include "lm_score_host.h"
 #include "spot_pick.h"
+#include "stream_host.h"
 
 using namespace dsmi;
 
@@ -1032,6 +1036,53 @@ static int run_spotwatch(int argc, char** argv) {
     return 0;
 }
 
+// ---- streampass: one session's schedule per line, from a fresh handle, through stream_pass_plan / stream_pass_commit -----------
+// Per pass "code padl padr ctxl tin0 tin1 to0 to1 buffering ncat nout keep : has_left has_hidden la_init la_rows pbase0 pbase1" (the flags
+// and two layers' parities after the pass), a refused pass "code why=SENTENCE : ..." with nothing committed; passes joined by " | ".
+static int run_streampass(int argc, char** argv) {
+    std::FILE* f = argc > 2 ? std::fopen(argv[2], "r") : nullptr;
+    if (!f) return 2;
+    int rc = 0;
+    char line[4096];
+    while (!rc && std::fgets(line, sizeof line, f)) {
+        int context, cap, have_probs, used = 0;
+        if (std::sscanf(line, "%d %d %d%n", &context, &cap, &have_probs, &used) != 3 || context < 1) { rc = 2; break; }
+        StreamFlags flags;
+        int pbase[2] = {0, 0};
+        std::string out;
+        const char* at = line + used;
+        int T, first, last;
+        while (std::sscanf(at, " | %d %d %d%n", &T, &first, &last, &used) == 3) {
+            at += used;
+            if (T < 1) { rc = 2; break; }      // both entry points refuse it before they plan
+            StreamPass p, untouched;
+            std::memset(&p, 0x5a, sizeof p);
+            std::memset(&untouched, 0x5a, sizeof untouched);
+            const StreamFlags before = flags;
+            const char* why = nullptr;
+            const int code = stream_pass_plan(flags, T, first != 0, last != 0, context, have_probs != 0, cap, &p, &why);
+            char buf[400];
+            if (code) {
+                if (!why || std::memcmp(&p, &untouched, sizeof p) || flags.has_left != before.has_left || flags.has_hidden != before.has_hidden ||
+                    flags.la_init != before.la_init || flags.la_rows != before.la_rows) { std::fprintf(stderr, "streampass: a refusal wrote something\n"); rc = 12; break; }
+                std::snprintf(buf, sizeof buf, "%d why=%s", code, why);
+            } else {
+                if (why) { std::fprintf(stderr, "streampass: a reason without a refusal\n"); rc = 12; break; }
+                std::snprintf(buf, sizeof buf, "0 %d %d %d %d %d %d %d %d %d %d %d", p.padl, p.padr, p.ctxl, p.tin[0], p.tin[1], p.to[0], p.to[1],
+                              (int)p.buffering, p.ncat, p.nout, p.keep);
+                stream_pass_commit(flags, pbase, 2, p, last != 0);
+            }
+            out += out.empty() ? "" : " | ";
+            out += buf;
+            std::snprintf(buf, sizeof buf, " : %d %d %d %d %d %d", (int)flags.has_left, (int)flags.has_hidden, (int)flags.la_init, flags.la_rows, pbase[0], pbase[1]);
+            out += buf;
+        }
+        std::printf("%s\n", out.c_str());
+    }
+    std::fclose(f);
+    return rc;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
@@ -1042,6 +1093,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]]\n");
+    if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
