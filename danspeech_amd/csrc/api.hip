@@ -202,7 +202,10 @@ static void run_rnn_layer(dsmi_model* m, int l, GemmLaunch gl, int B, int To, in
     m->last_xp_rows = gl.M; m->last_xp_cols = gl.ldc;
     hold.leave();
     if (run_rnn_plan(m, plan, l, B, To, dst, sumlen, s)) return;
-    // Launchers refuse what the predicates let through only by mistake; the layer still runs.
+    // The predicates and the launchers read one table of instantiations (rnn_plan.h: rnn_*_form), so what a launcher can still
+    // refuse is what the plan does not see: a ring launch whose T puts a direction's output rows past 2 GiB (rnn_ring_rows_fit),
+    // a stamp build asked for a shape without a stamp instantiation, the carried-state preconditions of launch_rnn_persist
+    // (tools/asan/host_fuzz.cpp rnn_plan_check holds every planned launch of its grid to the table).  The layer still runs.
     if (plan.x16) {
         // first: the x-projection is in the 16-unit column order, so redo it in the other, and plan without the 16-unit kernels
         // (the first-generation kernel if eligible)

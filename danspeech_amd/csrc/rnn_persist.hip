@@ -37,9 +37,8 @@
 // Requires all workgroups co-resident: the launcher checks grid <= number of CUs (the kernel
 // requests > 80 KiB of LDS so that at most one workgroup fits a CU) and otherwise falls back
 // to the per-step path.
-#include "common.h"
+#include "rnn_launch.h"
 #include "rnn_cell.h"
-#include <cstring>
 
 namespace dsmi {
 
@@ -302,53 +301,21 @@ __global__ __launch_bounds__(PNT) void rnn_persist_kernel(PersistArgs p) {
 
 template <int KIND>
 bool launch_kind(const PersistArgs& a, int ny, hipStream_t s, const EvPair& ev, bool carry) {
-    const int npw = ceil_div(a.npair, PNW);
+    const RnnForm f = rnn_persist_form(a.npair, a.nz, carry, a.dbg != nullptr);
     const dim3 grid(a.nwg, ny, 1), block(PNT);
-#define LAUNCH_P(N, MU, ST)                                                                                          \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_kernel<KIND, N, MU, ST>),                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)PERSIST_LDS);                      \
-        DSMI_LAUNCH((rnn_persist_kernel<KIND, N, MU, ST>), grid, block, PERSIST_LDS, s, ev, a);                       \
-    } while (0)
-    if (a.dbg) { if (npw > 7 || a.nz > 1) return false; LAUNCH_P(7, false, true); return true; }
-    if (carry) {
-#define LAUNCH_C(N, MU)                                                                                              \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_kernel<KIND, N, MU, false, true>),        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)PERSIST_LDS);                      \
-        DSMI_LAUNCH((rnn_persist_kernel<KIND, N, MU, false, true>), grid, block, PERSIST_LDS, s, ev, a);              \
-    } while (0)
-        const bool mu = a.nz > 1;
-        if (npw <= 2) { if (mu) LAUNCH_C(2, true); else LAUNCH_C(2, false); }
-        else if (npw <= 4) { if (mu) LAUNCH_C(4, true); else LAUNCH_C(4, false); }
-        else if (npw <= 7) { if (mu) LAUNCH_C(7, true); else LAUNCH_C(7, false); }
-        else if (npw <= 10) { if (mu) LAUNCH_C(10, true); else LAUNCH_C(10, false); }
-        else return false;
-#undef LAUNCH_C
-        return true;
-    }
-    if (a.nz > 1) {
-        if (npw <= 4) LAUNCH_P(4, true, false);
-        else if (npw <= 7) LAUNCH_P(7, true, false);
-        else if (npw <= 10) LAUNCH_P(10, true, false);
-        else return false;
-        return true;
-    }
-    if (npw <= 2) LAUNCH_P(2, false, false);
-    else if (npw <= 4) LAUNCH_P(4, false, false);
-    else if (npw <= 7) LAUNCH_P(7, false, false);
-    else if (npw <= 10) LAUNCH_P(10, false, false);
-    else return false;
-    return true;
+#define CASE(N, ...) case N: launch_lds(rnn_persist_kernel<KIND, N, __VA_ARGS__>, grid, block, PERSIST_LDS, s, ev, a); return true;
+#define CASES(...) CASE(4, __VA_ARGS__) CASE(7, __VA_ARGS__) CASE(10, __VA_ARGS__)
+    if (a.dbg) switch (f.n) { CASE(7, false, true) }
+    else if (carry && f.alt) switch (f.n) { CASE(2, true, false, true) CASES(true, false, true) }
+    else if (carry) switch (f.n) { CASE(2, false, false, true) CASES(false, false, true) }
+    else if (f.alt) switch (f.n) { CASES(true, false) }
+    else switch (f.n) { CASE(2, false, false) CASES(false, false) }
+#undef CASES
+#undef CASE
+    return false;
 }
 
 }  // namespace
-
-static inline uint16_t f16_bits(_Float16 h) {
-    uint16_t u;
-    std::memcpy(&u, &h, 2);
-    return u;
-}
 
 // w_hh [G*H][H] (torch layout) of one direction -> [wg][pair][plane][lane][8] fp16 terms (hi, lo * 2^11); lane
 // (i = gate row, hk) element e holds k = 16*pair + 8*hk + e, the same k the producer of units 8*(2*pair+hk).. publishes.
@@ -366,11 +333,9 @@ std::vector<uint16_t> pack_whh_split(const RnnGeom& g, const float* w_hh) {
                 for (int e = 0; e < 8; ++e) {
                     const int k = 16 * pq + 8 * hk + e;
                     if (k >= g.H) continue;
-                    const float x = w_hh[(size_t)(gate * g.H + unit) * g.H + k];
-                    const _Float16 h1 = (_Float16)x;
-                    const _Float16 h2 = (_Float16)((x - (float)h1) * kLoScale);
+                    const F16Pair x = f16_split_bits(w_hh[(size_t)(gate * g.H + unit) * g.H + k], kLoScale);
                     const size_t base = (((size_t)w * npair + pq) * 2) * 64 * 8 + (size_t)lane * 8 + e;
-                    out[base] = f16_bits(h1); out[base + 512] = f16_bits(h2);
+                    out[base] = x.hi; out[base + 512] = x.lo;
                 }
             }
     return out;
@@ -388,11 +353,7 @@ bool launch_rnn_persist(const RnnPersistLaunch& p, hipStream_t s) {
         if (p.g.D != 1 || p.ny != 1 || p.d0 != 0 || p.dbg) return false;
         a.bhh[1] = p.h0; a.out[1] = p.cst;
     }
-    switch (p.g.kind) {
-        case DSMI_RNN_GRU: return launch_kind<DSMI_RNN_GRU>(a, p.ny, s, p.ev, carry);
-        case DSMI_RNN_LSTM: return launch_kind<DSMI_RNN_LSTM>(a, p.ny, s, p.ev, carry);
-        default: return launch_kind<DSMI_RNN_TANH>(a, p.ny, s, p.ev, carry);
-    }
+    return by_kind(p.g.kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, p.ny, s, p.ev, carry); });
 }
 
 }  // namespace dsmi

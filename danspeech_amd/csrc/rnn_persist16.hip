@@ -18,7 +18,7 @@
 //   W_hh split, per direction:  [workgroup][kb][gate][plane 2][lane 64][8 fp16], lane = (unit u = lane & 15, kg = lane >> 4)
 //   state, per parity and chain: [kb][plane 2][kg 4][clip j 16][8 fp16]   (one 1-KiB MFMA B operand per (kb, plane))
 //   x-projection: geometry U = 16 (make_rnn_geom_u), one workgroup's G x 16 gate columns contiguous.
-#include "common.h"
+#include "rnn_launch.h"
 #include "rnn_cell.h"
 #include <cstring>
 #include <cstdlib>
@@ -581,71 +581,36 @@ __global__ __launch_bounds__(QNT) void rnn_persist16_pipe_kernel(P16Args p) {
     }
 }
 
-inline uint16_t q_f16_bits(_Float16 h) {
-    uint16_t u;
-    std::memcpy(&u, &h, 2);
-    return u;
-}
-
 template <int KIND>
 bool launch16(const P16Args& a, hipStream_t s, const EvPair& ev, int waves) {
-    const dim3 grid(a.nwg, a.D * a.pgroups, 1);
-#define LAUNCH_Q(N, W, LDS)                                                                                          \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist16_kernel<KIND, N, W>),                    \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS));                            \
-        DSMI_LAUNCH((rnn_persist16_kernel<KIND, N, W>), grid, dim3(W * 64), LDS, s, ev, a);                           \
-    } while (0)
-    if (waves == 4) {              // half-CU workgroups (see the kernel): one or two tiles per workgroup, no diagnostics build
-        const int nkw = ceil_div(a.nkb, 4);
-        if (a.dbg || ceil_div(a.ntiles, a.pgroups) > 2) return false;
-        if (nkw <= 2) LAUNCH_Q(2, 4, Q_LDS_HALF);
-        else if (nkw <= 4) LAUNCH_Q(4, 4, Q_LDS_HALF);
-        else if (nkw <= 6 && KIND != DSMI_RNN_LSTM) LAUNCH_Q(6, 4, Q_LDS_HALF);
-        else if (nkw <= 7 && KIND != DSMI_RNN_LSTM) LAUNCH_Q(7, 4, Q_LDS_HALF);
-        else return false;
-        return true;
+    const dim3 grid(a.nwg, a.D * a.pgroups, 1), block(waves == 4 ? 4 * 64 : QNT);
+    const int tiles = ceil_div(a.ntiles, a.pgroups);      // per workgroup
+#define CASE(N, W, LDS) case N: launch_lds(rnn_persist16_kernel<KIND, N, W>, grid, block, LDS, s, ev, a); return true;
+#define CASE_STAMPS(N) case N: launch_lds(rnn_persist16_kernel<KIND, N, QNW, true>, grid, block, Q_LDS, s, EvPair{}, a); return true;
+#define CASE_PIPE(N) case N: launch_lds(rnn_persist16_pipe_kernel<KIND, N>, grid, block, lds_pipe(N), s, ev, a); return true;
+    if (waves == 4) {              // half-CU workgroups (see the kernel)
+        switch (rnn_persist16_half_form(KIND, a.nkb, tiles, a.dbg != nullptr)) { CASE(2, 4, Q_LDS_HALF) CASE(4, 4, Q_LDS_HALF) CASE(6, 4, Q_LDS_HALF) CASE(7, 4, Q_LDS_HALF) }
+        return false;
     }
-    const int nkw = ceil_div(a.nkb, QNW);
-    const dim3 block(QNT);
-    if (a.dbg) {
-        if (nkw > 4) return false;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist16_kernel<KIND, 4, QNW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Q_LDS);
-        hipLaunchKernelGGL((rnn_persist16_kernel<KIND, 4, QNW, true>), grid, block, Q_LDS, s, a);
-        return true;
-    }
-    if (ceil_div(a.ntiles, a.pgroups) > 2) {      // three or more tiles per workgroup: the software-pipelined kernel (with two
-                                                   // tiles the next instance's producers were signalled a moment ago: nothing to overlap)
+    const RnnForm f = rnn_persist16_form(KIND, a.nkb, tiles, a.dbg != nullptr);
+    if (a.dbg) switch (f.n) { CASE_STAMPS(4) }
+    else if (f.alt) {              // the software-pipelined kernel
         constexpr int NGK = KIND == DSMI_RNN_GRU ? 3 : (KIND == DSMI_RNN_LSTM ? 4 : 1);
         auto lds_pipe = [](int nkw) {            // two reduce buffers, the dead flag, carried state of up to QMAXZ tiles, W_hh fragments
             return (size_t)2 * QNW * NGK * 16 * QRP * 4 + 128 + (size_t)3 * QMAXZ * 256 * 4 + (size_t)QNW * pipe_lds_frags(NGK, nkw) * 1024;
         };
-#define LAUNCH_QP(N)                                                                                                 \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist16_pipe_kernel<KIND, N>),                  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe(N));                      \
-        DSMI_LAUNCH((rnn_persist16_pipe_kernel<KIND, N>), grid, block, lds_pipe(N), s, ev, a);                        \
-    } while (0)
 #ifdef DSMI_EXPERIMENTS
-        if (a.skip && KIND == DSMI_RNN_GRU && nkw == 5) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist16_pipe_kernel<DSMI_RNN_GRU, 5, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe(5));
-            DSMI_LAUNCH((rnn_persist16_pipe_kernel<DSMI_RNN_GRU, 5, true>), grid, block, lds_pipe(5), s, ev, a);
-        } else
+        if (a.skip && KIND == DSMI_RNN_GRU && f.n == 5) {
+            launch_lds(rnn_persist16_pipe_kernel<DSMI_RNN_GRU, 5, true>, grid, block, lds_pipe(5), s, ev, a);
+            return true;
+        }
 #endif
-        if (nkw <= 2) LAUNCH_QP(2);
-        else if (nkw <= 4) LAUNCH_QP(4);
-        else if (nkw <= 5 && KIND != DSMI_RNN_LSTM) LAUNCH_QP(5);
-        else return false;
-#undef LAUNCH_QP
-        return true;
-    }
-    if (nkw <= 2) LAUNCH_Q(2, QNW, Q_LDS);
-    else if (nkw <= 4) LAUNCH_Q(4, QNW, Q_LDS);
-    else if (nkw <= 5 && KIND != DSMI_RNN_LSTM) LAUNCH_Q(5, QNW, Q_LDS);
-    else return false;
-#undef LAUNCH_Q
-    return true;
+        switch (f.n) { CASE_PIPE(2) CASE_PIPE(4) CASE_PIPE(5) }
+    } else switch (f.n) { CASE(2, QNW, Q_LDS) CASE(4, QNW, Q_LDS) CASE(5, QNW, Q_LDS) }
+#undef CASE_PIPE
+#undef CASE_STAMPS
+#undef CASE
+    return false;
 }
 
 }  // namespace
@@ -664,11 +629,9 @@ std::vector<uint16_t> pack_whh16(const RnnGeom& g16, const float* w_hh) {
                     for (int e = 0; e < 8; ++e) {
                         const int k = 32 * kb + 8 * (lane >> 4) + e;
                         if (k >= H) continue;
-                        const float x = w_hh[(size_t)(gate * H + unit) * H + k];
-                        const _Float16 h1 = (_Float16)x;
-                        const _Float16 h2 = (_Float16)((x - (float)h1) * kLoScale);
+                        const F16Pair x = f16_split_bits(w_hh[(size_t)(gate * H + unit) * H + k], kLoScale);
                         const size_t base = ((((size_t)w * nkb + kb) * G + gate) * 2) * 512 + (size_t)lane * 8 + e;
-                        out[base] = q_f16_bits(h1); out[base + 512] = q_f16_bits(h2);
+                        out[base] = x.hi; out[base + 512] = x.lo;
                     }
                 }
     return out;
@@ -680,18 +643,11 @@ size_t rnn_persist16_state_halfs(const RnnGeom& g16, int B) {
 
 bool launch_rnn_persist16(const RnnPersist16Launch& p, hipStream_t s) {
     P16Args a;
-    for (int d = 0; d < 2; ++d) { a.whh[d] = p.whh16[d]; a.bhh[d] = p.bhh[d]; a.out[d] = p.out[d]; }
-    a.xp = p.xp; a.lens = p.lens_dev; a.hpack = p.hpack16; a.cnt = p.counters; a.err = p.err;
-    a.B = p.B; a.T = p.T; a.H = p.g.H; a.Hs = p.g.Kp; a.Np = p.g.Np; a.nwg = p.g.nwg; a.nkb = ceil_div(p.g.H, 32);
-    a.ntiles = ceil_div(p.B, QB); a.pgroups = p.pgroups; a.D = p.g.D; a.dbg = p.dbg;
-    a.spin_limit = p.spin_limit; a.drop_wg = p.drop_wg; a.drop_step = p.drop_step;
+    fill_shared(a, p);
+    a.nwg = p.g.nwg; a.pgroups = p.pgroups;
     static const int skip_env = [] { const char* e = exp_env("DSMI_DEBUG_PIPE_SKIP"); return e ? std::atoi(e) : 0; }();
     a.skip = skip_env;
-    switch (p.g.kind) {
-        case DSMI_RNN_GRU: return launch16<DSMI_RNN_GRU>(a, s, p.ev, p.waves);
-        case DSMI_RNN_LSTM: return launch16<DSMI_RNN_LSTM>(a, s, p.ev, p.waves);
-        default: return launch16<DSMI_RNN_TANH>(a, s, p.ev, p.waves);
-    }
+    return by_kind(p.g.kind, [&](auto k) { return launch16<decltype(k)::value>(a, s, p.ev, p.waves); });
 }
 
 }  // namespace dsmi

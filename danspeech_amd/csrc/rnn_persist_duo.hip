@@ -23,7 +23,7 @@
 // Every busy slot of one half runs beside a waiting slot of the other, on every CU in the same order, so both chains
 // advance in lockstep anti-phase chip-wide.  A signal leaves ~0.45 us into a drain slot and its poll starts ~0.5 us later,
 // when most of the hand-off latency has passed.
-#include "common.h"
+#include "rnn_launch.h"
 #include "rnn_cell.h"
 #include <algorithm>
 #include <cstdlib>
@@ -305,63 +305,27 @@ __global__ __launch_bounds__(DNT, 2) void rnn_persist_duo_kernel(DuoArgs p) {
 
 template <int KIND>
 bool launch_duo(const DuoArgs& a, hipStream_t s, const EvPair& ev) {
-    const int nkw = ceil_div(a.nkb, 4);
-    constexpr int NGk = KIND == DSMI_RNN_GRU ? 3 : (KIND == DSMI_RNN_LSTM ? 4 : 1);
-    const int kq = a.nkb / 4, kr = a.nkb % 4;
-    const bool tail = kr > 0 && NGk * kr <= 4 && kq >= 1 && kq <= (KIND == DSMI_RNN_LSTM ? 4 : 6);
+    const RnnForm f = rnn_persist_duo_form(KIND, a.nkb, a.dbg != nullptr);
     const dim3 grid(a.nwg, a.D * a.npairs, 1), block(DNT);
+#define CASE(N, EV, ...) case N: launch_lds(rnn_persist_duo_kernel<KIND, N, __VA_ARGS__>, grid, block, D_LDS, s, EV, a); return true;
     if (a.dbg) {
-        if (KIND != DSMI_RNN_GRU || nkw != 7) return false;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_duo_kernel<DSMI_RNN_GRU, 7, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)D_LDS);
-        hipLaunchKernelGGL((rnn_persist_duo_kernel<DSMI_RNN_GRU, 7, true>), grid, block, D_LDS, s, a);
-        return true;
-    }
-#define LAUNCH_K(KERNEL, ...)                                                                                        \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL<KIND, __VA_ARGS__>),                           \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)D_LDS);                            \
-        DSMI_LAUNCH((KERNEL<KIND, __VA_ARGS__>), grid, block, D_LDS, s, ev, a);                                       \
-    } while (0)
-#define LAUNCH_T(N) LAUNCH_K(rnn_persist_duo_kernel, N, false, true)
-#define LAUNCH_D(N) LAUNCH_K(rnn_persist_duo_kernel, N, false, false)
-    if (tail) {
-        if (kq <= 2) LAUNCH_T(2);
-        else if (kq <= 4) LAUNCH_T(4);
-        else if constexpr (KIND != DSMI_RNN_LSTM) LAUNCH_T(6);
-        return true;
-    }
-    if (KIND == DSMI_RNN_LSTM) {
-        if (nkw <= 2) LAUNCH_D(2);
-        else if (nkw <= 4) LAUNCH_D(4);
-        else return false;
-        return true;
-    }
-    if (nkw <= 2) LAUNCH_D(2);
-    else if (nkw <= 4) LAUNCH_D(4);
-    else if (nkw <= 6) LAUNCH_D(6);
-    else if (nkw <= 7) LAUNCH_D(7);
-    else return false;
-#undef LAUNCH_T
-#undef LAUNCH_D
-#undef LAUNCH_K
-    return true;
+        if constexpr (KIND == DSMI_RNN_GRU) switch (f.n) { CASE(7, EvPair{}, true) }
+    } else if (f.alt) {
+        switch (f.n) { CASE(2, ev, false, true) CASE(4, ev, false, true) }
+        if constexpr (KIND != DSMI_RNN_LSTM) switch (f.n) { CASE(6, ev, false, true) }
+    } else switch (f.n) { CASE(2, ev, false, false) CASE(4, ev, false, false) CASE(6, ev, false, false) CASE(7, ev, false, false) }
+#undef CASE
+    return false;
 }
 
 }  // namespace
 
 bool launch_rnn_persist_duo(const RnnPersist16Launch& p, hipStream_t s) {
     DuoArgs a;
-    for (int d = 0; d < 2; ++d) { a.whh[d] = p.whh16[d]; a.bhh[d] = p.bhh[d]; a.out[d] = p.out[d]; }
-    a.xp = p.xp; a.lens = p.lens_dev; a.hpack = p.hpack16; a.cnt = p.counters; a.err = p.err;
-    a.B = p.B; a.T = p.T; a.H = p.g.H; a.Hs = p.g.Kp; a.Np = p.g.Np; a.nwg = p.g.nwg; a.nkb = ceil_div(p.g.H, 32);
-    a.ntiles = ceil_div(p.B, DB); a.D = p.g.D;
+    fill_shared(a, p);
+    a.nwg = p.g.nwg;
     a.pair0 = p.pair0; a.npairs = p.npairs > 0 ? p.npairs : (a.ntiles + 1) / 2;
-    a.spin_limit = p.spin_limit; a.drop_wg = p.drop_wg; a.drop_step = p.drop_step; a.dbg = p.dbg;
-    switch (p.g.kind) {
-        case DSMI_RNN_GRU: return launch_duo<DSMI_RNN_GRU>(a, s, p.ev);
-        case DSMI_RNN_LSTM: return launch_duo<DSMI_RNN_LSTM>(a, s, p.ev);
-        default: return launch_duo<DSMI_RNN_TANH>(a, s, p.ev);
-    }
+    return by_kind(p.g.kind, [&](auto k) { return launch_duo<decltype(k)::value>(a, s, p.ev); });
 }
 
 }  // namespace dsmi

@@ -31,7 +31,7 @@
 //     stores 16 bytes of each plane with sc1 -- one whole 128-byte line per plane and wave instruction (2-byte sc1 stores are one
 //     fabric write each).  Stores carry no branch: a lane with nothing to store has an offset beyond the buffer's range.
 //   Measured forms and what bounds the kernel: DESIGN.md 4 "The ring kernel", profiles/r04_ring_experiments.txt.
-#include "common.h"
+#include "rnn_launch.h"
 #include "rnn_cell.h"
 #include <algorithm>
 #include <cstdlib>
@@ -503,70 +503,39 @@ unsigned hchs = hchs_, cnts = cnts_, orows = orows_, xrows = xrows_;
 // (dynamic LDS of a workgroup: ring_lds_bytes, rnn_plan.h -- the same formula rnn_persist_ring_tiles holds against the CU's LDS)
 template <int KIND>
 bool launch_ring(const RingArgs& a, hipStream_t s, const EvPair& ev) {
-    const int nkw = ceil_div(a.nkb, 4);
+    const int nkw = rnn_persist_ring_form(KIND, a.nkb, a.ntw, a.dbg != nullptr);
     const size_t lds = ring_lds_bytes(KIND, a.nkb);
     const dim3 grid((a.nwg16 + 1) / 2, a.D, ceil_div(a.tile_end - a.tile0, a.ntw)), block(RNT);
-#define LAUNCH_R(N, ST)                                                                                              \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_ring_kernel<KIND, N, ST>),                \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-        DSMI_LAUNCH((rnn_persist_ring_kernel<KIND, N, ST>), grid, block, lds, s, ev, a);                              \
-    } while (0)
+#define CASE(N, ...) case N: launch_lds(rnn_persist_ring_kernel<KIND, N, __VA_ARGS__>, grid, block, lds, s, ev, a); return true;
     if (a.dbg) {
-        if constexpr (KIND == DSMI_RNN_GRU) { if (nkw == 7) { LAUNCH_R(7, true); return true; } }
+        if constexpr (KIND == DSMI_RNN_GRU) switch (nkw) { CASE(7, true) }
         return false;
     }
 #ifdef DSMI_EXPERIMENTS
     if (a.skip) {           // timing experiments (DSMI_DEBUG_RING_SKIP): cfgA's shape only
-        if constexpr (KIND == DSMI_RNN_GRU) {
-            if (nkw == 7) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_ring_kernel<KIND, 7, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                DSMI_LAUNCH((rnn_persist_ring_kernel<KIND, 7, false, true>), grid, block, lds, s, ev, a);
-                return true;
-            }
-        }
+        if constexpr (KIND == DSMI_RNN_GRU) switch (nkw) { CASE(7, false, true) }
         return false;
     }
 #endif
     // NKW exact: every wave owns NKW or NKW - 1 k-blocks, so only the last block of the unrolled loops is conditional
-    switch (nkw) {
-        case 1: LAUNCH_R(1, false); break;
-        case 2: LAUNCH_R(2, false); break;
-        case 3: LAUNCH_R(3, false); break;
-        case 4: LAUNCH_R(4, false); break;
-        default:
-            if constexpr (KIND == DSMI_RNN_LSTM) return false;
-            else {
-                if (nkw == 5) LAUNCH_R(5, false);
-                else if (nkw == 6) LAUNCH_R(6, false);
-                else if (nkw == 7) LAUNCH_R(7, false);
-                else return false;
-            }
-    }
-#undef LAUNCH_R
-    return true;
+    switch (nkw) { CASE(1, false) CASE(2, false) CASE(3, false) CASE(4, false) }
+    if constexpr (KIND != DSMI_RNN_LSTM) switch (nkw) { CASE(5, false) CASE(6, false) CASE(7, false) }
+#undef CASE
+    return false;
 }
 
 }  // namespace
 
 bool launch_rnn_persist_ring(const RnnPersist16Launch& p, hipStream_t s) {
     RingArgs a;
-    for (int d = 0; d < 2; ++d) { a.whh[d] = p.whh16[d]; a.bhh[d] = p.bhh[d]; a.out[d] = p.out[d]; }
-    a.xp = p.xp; a.lens = p.lens_dev; a.hpack = p.hpack16; a.cnt = p.counters; a.err = p.err;
-    a.B = p.B; a.T = p.T; a.H = p.g.H; a.Hs = p.g.Kp; a.Np = p.g.Np; a.nwg16 = p.g.nwg; a.nkb = ceil_div(p.g.H, 32);
-    a.ntiles = ceil_div(p.B, RB); a.D = p.g.D;
+    fill_shared(a, p);
+    a.nwg16 = p.g.nwg; a.tickets = p.tickets;
     a.tile0 = p.tile0; a.ntw = p.ntw > 0 ? p.ntw : a.ntiles - p.tile0;
     a.tile_end = std::min(a.ntiles, a.tile0 + a.ntw * std::max(p.nwin, 1));
-    if (a.ntw < 1 || a.ntw > RMINT || a.tile_end <= a.tile0) return false;
-    if ((size_t)p.T * p.B * p.g.Kp * 4 >= (1ull << 31)) return false;          // a direction's output rows below 2 GiB (store offsets, see OOR)
-    a.spin_limit = p.spin_limit; a.drop_wg = p.drop_wg; a.drop_step = p.drop_step; a.dbg = p.dbg; a.tickets = p.tickets;
+    if (a.ntw < 1 || a.ntw > RMINT || a.tile_end <= a.tile0 || !rnn_ring_rows_fit(p.g, p.B, p.T)) return false;
     static const int skip = exp_env("DSMI_DEBUG_RING_SKIP") ? std::atoi(exp_env("DSMI_DEBUG_RING_SKIP")) : 0;
     a.skip = skip;
-    switch (p.g.kind) {
-        case DSMI_RNN_GRU: return launch_ring<DSMI_RNN_GRU>(a, s, p.ev);
-        case DSMI_RNN_LSTM: return launch_ring<DSMI_RNN_LSTM>(a, s, p.ev);
-        default: return launch_ring<DSMI_RNN_TANH>(a, s, p.ev);
-    }
+    return by_kind(p.g.kind, [&](auto k) { return launch_ring<decltype(k)::value>(a, s, p.ev); });
 }
 
 }  // namespace dsmi

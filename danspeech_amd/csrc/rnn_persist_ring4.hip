@@ -42,7 +42,7 @@
 //     branch: a lane with nothing to store has an offset beyond the buffer's range.
 //   * The body of a phase is ONE basic block (no branch between the first MFMA and the last): requests that do not apply are
 //     clamped onto valid, harmless ones instead of being skipped, step 0 (h = 0: no MFMAs, no state) is a prologue of its own.
-#include "common.h"
+#include "rnn_launch.h"
 #include "rnn_cell.h"
 #include <algorithm>
 #include <cstdlib>
@@ -551,17 +551,12 @@ __global__ __launch_bounds__(XNT) void rnn_persist_ring4_kernel(Ring4Args p) {
 // (dynamic LDS of a workgroup: ring4_lds_bytes, rnn_plan.h -- the same formula rnn_persist_ring4_tiles holds against the CU's LDS)
 template <int KIND, int NT>
 bool launch_ring4_nt(const Ring4Args& a, hipStream_t s, const EvPair& ev) {
-    const int nkw = ceil_div(a.nkb, 2);
+    const int nkw = rnn_persist_ring4_form(KIND, a.nkb, a.ntw, a.dbg != nullptr);
     const size_t lds = ring4_lds_bytes(KIND, a.nkb);
     const dim3 grid((a.nwg16 + 1) / 2, a.D, ceil_div(a.tile_end - a.tile0, a.ntw)), block(XNT);
-#define LAUNCH_X(NK, ST)                                                                                              \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_ring4_kernel<KIND, NK, NT, ST>),         \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-        DSMI_LAUNCH((rnn_persist_ring4_kernel<KIND, NK, NT, ST>), grid, block, lds, s, ev, a);                        \
-    } while (0)
+#define CASE(N, ...) case N: launch_lds(rnn_persist_ring4_kernel<KIND, N, NT, __VA_ARGS__>, grid, block, lds, s, ev, a); return true;
     if (a.dbg) {
-        if constexpr (KIND == DSMI_RNN_GRU) { if (nkw == 13) { LAUNCH_X(13, true); return true; } }
+        if constexpr (KIND == DSMI_RNN_GRU) switch (nkw) { CASE(13, true) }
         return false;
     }
 #ifdef DSMI_EXPERIMENTS
@@ -569,76 +564,40 @@ bool launch_ring4_nt(const Ring4Args& a, hipStream_t s, const EvPair& ev) {
     if (skip) {           // timing experiments: cfgA's shape only, a fixed list of masks
         if constexpr (KIND == DSMI_RNN_GRU && NT == 4) {
             if (nkw != 13) return false;
-#define LAUNCH_SK(M)                                                                                                             \
-    case M:                                                                                                                      \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_persist_ring4_kernel<KIND, 13, NT, false, M>),               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                         \
-        DSMI_LAUNCH((rnn_persist_ring4_kernel<KIND, 13, NT, false, M>), grid, block, lds, s, ev, a);                             \
-        return true;
+#define SKIP_CASE(M) case M: launch_lds(rnn_persist_ring4_kernel<KIND, 13, NT, false, M>, grid, block, lds, s, ev, a); return true;
             switch (skip) {
-                LAUNCH_SK(1) LAUNCH_SK(2) LAUNCH_SK(4) LAUNCH_SK(8) LAUNCH_SK(16) LAUNCH_SK(32) LAUNCH_SK(9) LAUNCH_SK(13) LAUNCH_SK(29) LAUNCH_SK(31) LAUNCH_SK(61) LAUNCH_SK(63)
-                LAUNCH_SK(0x600) LAUNCH_SK(0x700) LAUNCH_SK(0x900) LAUNCH_SK(0xA00) LAUNCH_SK(0xB00)          // the complete kernel with the poll's first read at k-block 6 .. 11
-                default: return false;
+                SKIP_CASE(1) SKIP_CASE(2) SKIP_CASE(4) SKIP_CASE(8) SKIP_CASE(16) SKIP_CASE(32) SKIP_CASE(9) SKIP_CASE(13) SKIP_CASE(29) SKIP_CASE(31) SKIP_CASE(61) SKIP_CASE(63)
+                SKIP_CASE(0x600) SKIP_CASE(0x700) SKIP_CASE(0x900) SKIP_CASE(0xA00) SKIP_CASE(0xB00)          // the complete kernel with the poll's first read at k-block 6 .. 11
             }
-#undef LAUNCH_SK
+#undef SKIP_CASE
         }
         return false;
     }
 #endif
-    switch (nkw) {
-        case 1: LAUNCH_X(1, false); break;
-        case 2: LAUNCH_X(2, false); break;
-        case 3: LAUNCH_X(3, false); break;
-        case 4: LAUNCH_X(4, false); break;
-        case 5: LAUNCH_X(5, false); break;
-        case 6: LAUNCH_X(6, false); break;
-        case 7: LAUNCH_X(7, false); break;
-        case 8: LAUNCH_X(8, false); break;
-        default:
-            if constexpr (KIND == DSMI_RNN_LSTM) return false;
-            else {
-                if (nkw == 9) LAUNCH_X(9, false);
-                else if (nkw == 10) LAUNCH_X(10, false);
-                else if (nkw == 11) LAUNCH_X(11, false);
-                else if (nkw == 12) LAUNCH_X(12, false);
-                else if (nkw == 13) LAUNCH_X(13, false);
-                else if (nkw == 14) { if constexpr (NT > 4) return false; else LAUNCH_X(14, false); }     // (eight tiles' state per thread: no registers left at 14 k-blocks)
-                else return false;
-            }
-    }
-#undef LAUNCH_X
-    return true;
+    switch (nkw) { CASE(1, false) CASE(2, false) CASE(3, false) CASE(4, false) CASE(5, false) CASE(6, false) CASE(7, false) CASE(8, false) }
+    if constexpr (KIND != DSMI_RNN_LSTM) switch (nkw) { CASE(9, false) CASE(10, false) CASE(11, false) CASE(12, false) CASE(13, false) }
+    if constexpr (KIND != DSMI_RNN_LSTM && NT <= 4) switch (nkw) { CASE(14, false) }      // (the eight-tile schedule: see rnn_persist_ring4_form)
+#undef CASE
+    return false;
 }
 
 }  // namespace
 
 bool launch_rnn_persist_ring4(const RnnPersist16Launch& p, hipStream_t s) {
     Ring4Args a;
-    for (int d = 0; d < 2; ++d) { a.whh[d] = p.whh16[d]; a.bhh[d] = p.bhh[d]; a.out[d] = p.out[d]; }
-    a.xp = p.xp; a.lens = p.lens_dev; a.hpack = p.hpack16; a.cnt = p.counters; a.err = p.err;
-    a.B = p.B; a.T = p.T; a.H = p.g.H; a.Hs = p.g.Kp; a.Np = p.g.Np; a.nwg16 = p.g.nwg; a.nkb = ceil_div(p.g.H, 32);
-    a.ntiles = ceil_div(p.B, XB); a.D = p.g.D;
+    fill_shared(a, p);
+    a.nwg16 = p.g.nwg; a.tickets = p.tickets;
     a.tile0 = p.tile0; a.ntw = p.ntw > 0 ? p.ntw : a.ntiles - p.tile0;
     a.tile_end = std::min(a.ntiles, a.tile0 + a.ntw * std::max(p.nwin, 1));
-    if (a.ntw < 1 || a.ntw > XMAXT || a.tile_end <= a.tile0) return false;
-    if ((size_t)p.T * p.B * p.g.Kp * 4 >= (1ull << 31)) return false;          // a direction's output rows below 2 GiB (store offsets, see OOR)
-    a.spin_limit = p.spin_limit; a.drop_wg = p.drop_wg; a.drop_step = p.drop_step; a.dbg = p.dbg; a.tickets = p.tickets;
+    if (a.ntw < 1 || a.ntw > XMAXT || a.tile_end <= a.tile0 || !rnn_ring_rows_fit(p.g, p.B, p.T)) return false;
     if (a.ntw > 4) {          // more than four tiles per window: the eight-tile schedule (six: two phantom tiles); measured, no gain
 #ifndef DSMI_EXPERIMENTS
         return false;         // (DSMI_RING_TILES=6|8 exists in the experiments build only: rnn_persist_ring4_tiles never says more than four)
 #else
-        switch (p.g.kind) {
-            case DSMI_RNN_GRU: return launch_ring4_nt<DSMI_RNN_GRU, 8>(a, s, p.ev);
-            case DSMI_RNN_LSTM: return launch_ring4_nt<DSMI_RNN_LSTM, 8>(a, s, p.ev);
-            default: return launch_ring4_nt<DSMI_RNN_TANH, 8>(a, s, p.ev);
-        }
+        return by_kind(p.g.kind, [&](auto k) { return launch_ring4_nt<decltype(k)::value, 8>(a, s, p.ev); });
 #endif
     }
-    switch (p.g.kind) {
-        case DSMI_RNN_GRU: return launch_ring4_nt<DSMI_RNN_GRU, 4>(a, s, p.ev);
-        case DSMI_RNN_LSTM: return launch_ring4_nt<DSMI_RNN_LSTM, 4>(a, s, p.ev);
-        default: return launch_ring4_nt<DSMI_RNN_TANH, 4>(a, s, p.ev);
-    }
+    return by_kind(p.g.kind, [&](auto k) { return launch_ring4_nt<decltype(k)::value, 4>(a, s, p.ev); });
 }
 
 }  // namespace dsmi

@@ -2,11 +2,13 @@
 // function of the shape, the batch, what the caller said (dsmi_model_set_inflight / _set_ring_windows) and the DSMI_RNN_* switches.
 // Host-only and without a HIP include, like host_logic.h: api.hip plans a layer here and then launches the plan; `make asan` builds
 // the same header for the CPU (tools/asan/host_fuzz.cpp rnnplan, tests/test_rnn_plan_host.py: tests/rnn_plan_table.json row by row).
-// The kernel files take their tile sizes, wave counts and LDS formulas from here, so a predicate and its launcher cannot disagree.
+// The kernel files take their tile sizes, wave counts, LDS formulas and the table of their instantiations (rnn_*_form) from here, so
+// a predicate and its launcher cannot disagree.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/dsmi.h"
@@ -27,10 +29,11 @@ struct RnnGeom {
     int D;         // directions
     int Np;        // D * nwg * G * U : permuted + padded gate columns of the x-projection
 };
+inline int rnn_gates(int kind) { return kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1); }
 inline RnnGeom make_rnn_geom_u(int kind, int H, int D, int U) {
     RnnGeom g;
     g.kind = kind;
-    g.G = kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1);
+    g.G = rnn_gates(kind);
     g.H = H;
     g.U = U;
     g.nwg = ceil_div(H, U);
@@ -58,13 +61,74 @@ constexpr int kRingRedPitch = 20;       // row pitch (words) of its reduce buffe
 constexpr int kRingMaxTiles = 4;        // its schedule length in tiles = tiles a window walks at most
 constexpr int kRing4MaxTiles = 8;       // four-wave ring: tiles a window walks at most (more than four: experiments build)
 
+// ---- which template instantiation runs a shape: THE table, read by the predicates below and by the launchers ----------------
+// The predicates ask whether a shape has an instantiation; the launchers (rnn_launch.h: one `case` per instantiation) switch on the
+// same answer.  tools/asan/host_fuzz.cpp rnnforms prints the table; tests/rnn_form_table.json holds it as the launchers' own
+// if-ladders gave it before these functions existed.  `stamps`: the diagnostics build of a kernel (a launch with a dbg buffer).
+// The experiments build's instantiations with parts removed are not here: their launchers pick them behind DSMI_EXPERIMENTS.
+struct RnnForm {
+    int n = 0;             // the kernel's width argument (NPW / NKW); 0: no instantiation runs this shape
+    bool alt = false;      // persist8: MULTI, every workgroup walks several tiles; p16w8: the pipelined kernel; duo: TAIL
+};
+// v rounded up to a member of an ascending list (0: beyond the last)
+inline int round_up_to(int v, std::initializer_list<int> widths) {
+    for (int w : widths) if (v <= w) return w;
+    return 0;
+}
+// rnn_persist.hip: npair pairs of 16 k over eight waves, `tiles` 32-clip tiles, carried: chains start from a carried state
+inline RnnForm rnn_persist_form(int npair, int tiles, bool carried, bool stamps) {
+    const int npw = ceil_div(npair, kPersistWaves);
+    if (stamps) return {!carried && tiles == 1 && npw <= 7 ? 7 : 0, false};
+    if (tiles > 1 && !carried) return {round_up_to(npw, {4, 7, 10}), true};
+    return {round_up_to(npw, {2, 4, 7, 10}), tiles > 1};
+}
+// rnn_persist16.hip, whole-CU workgroups: nkb k-blocks of 32 over eight waves; the pipelined kernel where a workgroup walks more
+// than two tiles (with two the next instance's producers were signalled a moment ago: nothing to overlap)
+inline RnnForm rnn_persist16_form(int kind, int nkb, int tiles, bool stamps) {
+    const int nkw = ceil_div(nkb, kPersist16Waves);
+    if (stamps) return {nkw <= 4 ? 4 : 0, false};
+    const int n = round_up_to(nkw, {2, 4, 5});
+    return {n > 4 && kind == DSMI_RNN_LSTM ? 0 : n, tiles > 2};
+}
+// ... half-CU workgroups: four waves, at most two tiles per workgroup, no diagnostics build
+inline int rnn_persist16_half_form(int kind, int nkb, int tiles, bool stamps) {
+    if (stamps || tiles > 2) return 0;
+    const int n = round_up_to(ceil_div(nkb, 4), {2, 4, 6, 7});
+    return n > 4 && kind == DSMI_RNN_LSTM ? 0 : n;
+}
+// rnn_persist_duo.hip: four waves per half.  TAIL (see the kernel): every wave takes nkb / 4 whole k-blocks and the 1-3 left over
+// are dealt out gate by gate, where that is at most one (block, gate) item per wave
+inline RnnForm rnn_persist_duo_form(int kind, int nkb, bool stamps) {
+    const bool lstm = kind == DSMI_RNN_LSTM;
+    const int nkw = ceil_div(nkb, 4), kq = nkb / 4, kr = nkb % 4;
+    if (stamps) return {kind == DSMI_RNN_GRU && nkw == 7 ? 7 : 0, false};
+    if (kr > 0 && rnn_gates(kind) * kr <= 4 && kq >= 1 && kq <= (lstm ? 4 : 6)) return {round_up_to(kq, {2, 4, 6}), true};
+    const int n = round_up_to(nkw, {2, 4, 6, 7});
+    return {n > 4 && lstm ? 0 : n, false};
+}
+// rnn_persist_ring.hip: NKW exact (every wave of a half owns NKW or NKW - 1 k-blocks); a window of ntw tiles within its schedule
+inline int rnn_persist_ring_form(int kind, int nkb, int ntw, bool stamps) {
+    const int nkw = ceil_div(nkb, 4);
+    if (ntw < 1 || ntw > kRingMaxTiles || nkw > (kind == DSMI_RNN_LSTM ? 4 : 7)) return 0;
+    return !stamps || (kind == DSMI_RNN_GRU && nkw == 7) ? nkw : 0;
+}
+// rnn_persist_ring4.hip: NKW exact; more than four tiles per window run the eight-tile schedule (experiments build), which has
+// eight tiles' state per thread and no registers left at 14 k-blocks
+inline int rnn_persist_ring4_form(int kind, int nkb, int ntw, bool stamps) {
+    const int nkw = ceil_div(nkb, 2);
+    if (ntw < 1 || ntw > kRing4MaxTiles || nkw > (kind == DSMI_RNN_LSTM ? 8 : (ntw > 4 ? 13 : 14))) return 0;
+    return !stamps || (kind == DSMI_RNN_GRU && nkw == 13) ? nkw : 0;
+}
+// Both ring kernels: a direction's output rows below 2 GiB (store offsets, see OOR).  A launcher's refusal: T is not in the plan.
+inline bool rnn_ring_rows_fit(const RnnGeom& g16, int B, int T) { return (size_t)T * B * g16.Kp * 4 < (1ull << 31); }
+
 // ---- shape predicates (pure: what some of them used to read from the environment is an argument) ---------------------------
 
 // rnn_persist.hip: H up to 1280 (10 pairs of 16 k per wave: 80 + 80 operand VGPRs); every workgroup of a launch must own a CU, so
 // a layer whose two directions do not fit together (H > 1024 on 256 CUs) runs them as two launches, one after the other.
 inline bool rnn_persist_eligible(const RnnGeom& g, int B, int n_cus) {
     if (g.U != kPersistUnits || (g.H % 8) != 0) return false;
-    if (ceil_div(ceil_div(g.nq, 2), kPersistWaves) > 10) return false;
+    if (!rnn_persist_form(ceil_div(g.nq, 2), ceil_div(B, 32), false, false).n) return false;
     if (ceil_div(B, 32) > kPersistMaxTiles) return false;
     return g.nwg <= n_cus;
 }
@@ -73,12 +137,11 @@ inline bool rnn_persist_eligible(const RnnGeom& g, int B, int n_cus) {
 // a tile group co-resident, no more tiles per workgroup than the carried-state arrays hold.
 inline bool rnn_persist16_eligible(const RnnGeom& g16, int B, int n_cus, int* pgroups_out) {
     if (g16.U != kTileUnits || (g16.H % kTileUnits) != 0) return false;
-    const int nkb = ceil_div(g16.H, 32), nkw = ceil_div(nkb, kPersist16Waves);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 5)) return false;
     if (g16.nwg * g16.D > n_cus) return false;
     const int ntiles = ceil_div(B, kTileClips);
     const int pg = std::min(ntiles, n_cus / (g16.nwg * g16.D));
     if (ceil_div(ntiles, pg) > kPersist16MaxTiles) return false;
+    if (!rnn_persist16_form(g16.kind, ceil_div(g16.H, 32), ceil_div(ntiles, pg), false).n) return false;
     if (pgroups_out) *pgroups_out = pg;
     return true;
 }
@@ -87,12 +150,10 @@ inline bool rnn_persist16_eligible(const RnnGeom& g16, int B, int n_cus, int* pg
 // LSTM (H <= 512); at most two tiles per workgroup; one workgroup slot per CU and lane.
 inline bool rnn_persist16_half_eligible(const RnnGeom& g16, int B, int n_cus, int* pgroups_out) {
     if (g16.U != kTileUnits || (g16.H % kTileUnits) != 0) return false;
-    const int nkw = ceil_div(ceil_div(g16.H, 32), 4);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 7)) return false;
     if (g16.nwg * g16.D > n_cus) return false;
     const int ntiles = ceil_div(B, kTileClips);
     const int pg = std::min(ntiles, n_cus / (g16.nwg * g16.D));
-    if (ceil_div(ntiles, pg) > 2) return false;
+    if (!rnn_persist16_half_form(g16.kind, ceil_div(g16.H, 32), ceil_div(ntiles, pg), false)) return false;
     if (pgroups_out) *pgroups_out = pg;
     return true;
 }
@@ -102,8 +163,10 @@ inline bool rnn_persist16_half_eligible(const RnnGeom& g16, int B, int n_cus, in
 // (the caller passes one gate lane's CUs first, then the whole device).
 inline int rnn_persist_duo_pairs(const RnnGeom& g16, int B, int n_cus) {
     if (g16.U != kTileUnits || (g16.H % kTileUnits) != 0) return 0;
-    const int nkw = ceil_div(ceil_div(g16.H, 32), 4);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 7)) return 0;
+    const int nkb = ceil_div(g16.H, 32);
+    if (!rnn_persist_duo_form(g16.kind, nkb, false).n) return 0;
+    // The launcher also has a TAIL instantiation for an LSTM of 17 k-blocks (H = 528, 544): past the budget above, never planned
+    if (g16.kind == DSMI_RNN_LSTM && nkb > 16) return 0;
     const int ntiles = ceil_div(B, kTileClips);
     if (ntiles < 2) return 0;
     return std::min((ntiles + 1) / 2, n_cus / (g16.nwg * g16.D));
@@ -114,7 +177,7 @@ inline bool rnn_persist_duo_eligible(const RnnGeom& g16, int B, int n_cus) {
 
 // rnn_persist_ring.hip: dynamic LDS of a workgroup -- ring slots, reduce buffers, cell tiles, x-projection zone, tile table, sync, stamps
 inline size_t ring_lds_bytes(int kind, int nkb) {
-    const int NG = kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1);
+    const int NG = rnn_gates(kind);
     return (size_t)2 * nkb * 2048 + (size_t)2 * 4 * NG * 16 * kRingRedPitch * 4 +
            (size_t)kRingMaxTiles * kRingThreads * 4 * (kind == DSMI_RNN_LSTM ? 2 : 1) + (size_t)2 * NG * 256 * 4 + kRingMaxTiles * 16 * 4 +
            32 * 4 + 8 * 16 * 8;
@@ -125,8 +188,7 @@ inline size_t ring_lds_bytes(int kind, int nkb) {
 inline int rnn_persist_ring_tiles(const RnnGeom& g16, int B, int n_cus) {
     if (g16.U != kTileUnits || (g16.H % kTileUnits) != 0) return 0;
     const int nkb = ceil_div(g16.H, 32);
-    const int nkw = ceil_div(nkb, 4);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 4 : 7)) return 0;
+    if (!rnn_persist_ring_form(g16.kind, nkb, 1, false)) return 0;
     if (ring_lds_bytes(g16.kind, nkb) > (size_t)kCuLdsBytes) return 0;
     if (((g16.nwg + 1) / 2) * g16.D > n_cus) return 0;
     if ((size_t)g16.D * ceil_div(B, kTileClips) * nkb * 2048 * 2 >= (1ull << 31)) return 0;      // packed state below 2 GiB (store offsets, see OOR)
@@ -137,7 +199,7 @@ inline int rnn_persist_ring_cus(const RnnGeom& g16) { return ((g16.nwg + 1) / 2)
 
 // rnn_persist_ring4.hip: dynamic LDS of a workgroup -- ring slots, reduce buffers, x-projection zones, sync, stamps
 inline size_t ring4_lds_bytes(int kind, int nkb) {
-    const int NG = kind == DSMI_RNN_GRU ? 3 : (kind == DSMI_RNN_LSTM ? 4 : 1);
+    const int NG = rnn_gates(kind);
     return (size_t)2 * nkb * 2048 + (size_t)2 * 2 * 2 * NG * 256 * 4 + (size_t)3 * 2 * NG * 256 * 4 + 32 * 4 + 4 * 8 * 8;
 }
 // Tiles one launch of the four-wave kernel can walk for this shape on `n_cus` CUs (0: not this shape): the 16-unit geometry, W_hh
@@ -155,14 +217,13 @@ inline size_t ring4_lds_bytes(int kind, int nkb) {
 inline int rnn_persist_ring4_tiles(const RnnGeom& g16, int B, int n_cus, bool small_shapes, int most = 4) {
     if (g16.U != kTileUnits || (g16.H % kTileUnits) != 0) return 0;
     const int nkb = ceil_div(g16.H, 32);
-    const int nkw = ceil_div(nkb, 2);
-    if (nkw > (g16.kind == DSMI_RNN_LSTM ? 8 : 14)) return 0;
-    if (nkw < 4 && !small_shapes) return 0;
+    const int nkw = rnn_persist_ring4_form(g16.kind, nkb, 1, false);
+    if (!nkw || (nkw < 4 && !small_shapes)) return 0;
     if (ring4_lds_bytes(g16.kind, nkb) > (size_t)kCuLdsBytes) return 0;
     if (((g16.nwg + 1) / 2) * g16.D > n_cus) return 0;
     if ((size_t)g16.D * ceil_div(B, kTileClips) * nkb * 2048 * 2 >= (1ull << 31)) return 0;      // packed state below 2 GiB (store offsets, see OOR)
     if (most < 4 || most > kRing4MaxTiles) most = 4;
-    return std::min(ceil_div(B, kTileClips), nkw == 14 ? 4 : most);
+    return std::min(ceil_div(B, kTileClips), rnn_persist_ring4_form(g16.kind, nkb, most, false) ? most : 4);
 }
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------------

@@ -140,6 +140,18 @@ CASES = [
     _case("steps", "gru", 800, 32, env=STEPS_F32, note="fp32 MFMA in the GEMM and the recurrent product"),
     _case("steps", "gru", 800, 64, env=STEPS_F32, gain=6.0, lens="tail", T=21),
     _case("steps", "rnn", 100, 17, T=1, lens="equal"),
+    # ---- template instantiations the cases above do not reach (host_fuzz rnnforms says which shape runs which): the largest width
+    # that maps to each, the smallest batch its form takes.  As many as test_case_table_reaches_every_kernel's cap on this table
+    # leaves room for; the instantiations still unreached are listed in profiles/rnn_forms.txt
+    _case("ring4", "gru", 512, 1, T=5, inflight=2, env=R4, note="8 k-blocks per wave"),
+    _case("ring4", "gru", 768, 1, T=5, inflight=2, env=R4, note="12 k-blocks per wave"),
+    _case("ring4", "rnn", 896, 1, T=5, inflight=2, env=R4, note="14 k-blocks per wave, one gate"),
+    _case("ring4", "lstm", 448, 1, T=5, inflight=2, env=R4, note="7 k-blocks per wave"),
+    _case("ring8", "gru", 512, 1, T=5, inflight=2, env=R8, note="4 k-blocks per wave"),
+    _case("duo", "gru", 512, 17, T=5, inflight=2, env=DUO, note="4 k-blocks per wave, no tail"),
+    _case("p16w4", "gru", 512, 1, T=5, inflight=2, env=DUO, note="4 k-blocks per wave"),
+    _case("p16w8", "gru", 1024, 65, T=5, note="the pipelined kernel at 4 k-blocks per wave: three tiles walked"),
+    _case("persist8", "gru", 888, 1, T=5, note="7 k-pairs per wave, one tile"),
 ]
 assert len({c["name"] for c in CASES}) == len(CASES)
 

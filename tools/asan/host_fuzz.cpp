@@ -6,6 +6,8 @@
 //   host_fuzz rnnplan FILE    the recurrent-layer plan (rnn_plan.h) of every input row of FILE, one line of text per row, each plan
 //                             checked against the invariants below; rows: kind D H B inflight ring_windows lane KERNEL MODE DENSE n_cus
 //   host_fuzz rnnplan grid    the invariants over the grid of 29 315 520 inputs that the plan was compared on with the code it replaced
+//   host_fuzz rnnforms        which template instantiation of the persistent kernels runs which shape (rnn_plan.h: rnn_*_form): the grid
+//                             of tests/rnn_form_table.json, one point per line
 //   host_fuzz gate SEED N     the device gate's admission (gate_plan.h): a table of launches with the masks written out by hand, then N
 //                             random sequences of planned launches of models of different widths, checked against the invariants below
 //   host_fuzz scoreplan SEED N  the launch order of CTC transcript scoring (ctc_host.h: score_plan) on N random candidate lists with many
@@ -177,8 +179,24 @@ static std::string rnn_plan_text(const RnnPlan& plan) {
     return out;
 }
 
+// Does the launcher of launch `l` have a template instantiation for it (rnn_plan.h: rnn_*_form)?  The ring forms: for a window of
+// l.n tiles, which is where the planned n meets the schedule the instantiation allows.
+static bool rnn_launch_has_form(const RnnPlanInput& in, const RnnLaunch& l) {
+    const int kind = in.geom16.kind, nkb = ceil_div(in.geom16.H, 32), ntiles = ceil_div(in.B, kTileClips);
+    switch (l.kernel) {
+        case RNN_PERSIST8: return rnn_persist_form(ceil_div(in.geom.nq, 2), ceil_div(in.B, 32), false, false).n != 0;
+        case RNN_PERSIST16: return l.n >= 1 && rnn_persist16_form(kind, nkb, ceil_div(ntiles, l.n), false).n != 0;
+        case RNN_PERSIST16_HALF: return l.n >= 1 && rnn_persist16_half_form(kind, nkb, ceil_div(ntiles, l.n), false) != 0;
+        case RNN_DUO: return rnn_persist_duo_form(kind, nkb, false).n != 0;
+        case RNN_RING8: return rnn_persist_ring_form(kind, nkb, l.n, false) != 0;
+        case RNN_RING4: return rnn_persist_ring4_form(kind, nkb, l.n, false) != 0;
+        default: return true;      // per step: every shape
+    }
+}
+
 // Every real tile, tile pair or direction in exactly one launch; the gate slots within what the device holds; windows side by side
-// within the device's CUs; tiles per window within the form's cap; the launches' shares sum to 1.  0, or the number of the broken rule.
+// within the device's CUs; tiles per window within the form's cap; the launches' shares sum to 1; every launch has an instantiation
+// (rule 10).  0, or the number of the broken rule.
 static int rnn_plan_check(const RnnPlanInput& in, const RnnPlan& plan) {
     if (plan.launches.size() < 1) return 1;
     const int ntiles = ceil_div(in.B, kTileClips), k0 = plan.launches[0].kernel;
@@ -191,6 +209,7 @@ static int rnn_plan_check(const RnnPlanInput& in, const RnnPlan& plan) {
         const bool ring = l.kernel == RNN_RING8 || l.kernel == RNN_RING4;
         if (ring != (k0 == RNN_RING8 || k0 == RNN_RING4) || (!ring && l.kernel != k0)) return 3;      // one family per layer
         parts += l.part;
+        if (!rnn_launch_has_form(in, l)) return 10;
         if (ring) {
             if (l.n < 1 || l.n > (l.kernel == RNN_RING8 ? kRingMaxTiles : kRing4MaxTiles) || l.nwin < 1) return 4;
             if (l.kernel == RNN_RING8 ? l.n > rnn_persist_ring_tiles(in.geom16, in.B, l.cus)
@@ -260,6 +279,39 @@ static int run_rnnplan(int argc, char** argv) {
     }
     std::fclose(f);
     return rc;
+}
+
+// ---- rnnforms: the table of the persistent kernels' instantiations (rnn_plan.h: rnn_*_form), one grid point per line --------------
+// "form kind H tiles stamps carried|answer"; the answer: the kernel's template arguments behind KIND with the defaults written out,
+// "-" where no instantiation runs the shape (tests/rnn_form_table.json: the same grid from the launchers' if-ladders these replaced)
+static int run_rnnforms() {
+    static const char* const kinds[] = {"gru", "lstm", "rnn"};
+    std::vector<int> Hs;
+    for (int H = 16; H <= 1344; H += 16) Hs.push_back(H);
+    for (int H : {100, 904, 1288}) Hs.push_back(H);
+    for (int kind = 0; kind < 3; ++kind) for (int H : Hs) for (int tiles = 1; tiles <= 8; ++tiles) for (int st = 0; st < 2; ++st) {
+        const int nkb = ceil_div(H, 32);
+        // (the first argument is the form's n: 0 -> "-")
+        auto row = [&](const char* form, int ca, const char* kernel, std::initializer_list<int> args) {
+            std::string answer = *args.begin() ? kernel : "-";
+            const char* sep = "";
+            for (int v : args) if (*args.begin()) { answer += sep + std::to_string(v); sep = ","; }
+            std::printf("%s %s %d %d %d %d|%s\n", form, kinds[kind], H, tiles, st, ca, answer.c_str());
+        };
+        for (int ca = 0; ca < 2; ++ca) {
+            const RnnForm f = rnn_persist_form(ceil_div(make_rnn_geom(kind, H, 1).nq, 2), tiles, ca != 0, st != 0);
+            row("persist8", ca, "", {f.n, f.alt, st, ca});
+        }
+        const RnnForm f16 = rnn_persist16_form(kind, nkb, tiles, st != 0);
+        if (f16.alt) row("p16w8", 0, "pipe:", {f16.n, 0});
+        else row("p16w8", 0, "", {f16.n, kPersist16Waves, st});
+        row("p16w4", 0, "", {rnn_persist16_half_form(kind, nkb, tiles, st != 0), 4, st});
+        const RnnForm fd = rnn_persist_duo_form(kind, nkb, st != 0);
+        row("duo", 0, "", {fd.n, st, fd.alt});
+        row("ring8", 0, "", {rnn_persist_ring_form(kind, nkb, tiles, st != 0), st, 0});
+        row("ring4", 0, "", {rnn_persist_ring4_form(kind, nkb, tiles, st != 0), tiles > 4 ? 8 : 4, st, 0});
+    }
+    return 0;
 }
 
 // ---- gate: what a launch waits for and records at the per-device gate ----------------------------------------------------------
@@ -1087,6 +1139,7 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "lm")) return run_lm(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "plan")) return run_plan(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "rnnplan")) return run_rnnplan(argc, argv);
+    if (argc >= 2 && !std::strcmp(argv[1], "rnnforms")) return run_rnnforms();
     if (argc >= 2 && !std::strcmp(argv[1], "gate")) return run_gate(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
@@ -1094,6 +1147,6 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
