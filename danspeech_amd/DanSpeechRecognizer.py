@@ -869,6 +869,53 @@ class DanSpeechRecognizer(object):
             results[i] = (strings[pos], words, chars)
         return results
 
+    # ---- soft timings of known transcripts (CTC occupancy) -------------------------------------------------------------
+    def soft_align_batch(self, recordings, transcripts):
+        """When is each character and word of ``transcripts[i]`` spoken in ``recordings[i]``, over EVERY alignment rather
+        than the one best path of ``align_batch``?  Per recording ``None`` when the transcript cannot fit the recording's
+        frames, else ``(words, chars)``: ``chars = [(char, centre_s, spread_s, dwell_s), ...]`` for every character of the
+        normalised transcript (``Decoder.normalise_transcript``), spaces included -- the moments over the frames t of the
+        posterior ``tok[t, k]`` that frame t is emitted by character k (``dsmi_occupancy``, float64): ``centre`` its mean
+        frame ``sum t tok / sum tok``, ``spread`` its standard deviation, ``dwell`` the expected frames ``sum tok`` (at least
+        one), all in seconds (``frame_seconds``) -- and ``words = [(word, first character's centre_s, last character's
+        centre_s), ...]``.  A boundary the model cannot place shows as a wide spread.  Every transcript is checked before any
+        GPU work (``ValueError`` for characters that are not labels)."""
+        import torch
+        if self.model is None:
+            raise ModelNotInitialized("Trying to align without a DanSpeech model.")
+        if len(recordings) != len(transcripts):
+            raise ValueError("soft_align_batch: %d recordings and %d transcripts" % (len(recordings), len(transcripts)))
+        texts = [self.decoder.normalise_transcript(t) for t in transcripts]
+        ids = [self.decoder.transcript_ids(t) for t in texts]
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        occupied = self.decoder.occupancy_ids(job.probs, [ids[i] for i in job.order], job.sizes)
+        frame_s = self.frame_seconds()
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            if occupied[pos] is None:
+                continue
+            tok = occupied[pos][2]                                                   # [frames, L] on the device
+            t = torch.arange(tok.shape[0], dtype=tok.dtype, device=tok.device)[:, None]
+            dwell = tok.sum(0)
+            centre = (t * tok).sum(0) / dwell
+            spread = (((t - centre[None, :]) ** 2 * tok).sum(0) / dwell).sqrt()
+            m = (torch.stack((centre, spread, dwell), 1) * frame_s).cpu().numpy()    # [L, 3] seconds
+            chars = [(ch, float(m[k, 0]), float(m[k, 1]), float(m[k, 2])) for k, ch in enumerate(texts[i])]
+            words, k = [], 0
+            for word in texts[i].split():
+                k = texts[i].index(word, k)
+                words.append((word, chars[k][1], chars[k + len(word) - 1][1]))
+                k += len(word)
+            results[i] = (words, chars)
+        return results
+
+    def soft_align(self, recording, transcript):
+        """``soft_align_batch`` of one recording."""
+        return self.soft_align_batch([recording], [transcript])[0]
+
     # ---- long recordings and files ----------------------------------------------------------------------------------
     def transcribe_long(self, recording, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
                         max_batch=32, show_all=False, sample_rate=None, resample="polyphase"):

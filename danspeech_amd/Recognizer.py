@@ -119,6 +119,16 @@ class Recognizer(object):
         (``DanSpeechRecognizer.transcribe_confident_batch``)."""
         return self.danspeech_recognizer.transcribe_confident_batch(audio_list)
 
+    def soft_align(self, audio_data, transcript):
+        """Soft timings of a transcript of ``audio_data``, over every alignment: ``(words, chars)`` with ``chars = [(char,
+        centre_s, spread_s, dwell_s), ...]`` and ``words = [(word, first_centre_s, last_centre_s), ...]``, or ``None`` when
+        the transcript cannot fit the audio (``DanSpeechRecognizer.soft_align_batch``)."""
+        return self.danspeech_recognizer.soft_align(audio_data, transcript)
+
+    def soft_align_batch(self, audio_list, transcripts):
+        """``soft_align`` for a list of clips in one batched pass over the GPU; results in the caller's order."""
+        return self.danspeech_recognizer.soft_align_batch(audio_list, transcripts)
+
     def recognize_batches(self, batches, show_all=False):
         """Generator: ``recognize_batch`` over a sequence of batches, with the upload of the next batch and the
         decoding of the previous one overlapped with the GPU's work on the current one."""

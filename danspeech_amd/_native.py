@@ -35,6 +35,7 @@ SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
 SPOT_STREAM_MANY_MAX = 4096     # streams of one dsmi_spot_stream_advance_many launch
 SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
 ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes (L_stride)
+OCC_MAX_TOKENS = 1024           # the longest candidate dsmi_occupancy takes (L_stride)
 EDIT_MAX_TOKENS = 4096          # the longest sequence dsmi_edit_distance takes (L_stride)
 LM_SCORE_MAX_TOKENS = 4096      # the longest sequence dsmi_lm_score takes (L_stride)
 
@@ -195,6 +196,7 @@ _PROTOS = {
     "dsmi_score_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "dsmi_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "dsmi_occupancy": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_edit_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_edit_distance": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_lm_score_plan": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
@@ -1133,6 +1135,26 @@ class NativeDecoder(_Handle):
                                             _np_ptr(target_lens), N, tg.shape[1], _np_ptr(lp), _np_ptr(alt), _np_ptr(st),
                                             _stream(self.device)))
         return lp, alt, st
+
+    def occupancy(self, probs, sizes, cand_clip, targets, target_lens=None, want_occ=True, want_tok=True):
+        """CTC occupancy (``dsmi_occupancy``): for every candidate the posterior, given the transcript, that frame t carries
+        label c (``occ``) or is emitted by token k (``tok``).  Arguments as ``score``.  Returns ``(logp, occ, tok, status)``:
+        logp float64 [N] and status int32 [N] (1 = infeasible, logp = -inf) are numpy; occ [N, T, C] and tok [N, T, L_stride]
+        are CUDA float64 tensors written in full (zeros past a clip's frames, past a transcript's length and for an
+        infeasible candidate), or None where ``want_occ`` / ``want_tok`` is false."""
+        import torch
+        B, T = probs.shape[0], probs.shape[1]
+        clip = np.ascontiguousarray(cand_clip, dtype=np.int32).reshape(-1)
+        N = len(clip)
+        tg, target_lens = _padded_ids(targets, target_lens, N, 0, "occupancy: %d target sequences for %d candidates")
+        lp = np.zeros(N, dtype=np.float64)
+        st = np.zeros(N, dtype=np.int32)
+        occ = torch.empty((N, T, probs.shape[2]), dtype=torch.float64, device=probs.device) if want_occ else None
+        tok = torch.empty((N, T, tg.shape[1]), dtype=torch.float64, device=probs.device) if want_tok else None
+        self._check(lib().dsmi_occupancy(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, _np_ptr(clip), _np_ptr(tg),
+                                         _np_ptr(target_lens), N, tg.shape[1], _np_ptr(lp), occ.data_ptr() if want_occ else None,
+                                         tok.data_ptr() if want_tok and tok.numel() else None, _np_ptr(st), _stream(self.device)))
+        return lp, occ, tok, st
 
     def edit_distance(self, seqs, pairs, seq_lens=None):
         """Batched edit distance (``dsmi_edit_distance``).  seqs: the pool, an int array [M, L_stride] with ``seq_lens`` [M],

@@ -1,6 +1,6 @@
-// The host half of the four CTC trellis tools (dsmi_align, dsmi_spot, dsmi_score, dsmi_alternatives: ctc_tools.hip): the checks of everything a
+// The host half of the five CTC trellis tools (dsmi_align, dsmi_spot, dsmi_score, dsmi_alternatives, dsmi_occupancy: ctc_tools.hip): the checks of everything a
 // caller hands in, the packing of phrases into workgroups and the launch order of candidates.  No HIP: a plain C++ compiler
-// takes it, and tools/asan/host_fuzz.cpp (ctccheck, scoreplan) runs it under ASan + UBSan on exactly sized arrays.  A check
+// takes it, and tools/asan/host_fuzz.cpp (ctccheck, occcheck, scoreplan) runs it under ASan + UBSan on exactly sized arrays.  A check
 // returns DSMI_OK or a DSMI_ERR_* code with the message in `err`; what the numbers alone refuse is refused before any array is read.
 #pragma once
 #include <algorithm>
@@ -247,6 +247,32 @@ inline uint64_t alt_place(const int32_t* tl, const int32_t* frames, int N, int32
 constexpr uint64_t kAltOutCap = (uint64_t)1 << 24;       // N * L_stride * n_labels: the results, on the handle and copied back
 constexpr uint64_t kAltTrellisCap = (uint64_t)1 << 25;   // elements of one stored trellis over all candidates of a call
 
+// What the two tools with a stored trellis per candidate check alike, behind their own checks of the numbers: the sizes, every
+// candidate's clip and token row, the feasibility, and the stored trellises against their cap and in their places.
+inline int ctc_check_stored(const CtcRows& r, const int32_t* sizes, int B, int To, const int32_t* cand_clip, const int32_t* targets,
+                            const int32_t* target_lens, int N, int L_stride, int C, int blank, std::vector<int32_t>& sz,
+                            std::vector<int32_t>& tl, std::vector<int32_t>& frames, std::vector<int32_t>& base, int* L_max,
+                            uint64_t* trellis, std::string& err) {
+    sz.assign((size_t)B, 0); tl.assign((size_t)N, 0); frames.assign((size_t)N, 0);
+    if (int rc = ctc_check_sizes(r, sizes, B, To, sz.data(), err)) return rc;
+    *L_max = 0;
+    for (int n = 0; n < N; ++n) {
+        const int b = cand_clip[n];
+        if (b < 0 || b >= B) return ctc_refuse(err, DSMI_ERR_INVALID, std::string(r.tool) + ": candidate " + std::to_string(n) + ": clip outside 0 .. B-1");
+        int repeats = 0;
+        if (int rc = ctc_check_row(r, n, targets + (size_t)n * L_stride, target_lens[n], L_stride, C, blank, &repeats, err)) return rc;
+        frames[n] = sz[b];
+        tl[n] = ctc_feasible_len(target_lens[n], repeats, sz[b]);
+        *L_max = std::max(*L_max, (int)tl[n]);
+    }
+    *trellis = alt_place(tl.data(), frames.data(), N, nullptr);
+    if (*trellis > kAltTrellisCap)
+        return ctc_refuse(err, DSMI_ERR_CAPACITY, std::string(r.tool) + ": the stored trellises, the sum of frames * (2 * length + 1) over the candidates, exceed 2^25 elements (" + std::to_string(*trellis) + ")");
+    base.assign((size_t)N, 0);
+    alt_place(tl.data(), frames.data(), N, base.data());
+    return DSMI_OK;
+}
+
 // sz [B], tl [N] (-1: infeasible), frames [N], base [N] (alt_place), *L_max = the longest feasible candidate, *trellis = alt_place's total
 inline int alt_check(const int32_t* sizes, int B, int To, const int32_t* cand_clip, const int32_t* targets, const int32_t* target_lens,
                      int N, int L_stride, int C, int blank, std::vector<int32_t>& sz, std::vector<int32_t>& tl,
@@ -257,24 +283,24 @@ inline int alt_check(const int32_t* sizes, int B, int To, const int32_t* cand_cl
     if ((uint64_t)N * (uint64_t)L_stride * (uint64_t)C > kAltOutCap)
         return ctc_refuse(err, DSMI_ERR_CAPACITY, "alternatives: N * L_stride * n_labels exceeds 2^24 (the results)");
     if ((uint64_t)N * (uint64_t)L_stride > kAltOutCap) return ctc_refuse(err, DSMI_ERR_CAPACITY, "alternatives: N * L_stride exceeds 2^24");
-    sz.assign((size_t)B, 0); tl.assign((size_t)N, 0); frames.assign((size_t)N, 0);
-    if (int rc = ctc_check_sizes(kAltRows, sizes, B, To, sz.data(), err)) return rc;
-    *L_max = 0;
-    for (int n = 0; n < N; ++n) {
-        const int b = cand_clip[n];
-        if (b < 0 || b >= B) return ctc_refuse(err, DSMI_ERR_INVALID, "alternatives: candidate " + std::to_string(n) + ": clip outside 0 .. B-1");
-        int repeats = 0;
-        if (int rc = ctc_check_row(kAltRows, n, targets + (size_t)n * L_stride, target_lens[n], L_stride, C, blank, &repeats, err)) return rc;
-        frames[n] = sz[b];
-        tl[n] = ctc_feasible_len(target_lens[n], repeats, sz[b]);
-        *L_max = std::max(*L_max, (int)tl[n]);
-    }
-    *trellis = alt_place(tl.data(), frames.data(), N, nullptr);
-    if (*trellis > kAltTrellisCap)
-        return ctc_refuse(err, DSMI_ERR_CAPACITY, "alternatives: the stored trellises, the sum of frames * (2 * length + 1) over the candidates, exceed 2^25 elements (" + std::to_string(*trellis) + ")");
-    base.assign((size_t)N, 0);
-    alt_place(tl.data(), frames.data(), N, base.data());
-    return DSMI_OK;
+    return ctc_check_stored(kAltRows, sizes, B, To, cand_clip, targets, target_lens, N, L_stride, C, blank, sz, tl, frames, base, L_max, trellis, err);
+}
+
+// ---- occupancy: two stored trellises per feasible candidate, placed by alt_place and under alternatives' cap; the outputs are the
+// caller's own device arrays.  The per-label sums need no grouping from the host: an output thread walks its candidate's tokens
+// in order (occ.hip).
+constexpr CtcRows kOccRows{"occupancy", "candidate", "target length", "target id", "DSMI_OCC_MAX_TOKENS", 0, DSMI_OCC_MAX_TOKENS};
+constexpr uint64_t kOccUploadCap = (uint64_t)1 << 24;    // N * L_stride: the targets, uploaded to the handle
+
+// sz [B], tl [N] (-1: infeasible), frames [N], base [N] (alt_place), *L_max = the longest feasible candidate, *trellis = alt_place's total
+inline int occ_check(const int32_t* sizes, int B, int To, const int32_t* cand_clip, const int32_t* targets, const int32_t* target_lens,
+                     int N, int L_stride, int C, int blank, std::vector<int32_t>& sz, std::vector<int32_t>& tl,
+                     std::vector<int32_t>& frames, std::vector<int32_t>& base, int* L_max, uint64_t* trellis, std::string& err) {
+    if (B <= 0 || To <= 0 || N <= 0) return ctc_refuse(err, DSMI_ERR_INVALID, "occupancy: B, T_out and N must be positive");
+    if (L_stride < 0) return ctc_refuse(err, DSMI_ERR_INVALID, "occupancy: negative L_stride");
+    if (int rc = ctc_check_stride(kOccRows, L_stride, err)) return rc;
+    if ((uint64_t)N * (uint64_t)L_stride > kOccUploadCap) return ctc_refuse(err, DSMI_ERR_CAPACITY, "occupancy: N * L_stride exceeds 2^24 (the upload buffer)");
+    return ctc_check_stored(kOccRows, sizes, B, To, cand_clip, targets, target_lens, N, L_stride, C, blank, sz, tl, frames, base, L_max, trellis, err);
 }
 
 }  // namespace dsmi

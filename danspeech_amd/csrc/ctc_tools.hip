@@ -1,8 +1,8 @@
-// The four tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
-// (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip) and
-// token confidence (dsmi_alternatives; alt.hip) -- and, on the same handle and by the same conventions, the batched edit distance
-// of token sequences (dsmi_edit_distance; edit.hip) and the language-model score of known sentences (dsmi_lm_score; lmscore.hip),
-// which need no probabilities.
+// The five tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
+// (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip),
+// token confidence (dsmi_alternatives; alt.hip) and occupancy (dsmi_occupancy; occ.hip) -- and, on the same handle and by the
+// same conventions, the batched edit distance of token sequences (dsmi_edit_distance; edit.hip) and the language-model score of
+// known sentences (dsmi_lm_score; lmscore.hip), which need no probabilities.
 // Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
 // before any output write), grows its workspaces, uploads, launches and copies the results back.  A clip or candidate whose
 // transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
@@ -11,6 +11,7 @@
 #include "spot.h"
 #include "score.h"
 #include "alt.h"
+#include "occ.h"
 #include "edit.h"
 #include "lmscore.h"
 
@@ -220,6 +221,52 @@ extern "C" int dsmi_alternatives(dsmi_decoder* d, const float* probs, const int3
         const size_t written = tl[n] < 0 ? 0 : (size_t)tl[n] * C, row = (size_t)L_stride * C;      // (the kernel writes rows k < length)
         double* dst = alt_logp ? alt_logp + (size_t)n * row : nullptr;
         for (size_t i = 0; i < row; ++i) dst[i] = i < written ? rows[(size_t)n * row + i] : -INFINITY;
+    }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_occupancy(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const int32_t* cand_clip,
+                              const int32_t* targets, const int32_t* target_lens, int N, int L_stride, double* logp, double* occ,
+                              double* tok, int32_t* status, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !cand_clip || !target_lens || !logp || !status || (L_stride > 0 && !targets)) {
+        d->err = "bad occupancy arguments"; return DSMI_ERR_INVALID;
+    }
+    std::vector<int32_t> sz, tl, frames, base;
+    int L_max = 0;
+    uint64_t trellis = 0;
+    if (int rc = occ_check(sizes, B, To, cand_clip, targets, target_lens, N, L_stride, C, d->blank, sz, tl, frames, base, &L_max, &trellis, d->err)) return rc;
+    std::vector<int32_t> order(N);
+    score_plan(cand_clip, frames.data(), target_lens, N, order.data());
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- the workspaces: sizes [B], order [N], clips [N], lens [N], bases [N], targets [N][L], then logp [N] doubles; the stored
+    // trellises, forward and backward of `trellis` doubles each.  occ and tok are the caller's.
+    const size_t NL = (size_t)N * L_stride, in_words = ((size_t)B + 4 * (size_t)N + NL + 1) & ~(size_t)1;
+    if (int rc = reserve_all(d, d->occ_io, sizeof(int32_t) * (in_words + 2 * (size_t)N), &d->occ_ws, sizeof(double) * (2 * (size_t)trellis + 1))) return rc;
+    int32_t* w_sz = d->occ_io.as<int32_t>(); int32_t* w_or = w_sz + B; int32_t* w_cl = w_or + N; int32_t* w_tl = w_cl + N;
+    int32_t* w_ba = w_tl + N; int32_t* w_tg = w_ba + N;
+    double* w_lp = reinterpret_cast<double*>(w_sz + in_words);
+    DEC_HIP(d, hipMemcpyAsync(w_sz, sz.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_or, order.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_cl, cand_clip, sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_tl, tl.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemcpyAsync(w_ba, base.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s));
+    if (NL) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * NL, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_lp, 0, sizeof(double) * N, s));
+    OccArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank; a.N = N;
+    a.sizes = w_sz; a.order = w_or; a.cand_clip = w_cl; a.tlen = w_tl; a.targets = w_tg; a.base = w_ba; a.L_stride = L_stride;
+    a.S_max = 2 * L_max + 1; a.fwd = d->occ_ws.as<double>(); a.bwd = a.fwd + trellis;
+    a.logp = w_lp; a.occ = occ; a.tok = L_stride > 0 ? tok : nullptr; a.both = a.occ || a.tok;
+    DEC_HIP(d, launch_occ(a, s));
+    std::vector<double> out(N);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_lp, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    for (int n = 0; n < N; ++n) {
+        status[n] = tl[n] < 0 ? 1 : 0;
+        logp[n] = tl[n] < 0 ? -INFINITY : out[n];
     }
     return DSMI_OK;
 }

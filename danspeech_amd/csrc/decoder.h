@@ -1,5 +1,5 @@
 // The handle behind dsmi_decoder*, shared by decoder.hip (its life, greedy, beam search, the LM) and ctc_tools.hip (forced
-// alignment, phrase search, transcript scoring, token confidence, edit distance, LM sentence scoring).
+// alignment, phrase search, transcript scoring, token confidence, occupancy, edit distance, LM sentence scoring).
 #pragma once
 #include "common.h"
 #include "lm.h"
@@ -66,6 +66,8 @@ struct dsmi_decoder {
     // dsmi_alternatives: inputs of the launch and logp [N] as dsmi_score's, the results [N][L_stride][n_labels] doubles, the
     // stored trellises (doubles: forward pairs, backward, backward pair sums)
     DevBuf alt_io, alt_out, alt_ws;
+    // dsmi_occupancy: inputs of the launch and logp [N] as dsmi_score's, the two stored trellises (doubles: forward, backward)
+    DevBuf occ_io, occ_ws;
     // dsmi_edit_distance: the upload of the launch (int32 words: lens, pool, pairs, waves) and, behind it, the packed results
     DevBuf ed_io;
     // dsmi_lm_score: the upload of the launch (int32 words: lm_score_pack) and, behind it on 8 bytes, the results

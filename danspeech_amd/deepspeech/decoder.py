@@ -247,6 +247,38 @@ class Decoder(object):
         strings, _, ids = self._decode_best_ids(probs, sizes)
         return strings, ids, self.confidence_ids(probs, ids, sizes)
 
+    # ---- CTC occupancy (dsmi_occupancy): which frames each token occupies and which label each frame carries, given the transcript
+    def occupancy(self, probs, transcripts, sizes=None):
+        """The per-frame posteriors of ``transcripts[b]`` (normalised with ``normalise_transcript``) over the probabilities of
+        clip b (``probs`` [B,T,C], ``sizes`` frames per clip).  Per clip ``None`` when the transcript cannot fit the clip's
+        frames, else ``(logp, occ, tok)``: the natural log of the transcript's likelihood summed over every alignment, and
+        two CUDA float64 tensors over the clip's own frames -- ``occ`` [frames, C], the probability that frame t carries
+        label c given the transcript (each row sums to 1), and ``tok`` [frames, L], the probability that frame t is emitted
+        by character k (``sum_t tok[t, k]`` is the expected number of frames character k lasts)."""
+        ids = [self.transcript_ids(self.normalise_transcript(t)) for t in transcripts]      # every check before any GPU work
+        return self.occupancy_ids(probs, ids, sizes)
+
+    def occupancy_ids(self, probs, ids, sizes=None):
+        """``occupancy`` for label-id sequences as they are (no normalisation): ``ids[b]`` one id sequence for clip b."""
+        import torch
+        from .. import _native
+        if len(ids) != len(probs):
+            raise ValueError("occupancy: transcripts for %d clips and a batch of %d" % (len(ids), len(probs)))
+        longest = max([len(t) for t in ids] + [0])
+        if longest > _native.OCC_MAX_TOKENS:
+            raise ValueError("transcript of %d labels is longer than %d" % (longest, _native.OCC_MAX_TOKENS))
+        if not len(ids):
+            return []
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        lp, occ, tok, status = dec.occupancy(probs, sz, np.arange(len(ids)), ids)
+        out = []
+        for b, t in enumerate(ids):
+            frames = probs.shape[1] if sz is None else int(sz[b])
+            out.append(None if status[b] else (float(lp[b]), occ[b, :frames], tok[b, :frames, :len(t)]))
+        return out
+
     # ---- batched edit distance (dsmi_edit_distance): WER / CER with their error counts, and minimum-risk choice among the
     # hypotheses of an n-best list; the same on every decoder, a language model plays no part
     def _edit_device(self):

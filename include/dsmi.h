@@ -743,6 +743,49 @@ int dsmi_alternatives(dsmi_decoder* d, const float* probs_dev, const int32_t* si
                       const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host,
                       int N, int L_stride, double* logp_host, double* alt_logp_host, int32_t* status_host, void* stream);
 
+/* ---- CTC occupancy (no reference counterpart): which frames does each token of a known transcript occupy, and how probable is
+ * each label at each frame GIVEN the transcript?  The per-frame posteriors under alignment, scoring and token confidence: soft
+ * timings (a token's expected time, dwell and spread over every alignment, not one hard path), and the gradient of the CTC loss.
+ * probs_dev, sizes_host, cand_clip_host, targets_host, target_lens_host, N and L_stride are dsmi_score's.  Candidate n is a
+ * transcript y of L tokens on clip b with T frames.
+ * Definitions (the contract).  The states, the skip rule, alpha_0, lp(t, c) = log((double)fmaxf(p, FLT_MIN)) and logp are
+ * dsmi_score's.  beta_t(s) is dsmi_alternatives': the log probability of finishing from state s at frame t, frame t's emission
+ * included; at T-1 only S-1 and S-2 are finite:
+ *     beta_{T-1}(s) = lp(T-1, label(s)) for s >= S-2, else -inf
+ *     beta_t(s)     = logsumexp(beta_{t+1}(s), beta_{t+1}(s+1), beta_{t+1}(s+2) [only if s+2 is a token state and
+ *                     label(s+2) != label(s)]) + lp(t, label(s))
+ *     gamma_t(s)    = exp(alpha_t(s) + beta_t(s) - lp(t, label(s)) - logp), 0 where alpha or beta is -inf, never NaN
+ *     tok[n][t][k]  = gamma_t(2k+1)
+ *     occ[n][t][c]  = the sum of gamma_t(s) over the states s with label(s) == c (the blank's column collects the L+1 blank states)
+ * Every alignment passes through exactly one state per frame, so each row of occ sums to 1, and
+ * d logp / d lp(t, c) = occ[t][c]: the gradient of -logp with respect to the pre-softmax activations is p_t(c) - occ_t(c).
+ * Outputs: logp_host [N] and status_host [N] as dsmi_score's (1 = infeasible, logp = -inf).  occ_dev [N][T_out][n_labels] and
+ * tok_dev [N][T_out][L_stride] are float64, caller-allocated and stay on the DEVICE: they are as large as the probabilities
+ * and their consumers (the gradient, reductions over frames) are there.  Either may be NULL and is then not computed (with
+ * L_stride == 0 tok_dev has no element and is ignored).  Both are written in full: rows t >= frames, columns k >= length and
+ * everything of an infeasible candidate are 0.0, so the caller never clears them.  With 0 tokens occ_t(blank) is 1 within the
+ * bound for t < frames; with 0 frames the empty transcript has logp = 0 and all zeros, every other candidate is infeasible.
+ * The results are specified as values with a bound, not bit for bit: logp holds dsmi_score's bound, and every occ and tok
+ * element is within 32 * T * 2^-52 * max(1, |logp| + 88) of the recurrences evaluated exactly, in absolute terms.  alpha, beta
+ * and logp each carry 8 T 2^-52 max(1, |value|) (each is one non-expansive float64 recurrence of T steps).  For a state with
+ * exponent x = alpha + beta - lp - logp <= 0, |alpha| + |beta| <= |x| + |logp| + |lp| with |lp| <= 87.4 (-log FLT_MIN), so the
+ * exponent's error is at most 8 T 2^-52 (|x| + 2 |logp| + 91) and that of e^x is e^x times it.  e^x |x| <= 1/e for one state;
+ * over the states of one label, with g = e^x and sum g <= 1, sum g |x| <= ln S + 1 < 10 (S <= 2049).  Together at most
+ * 8 T 2^-52 (2 |logp| + 101), inside the stated bound; the sum of at most L + 1 <= T + 1 terms itself adds (L + 1) 2^-53.
+ * Deterministic and batch-invariant: a candidate's logp, occ and tok are bit-identical whatever else is in the call and from
+ * run to run -- a label's sum is formed over the candidate's own tokens in the order of k by one thread, with no floating-point
+ * atomic.  Frames past sizes[b] are never read.
+ * Refused before any launch with nothing written on host or device: DSMI_ERR_INVALID for everything dsmi_score refuses and for
+ * NULL logp_host or status_host; DSMI_ERR_CAPACITY, the limit named in the message, for L_stride > DSMI_OCC_MAX_TOKENS,
+ * N * L_stride > 2^24 (the upload buffer, kept on the handle), or a stored trellis -- the sum over the feasible candidates of
+ * frames * (2 * length + 1) -- above 2^25 elements (two of them in float64, kept on the handle).  What the numbers alone refuse
+ * is refused before any caller array is read.  Two kernel launches whatever N (one when both device arrays are NULL).
+ * Synchronises `stream`. */
+#define DSMI_OCC_MAX_TOKENS 1024
+int dsmi_occupancy(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+                   const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host,
+                   int N, int L_stride, double* logp_host, double* occ_dev, double* tok_dev, int32_t* status_host, void* stream);
+
 /* ---- Batched edit distance (the reference calls Levenshtein.distance once per pair, on the host): how far is this text from
  * that one, for many pairs at once -- WER / CER with their error counts, and the pairwise distances of n-best lists.
  * A pool of M token sequences: seqs_host [M][L_stride] with seq_lens_host [M].  Tokens are any int32 and are compared for

@@ -15,6 +15,9 @@
 //   host_fuzz ctccheck SEED N   the argument checks and the phrase packing of dsmi_align / dsmi_spot / dsmi_score / dsmi_alternatives (ctc_host.h) on N random
 //                             calls held in exactly sized heap arrays, against the definitions written out below; what is refused
 //                             on the numbers alone is called with null arrays
+//   host_fuzz occcheck SEED N   the argument check of dsmi_occupancy (ctc_host.h: occ_check) and where each candidate's stored trellis lies, on N random
+//                             calls held in exactly sized heap arrays, each good or with one fault, against the rules written out
+//                             below; the stored trellis against its cap; what is refused on the numbers alone is called with null arrays
 //   host_fuzz editcheck SEED N  the host half of dsmi_edit_distance (edit_host.h: edit_check, edit_plan, edit_pack, edit_unpack) on N random
 //                             calls held in exactly sized heap arrays, against the rules written out below; what is refused on the
 //                             numbers alone is called with null arrays
@@ -664,6 +667,95 @@ static int run_ctccheck(int argc, char** argv) {
     return 0;
 }
 
+// ---- occcheck: dsmi_occupancy's check (ctc_host.h: occ_check) and the placing of its stored trellis, each array a heap block of
+// exactly the size the call declares
+#define OCC_FAIL(what) do { std::fprintf(stderr, "occcheck: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
+
+static int run_occcheck(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long good = 0, refused = 0, infeasible = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        const int C = 2 + (int)(rng() % 127), blank = (int)(rng() % (unsigned)C);
+        const int B = 1 + (int)(rng() % 6), To = 1 + (int)(rng() % 40);
+        const int L_stride = (int)(rng() % 12), N = 1 + (int)(rng() % 9);
+        std::string err;
+        std::vector<int32_t> sz, tl, frames, base;
+        int L_max = -7;
+        uint64_t trellis = 7;
+        // ---- a whole call; with `fault` one thing is wrong with it, and the rule that refuses it is written out here
+        std::vector<int32_t> sizes = exact((size_t)B), clip = exact((size_t)N), lens = exact((size_t)N), tg = exact((size_t)N * L_stride);
+        for (auto& v : sizes) v = (int32_t)(rng() % (unsigned)(To + 1));
+        for (int n = 0; n < N; ++n) {
+            clip[(size_t)n] = (int32_t)(rng() % (unsigned)B);
+            lens[(size_t)n] = (int32_t)(rng() % (unsigned)(L_stride + 1));
+            random_row(rng, tg.data() + (size_t)n * L_stride, lens[(size_t)n], C, blank, false);
+        }
+        const bool no_sizes = rng() % 5 == 0;
+        const int fault = rng() % 2 ? 0 : 1 + (int)(rng() % 4);
+        const char* text = "";
+        if (fault == 1) { sizes[rng() % (unsigned)B] = rng() % 2 ? To + 1 : -1; text = "size outside 0 .. T_out"; }
+        if (fault == 2) { clip[rng() % (unsigned)N] = rng() % 2 ? B : -1; text = "clip outside 0 .. B-1"; }
+        if (fault == 3) { lens[rng() % (unsigned)N] = rng() % 2 ? L_stride + 1 : -1; text = "target length outside 0 .. L_stride"; }
+        if (fault == 4) {
+            int n = -1;
+            for (int m = 0; m < N; ++m) if (lens[(size_t)m] > 0) n = m;
+            if (n < 0) { text = nullptr; }      // (no token to spoil: a good call after all)
+            else { tg[(size_t)n * L_stride + rng() % (unsigned)lens[(size_t)n]] = rng() % 2 ? blank : C; text = "is the blank or not a label"; }
+        }
+        const bool bad = fault != 0 && text != nullptr && !(fault == 1 && no_sizes);
+        const int rc = occ_check(no_sizes ? nullptr : sizes.data(), B, To, clip.data(), ptr_or_null(tg), lens.data(), N, L_stride, C, blank,
+                                 sz, tl, frames, base, &L_max, &trellis, err);
+        if (bad) {
+            if (rc != DSMI_ERR_INVALID) OCC_FAIL("a bad call passed");
+            if (err.rfind("occupancy: ", 0) != 0 || err.find(text) == std::string::npos) OCC_FAIL("wrong message");
+            ++refused;
+        } else {
+            if (rc != DSMI_OK) OCC_FAIL("a good call refused");
+            if ((int)sz.size() != B || (int)tl.size() != N || (int)frames.size() != N || (int)base.size() != N) OCC_FAIL("the lengths of what the check hands on");
+            uint64_t at = 0;
+            int want_max = 0;
+            for (int n = 0; n < N; ++n) {
+                const int T = no_sizes ? To : sizes[(size_t)clip[(size_t)n]], L = lens[(size_t)n];
+                const int want = min_frames(tg.data() + (size_t)n * L_stride, L, blank) <= T ? L : -1;
+                if (frames[(size_t)n] != T || tl[(size_t)n] != want) OCC_FAIL("frames or feasibility");
+                if ((uint64_t)base[(size_t)n] != at) OCC_FAIL("a trellis out of place");
+                if (want >= 0) at += (uint64_t)T * (2 * (uint64_t)L + 1);       // [T][S], back to back
+                else ++infeasible;
+                want_max = std::max(want_max, want);
+            }
+            if (trellis != at || L_max != want_max) OCC_FAIL("the trellis total or the longest candidate");
+            ++good;
+        }
+        // ---- the stored trellis over the cap: candidates of 1024 tokens on 4096 frames, 2^25 elements hold three of them and not four
+        {
+            const int n_long = 3 + (int)(rng() % 3), Ll = DSMI_OCC_MAX_TOKENS, Tl = 4096;
+            std::vector<int32_t> one = exact(1, Tl), zero = exact((size_t)n_long, 0), full = exact((size_t)n_long, Ll), rows = exact((size_t)n_long * Ll);
+            for (size_t i = 0; i < rows.size(); ++i) rows[i] = (int32_t)((blank + 1 + (int)(i & 1)) % C == blank ? (blank + 2) % C : (blank + 1 + (int)(i & 1)) % C);
+            const int rc2 = occ_check(one.data(), 1, Tl, zero.data(), rows.data(), full.data(), n_long, Ll, C, blank, sz, tl, frames, base, &L_max, &trellis, err);
+            const uint64_t want = (uint64_t)n_long * Tl * (2 * (uint64_t)Ll + 1);
+            if (C > 2) {      // (two labels: one token label alone, no row of alternating tokens)
+                if (want > ((uint64_t)1 << 25) ? (rc2 != DSMI_ERR_CAPACITY || err.find("2^25") == std::string::npos) : rc2 != DSMI_OK) OCC_FAIL("the trellis cap");
+            }
+        }
+        // ---- refused on the numbers alone: no array exists
+        {
+            const int32_t* none = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            if (occ_check(none, 0, To, none, none, none, N, 3, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_INVALID) OCC_FAIL("B = 0");
+            if (occ_check(none, B, -big, none, none, none, N, 3, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_INVALID) OCC_FAIL("T_out < 0");
+            if (occ_check(none, B, To, none, none, none, 0, 3, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_INVALID) OCC_FAIL("N = 0");
+            if (occ_check(none, B, To, none, none, none, big, -1, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_INVALID) OCC_FAIL("L_stride < 0");
+            if (occ_check(none, B, To, none, none, none, big, DSMI_OCC_MAX_TOKENS + big, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_CAPACITY ||
+                err.find("DSMI_OCC_MAX_TOKENS") == std::string::npos) OCC_FAIL("L_stride over the limit");
+            if (occ_check(none, B, To, none, none, none, (1 << 24) / 1024 + big, 1024, C, blank, sz, tl, frames, base, &L_max, &trellis, err) != DSMI_ERR_CAPACITY ||
+                err.find("2^24") == std::string::npos) OCC_FAIL("N * L_stride over 2^24");
+        }
+    }
+    std::printf("%d occupancy calls ok, %ld good, %ld refused, %ld infeasible candidates\n", reps, good, refused, infeasible);
+    return good > 0 && refused > 0 ? 0 : 11;
+}
+
 // ---- editcheck: the rules of include/dsmi.h written out plainly, beside edit_host.h -------------------------------------------
 #define EDIT_FAIL(what) do { std::fprintf(stderr, "editcheck: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
 
@@ -1143,10 +1235,11 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "gate")) return run_gate(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
+    if (argc >= 2 && !std::strcmp(argv[1], "occcheck")) return run_occcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
