@@ -917,6 +917,21 @@ class DanSpeechRecognizer(object):
         return self.soft_align_batch([recording], [transcript])[0]
 
     # ---- long recordings and files ----------------------------------------------------------------------------------
+    def _cut_long(self, recording, energy_threshold, step, pause_threshold, phrase_threshold, sample_rate, resample):
+        """The recording on the device at the model's rate and its phrases ``[(start_sample, end_sample), ...]`` in time order:
+        the front of ``transcribe_long`` and ``align_long``."""
+        import torch
+        parser = self.audio_parser
+        if sample_rate is not None and int(sample_rate) != int(parser.sampling_rate):
+            pcm = parser.resample_batch([recording], int(sample_rate), resample).pcm
+        else:
+            pcm = torch.from_numpy(np.ascontiguousarray(recording, dtype=np.float64)).to("cuda:%d" % parser.device)
+        hop_seconds = step / float(parser.sampling_rate)
+        segs = parser._frontend().segment(pcm, energy_threshold=energy_threshold, step=step,
+                                          pause_hops=int(np.ceil(pause_threshold / hop_seconds)),
+                                          phrase_hops=int(np.ceil(phrase_threshold / hop_seconds)))
+        return pcm, segs
+
     def transcribe_long(self, recording, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
                         max_batch=32, show_all=False, sample_rate=None, resample="polyphase"):
         """Long-form transcription: the energy gate of the reference's
@@ -929,14 +944,7 @@ class DanSpeechRecognizer(object):
         rate (16 kHz), not the recording's."""
         import torch
         parser = self.audio_parser
-        if sample_rate is not None and int(sample_rate) != int(parser.sampling_rate):
-            pcm = parser.resample_batch([recording], int(sample_rate), resample).pcm
-        else:
-            pcm = torch.from_numpy(np.ascontiguousarray(recording, dtype=np.float64)).to("cuda:%d" % parser.device)
-        hop_seconds = step / float(parser.sampling_rate)
-        segs = parser._frontend().segment(pcm, energy_threshold=energy_threshold, step=step,
-                                          pause_hops=int(np.ceil(pause_threshold / hop_seconds)),
-                                          phrase_hops=int(np.ceil(phrase_threshold / hop_seconds)))
+        pcm, segs = self._cut_long(recording, energy_threshold, step, pause_threshold, phrase_threshold, sample_rate, resample)
         res = [None] * len(segs)
         order = sorted(range(len(segs)), key=lambda i: -(int(segs[i][1]) - int(segs[i][0])))
         for k in range(0, len(order), max_batch):
@@ -949,6 +957,72 @@ class DanSpeechRecognizer(object):
             for pos, i in enumerate(idxs):
                 res[i] = (int(segs[i][0]), int(segs[i][1]), decoded_output[pos] if show_all else decoded_output[pos][0])
         return res
+
+    def align_long(self, recording, sentences, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
+                   max_batch=32, sample_rate=None, resample="polyphase", window=30):
+        """Sentence and word timings of a whole recording with its transcript (a sitting, a lecture, a film with subtitles):
+        which phrase holds which sentence is what the alignment finds.  The recording is cut into phrases and forwarded exactly
+        as ``transcribe_long`` does it (the same gate, batching and optional rate conversion); the phrases' valid probability
+        rows are concatenated on the device in time order and ``" ".join`` of the normalised sentences is aligned to them with
+        both ends free (``Decoder.align_long_ids``: audio before the first and after the last sentence costs nothing).
+        Returns per sentence ``(start_s, end_s, confidence, words)``, or ``None`` for the whole call when the transcript cannot
+        fit the frames.  ``words`` are ``[(word, start_s, end_s, confidence), ...]`` as ``align`` gives them.  ``confidence``
+        is the least mean of the characters' mean probabilities over any ``window`` consecutive characters of the sentence (the
+        whole sentence when it is shorter): the worst stretch gives away a sentence that is not in the audio.  Times are
+        seconds at the model's rate, counted on the recording (the pauses between phrases included): a frame of phrase i lies
+        at the phrase's start plus its index times ``frame_seconds()``; an exclusive end is its last frame's time plus one frame.
+        Every sentence is checked before any GPU work: ``ValueError`` for a character that is not a label and for a sentence
+        that is empty after normalising."""
+        import torch
+        if self.model is None:
+            raise ModelNotInitialized("Trying to align without a DanSpeech model.")
+        texts = [self.decoder.normalise_transcript(t) for t in sentences]
+        for i, t in enumerate(texts):
+            self.decoder.transcript_ids(t)
+            if not t:
+                raise ValueError("sentence %d is empty after normalisation: %r" % (i, sentences[i]))
+        if int(window) < 1:
+            raise ValueError("window must be at least 1")
+        if not texts:
+            return []
+        whole = " ".join(texts)
+        ids = self.decoder.transcript_ids(whole)
+        parser = self.audio_parser
+        pcm, segs = self._cut_long(recording, energy_threshold, step, pause_threshold, phrase_threshold, sample_rate, resample)
+        if len(segs) == 0:
+            return None
+        rows = [None] * len(segs)
+        order = sorted(range(len(segs)), key=lambda i: -(int(segs[i][1]) - int(segs[i][0])))
+        for k in range(0, len(order), max_batch):
+            idxs = order[k:k + max_batch]
+            n = np.array([int(segs[i][1] - segs[i][0]) for i in idxs], dtype=np.int64)
+            cat = torch.cat([pcm[int(segs[i][0]):int(segs[i][1])] for i in idxs])
+            feats, frames = parser._frontend().features(cat, n)
+            out, output_sizes = self.model(feats, torch.from_numpy(frames.astype(np.int32)))
+            sizes = np.asarray(torch.as_tensor(output_sizes).cpu()).astype(np.int64)
+            for pos, i in enumerate(idxs):
+                rows[i] = out[pos, :int(sizes[pos])]
+        counts = np.array([r.shape[0] for r in rows], dtype=np.int64)
+        aligned = self.decoder.align_long_ids(torch.cat(rows).float().contiguous(), ids, True, True)
+        if aligned is None:
+            return None
+        spans, token_probs, _ = aligned
+        # the time of every concatenated frame: its phrase's start on the recording plus its index in the phrase
+        frame_s, rate = self.frame_seconds(), float(parser.sampling_rate)
+        first = np.concatenate(([0], np.cumsum(counts)[:-1]))
+        starts = np.array([int(sg[0]) for sg in segs], dtype=np.float64) / rate
+        frame_t = np.repeat(starts, counts) + (np.arange(int(counts.sum())) - np.repeat(first, counts)) * frame_s
+        begin = lambda f: float(frame_t[int(f)])
+        end = lambda f: float(frame_t[int(f) - 1] + frame_s)
+        results, at, w = [], 0, int(window)
+        for t in texts:
+            sp, tp = spans[at:at + len(t)], token_probs[at:at + len(t)]
+            at += len(t) + 1
+            sums = np.concatenate(([0.0], np.cumsum(tp.astype(np.float64))))
+            conf = float(sums[-1] / len(t)) if len(t) <= w else float(np.min(sums[w:] - sums[:-w]) / w)
+            words = [(wd, begin(a), end(b), c) for wd, a, b, c in _words(t, sp, tp, 1)]
+            results.append((begin(sp[0][0]), end(sp[-1][1]), conf, words))
+        return results
 
     def transcribe_files(self, paths, show_all=False, resample=None):
         """``transcribe_batch([load_audio(p) for p in paths])`` without decoding the files on the host:

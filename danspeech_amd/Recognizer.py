@@ -412,6 +412,15 @@ class Recognizer(object):
                                                          max_batch=max_batch, show_all=show_all, sample_rate=sample_rate,
                                                          resample=resample)
 
+    def align_long(self, audio_data, sentences, energy_threshold=600, step=1024, pause_threshold=0.55, phrase_threshold=0.2,
+                   max_batch=32, sample_rate=None, resample="polyphase", window=30):
+        """Sentence and word timings of a long recording with its transcript, cut into phrases as ``recognize_long`` cuts it:
+        per sentence ``(start_s, end_s, confidence, [(word, start_s, end_s, confidence), ...])``, or ``None`` when the transcript
+        cannot fit the recording (``DanSpeechRecognizer.align_long``)."""
+        return self.danspeech_recognizer.align_long(audio_data, sentences, energy_threshold=energy_threshold, step=step,
+                                                    pause_threshold=pause_threshold, phrase_threshold=phrase_threshold,
+                                                    max_batch=max_batch, sample_rate=sample_rate, resample=resample, window=window)
+
     def recognize_files(self, paths, show_all=False, resample=None):
         """``[recognize(load_audio(p)) for p in paths]`` in batched passes, WAV decoding on the GPU.  ``resample``: None takes
         every file as 16 kHz audio (``load_audio``'s contract); "polyphase" or "ratecv" reads each file's frame rate and

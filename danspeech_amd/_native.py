@@ -29,6 +29,8 @@ ENDPOINT_MAX = 256              # sessions of one dsmi_endpointer_push_many call
 STREAM_MANY_MAX = 256           # sessions of one dsmi_stream_forward_many call
 BEAM_STREAM_MANY_MAX = 4096     # streams of one dsmi_beam_stream_advance_many launch
 ALIGN_MAX_TOKENS = 4096         # the longest transcript dsmi_align takes (L_stride)
+ALIGN_LONG_MAX_TOKENS = 1 << 20 # the longest transcript dsmi_align_long takes
+ALIGN_LONG_MAX_FRAMES = 1 << 22 # the most frames dsmi_align_long takes
 SPOT_MAX_TOKENS = 128           # the longest phrase dsmi_spot takes (L_stride)
 SPOT_MAX_PHRASES = 4096         # phrases of one dsmi_spot call
 SPOT_MAX_HITS = 64              # hits per (clip, phrase) of one dsmi_spot call
@@ -180,6 +182,8 @@ _PROTOS = {
     "dsmi_beam_stream_advance_many": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "dsmi_beam_stream_collect_many": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_align": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_align_long": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_align_long_plan": (C.c_int, [C.c_int, C.c_int, _i64p]),
     "dsmi_spot_plan": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "dsmi_spot": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_spot_watch_create": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(_vp)]),
@@ -1085,6 +1089,25 @@ class NativeDecoder(_Handle):
                                      _stream(self.device)))
         return spans, tp, lp, st
 
+    def align_long(self, probs, targets, lead_free=True, tail_free=True):
+        """Long-form CTC forced alignment (``dsmi_align_long``) of one recording.  probs: CUDA [T,C], the softmax rows of the
+        recording's phrases in time order; targets: the whole transcript as label ids; ``lead_free`` / ``tail_free``: the
+        frames before the first and after the last token cost nothing.  Returns (spans int32 [L,2], token_probs float32 [L],
+        path_logp float, status int: 1 = infeasible)."""
+        if probs.dim() != 2:
+            raise ValueError("align_long: probs must be [T, C]")
+        T = probs.shape[0]
+        tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        L = len(tg)
+        spans = np.zeros((L, 2), dtype=np.int32)
+        tp = np.zeros(L, dtype=np.float32)
+        lp = np.zeros(1, dtype=np.float32)
+        st = np.zeros(1, dtype=np.int32)
+        self._check(lib().dsmi_align_long(self._h, probs.data_ptr(), T, _np_ptr(tg) if L else None, L, int(lead_free), int(tail_free),
+                                          _np_ptr(spans) if L else None, _np_ptr(tp) if L else None, _np_ptr(lp), _np_ptr(st),
+                                          _stream(self.device)))
+        return spans, tp, float(lp[0]), int(st[0])
+
     def spot(self, probs, sizes, phrases, max_hits, min_mean_logp, tracks=False):
         """CTC phrase search (``dsmi_spot``): every phrase in every clip.  probs: CUDA [B,T,C]; sizes: [B] frames or None (= T);
         phrases: a list of K label-id sequences.  Returns numpy arrays (hits int32 [B,K,max_hits,2] frames [start, end), scores
@@ -1239,6 +1262,16 @@ def spot_plan(phrase_lens):
     if rc < 0:
         raise DsmiError(rc, "dsmi_spot_plan: 1 .. %d phrases of 1 .. %d tokens" % (SPOT_MAX_PHRASES, SPOT_MAX_TOKENS))
     return rc, group_of, first_state
+
+
+def align_long_plan(T, L):
+    """dsmi_align_long_plan (host only): the geometry dsmi_align_long uses for T frames and L tokens, as a dict."""
+    info = np.zeros(6, dtype=np.int64)
+    rc = lib().dsmi_align_long_plan(int(T), int(L), info.ctypes.data_as(_i64p))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_align_long_plan: 1 .. %d frames, 0 .. %d tokens, checkpoint rows of at most 4 GiB"
+                        % (ALIGN_LONG_MAX_FRAMES, ALIGN_LONG_MAX_TOKENS))
+    return dict(zip(("W", "F", "state_tiles", "frame_tiles", "rows", "bytes"), (int(v) for v in info)))
 
 
 def score_plan(cand_clip, cand_frames, target_lens):

@@ -1,5 +1,5 @@
-// The five tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
-// (dsmi_align; the kernel: align.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip),
+// The six tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
+// (dsmi_align; the kernel: align.hip), of one long recording (dsmi_align_long; align_long.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip),
 // token confidence (dsmi_alternatives; alt.hip) and occupancy (dsmi_occupancy; occ.hip) -- and, on the same handle and by the
 // same conventions, the batched edit distance of token sequences (dsmi_edit_distance; edit.hip) and the language-model score of
 // known sentences (dsmi_lm_score; lmscore.hip), which need no probabilities.
@@ -8,6 +8,7 @@
 // transcript cannot fit its frames (one frame per token, one more between two equal tokens) is skipped and marked.
 #include "decoder.h"
 #include "align.h"
+#include "align_long.h"
 #include "spot.h"
 #include "score.h"
 #include "alt.h"
@@ -71,6 +72,64 @@ extern "C" int dsmi_align(dsmi_decoder* d, const float* probs, const int32_t* si
         status[b] = tl[b] < 0 ? 1 : 0;
         if (tl[b] < 0) path_logp[b] = -INFINITY;
     }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_align_long_plan(int T, int L, int64_t* info) {
+    if (!info) return DSMI_ERR_INVALID;
+    return align_long_plan(T, L, info);
+}
+
+extern "C" int dsmi_align_long(dsmi_decoder* d, const float* probs, int T, const int32_t* targets, int L, int lead_free, int tail_free,
+                               int32_t* spans, float* token_probs, float* path_logp, int32_t* status, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !path_logp || !status || (L > 0 && (!targets || !spans || !token_probs))) {
+        d->err = "bad align_long arguments"; return DSMI_ERR_INVALID;
+    }
+    AlongPlan plan;
+    bool feasible = false;
+    if (int rc = align_long_check(T, L, lead_free, tail_free, targets, C, d->blank, &plan, &feasible, d->err)) return rc;
+    if (!feasible) {
+        for (int k = 0; k < L; ++k) { spans[2 * k] = spans[2 * k + 1] = 0; token_probs[k] = 0.f; }
+        path_logp[0] = -INFINITY;
+        status[0] = 1;
+        return DSMI_OK;
+    }
+#ifdef DSMI_EXPERIMENTS
+    // DSMI_DEBUG_ALONG_FORM=w1792f128 | w896f64 | w128f64: the geometries that were measured and not adopted; the plan
+    // entry does not follow
+    if (const char* form = exp_env("DSMI_DEBUG_ALONG_FORM")) {
+        if (std::string(form) == "w1792f128") plan = align_long_geometry(T, L, 1792, 128);
+        if (std::string(form) == "w896f64") plan = align_long_geometry(T, L, 896, 64);
+        if (std::string(form) == "w128f64") plan = align_long_geometry(T, L, 128, 64);
+    }
+#endif
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces: io = targets [L], spans [L][2], token probs [L], logp [1]; the checkpoint rows [plan.rows][S] floats
+    const size_t Ls = (size_t)L;
+    if (int rc = reserve_all(d, d->along_io, sizeof(int32_t) * (4 * Ls + 1), &d->along_rows, (size_t)plan.bytes)) return rc;
+    int32_t* w_tg = d->along_io.as<int32_t>(); int32_t* w_sp = w_tg + Ls;
+    float* w_tp = reinterpret_cast<float*>(w_sp + 2 * Ls); float* w_lp = w_tp + Ls;
+    if (L) DEC_HIP(d, hipMemcpyAsync(w_tg, targets, sizeof(int32_t) * Ls, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_sp, 0, sizeof(int32_t) * (3 * Ls + 1), s));
+    AlongArgs a{};
+    a.probs = probs; a.T = T; a.C = C; a.blank = d->blank; a.L = L; a.S = 2 * L + 1;
+    a.lead_free = lead_free; a.tail_free = tail_free; a.targets = w_tg; a.rows = d->along_rows.as<float>();
+    a.W = (int)plan.W; a.F = (int)plan.F; a.frame_tiles = (int)plan.frame_tiles; a.state_tiles = (int)plan.state_tiles;
+    a.spans = w_sp; a.token_probs = w_tp; a.path_logp = w_lp;
+    DEC_HIP(d, launch_align_long(a, s));
+    // the results come back into an image of the call's own and reach the caller's arrays only when everything has succeeded
+    std::vector<int32_t> out(3 * Ls + 1);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_sp, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    if (L) {
+        std::memcpy(spans, out.data(), sizeof(int32_t) * 2 * Ls);
+        std::memcpy(token_probs, out.data() + 2 * Ls, sizeof(float) * Ls);
+    }
+    std::memcpy(path_logp, out.data() + 3 * Ls, sizeof(float));
+    status[0] = 0;
     return DSMI_OK;
 }
 

@@ -1,5 +1,5 @@
 // The handle behind dsmi_decoder*, shared by decoder.hip (its life, greedy, beam search, the LM) and ctc_tools.hip (forced
-// alignment, phrase search, transcript scoring, token confidence, occupancy, edit distance, LM sentence scoring).
+// alignment of clips and of one long recording, phrase search, transcript scoring, token confidence, occupancy, edit distance, LM sentence scoring).
 #pragma once
 #include "common.h"
 #include "lm.h"
@@ -59,6 +59,8 @@ struct dsmi_decoder {
     unsigned char *bs_dev = nullptr, *bs_pin = nullptr; size_t bs_dev_cap = 0, bs_pin_cap = 0;
     // ctc_tools.hip -- dsmi_align: inputs and outputs of the launch (int32 words), backpointers [B][T_out][S_stride] bytes
     DevBuf al_io, al_bp;
+    // dsmi_align_long: targets and outputs of the call (int32 words), the checkpoint rows [frame tiles + 1][S] floats
+    DevBuf along_io, along_rows;
     // dsmi_spot: inputs and hits of the launch (int32 words), the E and ST tracks 2 x [B][K][T_out] words
     DevBuf sp_io, sp_tr;
     // dsmi_score: inputs of the launch (int32 words) and, behind them on 8 bytes, the results [N] doubles

@@ -124,6 +124,22 @@ class Decoder(object):
             out.append(None if status[b] else (spans[b, :L].copy(), tp[b, :L].copy(), float(lp[b])))
         return out
 
+    # ---- long-form CTC forced alignment (dsmi_align_long): one recording, its whole transcript, no limit from LDS
+    def align_long(self, probs, transcript, lead_free=True, tail_free=True):
+        """Forced alignment of ``transcript`` (normalised with ``normalise_transcript``) to the probabilities ``probs`` [T,C] of
+        one long recording: the softmax rows of its phrases, concatenated in time order.  ``lead_free`` / ``tail_free``: the
+        frames before the first and after the last character cost nothing.  ``None`` when the transcript cannot fit the
+        frames, else ``(spans int32 [L,2], token_probs float32 [L], path_logp)`` as ``align`` gives them for one clip."""
+        ids = self.transcript_ids(self.normalise_transcript(transcript))                     # every check before any GPU work
+        return self.align_long_ids(probs, ids, lead_free, tail_free)
+
+    def align_long_ids(self, probs, ids, lead_free=True, tail_free=True):
+        """``align_long`` for a label-id sequence as it is (no normalisation)."""
+        probs = self._on_gpu(probs)
+        dec = self._dec(probs.device.index or 0)
+        spans, tp, lp, status = dec.align_long(probs, ids, lead_free, tail_free)
+        return None if status else (spans, tp, lp)
+
     # ---- CTC phrase search (dsmi_spot): where are given phrases spoken; the same on every decoder, no language model
     def spot(self, probs, phrases, sizes=None, max_hits=5, min_mean_logp=-np.inf):
         """Occurrences of ``phrases[k]`` (normalised with ``normalise_transcript``) in the probabilities of every clip

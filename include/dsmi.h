@@ -556,6 +556,47 @@ int dsmi_align(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_hos
                int32_t* spans_host, float* token_probs_host, float* path_logp_host, int32_t* status_host,
                void* stream);
 
+/* ---- Long-form CTC forced alignment (no reference counterpart): dsmi_align for ONE recording that is too long for it -- a
+ * sitting, a lecture, a film with its subtitles -- whose probabilities are the softmax rows of all its phrases, concatenated in
+ * time order, and whose transcript is the whole text.  Where each sentence lies is what the alignment finds ("CTC
+ * segmentation").  The decoder's language model plays no part.
+ * probs_dev [T][n_labels] float32; targets_host [L] label ids, never the blank (L = 0 is legal: the path is all blanks).
+ * The recurrence (the contract) is dsmi_align's, word for word: S = 2L + 1 states, blank, t_1, blank, ..., blank; lp(t, c) =
+ * logf(fmaxf(p, FLT_MIN)), accumulated in float32 over frames in order;
+ *     alpha_t(s) = max(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2) [only if s is a token state and
+ *                  label(s) != label(s-2)]) + lp(t, label(s)),   alpha_0 = {lp(0, blank), lp(0, t_1), -inf, ...};
+ * a state's predecessor on equal alpha is s, then s-1, then s-2; the path ends in the trailing blank S-1 unless alpha(S-2)
+ * (the last token) is strictly larger.
+ * One addition: a FREE blank state costs 0 at every frame it holds, frame 0 included (its lp(t, blank) is replaced by 0.0f in
+ * alpha_0 and in the recurrence).  State 0 is free when lead_free is 1, state S-1 when tail_free is 1; with L = 0 the single
+ * state is free when either is.  So audio before the transcript starts, or after it ends, costs nothing.  The tie rules are
+ * unchanged.
+ * Outputs, as dsmi_align's for one clip: spans_host [L][2] = frames [start, end) the path spends in token k's state;
+ * token_probs_host [L] = the float32 mean of p(t, label_k) over them (summed in frame order); path_logp_host [1]; status_host
+ * [1] = 0 aligned, 1 infeasible (L + #{k : t_k == t_{k+1}} > T: path_logp = -inf, the rows are 0).  With both flags 0 and L <=
+ * DSMI_ALIGN_MAX_TOKENS every output is bit-identical to dsmi_align's of the same clip: each alpha is formed from the same
+ * operands by the same additions, however the trellis is tiled.
+ * How it runs: the trellis is cut into frame tiles of F frames and state tiles of W states (dsmi_align_long_plan).  Per frame
+ * tile one launch, one workgroup per state tile, which reloads alpha of the tile's first frame on its states and the 2F to their
+ * left, runs the F frames in LDS and stores its own states' last row: one float32 row of S per frame tile stays on the handle
+ * ("checkpoint rows": frame tiles + 1 of them), and no backpointers.  One more launch walks the path back tile by tile,
+ * recomputing at most 2F + 1 states of each; a last one forms the token means.  No launch signals between its workgroups.
+ * Refused with nothing written: DSMI_ERR_INVALID for T <= 0, L < 0, a flag outside 0 / 1, a target that is the blank or not a
+ * label, a NULL d, probs_dev, path_logp_host or status_host, or with L > 0 a NULL targets_host, spans_host or
+ * token_probs_host; DSMI_ERR_CAPACITY, the limit named in the message, for L > DSMI_ALIGN_LONG_MAX_TOKENS, T >
+ * DSMI_ALIGN_LONG_MAX_FRAMES or checkpoint rows above DSMI_ALIGN_LONG_MAX_WORKSPACE bytes.  What the numbers alone refuse is
+ * refused before any array is read.  The workspace lives on the handle and grows on demand.  Synchronises `stream`.
+ * dsmi_align_long_plan (host only, no handle): the geometry the call will use, info = {states per state tile W, frames per frame
+ * tile F, state tiles = ceil(S / W), frame tiles = ceil((T - 1) / F), checkpoint rows, their bytes = rows * S * 4}.  Returns
+ * DSMI_OK, or the code with which dsmi_align_long would refuse T and L on the numbers; DSMI_ERR_INVALID for a NULL info. */
+#define DSMI_ALIGN_LONG_MAX_TOKENS (1 << 20)
+#define DSMI_ALIGN_LONG_MAX_FRAMES (1 << 22)
+#define DSMI_ALIGN_LONG_MAX_WORKSPACE (4ull << 30)
+int dsmi_align_long(dsmi_decoder* d, const float* probs_dev, int T, const int32_t* targets_host, int L,
+                    int lead_free, int tail_free, int32_t* spans_host, float* token_probs_host, float* path_logp_host,
+                    int32_t* status_host, void* stream);
+int dsmi_align_long_plan(int T, int L, int64_t* info);
+
 /* ---- CTC phrase search (no reference counterpart): where in each clip is each of K phrases spoken?  The same trellis as
  * dsmi_align with a free start and a free end, over the probabilities dsmi_forward wrote; every phrase is searched in every
  * clip.  The decoder's language model plays no part.

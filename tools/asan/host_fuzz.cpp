@@ -18,6 +18,10 @@
 //   host_fuzz occcheck SEED N   the argument check of dsmi_occupancy (ctc_host.h: occ_check) and where each candidate's stored trellis lies, on N random
 //                             calls held in exactly sized heap arrays, each good or with one fault, against the rules written out
 //                             below; the stored trellis against its cap; what is refused on the numbers alone is called with null arrays
+//   host_fuzz alignlong SEED N  the host half of dsmi_align_long (align_long_host.h: align_long_check, align_long_plan) on N random calls whose
+//                             transcript is an exactly sized heap array, each good or with one fault, against the rules written out
+//                             below; the checkpoint rows on either side of their cap; what is refused on the numbers alone is called
+//                             with a null array
 //   host_fuzz editcheck SEED N  the host half of dsmi_edit_distance (edit_host.h: edit_check, edit_plan, edit_pack, edit_unpack) on N random
 //                             calls held in exactly sized heap arrays, against the rules written out below; what is refused on the
 //                             numbers alone is called with null arrays
@@ -46,6 +50,7 @@
 #include "rnn_plan.h"
 #include "gate_plan.h"
 #include "ctc_host.h"
+#include "align_long_host.h"
 #include "edit_host.h"
 #include "lm_score_host.h"
 #include "spot_pick.h"
@@ -756,6 +761,80 @@ static int run_occcheck(int argc, char** argv) {
     return good > 0 && refused > 0 ? 0 : 11;
 }
 
+// ---- alignlong: dsmi_align_long's check and plan (align_long_host.h), the transcript a heap block of exactly L words
+#define ALONG_FAIL(what) do { std::fprintf(stderr, "alignlong: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
+
+static int run_alignlong(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long good = 0, refused = 0, infeasible = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        const int C = 2 + (int)(rng() % 127), blank = (int)(rng() % (unsigned)C);
+        const int T = 1 + (int)(rng() % 3000), L = rng() % 4 == 0 ? 0 : (int)(rng() % 2500);
+        const int lead = (int)(rng() % 2), tail = (int)(rng() % 2);
+        std::string err;
+        AlongPlan plan{-7, -7, -7, -7, -7, -7};
+        bool feasible = false;
+        std::vector<int32_t> tg = exact((size_t)L);
+        random_row(rng, tg.data(), L, C, blank, false);
+        const int fault = rng() % 2 ? 0 : 1 + (int)(rng() % 2);
+        const char* text = nullptr;
+        int lead_in = lead, tail_in = tail;
+        if (fault == 1 && L > 0) { tg[rng() % (unsigned)L] = rng() % 3 == 0 ? blank : rng() % 2 ? C : -1; text = "is the blank or not a label"; }
+        if (fault == 2) { (rng() % 2 ? lead_in : tail_in) = rng() % 2 ? 2 : -1; text = "lead_free and tail_free are 0 or 1"; }
+        const int rc = align_long_check(T, L, lead_in, tail_in, ptr_or_null(tg), C, blank, &plan, &feasible, err);
+        if (text) {
+            if (rc != DSMI_ERR_INVALID) ALONG_FAIL("a bad call passed");
+            if (err.rfind("align_long: ", 0) != 0 || err.find(text) == std::string::npos) ALONG_FAIL("wrong message");
+            ++refused;
+        } else {
+            if (rc != DSMI_OK) ALONG_FAIL("a good call refused");
+            if (feasible != (min_frames(tg.data(), L, blank) <= T)) ALONG_FAIL("feasibility");
+            infeasible += !feasible;
+            // the geometry, written out: tiles that cover the states and the frames behind frame 0, one row more than frame tiles
+            const int64_t S = 2 * (int64_t)L + 1;
+            if (plan.W < 1 || plan.F < 1) ALONG_FAIL("tile sizes");
+            if (plan.state_tiles * plan.W < S || (plan.state_tiles - 1) * plan.W >= S) ALONG_FAIL("state tiles");
+            if (plan.frame_tiles * plan.F < T - 1 || (plan.frame_tiles > 0 && (plan.frame_tiles - 1) * plan.F >= T - 1)) ALONG_FAIL("frame tiles");
+            if (plan.rows != plan.frame_tiles + 1 || plan.bytes != plan.rows * S * 4) ALONG_FAIL("rows or bytes");
+            int64_t info[6] = {-7, -7, -7, -7, -7, -7};
+            if (align_long_plan(T, L, info) != DSMI_OK || info[0] != plan.W || info[1] != plan.F || info[2] != plan.state_tiles ||
+                info[3] != plan.frame_tiles || info[4] != plan.rows || info[5] != plan.bytes) ALONG_FAIL("the plan is not the check's");
+            ++good;
+        }
+        // ---- refused on the numbers alone: no array exists, nothing is written
+        {
+            const int32_t* none = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            AlongPlan q{-7, -7, -7, -7, -7, -7};
+            int64_t info[6] = {-7, -7, -7, -7, -7, -7};
+            bool f = true;
+            if (align_long_check(0, L, 0, 0, none, C, blank, &q, &f, err) != DSMI_ERR_INVALID) ALONG_FAIL("T = 0");
+            if (align_long_check(-big, big, 1, 1, none, C, blank, &q, &f, err) != DSMI_ERR_INVALID) ALONG_FAIL("T < 0");
+            if (align_long_check(T, -big, 0, 1, none, C, blank, &q, &f, err) != DSMI_ERR_INVALID) ALONG_FAIL("L < 0");
+            if (align_long_check(T, big, 2, 0, none, C, blank, &q, &f, err) != DSMI_ERR_INVALID) ALONG_FAIL("a flag of 2");
+            if (align_long_check(T, DSMI_ALIGN_LONG_MAX_TOKENS + big, 0, 0, none, C, blank, &q, &f, err) != DSMI_ERR_CAPACITY ||
+                err.find("DSMI_ALIGN_LONG_MAX_TOKENS") == std::string::npos) ALONG_FAIL("L over the limit");
+            if (align_long_check(DSMI_ALIGN_LONG_MAX_FRAMES + big, big, 0, 0, none, C, blank, &q, &f, err) != DSMI_ERR_CAPACITY ||
+                err.find("DSMI_ALIGN_LONG_MAX_FRAMES") == std::string::npos) ALONG_FAIL("T over the limit");
+            // the checkpoint rows on either side of 4 GiB: rows of 2L + 1 floats, one per frame tile and one more
+            const int Tl = DSMI_ALIGN_LONG_MAX_FRAMES - (int)(rng() % 100000);
+            const int64_t rows = align_long_geometry(Tl, 0).rows;
+            const int L_fit = (int)((((int64_t)1 << 30) / rows - 1) / 2);      // the most tokens with rows * (2L + 1) * 4 <= 2^32
+            if (align_long_check(Tl, L_fit + 1, 0, 0, none, C, blank, &q, &f, err) != DSMI_ERR_CAPACITY ||
+                err.find("DSMI_ALIGN_LONG_MAX_WORKSPACE") == std::string::npos) ALONG_FAIL("the workspace over its cap");
+            if (q.W != -7 || q.bytes != -7) ALONG_FAIL("a refusal wrote the plan");
+            if (align_long_plan(Tl, L_fit + 1, info) != DSMI_ERR_CAPACITY || info[0] != -7 || info[5] != -7) ALONG_FAIL("a refused plan wrote");
+            if (align_long_plan(Tl, L_fit, info) != DSMI_OK || info[5] > (int64_t)DSMI_ALIGN_LONG_MAX_WORKSPACE ||
+                info[5] + info[4] * 8 <= (int64_t)DSMI_ALIGN_LONG_MAX_WORKSPACE) ALONG_FAIL("the workspace under its cap");
+            if (align_long_plan(0, 0, info) != DSMI_ERR_INVALID || align_long_plan(1, -1, info) != DSMI_ERR_INVALID) ALONG_FAIL("the plan's refusals");
+            if (!f) ALONG_FAIL("a refusal wrote the feasibility");
+        }
+    }
+    std::printf("%d align_long calls ok, %ld good, %ld refused, %ld infeasible\n", reps, good, refused, infeasible);
+    return good > 0 && refused > 0 ? 0 : 11;
+}
+
 // ---- editcheck: the rules of include/dsmi.h written out plainly, beside edit_host.h -------------------------------------------
 #define EDIT_FAIL(what) do { std::fprintf(stderr, "editcheck: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
 
@@ -1236,10 +1315,11 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "occcheck")) return run_occcheck(argc, argv);
+    if (argc >= 2 && !std::strcmp(argv[1], "alignlong")) return run_alignlong(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
