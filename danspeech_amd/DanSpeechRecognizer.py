@@ -678,6 +678,41 @@ class DanSpeechRecognizer(object):
         """``align_batch`` of one recording."""
         return self.align_batch([recording], [transcript])[0]
 
+    # ---- the best sentence of a grammar (CTC grammar decoding) --------------------------------------------------------
+    def transcribe_grammar_batch(self, recordings, grammar):
+        """What was said in ``recordings[i]``, given that it is a sentence of ``grammar`` (a ``danspeech_amd.grammar.Grammar``,
+        its text, or a list with one of either per recording)?  Per recording ``None`` when no sentence of the grammar fits the
+        recording's frames, else ``(text, [(word, start_s, end_s, confidence), ...], path_logp, logp)``: the sentence of the
+        most probable path through the grammar (``dsmi_grammar``), its words timed as ``align_batch`` times them, the path's
+        natural-log probability with the grammar's weights, and the natural log of the probability that the model emits
+        exactly ``text``, summed over every alignment (``dsmi_score``: one more call for the batch).  The grammar is compiled
+        before any GPU work (``ValueError`` for its faults)."""
+        if self.model is None:
+            raise ModelNotInitialized("Trying to decode with a grammar without a DanSpeech model.")
+        per_clip = isinstance(grammar, (list, tuple))
+        if per_clip and len(grammar) != len(recordings):
+            raise ValueError("transcribe_grammar_batch: %d recordings and %d grammars" % (len(recordings), len(grammar)))
+        graphs = [self.decoder.grammar(g) for g in grammar] if per_clip else self.decoder.grammar(grammar)
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        decoded = self.decoder.decode_grammar(job.probs, [graphs[i] for i in job.order] if per_clip else graphs, job.sizes)
+        ids = [[] if d is None else [self.decoder.transcript_ids(d[0])] for d in decoded]
+        scored = self.decoder.score_ids(job.probs, ids, job.sizes)
+        frame_s = self.frame_seconds()
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            if decoded[pos] is not None:
+                text, chars, path_logp = decoded[pos]
+                words = _words(text, [(a, e) for _, a, e, _ in chars], [p for *_, p in chars], frame_s)
+                results[i] = (text, words, path_logp, scored[pos][0])
+        return results
+
+    def transcribe_grammar(self, recording, grammar):
+        """``transcribe_grammar_batch`` of one recording."""
+        return self.transcribe_grammar_batch([recording], grammar if not isinstance(grammar, (list, tuple)) else list(grammar))[0]
+
     # ---- where given phrases are spoken (CTC phrase search) -----------------------------------------------------------
     def find_phrases_batch(self, recordings, phrases, max_hits=5, min_confidence=0.0):
         """Where in ``recordings[i]`` is ``phrases[k]`` spoken?  ``result[i][k]`` is a list of ``(start_s, end_s, confidence,

@@ -58,6 +58,19 @@ class Recognizer(object):
         """``align`` for a list of clips in one batched pass over the GPU; results in the caller's order."""
         return self.danspeech_recognizer.align_batch(audio_list, transcripts)
 
+    def recognize_grammar(self, audio_list, grammar):
+        """What was said in each clip, given that it is a sentence of ``grammar`` (``danspeech_amd.grammar``: commands, digits,
+        a closed vocabulary, a transcript with alternatives): per clip ``(text, [(word, start_s, end_s, confidence), ...],
+        path_logp, logp)``, or ``None`` when no sentence of the grammar fits the audio; one batched pass over the GPU, results
+        in the caller's order (``DanSpeechRecognizer.transcribe_grammar_batch``)."""
+        return self.danspeech_recognizer.transcribe_grammar_batch(audio_list, grammar)
+
+    def align_flexible(self, audio_data, grammar_text):
+        """``align`` for a transcript that is almost right: ``grammar_text`` is the transcript with alternatives ``(2 | to |
+        toogtyve)`` and optional words ``[øh]`` (``danspeech_amd.grammar``).  ``(text, [(word, start_s, end_s, confidence),
+        ...], path_logp, logp)`` with the variant that was spoken and its word timings, or ``None`` when no variant fits."""
+        return self.danspeech_recognizer.transcribe_grammar(audio_data, grammar_text)
+
     def find_phrases(self, audio_data, phrases, max_hits=5, min_confidence=0.0):
         """Where in the clip each of ``phrases`` is spoken: per phrase a list of ``(start_s, end_s, confidence, logp)``, best
         first (``DanSpeechRecognizer.find_phrases_batch``)."""

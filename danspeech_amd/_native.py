@@ -38,6 +38,9 @@ SPOT_STREAM_MANY_MAX = 4096     # streams of one dsmi_spot_stream_advance_many l
 SCORE_MAX_TOKENS = 2048         # the longest candidate dsmi_score takes (L_stride)
 ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes (L_stride)
 OCC_MAX_TOKENS = 1024           # the longest candidate dsmi_occupancy takes (L_stride)
+GRAMMAR_MAX_NODES = 2048        # the most nodes of one graph dsmi_grammar takes
+GRAMMAR_MAX_ARCS = 8192         # the most arcs of one graph dsmi_grammar takes
+GRAMMAR_START, GRAMMAR_FINAL = 1, 2   # DSMI_GRAMMAR_START, DSMI_GRAMMAR_FINAL: a node's flags
 EDIT_MAX_TOKENS = 4096          # the longest sequence dsmi_edit_distance takes (L_stride)
 LM_SCORE_MAX_TOKENS = 4096      # the longest sequence dsmi_lm_score takes (L_stride)
 
@@ -81,6 +84,13 @@ class FrontendDesc(C.Structure):
     _fields_ = [
         ("sample_rate", C.c_int32), ("window_size", C.c_double), ("window_stride", C.c_double),
         ("window", C.c_int32), ("normalize", C.c_int32), ("pad_mode", C.c_int32),
+    ]
+
+
+class GrammarPool(C.Structure):
+    _fields_ = [
+        ("K", C.c_int32), ("node_off", C.c_void_p), ("labels", C.c_void_p), ("weights", C.c_void_p), ("flags", C.c_void_p),
+        ("arc_off", C.c_void_p), ("arc_pred", C.c_void_p), ("empty_ok", C.c_void_p),
     ]
 
 
@@ -200,6 +210,8 @@ _PROTOS = {
     "dsmi_score_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "dsmi_score": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "dsmi_grammar": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(GrammarPool), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_grammar_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i64p]),
     "dsmi_occupancy": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_edit_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_edit_distance": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
@@ -1179,6 +1191,29 @@ class NativeDecoder(_Handle):
                                          tok.data_ptr() if want_tok and tok.numel() else None, _np_ptr(st), _stream(self.device)))
         return lp, occ, tok, st
 
+    def grammar(self, probs, sizes, graphs, clip_graph=None):
+        """CTC grammar decoding (``dsmi_grammar``): the best CTC path of any sentence a token graph accepts.  probs: CUDA
+        [B,T,C]; sizes: [B] frames or None (= T); graphs: one graph or a list of K -- a ``grammar.Grammar`` or anything with its
+        arrays ``labels``, ``weights``, ``flags``, ``arc_off``, ``arc_pred`` and ``empty_ok``; clip_graph: [B] the graph of each
+        clip or None (= graph 0).  Returns numpy arrays (path_lens int32 [B], path_nodes int32 [B,T], path_spans int32 [B,T,2],
+        token_probs float32 [B,T], path_logp float32 [B], status int32 [B]: 1 = no accepted sentence fits)."""
+        B, T = probs.shape[0], probs.shape[1]
+        pool, keep = grammar_pool(graphs)
+        cg = None if clip_graph is None else np.ascontiguousarray(clip_graph, dtype=np.int32).reshape(-1)
+        if cg is not None and len(cg) != B:
+            raise ValueError("grammar: %d graph indices for a batch of %d" % (len(cg), B))
+        lens = np.zeros(B, dtype=np.int32)
+        nodes = np.zeros((B, T), dtype=np.int32)
+        spans = np.zeros((B, T, 2), dtype=np.int32)
+        tp = np.zeros((B, T), dtype=np.float32)
+        lp = np.zeros(B, dtype=np.float32)
+        st = np.zeros(B, dtype=np.int32)
+        self._check(lib().dsmi_grammar(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, C.byref(pool), None if cg is None else _np_ptr(cg),
+                                       _np_ptr(lens), _np_ptr(nodes), _np_ptr(spans), _np_ptr(tp), _np_ptr(lp), _np_ptr(st),
+                                       _stream(self.device)))
+        del keep
+        return lens, nodes, spans, tp, lp, st
+
     def edit_distance(self, seqs, pairs, seq_lens=None):
         """Batched edit distance (``dsmi_edit_distance``).  seqs: the pool, an int array [M, L_stride] with ``seq_lens`` [M],
         or a list of M id sequences (``seq_lens`` None); tokens are any int32.  pairs: int [N, 2], row n = (a, b) compares
@@ -1251,6 +1286,48 @@ def _padded_ids(rows, lens, count, min_width, mismatch):
     for i, t in enumerate(seqs):
         ids[i, :len(t)] = t
     return ids, lens
+
+
+def grammar_pool(graphs):
+    """The dsmi_grammar_pool of one graph or a list of graphs (objects with the arrays ``labels``, ``weights`` (or None),
+    ``flags``, ``arc_off``, ``arc_pred`` and the flag ``empty_ok``): (the ctypes structure, the arrays it points into -- keep them
+    alive for as long as the structure is used)."""
+    if hasattr(graphs, "arc_off"):
+        graphs = [graphs]
+    graphs = list(graphs)
+    i32 = lambda rows: np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.int32).reshape(-1) for r in rows]) if rows else [], dtype=np.int32)
+    node_off = np.zeros(len(graphs) + 1, dtype=np.int32)
+    node_off[1:] = np.cumsum([len(g.labels) for g in graphs])
+    labels, flags = i32([g.labels for g in graphs]), i32([g.flags for g in graphs])
+    arc_pred = i32([g.arc_pred for g in graphs])
+    arc_off, base = [np.zeros(1, dtype=np.int32)], 0
+    for g in graphs:
+        off = np.asarray(g.arc_off, dtype=np.int64).reshape(-1)
+        if len(off) != len(g.labels) + 1:
+            raise ValueError("grammar: arc_off must have one entry more than there are nodes")
+        arc_off.append((off[1:] + base).astype(np.int32))
+        base += int(off[-1])
+    arc_off = np.ascontiguousarray(np.concatenate(arc_off), dtype=np.int32)
+    weights = None
+    if any(getattr(g, "weights", None) is not None for g in graphs):
+        weights = np.ascontiguousarray(np.concatenate([np.zeros(len(g.labels), dtype=np.float32) if getattr(g, "weights", None) is None
+                                                       else np.asarray(g.weights, dtype=np.float32).reshape(-1) for g in graphs]), dtype=np.float32)
+    empty_ok = np.array([1 if g.empty_ok else 0 for g in graphs], dtype=np.int32)
+    keep = (node_off, labels, weights, flags, arc_off, arc_pred, empty_ok)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    pool = GrammarPool(len(graphs), ptr(node_off), ptr(labels), ptr(weights), ptr(flags), ptr(arc_off), ptr(arc_pred), ptr(empty_ok))
+    return pool, keep
+
+
+def grammar_plan(B, T_out, n_nodes, n_arcs):
+    """dsmi_grammar_plan (host only): the geometry of a dsmi_grammar call of B clips of T_out frames whose largest graph has
+    n_nodes nodes and n_arcs arcs, as a dict; DsmiError with the code dsmi_grammar would refuse these numbers with."""
+    info = np.zeros(3, dtype=np.int64)
+    rc = lib().dsmi_grammar_plan(int(B), int(T_out), int(n_nodes), int(n_arcs), info.ctypes.data_as(_i64p))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_grammar_plan: B and T_out positive, 0 .. %d nodes, 0 .. %d arcs, at most 2^31 bytes of backpointers"
+                        % (GRAMMAR_MAX_NODES, GRAMMAR_MAX_ARCS))
+    return dict(zip(("node_stride", "lds_bytes", "bp_bytes"), (int(v) for v in info)))
 
 
 def spot_plan(phrase_lens):

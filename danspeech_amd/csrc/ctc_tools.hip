@@ -1,6 +1,6 @@
 // The six tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
 // (dsmi_align; the kernel: align.hip), of one long recording (dsmi_align_long; align_long.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip),
-// token confidence (dsmi_alternatives; alt.hip) and occupancy (dsmi_occupancy; occ.hip) -- and, on the same handle and by the
+// token confidence (dsmi_alternatives; alt.hip), occupancy (dsmi_occupancy; occ.hip) and grammar decoding (dsmi_grammar; grammar.hip) -- and, on the same handle and by the
 // same conventions, the batched edit distance of token sequences (dsmi_edit_distance; edit.hip) and the language-model score of
 // known sentences (dsmi_lm_score; lmscore.hip), which need no probabilities.
 // Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
@@ -13,6 +13,7 @@
 #include "score.h"
 #include "alt.h"
 #include "occ.h"
+#include "grammar.h"
 #include "edit.h"
 #include "lmscore.h"
 
@@ -327,6 +328,93 @@ extern "C" int dsmi_occupancy(dsmi_decoder* d, const float* probs, const int32_t
         status[n] = tl[n] < 0 ? 1 : 0;
         logp[n] = tl[n] < 0 ? -INFINITY : out[n];
     }
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_grammar_plan(int B, int To, int n_nodes, int n_arcs, int64_t* info) {
+    if (!info) return DSMI_ERR_INVALID;
+    GrammarPlan plan;
+    std::string err;
+    if (int rc = grammar_plan(B, To, n_nodes, n_arcs, &plan, err)) return rc;
+    info[0] = plan.node_stride; info[1] = plan.lds_bytes; info[2] = plan.bp_bytes;
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_grammar(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const dsmi_grammar_pool* pool,
+                            const int32_t* clip_graph, int32_t* path_lens, int32_t* path_nodes, int32_t* path_spans, float* token_probs,
+                            float* path_logp, int32_t* status, void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !pool || !path_lens || !path_nodes || !path_spans || !token_probs || !path_logp || !status) {
+        d->err = "bad grammar arguments"; return DSMI_ERR_INVALID;
+    }
+    const int K = pool->K;
+    if (K > 0 && (!pool->node_off || !pool->labels || !pool->flags || !pool->arc_off || !pool->arc_pred || !pool->empty_ok)) {
+        d->err = "grammar: a NULL array in the pool"; return DSMI_ERR_INVALID;
+    }
+    std::vector<int32_t> sz, cg;
+    int n_nodes = 0, n_arcs = 0;
+    if (int rc = grammar_check(sizes, B, To, K, pool->node_off, pool->labels, pool->weights, pool->flags, pool->arc_off, pool->arc_pred,
+                               pool->empty_ok, clip_graph, C, d->blank, sz, cg, &n_nodes, &n_arcs, d->err)) return rc;
+    GrammarPlan plan;
+    if (int rc = grammar_plan(B, To, n_nodes, n_arcs, &plan, d->err)) return rc;
+    // ---- the upload, int32 words: sizes [B], graphs [B], node_off [K + 1], empty_ok [K], node words [nodes], weights [nodes],
+    // arc_off [nodes + 1], then the arcs as 16-bit words (the predecessor | kGrammarArcTok where the two labels differ)
+    const size_t total = (size_t)pool->node_off[K], n_arc_all = (size_t)pool->arc_off[total], BT = (size_t)B * To;
+    const size_t o_cg = B, o_no = o_cg + B, o_eo = o_no + K + 1, o_wd = o_eo + K, o_wt = o_wd + total, o_ao = o_wt + total, o_ar = o_ao + total + 1;
+    const size_t in_words = o_ar + (n_arc_all + 1) / 2, out_words = 4 * BT + 3 * (size_t)B;
+    std::vector<int32_t> up(in_words, 0);
+    std::memcpy(up.data(), sz.data(), sizeof(int32_t) * B);
+    std::memcpy(up.data() + o_cg, cg.data(), sizeof(int32_t) * B);
+    std::memcpy(up.data() + o_no, pool->node_off, sizeof(int32_t) * (K + 1));
+    std::memcpy(up.data() + o_eo, pool->empty_ok, sizeof(int32_t) * K);
+    std::memcpy(up.data() + o_ao, pool->arc_off, sizeof(int32_t) * (total + 1));
+    if (pool->weights && total) std::memcpy(up.data() + o_wt, pool->weights, sizeof(float) * total);
+    uint16_t* arc16 = reinterpret_cast<uint16_t*>(up.data() + o_ar);
+    for (int g = 0; g < K; ++g) {
+        const int n0 = pool->node_off[g];
+        for (int i = n0; i < pool->node_off[g + 1]; ++i) {
+            up[o_wd + i] = pool->labels[i] | ((pool->flags[i] & DSMI_GRAMMAR_START) ? kGrammarStart : 0) | ((pool->flags[i] & DSMI_GRAMMAR_FINAL) ? kGrammarFinal : 0);
+            for (int j = pool->arc_off[i]; j < pool->arc_off[i + 1]; ++j) {
+                const int p = pool->arc_pred[j];
+                arc16[j] = (uint16_t)(p | (pool->labels[n0 + p] != pool->labels[i] ? kGrammarArcTok : 0));
+            }
+        }
+    }
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces: io = the upload, then path_lens [B], path_nodes [B][T], path_spans [B][T][2], token_probs [B][T], logp [B],
+    // status [B]; the backpointers [B][T_out][node stride] of 16 bits
+    if (int rc = reserve_all(d, d->gr_io, sizeof(int32_t) * (in_words + out_words), &d->gr_bp, (size_t)plan.bp_bytes)) return rc;
+    int32_t* w = d->gr_io.as<int32_t>();
+    int32_t* w_out = w + in_words;
+    DEC_HIP(d, hipMemcpyAsync(w, up.data(), sizeof(int32_t) * in_words, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_out, 0, sizeof(int32_t) * out_words, s));
+    GrammarArgs a{};
+    a.probs = probs; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w; a.clip_graph = w + o_cg; a.node_off = w + o_no; a.empty_ok = w + o_eo; a.words = w + o_wd;
+    a.weights = reinterpret_cast<const float*>(w + o_wt); a.arc_off = w + o_ao; a.arc_words16 = reinterpret_cast<const uint16_t*>(w + o_ar);
+    a.node_stride = (int)plan.node_stride; a.arc_words = (int)grammar_arc_words(n_arcs);
+    a.bp = d->gr_bp.as<uint16_t>();
+    a.path_lens = w_out; a.path_nodes = a.path_lens + B; a.path_spans = a.path_nodes + BT;
+    a.token_probs = reinterpret_cast<float*>(a.path_spans + 2 * BT); a.path_logp = a.token_probs + BT;
+    a.status = reinterpret_cast<int32_t*>(a.path_logp + B);
+#ifdef DSMI_EXPERIMENTS
+    // DSMI_DEBUG_GRAMMAR_TRACE=serial: the backtrace by one lane with a load per frame, measured and not adopted;
+    // =none: no backtrace (timing only: what the forward pass costs alone)
+    if (const char* form = exp_env("DSMI_DEBUG_GRAMMAR_TRACE")) a.trace_form = std::string(form) == "serial" ? 1 : std::string(form) == "none" ? 2 : 0;
+#endif
+    DEC_HIP(d, launch_grammar(a, B, s));
+    // the results come back into an image of the call's own and reach the caller's arrays only when everything has succeeded
+    std::vector<int32_t> out(out_words);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_out, sizeof(int32_t) * out_words, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    std::memcpy(path_lens, out.data(), sizeof(int32_t) * B);
+    std::memcpy(path_nodes, out.data() + B, sizeof(int32_t) * BT);
+    std::memcpy(path_spans, out.data() + B + BT, sizeof(int32_t) * 2 * BT);
+    std::memcpy(token_probs, out.data() + B + 3 * BT, sizeof(float) * BT);
+    std::memcpy(path_logp, out.data() + B + 4 * BT, sizeof(float) * B);
+    std::memcpy(status, out.data() + 2 * B + 4 * BT, sizeof(int32_t) * B);
     return DSMI_OK;
 }
 

@@ -1,5 +1,5 @@
 // The handle behind dsmi_decoder*, shared by decoder.hip (its life, greedy, beam search, the LM) and ctc_tools.hip (forced
-// alignment of clips and of one long recording, phrase search, transcript scoring, token confidence, occupancy, edit distance, LM sentence scoring).
+// alignment of clips and of one long recording, phrase search, transcript scoring, token confidence, occupancy, grammar decoding, edit distance, LM sentence scoring).
 #pragma once
 #include "common.h"
 #include "lm.h"
@@ -70,6 +70,8 @@ struct dsmi_decoder {
     DevBuf alt_io, alt_out, alt_ws;
     // dsmi_occupancy: inputs of the launch and logp [N] as dsmi_score's, the two stored trellises (doubles: forward, backward)
     DevBuf occ_io, occ_ws;
+    // dsmi_grammar: the upload and the results of the launch (int32 words), the backpointers [B][T_out][node stride] of 16 bits
+    DevBuf gr_io, gr_bp;
     // dsmi_edit_distance: the upload of the launch (int32 words: lens, pool, pairs, waves) and, behind it, the packed results
     DevBuf ed_io;
     // dsmi_lm_score: the upload of the launch (int32 words: lm_score_pack) and, behind it on 8 bytes, the results

@@ -124,6 +124,40 @@ class Decoder(object):
             out.append(None if status[b] else (spans[b, :L].copy(), tp[b, :L].copy(), float(lp[b])))
         return out
 
+    # ---- CTC grammar decoding (dsmi_grammar): the best sentence of a word graph; a language model plays no part
+    def grammar(self, text):
+        """``text`` compiled for this decoder's labels (``danspeech_amd.grammar.Grammar``); a Grammar passes through."""
+        from ..grammar import Grammar
+        return text if isinstance(text, Grammar) else Grammar(text, self.labels, self.blank_index)
+
+    def decode_grammar(self, probs, grammar_or_list, sizes=None):
+        """The most probable CTC path of any sentence a grammar accepts (``probs`` [B,T,C], ``sizes`` frames per clip).
+        ``grammar_or_list``: one grammar (a ``Grammar`` or its text) for every clip, or a list with one per clip.  Per clip
+        ``None`` when no accepted sentence fits the clip's frames, else ``(text, chars, path_logp)``: the labels of the path,
+        ``chars = [(char, start_frame, end_frame, prob), ...]`` with the frames [start, end) of each character and the mean
+        probability of the character over them, and the path's natural-log probability, the grammar's weights included."""
+        import torch
+        probs = self._on_gpu(probs)
+        B = probs.shape[0]
+        if isinstance(grammar_or_list, (list, tuple)):
+            if len(grammar_or_list) != B:
+                raise ValueError("decode_grammar: %d grammars for a batch of %d" % (len(grammar_or_list), B))
+            graphs, clip_graph = [self.grammar(g) for g in grammar_or_list], np.arange(B, dtype=np.int32)
+        else:
+            graphs, clip_graph = [self.grammar(grammar_or_list)], None
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        lens, nodes, spans, tp, lp, status = dec.grammar(probs, sz, graphs, clip_graph)
+        out = []
+        for b in range(B):
+            if status[b]:
+                out.append(None)
+                continue
+            g, M = graphs[0 if clip_graph is None else b], int(lens[b])
+            text = g.text_of(nodes[b, :M])
+            out.append((text, [(text[k], int(spans[b, k, 0]), int(spans[b, k, 1]), float(tp[b, k])) for k in range(M)], float(lp[b])))
+        return out
+
     # ---- long-form CTC forced alignment (dsmi_align_long): one recording, its whole transcript, no limit from LDS
     def align_long(self, probs, transcript, lead_free=True, tail_free=True):
         """Forced alignment of ``transcript`` (normalised with ``normalise_transcript``) to the probabilities ``probs`` [T,C] of

@@ -827,6 +827,72 @@ int dsmi_occupancy(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes
                    const int32_t* cand_clip_host, const int32_t* targets_host, const int32_t* target_lens_host,
                    int N, int L_stride, double* logp_host, double* occ_dev, double* tok_dev, int32_t* status_host, void* stream);
 
+/* ---- CTC grammar decoding (no reference counterpart): the text is known only up to a grammar -- commands, digits, a closed
+ * vocabulary said any number of times, a transcript with alternatives and optional words.  The most probable frame-level CTC
+ * path of ANY sentence a token graph accepts, through the probabilities dsmi_forward wrote: dsmi_align's max-plus recurrence
+ * over a graph of token nodes where dsmi_align has a chain.  The decoder's language model plays no part.
+ * The graph (the contract).  N nodes; node n has a label lab[n], never the blank; a weight w[n], a finite float32 added once
+ * when the node is entered; a start flag and a final flag; an ordered list of predecessor nodes pred[n][0..), stored as CSR.
+ * Cycles and self-loops are legal (a self-loop is "the same token again", which CTC lets through only over a blank).  empty_ok:
+ * the empty sentence is accepted.  Each node carries two states, tok(n) and blk(n) (the blank after it); one more state, lead,
+ * is the blank before the first token.  With lp(t, c) = logf(fmaxf(p, FLT_MIN)), everything float32 and accumulated in frame
+ * order:
+ *     t = 0:  lead = lp(0, blank);  tok(n) = start[n] ? lp(0, lab[n]) + w[n] : -inf;  blk(n) = -inf
+ *     t >= 1: ent(n)  = max{ lead [if start[n]];  for j in order: blk(pred j), then tok(pred j) [only if lab[pred j] != lab[n]] }
+ *             tok'(n) = max(tok(n), ent(n) + w[n]) + lp(t, lab[n])
+ *             blk'(n) = max(blk(n), tok(n)) + lp(t, blank)
+ *             lead'   = lead + lp(t, blank)
+ *     end:    max{ lead [if empty_ok];  for final n ascending: blk(n), then tok(n) }
+ * Tie rule (part of the contract): a later candidate replaces an earlier one only when strictly greater, the candidates taken
+ * in the order written: stay before any entry; among entries lead, then the predecessors in list order, each blk before tok;
+ * entries are compared before w[n] is added; for blk', stay before tok.  With this order a chain graph (node k's only
+ * predecessor is k-1, node 0 start, node L-1 final, empty_ok = (L == 0), weights 0) gives dsmi_align's results bit for bit.
+ * Inputs: probs_dev [B][T_out][n_labels]; sizes_host [B] frames per clip (NULL = T_out for all).  pool: K graphs concatenated.
+ * Graph g owns the nodes node_off[g] .. node_off[g+1] of labels, weights (NULL = all 0) and flags (DSMI_GRAMMAR_START |
+ * DSMI_GRAMMAR_FINAL); node i of the pool has the predecessors arc_pred[arc_off[i] .. arc_off[i+1]), graph-local ids; node_off
+ * [K+1] and arc_off [node_off[K] + 1] ascend from 0; empty_ok [K] (non-zero = accepted).  clip_graph_host [B] = the graph of
+ * each clip (NULL = graph 0 for all): one grammar for many clips, or each clip its own transcript graph.  A graph without
+ * nodes is legal and accepts exactly the empty sentence, when empty_ok holds.
+ * Outputs per clip, host arrays, the three path arrays with row stride T_out (a path has at most one visit per frame):
+ * path_lens [B] = M, the node visits (a visit: a maximal run of consecutive frames in tok(n) linked by "stay"); path_nodes
+ * [B][T_out] graph-local node ids; path_spans [B][T_out][2] frames [start, end); token_probs [B][T_out] = the float32 mean
+ * of p(t, lab) over the span, summed in frame order; path_logp [B], weights included; status [B] = 0 decoded, 1 when no
+ * accepted sentence fits the clip's frames (path_logp = -inf, M = 0).  Rows past M are 0.  lp >= logf(FLT_MIN) is finite, so
+ * -inf at the end means unreachable and nothing else: the device decides the status.  A clip of 0 frames is decoded only
+ * when empty_ok holds (path_logp = 0).  A clip's results are the same bits whatever else is in the call.
+ * Refused before any launch with nothing written (DSMI_ERR_INVALID, each fault with its own message): B, T_out or K <= 0, a
+ * NULL argument (weights and clip_graph_host may be NULL), sizes[b] outside 0 .. T_out, clip_graph[b] outside 0 .. K-1,
+ * offsets that do not start at 0 or do not ascend, a label that is the blank or >= n_labels, a predecessor outside its graph,
+ * a weight that is NaN or infinite, a graph with nodes but no start node or no final node.  DSMI_ERR_CAPACITY, the limit
+ * named: a graph of more than DSMI_GRAMMAR_MAX_NODES nodes or DSMI_GRAMMAR_MAX_ARCS arcs (LDS: two double-buffered float32
+ * rows per node, the node words, weights and offsets, the arcs as 16-bit words, the probabilities' image: 84 KB of 160 KB at
+ * both limits), more than 2^24 nodes or arcs in the pool, more than 2^31 bytes of backpointers (2 * B * T_out * node stride,
+ * kept on the handle; 66 MB for 32 clips of 501 frames at the node limit).  What the numbers alone refuse (B, T_out, K) is
+ * refused before any array is read.  One kernel launch, one workgroup per clip.  Synchronises `stream`.
+ * dsmi_grammar_plan (host only, no handle): for a call of B clips of T_out frames whose largest graph has n_nodes nodes and
+ * n_arcs arcs, info = {node stride (n_nodes rounded up to a multiple of 4, at least 4), LDS bytes per workgroup, backpointer
+ * workspace bytes}.  Returns DSMI_OK, or the code with which dsmi_grammar would refuse these numbers; DSMI_ERR_INVALID for a
+ * NULL info. */
+#define DSMI_GRAMMAR_MAX_NODES 2048
+#define DSMI_GRAMMAR_MAX_ARCS 8192
+#define DSMI_GRAMMAR_START 1
+#define DSMI_GRAMMAR_FINAL 2
+typedef struct {
+    int32_t K;                   /* graphs */
+    const int32_t* node_off;     /* [K + 1] */
+    const int32_t* labels;       /* [node_off[K]] */
+    const float* weights;        /* [node_off[K]], or NULL = 0 */
+    const int32_t* flags;        /* [node_off[K]] DSMI_GRAMMAR_START | DSMI_GRAMMAR_FINAL */
+    const int32_t* arc_off;      /* [node_off[K] + 1] */
+    const int32_t* arc_pred;     /* [arc_off[node_off[K]]] graph-local node ids */
+    const int32_t* empty_ok;     /* [K] */
+} dsmi_grammar_pool;
+int dsmi_grammar(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+                 const dsmi_grammar_pool* pool, const int32_t* clip_graph_host, int32_t* path_lens_host,
+                 int32_t* path_nodes_host, int32_t* path_spans_host, float* token_probs_host, float* path_logp_host,
+                 int32_t* status_host, void* stream);
+int dsmi_grammar_plan(int B, int T_out, int n_nodes, int n_arcs, int64_t* info);
+
 /* ---- Batched edit distance (the reference calls Levenshtein.distance once per pair, on the host): how far is this text from
  * that one, for many pairs at once -- WER / CER with their error counts, and the pairwise distances of n-best lists.
  * A pool of M token sequences: seqs_host [M][L_stride] with seq_lens_host [M].  Tokens are any int32 and are compared for

@@ -18,6 +18,9 @@
 //   host_fuzz occcheck SEED N   the argument check of dsmi_occupancy (ctc_host.h: occ_check) and where each candidate's stored trellis lies, on N random
 //                             calls held in exactly sized heap arrays, each good or with one fault, against the rules written out
 //                             below; the stored trellis against its cap; what is refused on the numbers alone is called with null arrays
+//   host_fuzz grammarcheck SEED N  the host half of dsmi_grammar (grammar_host.h: grammar_check, grammar_plan) on N random calls whose pool of
+//                             graphs lies in exactly sized heap arrays, each good or with one fault, against the rules written out
+//                             below; one node or arc over each limit; what is refused on the numbers alone is called with null arrays
 //   host_fuzz alignlong SEED N  the host half of dsmi_align_long (align_long_host.h: align_long_check, align_long_plan) on N random calls whose
 //                             transcript is an exactly sized heap array, each good or with one fault, against the rules written out
 //                             below; the checkpoint rows on either side of their cap; what is refused on the numbers alone is called
@@ -51,6 +54,7 @@
 #include "gate_plan.h"
 #include "ctc_host.h"
 #include "align_long_host.h"
+#include "grammar_host.h"
 #include "edit_host.h"
 #include "lm_score_host.h"
 #include "spot_pick.h"
@@ -761,6 +765,139 @@ static int run_occcheck(int argc, char** argv) {
     return good > 0 && refused > 0 ? 0 : 11;
 }
 
+// ---- grammarcheck: dsmi_grammar's check and plan (grammar_host.h), every array of the pool a heap block of exactly the size the
+// offsets declare
+#define GR_FAIL(what) do { std::fprintf(stderr, "grammarcheck: %s (repetition %d, line %d): %s\n", what, rep, __LINE__, err.c_str()); return 11; } while (0)
+
+static int run_grammarcheck(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long good = 0, refused = 0, empty_graphs = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        const int C = 2 + (int)(rng() % 127), blank = (int)(rng() % (unsigned)C);
+        const int B = 1 + (int)(rng() % 6), To = 1 + (int)(rng() % 40), K = 1 + (int)(rng() % 4);
+        std::string err;
+        // ---- a whole pool: graph g of n[g] nodes, every node a label, flags, a weight and up to 4 predecessors
+        std::vector<int32_t> node_off = exact((size_t)K + 1);
+        for (int g = 0; g < K; ++g) node_off[(size_t)g + 1] = node_off[(size_t)g] + (int32_t)(rng() % 4 == 0 ? 0 : 1 + rng() % 9);
+        const int total = node_off[(size_t)K];
+        std::vector<int32_t> labels = exact((size_t)total), flags = exact((size_t)total), arc_off = exact((size_t)total + 1), empty_ok = exact((size_t)K);
+        std::vector<float> weights((size_t)total);
+        weights.shrink_to_fit();
+        std::vector<int32_t> preds;
+        for (int g = 0; g < K; ++g) {
+            const int n0 = node_off[(size_t)g], N = node_off[(size_t)g + 1] - n0;
+            empty_ok[(size_t)g] = (int32_t)(rng() % 2);
+            if (N == 0) ++empty_graphs;
+            for (int n = 0; n < N; ++n) {
+                int lab = (int)(rng() % (unsigned)C);
+                if (lab == blank) lab = (blank + 1) % C;
+                labels[(size_t)(n0 + n)] = lab;
+                flags[(size_t)(n0 + n)] = (int32_t)(rng() % 4);
+                weights[(size_t)(n0 + n)] = -(float)(rng() % 1000) / 250.f;
+                const int fan = (int)(rng() % 5);
+                for (int j = 0; j < fan; ++j) preds.push_back((int32_t)(rng() % (unsigned)N));      // self-loops and cycles are legal
+                arc_off[(size_t)(n0 + n) + 1] = (int32_t)preds.size();
+            }
+            if (N > 0) { flags[(size_t)n0 + rng() % (unsigned)N] |= DSMI_GRAMMAR_START; flags[(size_t)n0 + rng() % (unsigned)N] |= DSMI_GRAMMAR_FINAL; }
+        }
+        std::vector<int32_t> arc_pred(preds);
+        arc_pred.shrink_to_fit();
+        std::vector<int32_t> sizes = exact((size_t)B), clip_graph = exact((size_t)B);
+        for (auto& v : sizes) v = (int32_t)(rng() % (unsigned)(To + 1));
+        for (auto& v : clip_graph) v = (int32_t)(rng() % (unsigned)K);
+        const bool no_sizes = rng() % 5 == 0, no_weights = rng() % 4 == 0, no_clip_graph = rng() % 5 == 0;
+        // ---- with `fault` one thing is wrong with the call, and the rule that refuses it is written out here
+        int fault = rng() % 2 ? 0 : 1 + (int)(rng() % 10);
+        const char* text = "";
+        int g_big = -1;                  // a graph with nodes
+        for (int g = 0; g < K; ++g) if (node_off[(size_t)g + 1] > node_off[(size_t)g]) g_big = g;
+        const int n0 = g_big >= 0 ? node_off[(size_t)g_big] : 0, Nb = g_big >= 0 ? node_off[(size_t)g_big + 1] - n0 : 0;
+        if (fault >= 5 && g_big < 0) fault = 0;
+        if (fault == 1) { if (no_sizes) fault = 0; else { sizes[rng() % (unsigned)B] = rng() % 2 ? To + 1 : -1; text = "size outside 0 .. T_out"; } }
+        if (fault == 2) { if (no_clip_graph) fault = 0; else { clip_graph[rng() % (unsigned)B] = rng() % 2 ? K : -1; text = "graph outside 0 .. K-1"; } }
+        if (fault == 3) { node_off[0] = 1; text = "node_off[0] must be 0"; }
+        if (fault == 4) { arc_off[0] = -1; text = "arc_off[0] must be 0"; }
+        if (fault == 5) {                // the last graph with nodes ends before it starts: nothing behind the offsets is read
+            node_off[(size_t)g_big + 1] = node_off[(size_t)g_big] - 1;
+            if (node_off[(size_t)g_big + 1] < 0 || g_big + 1 != K) { node_off[(size_t)g_big + 1] = n0 + Nb; fault = 0; } else text = "node offsets not ascending";
+        }
+        if (fault == 6) { labels[(size_t)n0 + rng() % (unsigned)Nb] = rng() % 2 ? blank : C; text = "is the blank or not a label"; }
+        if (fault == 7) {
+            const int n = n0 + (int)(rng() % (unsigned)Nb);
+            if (arc_off[(size_t)n + 1] == arc_off[(size_t)n]) fault = 0;
+            else { arc_pred[(size_t)arc_off[(size_t)n]] = rng() % 2 ? Nb : -1; text = "outside the graph"; }
+        }
+        if (fault == 8) { if (no_weights) fault = 0; else { weights[(size_t)n0 + rng() % (unsigned)Nb] = rng() % 2 ? NAN : -INFINITY; text = "weight is not finite"; } }
+        if (fault == 9) { for (int n = 0; n < Nb; ++n) flags[(size_t)(n0 + n)] &= ~DSMI_GRAMMAR_START; text = "no start node"; }
+        if (fault == 10) { for (int n = 0; n < Nb; ++n) flags[(size_t)(n0 + n)] &= ~DSMI_GRAMMAR_FINAL; text = "no final node"; }
+        std::vector<int32_t> sz, cg;
+        int n_nodes = -7, n_arcs = -7;
+        const int rc = grammar_check(no_sizes ? nullptr : sizes.data(), B, To, K, node_off.data(), ptr_or_null(labels), no_weights || weights.empty() ? nullptr : weights.data(),
+                                     ptr_or_null(flags), arc_off.data(), ptr_or_null(arc_pred), empty_ok.data(), no_clip_graph ? nullptr : clip_graph.data(),
+                                     C, blank, sz, cg, &n_nodes, &n_arcs, err);
+        if (fault) {
+            if (rc != DSMI_ERR_INVALID) GR_FAIL("a bad call passed");
+            if (err.rfind("grammar: ", 0) != 0 || err.find(text) == std::string::npos) GR_FAIL("wrong message");
+            ++refused;
+        } else {
+            if (rc != DSMI_OK) GR_FAIL("a good call refused");
+            if ((int)sz.size() != B || (int)cg.size() != B) GR_FAIL("the lengths of what the check hands on");
+            int want_nodes = 0, want_arcs = 0;
+            for (int g = 0; g < K; ++g) {
+                want_nodes = std::max(want_nodes, node_off[(size_t)g + 1] - node_off[(size_t)g]);
+                want_arcs = std::max(want_arcs, arc_off[(size_t)node_off[(size_t)g + 1]] - arc_off[(size_t)node_off[(size_t)g]]);
+            }
+            if (n_nodes != want_nodes || n_arcs != want_arcs) GR_FAIL("the largest graph");
+            for (int b = 0; b < B; ++b)
+                if (sz[(size_t)b] != (no_sizes ? To : sizes[(size_t)b]) || cg[(size_t)b] != (no_clip_graph ? 0 : clip_graph[(size_t)b])) GR_FAIL("sizes or graphs");
+            GrammarPlan plan{};
+            if (grammar_plan(B, To, n_nodes, n_arcs, &plan, err) != DSMI_OK) GR_FAIL("the plan of a good call");
+            if (plan.node_stride < n_nodes || plan.node_stride % 4 || plan.node_stride < 4 || plan.node_stride > n_nodes + 4) GR_FAIL("the node stride");
+            if (plan.bp_bytes != 2 * (int64_t)B * To * plan.node_stride) GR_FAIL("the backpointer bytes");
+            if (plan.lds_bytes != 26 * plan.node_stride + 8 + 2 * ((n_arcs + 3) / 4 * 4) + 16384 || plan.lds_bytes > 160 * 1024) GR_FAIL("the LDS bytes");
+            ++good;
+        }
+        // ---- one node and one arc over the limits: a single graph, offsets alone (the check refuses before it reads a node)
+        {
+            std::vector<int32_t> off2 = exact(2);
+            off2[1] = DSMI_GRAMMAR_MAX_NODES + 1;
+            std::vector<int32_t> aoff = exact((size_t)DSMI_GRAMMAR_MAX_NODES + 2, 0), one = exact(1, 0);
+            const int32_t* none = nullptr;
+            if (grammar_check(none, B, To, 1, off2.data(), none, nullptr, none, aoff.data(), none, one.data(), none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_CAPACITY ||
+                err.find("DSMI_GRAMMAR_MAX_NODES") == std::string::npos) GR_FAIL("one node over the limit");
+            off2[1] = 2;
+            std::vector<int32_t> a3 = exact(3, 0);
+            a3[1] = 5; a3[2] = DSMI_GRAMMAR_MAX_ARCS + 1;
+            if (grammar_check(none, B, To, 1, off2.data(), none, nullptr, none, a3.data(), none, one.data(), none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_CAPACITY ||
+                err.find("DSMI_GRAMMAR_MAX_ARCS") == std::string::npos) GR_FAIL("one arc over the limit");
+            a3[2] = 4;
+            if (grammar_check(none, B, To, 1, off2.data(), none, nullptr, none, a3.data(), none, one.data(), none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_INVALID ||
+                err.find("arc offsets not ascending") == std::string::npos) GR_FAIL("arc offsets that descend");
+            GrammarPlan plan{};
+            if (grammar_plan(B, To, DSMI_GRAMMAR_MAX_NODES + 1, 0, &plan, err) != DSMI_ERR_CAPACITY) GR_FAIL("the plan, one node over");
+            if (grammar_plan(B, To, 1, DSMI_GRAMMAR_MAX_ARCS + 1, &plan, err) != DSMI_ERR_CAPACITY) GR_FAIL("the plan, one arc over");
+            if (grammar_plan(B, To, DSMI_GRAMMAR_MAX_NODES, DSMI_GRAMMAR_MAX_ARCS, &plan, err) != DSMI_OK || plan.lds_bytes > 160 * 1024) GR_FAIL("the plan at both limits");
+            if (grammar_plan(1 << 10, 1 << 10, DSMI_GRAMMAR_MAX_NODES, 0, &plan, err) != DSMI_ERR_CAPACITY || err.find("2^31") == std::string::npos) GR_FAIL("the backpointer cap");
+        }
+        // ---- refused on the numbers alone: no array exists
+        {
+            const int32_t* none = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            if (grammar_check(none, 0, To, K, none, none, nullptr, none, none, none, none, none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_INVALID) GR_FAIL("B = 0");
+            if (grammar_check(none, B, -big, K, none, none, nullptr, none, none, none, none, none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_INVALID) GR_FAIL("T_out < 0");
+            if (grammar_check(none, B, To, 0, none, none, nullptr, none, none, none, none, none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_INVALID) GR_FAIL("K = 0");
+            if (grammar_check(none, B, To, -big, none, none, nullptr, none, none, none, none, none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_INVALID) GR_FAIL("K < 0");
+            if (grammar_check(none, B, To, (1 << 24) + big, none, none, nullptr, none, none, none, none, none, C, blank, sz, cg, &n_nodes, &n_arcs, err) != DSMI_ERR_CAPACITY) GR_FAIL("K over 2^24");
+            GrammarPlan plan{};
+            if (grammar_plan(0, To, 1, 1, &plan, err) != DSMI_ERR_INVALID || grammar_plan(B, 0, 1, 1, &plan, err) != DSMI_ERR_INVALID ||
+                grammar_plan(B, To, -big, 1, &plan, err) != DSMI_ERR_INVALID || grammar_plan(B, To, 1, -big, &plan, err) != DSMI_ERR_INVALID) GR_FAIL("the plan's numbers");
+        }
+    }
+    std::printf("%d grammar calls ok, %ld good, %ld refused, %ld empty graphs\n", reps, good, refused, empty_graphs);
+    return good > 0 && refused > 0 ? 0 : 11;
+}
+
 // ---- alignlong: dsmi_align_long's check and plan (align_long_host.h), the transcript a heap block of exactly L words
 #define ALONG_FAIL(what) do { std::fprintf(stderr, "alignlong: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
 
@@ -1315,11 +1452,12 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "scoreplan")) return run_scoreplan(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "occcheck")) return run_occcheck(argc, argv);
+    if (argc >= 2 && !std::strcmp(argv[1], "grammarcheck")) return run_grammarcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "alignlong")) return run_alignlong(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz grammarcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
