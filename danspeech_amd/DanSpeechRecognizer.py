@@ -43,9 +43,12 @@ class _StreamingSession(object):
     whose source has another rate than the model's owns a ``NativeResampler`` (``resampler``; ``source`` = (rate, method)); the
     converted samples that a pass did not take wait in ``pending`` (a float64 CUDA tensor).  With ``watching`` (a phrase watch,
     ``enable_streaming(watch=...)``) also the utterance's phrase search, carried from part to part (``spot``, a
-    ``NativeSpotStream``), the detections nobody has taken yet and the ordinal of the utterance under way."""
+    ``NativeSpotStream``), the detections nobody has taken yet and the ordinal of the utterance under way.  With ``commanding`` (a
+    grammar, ``enable_streaming(grammar=...)``) the utterance's graph search, carried from part to part (``command``, a
+    ``NativeGrammarStream``), the commands nobody has taken yet, the ordinal of the utterance it is on and whether that utterance
+    has outgrown the search's frames."""
 
-    def __init__(self, secondary_model, string_parts, lm_partials=False, watching=False):
+    def __init__(self, secondary_model, string_parts, lm_partials=False, watching=False, commanding=False):
         self.secondary_model = secondary_model
         self.string_parts = string_parts
         self.lm_partials = lm_partials
@@ -53,6 +56,11 @@ class _StreamingSession(object):
         self.spot = None
         self.detections = []
         self.utterance = 0
+        self.commanding = commanding
+        self.command = None
+        self.commands = []
+        self.command_utterance = 0
+        self.command_overrun = False
         self.beam = None
         self.beam_decoder = None
         self.resampler = None
@@ -69,6 +77,9 @@ class _StreamingSession(object):
             self.beam.reset()
         if self.spot is not None:
             self.spot.reset()
+        if self.command is not None:
+            self.command.reset()
+        self.command_overrun = False
         if self.resampler is not None:
             self.resampler.reset()
 
@@ -76,6 +87,14 @@ class _StreamingSession(object):
         """The phrase watch's detections since the last call, in firing order: ``(utterance_ordinal, phrase, start_s, end_s,
         confidence, logp)``, seconds from the utterance's first output frame."""
         found, self.detections = self.detections, []
+        return found
+
+    def take_commands(self):
+        """The grammar's results since the last call, in order: partials ``(utterance_ordinal, False, (text, complete))`` --
+        the best sentence prefix so far and whether the grammar accepts it as it stands -- and per utterance one final
+        ``(utterance_ordinal, True, None | (text, [(word, start_s, end_s, confidence), ...], path_logp))``, ``None`` when no
+        sentence of the grammar fits the utterance (or it outgrew ``grammar_max_s``)."""
+        found, self.commands = self.commands, []
         return found
 
     def set_source(self, parser, sample_rate, resample):
@@ -102,6 +121,9 @@ class _StreamingSession(object):
         if self.spot is not None:
             self.spot.close()
             self.spot = None
+        if self.command is not None:
+            self.command.close()
+            self.command = None
         if self.resampler is not None:
             self.resampler.close()
             self.resampler = None
@@ -125,6 +147,9 @@ class LiveSessionHandle:
     def take_detections(self):
         return self.session.take_detections()
 
+    def take_commands(self):
+        return self.session.take_commands()
+
     def close(self):
         self.endpointer.close()
         if self.resampler is not None:
@@ -145,6 +170,9 @@ class StreamingSessionHandle(object):
 
     def take_detections(self):
         return self.state.take_detections()
+
+    def take_commands(self):
+        return self.state.take_commands()
 
     def close(self):
         self.stream.close()
@@ -248,6 +276,7 @@ class DanSpeechRecognizer(object):
         self.alpha, self.beta, self.beam_width = alpha, beta, beam_width
         self.model = self.model_name = self.labels = self.audio_config = self.audio_parser = None
         self._session = None
+        self._grammar_spec = self._grammar_net = None      # enable_streaming(grammar=...): (Grammar, partials, max frames), its NativeGrammarNet
         self._watch_spec = self._watch = None      # enable_streaming(watch=...): (phrases, ids, confidence, settle frames), its NativeSpotWatch
         self._side_streams = {}
         self._replicas = []
@@ -1096,7 +1125,7 @@ class DanSpeechRecognizer(object):
 
     # ---- utterances that arrive in parts ----------------------------------------------------------------------------
     def enable_streaming(self, secondary_model=None, return_string_parts=True, lm_partials=False, sample_rate=None, resample="polyphase",
-                         watch=None, watch_confidence=0.5, watch_settle_s=0.5):
+                         watch=None, watch_confidence=0.5, watch_settle_s=0.5, grammar=None, grammar_partials=False, grammar_max_s=30.0):
         """Streaming mode.  ``sample_rate``: the rate of the parts ``streaming_transcribe`` will be given when it is not the
         model's (telephony's 8 kHz, a sound card's 44.1 or 48 kHz): each part is then converted on the GPU as it arrives
         (``resample``: "polyphase" or "ratecv"), with the state carried from part to part, so that the converted parts are bit
@@ -1112,7 +1141,15 @@ class DanSpeechRecognizer(object):
         reported ``watch_settle_s`` seconds after its end (unless a better window that meets it has come up by then, or the
         utterance ends first).  Detections wait on the session for ``take_detections()``: ``(utterance_ordinal, phrase, start_s,
         end_s, confidence, logp)`` in seconds from the utterance's first output frame, ``confidence = exp(logp / frames)`` as
-        ``find_phrases`` reports it.  What the streaming calls return is the same with and without a watch."""
+        ``find_phrases`` reports it.  What the streaming calls return is the same with and without a watch.
+        ``grammar``: a ``Grammar`` or its text (compiled before any GPU work, ``ValueError`` for its faults): every utterance is
+        then also decoded as a sentence of the grammar, live.  Every session carries a graph search of its own on the one shared
+        net (``Decoder.grammar_net``); all due sessions' searches advance in one launch after the model pass, over exactly the
+        rows the pass produced, and the last part reports the final result: ``transcribe_grammar``'s text, word timings and
+        ``path_logp`` of the utterance's rows, bit for bit.  With ``grammar_partials`` every middle part also reports the best
+        sentence prefix so far.  Results wait on the session for ``take_commands()``.  A search holds ``grammar_max_s`` seconds
+        of frames; a longer utterance gets one warning and ``None`` for its final, and no call is refused because of it.  What
+        the streaming calls return is the same with and without a grammar; ``watch`` and ``grammar`` may both be set."""
         if lm_partials and not isinstance(self.decoder, BeamCTCDecoder):
             raise ValueError("lm_partials needs a language-model decoder (update_decoder(lm=...)); this recogniser decodes greedily")
         spec = None
@@ -1125,12 +1162,18 @@ class DanSpeechRecognizer(object):
                 raise ValueError("watch_settle_s must be positive")
             spec = (phrases, ids, float(watch_confidence), max(1, int(round(watch_settle_s / self.frame_seconds()))))
         self._watch_spec, self._watch = spec, None
+        gspec = None
+        if grammar is not None:
+            if not grammar_max_s > 0:
+                raise ValueError("grammar_max_s must be positive")
+            gspec = (self.decoder.grammar(grammar), bool(grammar_partials), max(1, int(round(grammar_max_s / self.frame_seconds()))))
+        self._grammar_spec, self._grammar_net = gspec, None
         if secondary_model:
             secondary_model = secondary_model.to(self.device)
             secondary_model.eval()
         if self._session:
             self._session.close()
-        self._session = _StreamingSession(secondary_model or None, bool(return_string_parts), bool(lm_partials), spec is not None)
+        self._session = _StreamingSession(secondary_model or None, bool(return_string_parts), bool(lm_partials), spec is not None, gspec is not None)
         self.greedy_decoder = GreedyDecoder(labels=self.labels, blank_index=self.labels.index('_'))
         self.audio_parser = InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index())
         self.set_streaming_source(sample_rate, resample)
@@ -1147,6 +1190,7 @@ class DanSpeechRecognizer(object):
             self._session.close()
         self._session = _StreamingSession(kept, False)
         self._watch_spec = self._watch = None
+        self._grammar_spec = self._grammar_net = None
 
     def reset_streaming_params(self):
         if self._session:
@@ -1189,7 +1233,8 @@ class DanSpeechRecognizer(object):
         native = getattr(self.model, "_native", None)
         if native is None:
             raise RuntimeError("the streaming model runs only on an MI355X: call model.to('cuda') first (no CPU path)")
-        state = _StreamingSession(self._session.secondary_model, self._session.string_parts, self._session.lm_partials, self._session.watching)
+        state = _StreamingSession(self._session.secondary_model, self._session.string_parts, self._session.lm_partials, self._session.watching,
+                                  self._session.commanding)
         # the resamplers of all sessions belong to ONE frontend (the engine's streaming parser's): one push_many serves them all
         state.set_source(self.audio_parser, sample_rate, resample)
         return StreamingSessionHandle(InferenceSpectrogramAudioParser(audio_config=self.audio_config, device=self._device_index()),
@@ -1349,11 +1394,63 @@ class DanSpeechRecognizer(object):
         """The phrase watch's detections of ``streaming_transcribe``'s own session since the last call (``enable_streaming``)."""
         return self._session.take_detections() if self._session else []
 
+    def take_commands(self):
+        """The grammar's results of ``streaming_transcribe``'s own session since the last call (``enable_streaming``)."""
+        return self._session.take_commands() if self._session else []
+
+    def _advance_grammar(self, items):
+        """The grammar: advance the carried graph searches of several sessions in ONE launch, [(session state, the rows the pass
+        appended to its outputs or None, is_last)], and queue the results on each session.  The last part takes the final
+        result and resets the search for the session's next utterance."""
+        from . import _native
+        items = [it for it in items if it[0].commanding]
+        if not items:
+            return
+        g, partials, max_frames = self._grammar_spec
+        if self._grammar_net is None:
+            self._grammar_net = self.greedy_decoder.grammar_net(g, self._device_index())
+        streams, rows, modes, due = [], [], [], []
+        for ses, probs, last in items:
+            if ses.command is None or ses.command.net is not self._grammar_net:
+                if ses.command is not None:
+                    ses.command.close()
+                ses.command = _native.NativeGrammarStream(self._grammar_net, 0, max_frames)
+            new = 0 if probs is None else int(probs.shape[-2])
+            if not ses.command_overrun and ses.command.frames() + new > max_frames:
+                ses.command_overrun = True
+                warnings.warn("grammar: an utterance is longer than grammar_max_s (%d frames); it gets no command" % max_frames)
+            if ses.command_overrun:
+                if last:
+                    ses.commands.append((ses.command_utterance, True, None))
+                    ses.command.reset()
+                    ses.command_overrun = False
+                    ses.command_utterance += 1
+                continue
+            if not (new or last or partials):
+                continue
+            streams.append(ses.command); rows.append(probs); modes.append(2 if last else 1 if partials else 0)
+            due.append(ses)
+        if not streams:
+            return
+        frame_s = self.frame_seconds()
+        for ses, mode, res in zip(due, modes, _native.NativeGrammarStream.advance_many(streams, rows, modes)):
+            if mode == 0:
+                continue
+            M, nodes, spans, tp, logp, status, complete = res
+            text = g.text_of(nodes[:M])
+            if mode == 1:
+                ses.commands.append((ses.command_utterance, False, (text, bool(complete))))
+                continue
+            ses.commands.append((ses.command_utterance, True, None if status else (text, _words(text, spans[:M], tp[:M], frame_s), logp)))
+            ses.command.reset()
+            ses.command_utterance += 1
+
     def _advance_watch(self, items):
         """The phrase watch: advance the carried searches of several sessions in ONE launch, [(session state, the rows the pass
         appended to its outputs or None, is_last)], and queue what fired on each session.  The last part flushes the search and
         resets it for the session's next utterance."""
         from . import _native
+        items = [it for it in items if it[0].watching]
         if not items:
             return
         phrases, ids, confidence, settle = self._watch_spec
@@ -1414,8 +1511,10 @@ class DanSpeechRecognizer(object):
             if ses.lm_partials and (k in probs or is_last[k]):
                 lm_items.append((ses, probs.get(k)))
         self._advance_lm_partials(lm_items)          # every due session's search in one launch, last parts included
-        self._advance_watch([(sessions[k].state, probs[k] if k in probs and not is_first[k] else None, is_last[k]) for k in range(n)
-                             if sessions[k].state.watching and ((k in probs and not is_first[k]) or is_last[k])])
+        due = [(sessions[k].state, probs[k] if k in probs and not is_first[k] else None, is_last[k]) for k in range(n)
+               if (k in probs and not is_first[k]) or is_last[k]]
+        self._advance_watch(due)
+        self._advance_grammar(due)
         said = []
         for k in range(n):
             ses = sessions[k].state
@@ -1444,8 +1543,9 @@ class DanSpeechRecognizer(object):
             spect = spect.view(1, 1, spect.size(0), spect.size(1)).to(self.device)
             probs = self.model(spect, is_first, is_last)
             if is_first:
-                if ses.watching and is_last:
+                if is_last:
                     self._advance_watch([(ses, None, True)])
+                    self._advance_grammar([(ses, None, True)])
                 return ""
             ses.outputs.append(probs)
             piece = ses.extend_text(self.greedy_decoder.decode(probs)[0][0][0])
@@ -1454,8 +1554,9 @@ class DanSpeechRecognizer(object):
             self._advance_lm_partials([(ses, probs)])
             if len(spect) != 0 and ses.beam_text is not None:
                 said = ses.beam_text
-        if ses.watching and (probs is not None or is_last):
+        if probs is not None or is_last:
             self._advance_watch([(ses, probs, is_last)])
+            self._advance_grammar([(ses, probs, is_last)])
         if not is_last:
             return said
         return self._final_text(ses) if len(ses.text) > 1 else ""

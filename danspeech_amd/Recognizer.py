@@ -161,17 +161,22 @@ class Recognizer(object):
 
     # ---- real-time streaming (Recognizer.py:499-720) without the microphone -----------------------------
     def enable_real_time_streaming(self, streaming_model, secondary_model=None, string_parts=True, lm_partials=False, watch=None,
-                                   watch_confidence=0.5, watch_settle_s=0.5):
+                                   watch_confidence=0.5, watch_settle_s=0.5, grammar=None, grammar_partials=False, grammar_max_s=30.0):
         """Recognizer.py:499-533: switch to a unidirectional streaming model (e.g.
         ``pretrained_models.GPUStreamingRNN``), optionally with a secondary model for the final text.  ``lm_partials``
         (needs a language model): every middle output is the language-model decoder's best text of the whole utterance so
         far, from a beam search carried from part to part (``DanSpeechRecognizer.enable_streaming``).  ``watch``: phrases to
         listen for in every stream -- a name, a command, a wake word; ``stream_recording``, ``stream_recordings`` and
         ``stream_live`` then report each occurrence to their ``on_detection`` callback ``watch_settle_s`` seconds after it was
-        said, when its per-frame confidence is at least ``watch_confidence`` (``DanSpeechRecognizer.enable_streaming``)."""
+        said, when its per-frame confidence is at least ``watch_confidence`` (``DanSpeechRecognizer.enable_streaming``).
+        ``grammar``: a ``Grammar`` or its text -- commands, digits, a closed vocabulary: every utterance of every stream is then
+        also decoded live as a sentence of the grammar and reported to the ``on_command`` callback of the three calls; with
+        ``grammar_partials`` the best sentence prefix so far after every part, too.  ``grammar_max_s``: the longest utterance
+        the search holds (a longer one gets a warning and ``None``).  ``ValueError`` for a faulty grammar, before any GPU work."""
         self.update_model(streaming_model)
         self.danspeech_recognizer.enable_streaming(secondary_model, string_parts, lm_partials, watch=watch, watch_confidence=watch_confidence,
-                                                   watch_settle_s=watch_settle_s)
+                                                   watch_settle_s=watch_settle_s, grammar=grammar, grammar_partials=grammar_partials,
+                                                   grammar_max_s=grammar_max_s)
         self.stream = True
 
     def disable_real_time_streaming(self, keep_secondary_model_loaded=False):
@@ -183,13 +188,16 @@ class Recognizer(object):
             print("No stream is running for the Recognizer")
 
     @staticmethod
-    def _report(on_detection, index, session):
-        """Hand the detections that wait on ``session`` to the callback (without one they are dropped)."""
+    def _report(on_detection, index, session, on_command=None):
+        """Hand the detections and the grammar's results that wait on ``session`` to the callbacks (without one they are dropped)."""
         for ordinal, phrase, start_s, end_s, confidence, logp in session.take_detections():
             if on_detection is not None:
                 on_detection(index, ordinal, phrase, start_s, end_s, confidence, logp)
+        for item in session.take_commands():
+            if on_command is not None:
+                on_command(index, *item)
 
-    def stream_recording(self, audio_data, chunk_samples=None, sample_rate=None, resample="polyphase", on_detection=None):
+    def stream_recording(self, audio_data, chunk_samples=None, sample_rate=None, resample="polyphase", on_detection=None, on_command=None):
         """The body of ``real_time_streaming`` (Recognizer.py:560-710) driven by an array instead of the
         microphone thread: the utterance is cut with the reference's sample requirements (first pass
         ``general + 15 * samples_pr_10ms``, later passes ``general``, :598-612; ``chunk_samples`` is the size
@@ -202,7 +210,9 @@ class Recognizer(object):
         the yields equal ``stream_recording(audio.resample(audio_data, sample_rate, method=resample), chunk_samples)``.
         ``on_detection``: with a phrase watch (``enable_real_time_streaming(watch=...)``), called as ``on_detection(index,
         utterance_ordinal, phrase, start_s, end_s, confidence, logp)`` for every occurrence, before the part's text is yielded
-        (``index`` is 0 here); what is yielded is the same with and without it."""
+        (``index`` is 0 here); what is yielded is the same with and without it.
+        ``on_command``: with a grammar (``enable_real_time_streaming(grammar=...)``), called as ``on_command(index,
+        utterance_ordinal, is_final, result)`` with what ``take_commands()`` holds, before the part's text is yielded."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
@@ -210,7 +220,7 @@ class Recognizer(object):
             audio_data = np.asarray(audio_data, dtype=np.float64)
             for lo, hi, is_first, is_last in self._cut_plan(len(audio_data), chunk_samples):
                 output = rec.streaming_transcribe(audio_data[lo:hi], is_last=is_last, is_first=is_first)
-                self._report(on_detection, 0, rec)
+                self._report(on_detection, 0, rec, on_command)
                 if output:
                     yield is_last, output
             return
@@ -221,13 +231,13 @@ class Recognizer(object):
         try:
             for (lo, hi, is_first, is_last), (a, b, flush) in zip(plan, feed):
                 output = rec.streaming_transcribe(audio_data[a:b], is_last=is_last, is_first=is_first, take=hi - lo, flush=flush)
-                self._report(on_detection, 0, rec)
+                self._report(on_detection, 0, rec, on_command)
                 if output:
                     yield is_last, output
         finally:
             rec.set_streaming_source(*(before or (None, "polyphase")))
 
-    def stream_recordings(self, audio_list, chunk_samples=None, sample_rate=None, resample="polyphase", on_detection=None):
+    def stream_recordings(self, audio_list, chunk_samples=None, sample_rate=None, resample="polyphase", on_detection=None, on_command=None):
         """``stream_recording`` for many recordings at once, one streaming session each: every recording is cut as
         ``stream_recording`` cuts it, and in each round every session that has a part due advances in ONE batched pass
         (``DanSpeechRecognizer.streaming_transcribe_many``).  Yields ``(index, is_last, text)``; for every index the
@@ -236,8 +246,8 @@ class Recognizer(object):
         ``enable_real_time_streaming``.
         ``sample_rate``: the recordings' rate, or a list with one rate per recording (None among them: the model's); the
         sessions of other rates are converted together, one launch per round and method (``stream_recording``).
-        ``on_detection``: as ``stream_recording``'s, ``index`` the recording's; a round's detections are reported before the
-        round's texts are yielded."""
+        ``on_detection`` and ``on_command``: as ``stream_recording``'s, ``index`` the recording's; a round's detections and
+        commands are reported before the round's texts are yielded."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         rec = self.danspeech_recognizer
@@ -265,7 +275,7 @@ class Recognizer(object):
                                                       [c[3] for _, c in due], [c[2] for _, c in due],
                                                       take=[c[1] - c[0] for _, c in due], flush=[feeds[k][r][2] for k, _ in due])
                 for k, _ in due:
-                    self._report(on_detection, k, sessions[k])
+                    self._report(on_detection, k, sessions[k], on_command)
                 for (k, c), text in zip(due, texts):
                     if text:
                         yield k, c[3], text
@@ -273,7 +283,7 @@ class Recognizer(object):
             for ses in sessions.values():
                 ses.close()
 
-    def stream_live(self, sources, chunk=1024, sample_rate=None, resample="polyphase", on_detection=None):
+    def stream_live(self, sources, chunk=1024, sample_rate=None, resample="polyphase", on_detection=None, on_command=None):
         """Continuous audio from many sources -> per-utterance texts: ``real_time_streaming`` (Recognizer.py:560-715) for every
         source at once, with the listener's gate (``listen_stream``, :218-324), the conversion to the model's rate and the
         model passes all on the GPU.  ``sources``: a list of iterables of sample arrays of any lengths (int16 -- ``[n, 2]``
@@ -284,7 +294,7 @@ class Recognizer(object):
         ``energy_threshold``, ``pause_threshold``, ``phrase_threshold`` and ``non_speaking_duration`` as they are when a source
         delivers its first array.  Requires ``enable_real_time_streaming``.  ``on_detection``: as ``stream_recording``'s, ``index``
         the source's and ``utterance_ordinal`` counting the utterances the gate has found in it; a round's detections are
-        reported before the round's texts are yielded."""
+        reported before the round's texts are yielded.  ``on_command``: as ``stream_recording``'s, in the same place."""
         if not getattr(self, "stream", False):
             raise RuntimeError("call enable_real_time_streaming(streaming_model) first")
         if resample != "polyphase":
@@ -317,7 +327,7 @@ class Recognizer(object):
                     continue
                 heard = rec.streaming_listen_many([sessions[k] for k in ks], parts, eos)
                 for k in ks:
-                    self._report(on_detection, k, sessions[k])
+                    self._report(on_detection, k, sessions[k], on_command)
                 for k, said in zip(ks, heard):
                     for is_last, text in said:
                         yield k, is_last, text

@@ -40,6 +40,8 @@ ALT_MAX_TOKENS = 1024           # the longest candidate dsmi_alternatives takes 
 OCC_MAX_TOKENS = 1024           # the longest candidate dsmi_occupancy takes (L_stride)
 GRAMMAR_MAX_NODES = 2048        # the most nodes of one graph dsmi_grammar takes
 GRAMMAR_MAX_ARCS = 8192         # the most arcs of one graph dsmi_grammar takes
+GRAMMAR_STREAM_MANY_MAX = 4096  # streams of one dsmi_grammar_stream_advance_many launch
+GRAMMAR_STREAM_MAX_FRAMES = 1 << 20      # the most frames of one dsmi_grammar_stream's utterance
 GRAMMAR_START, GRAMMAR_FINAL = 1, 2   # DSMI_GRAMMAR_START, DSMI_GRAMMAR_FINAL: a node's flags
 EDIT_MAX_TOKENS = 4096          # the longest sequence dsmi_edit_distance takes (L_stride)
 LM_SCORE_MAX_TOKENS = 4096      # the longest sequence dsmi_lm_score takes (L_stride)
@@ -212,6 +214,17 @@ _PROTOS = {
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "dsmi_grammar": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(GrammarPool), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_grammar_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i64p]),
+    "dsmi_grammar_net_create": (C.c_int, [_vp, C.POINTER(GrammarPool), C.POINTER(_vp)]),
+    "dsmi_grammar_net_destroy": (None, [_vp]),
+    "dsmi_grammar_net_last_error": (C.c_char_p, [_vp]),
+    "dsmi_grammar_net_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dsmi_grammar_stream_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "dsmi_grammar_stream_destroy": (None, [_vp]),
+    "dsmi_grammar_stream_last_error": (C.c_char_p, [_vp]),
+    "dsmi_grammar_stream_reset": (C.c_int, [_vp]),
+    "dsmi_grammar_stream_frames": (C.c_int, [_vp, _i64p]),
+    "dsmi_grammar_stream_advance_many": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_grammar_stream_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i64p]),
     "dsmi_occupancy": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_edit_plan": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "dsmi_edit_distance": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
@@ -1330,6 +1343,17 @@ def grammar_plan(B, T_out, n_nodes, n_arcs):
     return dict(zip(("node_stride", "lds_bytes", "bp_bytes"), (int(v) for v in info)))
 
 
+def grammar_stream_plan(n_nodes, n_arcs, n_labels, max_frames):
+    """dsmi_grammar_stream_plan (host only): the geometry of one dsmi_grammar_stream over a graph of n_nodes nodes and n_arcs arcs
+    with n_labels labels and room for max_frames frames, as a dict; DsmiError with the code a create would refuse these numbers with."""
+    info = np.zeros(3, dtype=np.int64)
+    rc = lib().dsmi_grammar_stream_plan(int(n_nodes), int(n_arcs), int(n_labels), int(max_frames), info.ctypes.data_as(_i64p))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_grammar_stream_plan: 1 .. %d frames, 0 .. %d nodes, 0 .. %d arcs, 1 .. 128 labels, at most 2^31 bytes"
+                        % (GRAMMAR_STREAM_MAX_FRAMES, GRAMMAR_MAX_NODES, GRAMMAR_MAX_ARCS))
+    return dict(zip(("node_stride", "lds_bytes", "block_bytes"), (int(v) for v in info)))
+
+
 def spot_plan(phrase_lens):
     """dsmi_spot_plan (host only): (n_groups, group_of, first_state) of phrases with these token counts, as dsmi_spot packs them."""
     lens = np.ascontiguousarray(phrase_lens, dtype=np.int32).reshape(-1)
@@ -1573,6 +1597,87 @@ class NativeSpotStream(_Handle):
 
     def advance(self, probs, flush=False, max_events=4, tracks=False):
         return NativeSpotStream.advance_many([self], [probs], [flush], max_events, tracks)[0]
+
+
+class NativeGrammarNet(_Handle):
+    """Owns one dsmi_grammar_net handle: one graph or a list of K (as ``NativeDecoder.grammar`` takes them) checked, packed and
+    uploaded once for ``decoder`` (a ``NativeDecoder``, kept alive by the net)."""
+    _destroy, _last_error = "dsmi_grammar_net_destroy", "dsmi_grammar_net_last_error"
+
+    def __init__(self, decoder, graphs):
+        self.decoder = decoder
+        pool, keep = grammar_pool(graphs)
+        self._create("dsmi_grammar_net_create", decoder._h, C.byref(pool))
+        del keep
+        K, N, A = C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().dsmi_grammar_net_info(self._h, C.byref(K), C.byref(N), C.byref(A)))
+        self.K, self.max_nodes, self.max_arcs = K.value, N.value, A.value
+
+
+class NativeGrammarStream(_Handle):
+    """Owns one dsmi_grammar_stream handle: one live utterance's search over graph ``graph`` of ``net`` (a ``NativeGrammarNet``,
+    kept alive by the stream), carried from chunk to chunk for at most ``max_frames`` frames."""
+    _destroy, _last_error = "dsmi_grammar_stream_destroy", "dsmi_grammar_stream_last_error"
+
+    def __init__(self, net, graph=0, max_frames=1500):
+        self.net, self.graph, self.max_frames = net, int(graph), int(max_frames)
+        self._create("dsmi_grammar_stream_create", net._h, self.graph, self.max_frames)
+
+    def close(self):
+        if getattr(self.net, "_h", None):        # (the handle points into its net: after the net has gone there is nothing to free safely)
+            super().close()
+        self._h = None
+
+    def frames(self):
+        f = C.c_int64()
+        if lib().dsmi_grammar_stream_frames(self._h, C.byref(f)) != 0:
+            raise DsmiError(DSMI_ERR_INVALID, "closed grammar stream")
+        return int(f.value)
+
+    def reset(self):
+        if lib().dsmi_grammar_stream_reset(self._h) != 0:
+            raise DsmiError(DSMI_ERR_INVALID, "closed grammar stream")
+
+    @staticmethod
+    def advance_many(streams, rows, modes):
+        """dsmi_grammar_stream_advance_many: advance distinct ``NativeGrammarStream`` of one net in one launch, stream i by the
+        frames of ``rows[i]`` (CUDA float32 [T,C] or [1,T,C]; None or T = 0: no frames).  ``modes[i]``: 0 advance only, 1 then
+        the partial result (the best path into any state), 2 then the final result (the utterance is over).  -> per stream
+        None (mode 0) or (lens int, nodes int32 [F], spans int32 [F,2], token_probs float32 [F], logp float, status int,
+        complete int) over the F frames of its utterance so far: what ``NativeDecoder.grammar`` gives for their concatenation.
+        Longer lists than GRAMMAR_STREAM_MANY_MAX run as several launches."""
+        import torch
+        if not (len(rows) == len(modes) == len(streams)):
+            raise ValueError("streams, rows and modes must have one entry per stream")
+        probs, new = [], []
+        for p in rows:
+            t = 0
+            if p is not None:
+                t = p.shape[-2]
+                p = p.reshape(t, p.shape[-1]).contiguous()
+                assert p.is_cuda and p.dtype == torch.float32
+            probs.append(p if t > 0 else None)
+            new.append(t)
+        outs = []
+        for ss, ps, ts, md in _cut(GRAMMAR_STREAM_MANY_MAX, streams, probs, new, [int(m) for m in modes]):
+            n = len(ss)
+            fr, mo = np.array(ts, dtype=np.int32), np.array(md, dtype=np.int32)
+            due = [i for i in range(n) if md[i] != 0]
+            after = [ss[i].frames() + ts[i] for i in due]
+            P = max(after, default=0)
+            lens, lp, st, cp = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+            nodes, spans, tp = np.zeros((n, P), dtype=np.int32), np.zeros((n, P, 2), dtype=np.int32), np.zeros((n, P), dtype=np.float32)
+            NativeGrammarStream._check_thread(lib().dsmi_grammar_stream_advance_many(
+                _handle_array(ss), n, _ptr_array(ps), _np_ptr(fr), _np_ptr(mo), P, _np_ptr(lens), _np_ptr(nodes), _np_ptr(spans), _np_ptr(tp),
+                _np_ptr(lp), _np_ptr(st), _np_ptr(cp), _stream(ss[0].net.decoder.device)))
+            res = [None] * n
+            for i, F in zip(due, after):
+                res[i] = (int(lens[i]), nodes[i, :F].copy(), spans[i, :F].copy(), tp[i, :F].copy(), float(lp[i]), int(st[i]), int(cp[i]))
+            outs += res
+        return outs
+
+    def advance(self, rows, mode=0):
+        return NativeGrammarStream.advance_many([self], [rows], [mode])[0]
 
 
 class NativeLM(_Handle):

@@ -158,6 +158,18 @@ class Decoder(object):
             out.append((text, [(text[k], int(spans[b, k, 0]), int(spans[b, k, 1]), float(tp[b, k])) for k in range(M)], float(lp[b])))
         return out
 
+    def grammar_net(self, grammar_or_list, device_index=0):
+        """Streaming grammar decoding (``dsmi_grammar_net_*``): one grammar or a list of them (``Grammar`` or text), compiled,
+        checked, packed and uploaded once -> a ``NativeGrammarNet`` whose ``NativeGrammarStream``s carry one live utterance's
+        search each; ``NativeGrammarStream.advance_many`` advances any number of them in one launch, and its final result is
+        ``decode_grammar``'s of the rows laid end to end, bit for bit."""
+        from .. import _native
+        many = isinstance(grammar_or_list, (list, tuple))
+        graphs = [self.grammar(g) for g in grammar_or_list] if many else [self.grammar(grammar_or_list)]
+        net = _native.NativeGrammarNet(self._dec(device_index), graphs)
+        net.graphs = graphs
+        return net
+
     # ---- long-form CTC forced alignment (dsmi_align_long): one recording, its whole transcript, no limit from LDS
     def align_long(self, probs, transcript, lead_free=True, tail_free=True):
         """Forced alignment of ``transcript`` (normalised with ``normalise_transcript``) to the probabilities ``probs`` [T,C] of

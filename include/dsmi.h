@@ -893,6 +893,69 @@ int dsmi_grammar(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_h
                  int32_t* status_host, void* stream);
 int dsmi_grammar_plan(int B, int T_out, int n_nodes, int n_arcs, int64_t* info);
 
+/* ---- Streaming grammar decoding (no reference counterpart): dsmi_grammar's search carried from one chunk of a live session's
+ * probabilities to the next, so that a streaming caller pays for each frame once and neither keeps the rows nor packs the
+ * graph again.  A dsmi_grammar_net is a pool of K graphs bound to one dsmi_decoder: dsmi_grammar_net_create applies
+ * dsmi_grammar's rules to the pool (the same faults, codes and messages; the clip and size rules have nothing to apply to),
+ * packs the arcs as dsmi_grammar does, lists the nodes with more than 32 predecessors and uploads once.
+ * dsmi_grammar_net_info tells K and the most nodes and arcs of one graph (each pointer may be NULL).  A dsmi_grammar_stream is
+ * one live utterance's carried search over graph `graph` of a net, for at most max_frames frames (1 <= max_frames <=
+ * DSMI_GRAMMAR_STREAM_MAX_FRAMES): one device block with a 16-byte header (lead and the frame count), the float32 tok / blk
+ * pair of every node as of the last frame consumed, the probability rows consumed [max_frames][n_labels] float32 (the
+ * per-visit means need them) and the 16-bit backpointers [max_frames][node stride] of the frames consumed.
+ * dsmi_grammar_stream_reset starts a new utterance (nothing of the block is read again); dsmi_grammar_stream_frames tells the
+ * frames consumed since.  A net serves any number of streams; destroy every stream before its net, and every net before its
+ * decoder.
+ * dsmi_grammar_stream_plan (host only, no handle): for a graph of n_nodes nodes and n_arcs arcs, n_labels labels and
+ * max_frames frames, info = {node stride, LDS bytes per workgroup, device bytes per stream}.  DSMI_ERR_INVALID: a NULL info,
+ * max_frames < 1, negative counts, n_labels outside 1 .. 128; DSMI_ERR_CAPACITY: max_frames above
+ * DSMI_GRAMMAR_STREAM_MAX_FRAMES, node or arc counts above dsmi_grammar's limits, a block above 2^31 bytes.  (At 1500 frames a
+ * 28-node digit loop needs 84 KB of backpointers, the node limit 6.1 MB.)
+ *
+ * dsmi_grammar_stream_advance_many advances n distinct streams of one net in ONE launch whatever n (1 <= n <=
+ * DSMI_GRAMMAR_STREAM_MANY_MAX), one workgroup per stream: stream i by frames[i] >= 0 rows of probs_dev[i] (device,
+ * [frames[i]][n_labels] float32, the softmax output; may be NULL when frames[i] = 0).  mode[i] = 0: advance only; 1: advance,
+ * then report the partial result; 2: advance, then report the final result -- the utterance is over, and a later call with
+ * frames > 0 on this stream is refused until dsmi_grammar_stream_reset.  A call in which no stream has frames or a result due
+ * launches nothing.
+ * The contract is equality with dsmi_grammar.  Let X be the rows of stream i over all its calls laid end to end and F their
+ * count.  With mode 2 the six outputs of stream i -- path_lens, path_nodes, path_spans, token_probs, path_logp, status -- are
+ * the bits dsmi_grammar gives for the single clip X (B = 1, T_out = F) on the stream's graph, however the utterance was cut
+ * into calls and whatever else is in the call.  With mode 1 they are the bits dsmi_grammar gives for X on the same graph with
+ * EVERY node final and empty_ok = 1: the best path into any state, lead first, then the nodes ascending, blk before tok -- the
+ * same tie rule -- and complete_host[i] = 1 when that path's end state is one the real graph accepts (lead with the graph's
+ * empty_ok, or a node with DSMI_GRAMMAR_FINAL).  With mode 2 complete_host[i] = 1 - status.  With F = 0, mode 2 gives
+ * dsmi_grammar's zero-frame result and mode 1 the empty path with path_logp 0, status 0 and complete = empty_ok.
+ * Outputs, host arrays: path_lens, path_logp, status and complete [n]; path_nodes and token_probs [n][P_stride], path_spans
+ * [n][P_stride][2]; P_stride >= the utterance's frame count after this call of every stream with mode != 0.  Rows past M are
+ * 0.  A stream with mode 0 has nothing written for it; complete_host may be NULL.
+ * A node with more than 32 predecessors is entered by a whole wave whose lanes stride the list; the reduction takes the
+ * greater value and, among equal values, the earlier candidate, which is the sequential rule exactly: no bit depends on it.
+ * Either every stream advances or the call is refused before any launch, with no stream's state changed and nothing written;
+ * the error text (dsmi_grammar_stream_last_error(NULL)) names the stream index.  DSMI_ERR_INVALID: NULL arguments or handles,
+ * n outside its range, a handle listed twice, streams of different nets, frames[i] < 0, probabilities missing for frames[i] >
+ * 0, a mode outside 0 .. 2, frames for a stream that has ended, P_stride below the frame count of a stream with mode != 0, a
+ * NULL output when any mode != 0.  DSMI_ERR_CAPACITY: a stream that would pass its max_frames (the message says both
+ * numbers), n * P_stride > 2^24.  Synchronises `stream`. */
+typedef struct dsmi_grammar_net dsmi_grammar_net;
+typedef struct dsmi_grammar_stream dsmi_grammar_stream;
+#define DSMI_GRAMMAR_STREAM_MANY_MAX 4096
+#define DSMI_GRAMMAR_STREAM_MAX_FRAMES (1 << 20)
+int dsmi_grammar_net_create(dsmi_decoder* d, const dsmi_grammar_pool* pool, dsmi_grammar_net** out);
+void dsmi_grammar_net_destroy(dsmi_grammar_net* n);
+const char* dsmi_grammar_net_last_error(const dsmi_grammar_net* n);
+int dsmi_grammar_net_info(const dsmi_grammar_net* n, int* K, int* max_nodes, int* max_arcs);
+int dsmi_grammar_stream_create(dsmi_grammar_net* n, int graph, int max_frames, dsmi_grammar_stream** out);
+void dsmi_grammar_stream_destroy(dsmi_grammar_stream* s);
+const char* dsmi_grammar_stream_last_error(const dsmi_grammar_stream* s);
+int dsmi_grammar_stream_reset(dsmi_grammar_stream* s);
+int dsmi_grammar_stream_frames(const dsmi_grammar_stream* s, int64_t* frames);
+int dsmi_grammar_stream_advance_many(dsmi_grammar_stream* const* streams, int n, const float* const* probs_dev,
+                                     const int32_t* frames, const int32_t* mode, int P_stride, int32_t* path_lens_host,
+                                     int32_t* path_nodes_host, int32_t* path_spans_host, float* token_probs_host,
+                                     float* path_logp_host, int32_t* status_host, int32_t* complete_host, void* stream);
+int dsmi_grammar_stream_plan(int n_nodes, int n_arcs, int n_labels, int max_frames, int64_t* info);
+
 /* ---- Batched edit distance (the reference calls Levenshtein.distance once per pair, on the host): how far is this text from
  * that one, for many pairs at once -- WER / CER with their error counts, and the pairwise distances of n-best lists.
  * A pool of M token sequences: seqs_host [M][L_stride] with seq_lens_host [M].  Tokens are any int32 and are compared for

@@ -21,6 +21,9 @@
 //   host_fuzz grammarcheck SEED N  the host half of dsmi_grammar (grammar_host.h: grammar_check, grammar_plan) on N random calls whose pool of
 //                             graphs lies in exactly sized heap arrays, each good or with one fault, against the rules written out
 //                             below; one node or arc over each limit; what is refused on the numbers alone is called with null arrays
+//   host_fuzz grammarstreamcheck SEED N  the host half of streaming grammar decoding (grammar_stream_host.h: grammar_stream_plan,
+//                             grammar_heavy_list, grammar_stream_check) on N random advance calls held in exactly sized heap arrays, each
+//                             good or with one fault, against the rules written out below; the plan's numbers and refusals
 //   host_fuzz alignlong SEED N  the host half of dsmi_align_long (align_long_host.h: align_long_check, align_long_plan) on N random calls whose
 //                             transcript is an exactly sized heap array, each good or with one fault, against the rules written out
 //                             below; the checkpoint rows on either side of their cap; what is refused on the numbers alone is called
@@ -55,6 +58,7 @@
 #include "ctc_host.h"
 #include "align_long_host.h"
 #include "grammar_host.h"
+#include "grammar_stream_host.h"
 #include "edit_host.h"
 #include "lm_score_host.h"
 #include "spot_pick.h"
@@ -898,6 +902,129 @@ static int run_grammarcheck(int argc, char** argv) {
     return good > 0 && refused > 0 ? 0 : 11;
 }
 
+// ---- grammarstreamcheck: the plan of a stream's block, the heavy list and the check of an advance call (grammar_stream_host.h),
+// every array a heap block of exactly n entries
+#define GS_FAIL(what) do { std::fprintf(stderr, "grammarstreamcheck: %s (repetition %d, line %d): %s\n", what, rep, __LINE__, err.c_str()); return 11; } while (0)
+
+static int run_grammarstreamcheck(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long good = 0, refused = 0, heavy_nodes = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        std::string err;
+        // ---- the plan: the rules written out plainly
+        {
+            const int N = (int)(rng() % (DSMI_GRAMMAR_MAX_NODES + 1)), A = (int)(rng() % (DSMI_GRAMMAR_MAX_ARCS + 1));
+            const int C = 1 + (int)(rng() % kCtcMaxLabels), F = 1 + (int)(rng() % 3000);
+            GrammarStreamPlan p{};
+            if (grammar_stream_plan(N, A, C, F, &p, err) != DSMI_OK) GS_FAIL("the plan of good numbers");
+            const int64_t stride = std::max(4, (N + 3) / 4 * 4);
+            const int64_t lds = 16 * stride + 8 * stride + 2 * (stride + 4) + 2 * (int64_t)((A + 3) / 4 * 4) + 2 * 4 * kCtcChunk * kCtcMaxLabels + 512;
+            const int64_t bytes = 16 + 8 * stride + 4 * (int64_t)F * C + 2 * (int64_t)F * stride;
+            if (p.node_stride != stride || p.lds_bytes != lds || p.block_bytes != bytes) GS_FAIL("the plan's numbers");
+            if (p.pairs_at != 16 || p.hist_at != 16 + 8 * stride || p.bp_at != p.hist_at + 4 * (int64_t)F * C || p.bp_at % 4 != 0) GS_FAIL("the block's layout");
+            if (grammar_stream_plan(N, A, C, 0, &p, err) != DSMI_ERR_INVALID || grammar_stream_plan(N, A, C, -F, &p, err) != DSMI_ERR_INVALID) GS_FAIL("max_frames < 1");
+            if (grammar_stream_plan(N, A, C, DSMI_GRAMMAR_STREAM_MAX_FRAMES + 1, &p, err) != DSMI_ERR_CAPACITY) GS_FAIL("max_frames over the limit");
+            if (grammar_stream_plan(N, A, 0, F, &p, err) != DSMI_ERR_INVALID || grammar_stream_plan(N, A, kCtcMaxLabels + 1, F, &p, err) != DSMI_ERR_INVALID) GS_FAIL("n_labels");
+            if (grammar_stream_plan(DSMI_GRAMMAR_MAX_NODES + 1, A, C, F, &p, err) != DSMI_ERR_CAPACITY || grammar_stream_plan(N, DSMI_GRAMMAR_MAX_ARCS + 1, C, F, &p, err) != DSMI_ERR_CAPACITY) GS_FAIL("one over a limit");
+            if (grammar_stream_plan(-1, A, C, F, &p, err) != DSMI_ERR_INVALID || grammar_stream_plan(N, -1, C, F, &p, err) != DSMI_ERR_INVALID) GS_FAIL("negative counts");
+            if (grammar_stream_plan(DSMI_GRAMMAR_MAX_NODES, 0, 128, DSMI_GRAMMAR_STREAM_MAX_FRAMES, &p, err) != DSMI_ERR_CAPACITY || err.find("2^31") == std::string::npos) GS_FAIL("the block cap");
+            if (grammar_stream_plan(DSMI_GRAMMAR_MAX_NODES, DSMI_GRAMMAR_MAX_ARCS, 128, 1500, &p, err) != DSMI_OK || p.lds_bytes > 160 * 1024) GS_FAIL("the plan at both limits");
+        }
+        // ---- the heavy list of a pool: nodes with more than 32 predecessors, graph-local, ascending
+        {
+            const int K = 1 + (int)(rng() % 3);
+            std::vector<int32_t> node_off = exact((size_t)K + 1);
+            for (int g = 0; g < K; ++g) node_off[(size_t)g + 1] = node_off[(size_t)g] + (int32_t)(rng() % 12);
+            const int total = node_off[(size_t)K];
+            std::vector<int32_t> arc_off = exact((size_t)total + 1);
+            for (int i = 0; i < total; ++i) arc_off[(size_t)i + 1] = arc_off[(size_t)i] + (int32_t)(rng() % 3 == 0 ? 31 + rng() % 4 : rng() % 5);
+            std::vector<int32_t> hoff;
+            std::vector<uint16_t> heavy;
+            grammar_heavy_list(K, node_off.data(), arc_off.data(), hoff, heavy);
+            size_t at = 0;
+            if (hoff.size() != (size_t)K + 1 || hoff[0] != 0) GS_FAIL("the heavy offsets");
+            for (int g = 0; g < K; ++g) {
+                for (int i = node_off[(size_t)g]; i < node_off[(size_t)g + 1]; ++i)
+                    if (arc_off[(size_t)i + 1] - arc_off[(size_t)i] >= 33) {
+                        if (at >= heavy.size() || heavy[at] != i - node_off[(size_t)g]) GS_FAIL("the heavy list");
+                        ++at; ++heavy_nodes;
+                    }
+                if (hoff[(size_t)g + 1] != (int32_t)at) GS_FAIL("the heavy offsets");
+            }
+            if (at != heavy.size()) GS_FAIL("the heavy list's length");
+        }
+        // ---- an advance call of n streams
+        const int n = 1 + (int)(rng() % 8);
+        std::vector<int> tokens((size_t)n + 1);      // (addresses to stand for handles and nets)
+        std::vector<const void*> handles((size_t)n), nets((size_t)n), rows_of((size_t)n);
+        handles.shrink_to_fit(); nets.shrink_to_fit(); rows_of.shrink_to_fit();
+        std::vector<int64_t> consumed((size_t)n);
+        consumed.shrink_to_fit();
+        std::vector<int32_t> ended = exact((size_t)n), cap = exact((size_t)n), frames = exact((size_t)n), mode = exact((size_t)n);
+        static const float some_rows[1] = {0.f};
+        int64_t longest = 0;
+        for (int i = 0; i < n; ++i) {
+            handles[(size_t)i] = &tokens[(size_t)i]; nets[(size_t)i] = &tokens[(size_t)n];
+            cap[(size_t)i] = 1 + (int32_t)(rng() % 200);
+            consumed[(size_t)i] = (int64_t)(rng() % (unsigned)(cap[(size_t)i] + 1));
+            frames[(size_t)i] = (int32_t)(rng() % (unsigned)(cap[(size_t)i] - consumed[(size_t)i] + 1));
+            mode[(size_t)i] = (int32_t)(rng() % 3);
+            ended[(size_t)i] = frames[(size_t)i] == 0 && rng() % 3 == 0;
+            rows_of[(size_t)i] = frames[(size_t)i] > 0 || rng() % 2 ? some_rows : nullptr;
+            if (mode[(size_t)i]) longest = std::max(longest, consumed[(size_t)i] + frames[(size_t)i]);
+        }
+        int P = (int)longest + (int)(rng() % 3);
+        bool outputs = true;
+        int n_arg = n, code = DSMI_ERR_INVALID;
+        bool due = false;
+        for (int i = 0; i < n; ++i) due |= mode[(size_t)i] != 0;
+        int fault = rng() % 2 ? 0 : 1 + (int)(rng() % 12);
+        const int v = (int)(rng() % (unsigned)n);      // the stream at fault
+        std::string text;
+        auto at = [&](int i) { return "grammar stream " + std::to_string(i) + ": "; };
+        // (a fault is placed so that no earlier stream has one: the check names the first)
+        if (fault == 1) { n_arg = rng() % 2 ? 0 : DSMI_GRAMMAR_STREAM_MANY_MAX + 1; text = "n outside 1 .. DSMI_GRAMMAR_STREAM_MANY_MAX"; }
+        if (fault == 2) { if (n < 2 || v == 0) fault = 0; else { handles[(size_t)v] = handles[(size_t)(v - 1)]; text = at(v) + "the same handle appears twice"; } }
+        if (fault == 3) { if (v == 0) fault = 0; else { nets[(size_t)v] = &tokens[0]; text = at(v) + "the streams of one call must belong to one net"; } }
+        if (fault == 4) { frames[(size_t)v] = -1 - (int32_t)(rng() % 5); text = at(v) + "negative frame count"; }
+        if (fault == 5) { if (frames[(size_t)v] == 0) fault = 0; else { rows_of[(size_t)v] = nullptr; text = at(v) + "no probabilities for " + std::to_string(frames[(size_t)v]) + " frames"; } }
+        if (fault == 6) { mode[(size_t)v] = rng() % 2 ? 3 : -1; text = at(v) + "mode " + std::to_string(mode[(size_t)v]) + " outside 0 .. 2"; }
+        if (fault == 7) { if (frames[(size_t)v] == 0) fault = 0; else { ended[(size_t)v] = 1; text = at(v) + "the utterance has ended"; } }
+        if (fault == 8) {
+            frames[(size_t)v] = cap[(size_t)v] - (int32_t)consumed[(size_t)v] + 1; rows_of[(size_t)v] = some_rows; ended[(size_t)v] = 0;
+            code = DSMI_ERR_CAPACITY;
+            text = at(v) + "the utterance would reach " + std::to_string(cap[(size_t)v] + 1) + " frames, max_frames is " + std::to_string(cap[(size_t)v]);
+        }
+        if (fault == 9) {
+            if (mode[(size_t)v] == 0 || consumed[(size_t)v] + frames[(size_t)v] == 0) fault = 0;
+            else {                       // below this stream's count, and no stream before it is above the stride either
+                P = (int)(consumed[(size_t)v] + frames[(size_t)v]) - 1;
+                for (int i = 0; i < v; ++i) if (mode[(size_t)i] && consumed[(size_t)i] + frames[(size_t)i] > P) mode[(size_t)i] = 0;
+                text = at(v) + "P_stride " + std::to_string(P) + " is below the utterance's " + std::to_string(P + 1) + " frames";
+            }
+        }
+        if (fault == 10) { if (!due) fault = 0; else { outputs = false; text = "an output array is NULL"; } }
+        if (fault == 11) { if (!due) fault = 0; else { P = (1 << 24) / n + 1; code = DSMI_ERR_CAPACITY; text = "n * P_stride exceeds 2^24"; } }
+        if (fault == 12) {               // the numbers alone: no array is read
+            if (grammar_stream_check(nullptr, nullptr, nullptr, nullptr, nullptr, -3, nullptr, nullptr, nullptr, 0, true, err) != DSMI_ERR_INVALID) GS_FAIL("n < 0 with no arrays");
+            fault = 0;
+        }
+        const int rc = grammar_stream_check(handles.data(), nets.data(), consumed.data(), ended.data(), cap.data(), n_arg,
+                                            reinterpret_cast<const float* const*>(rows_of.data()), frames.data(), mode.data(), P, outputs, err);
+        if (fault) {
+            if (rc != code) GS_FAIL("a fault with the wrong code");
+            if (err.rfind("grammar stream", 0) != 0 || err.find(text) == std::string::npos) GS_FAIL("wrong message");
+            ++refused;
+        } else {
+            if (rc != DSMI_OK) GS_FAIL("a good call refused");
+            ++good;
+        }
+    }
+    std::printf("%d grammar stream calls ok, %ld good, %ld refused, %ld heavy nodes\n", reps, good, refused, heavy_nodes);
+    return good > 0 && refused > 0 && heavy_nodes > 0 ? 0 : 11;
+}
+
 // ---- alignlong: dsmi_align_long's check and plan (align_long_host.h), the transcript a heap block of exactly L words
 #define ALONG_FAIL(what) do { std::fprintf(stderr, "alignlong: %s (repetition %d, line %d)\n", what, rep, __LINE__); return 11; } while (0)
 
@@ -1453,11 +1580,12 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "occcheck")) return run_occcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "grammarcheck")) return run_grammarcheck(argc, argv);
+    if (argc >= 2 && !std::strcmp(argv[1], "grammarstreamcheck")) return run_grammarstreamcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "alignlong")) return run_alignlong(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz grammarcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz grammarcheck [SEED [N]] | host_fuzz grammarstreamcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
