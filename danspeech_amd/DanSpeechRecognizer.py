@@ -742,6 +742,45 @@ class DanSpeechRecognizer(object):
         """``transcribe_grammar_batch`` of one recording."""
         return self.transcribe_grammar_batch([recording], grammar if not isinstance(grammar, (list, tuple)) else list(grammar))[0]
 
+    # ---- was a sentence of the grammar said, and how sure is the decoded one (CTC grammar posterior) ---------------------
+    def grammar_confidence_batch(self, recordings, grammar):
+        """Was a sentence of ``grammar`` (as for ``transcribe_grammar_batch``) said in ``recordings[i]``, and how sure is the
+        decoded one?  Per recording ``None`` when no sentence of the grammar fits the recording's frames, else a dict:
+        ``text``, ``chars`` and ``path_logp``, the best sentence, its characters ``[(char, start_frame, end_frame, prob), ...]``
+        and its path's natural-log probability as ``transcribe_grammar_batch`` finds them; ``grammar_logp``, the natural log
+        of the summed probability of every path the grammar accepts (``dsmi_grammar_posterior``) -- the posterior that a
+        sentence of the grammar was said at all, the rejection score; ``sentence_posterior``, exp(the likelihood of ``text``
+        summed over every alignment + its weight in the grammar - grammar_logp): how sure ``text`` is, given that a sentence
+        of the grammar was said.  One forward and three decoder calls for the batch."""
+        if self.model is None:
+            raise ModelNotInitialized("Trying to decode with a grammar without a DanSpeech model.")
+        per_clip = isinstance(grammar, (list, tuple))
+        if per_clip and len(grammar) != len(recordings):
+            raise ValueError("grammar_confidence_batch: %d recordings and %d grammars" % (len(recordings), len(grammar)))
+        graphs = [self.decoder.grammar(g) for g in grammar] if per_clip else self.decoder.grammar(grammar)
+        if len(recordings) == 0:
+            return []
+        job = self._enqueue_batch(recordings)
+        job.collect_forward()                    # waits for the forward; a timed-out batch has been recomputed by now
+        ordered = [graphs[i] for i in job.order] if per_clip else graphs
+        decoded = self.decoder.decode_grammar(job.probs, ordered, job.sizes)
+        summed = self.decoder.grammar_posterior(job.probs, ordered, job.sizes)
+        ids = [[] if d is None else [self.decoder.transcript_ids(d[0])] for d in decoded]
+        scored = self.decoder.score_ids(job.probs, ids, job.sizes)
+        results = [None] * job.count
+        for pos, i in enumerate(job.order):
+            if decoded[pos] is not None and summed[pos] is not None:
+                text, chars, path_logp = decoded[pos]
+                g = ordered[pos] if per_clip else graphs
+                total = summed[pos]["logp"]
+                results[i] = dict(text=text, chars=chars, path_logp=path_logp, grammar_logp=total,
+                                  sentence_posterior=float(np.exp(scored[pos][0] + g.weight_of(text) - total)))
+        return results
+
+    def grammar_confidence(self, recording, grammar):
+        """``grammar_confidence_batch`` of one recording."""
+        return self.grammar_confidence_batch([recording], grammar if not isinstance(grammar, (list, tuple)) else list(grammar))[0]
+
     # ---- where given phrases are spoken (CTC phrase search) -----------------------------------------------------------
     def find_phrases_batch(self, recordings, phrases, max_hits=5, min_confidence=0.0):
         """Where in ``recordings[i]`` is ``phrases[k]`` spoken?  ``result[i][k]`` is a list of ``(start_s, end_s, confidence,

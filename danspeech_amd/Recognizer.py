@@ -65,6 +65,17 @@ class Recognizer(object):
         in the caller's order (``DanSpeechRecognizer.transcribe_grammar_batch``)."""
         return self.danspeech_recognizer.transcribe_grammar_batch(audio_list, grammar)
 
+    def grammar_confidence_batch(self, audio_list, grammar):
+        """Was a sentence of ``grammar`` said in each clip, and how sure is the decoded one?  Per clip ``None`` when no sentence
+        fits the audio, else ``dict(text, chars, path_logp, grammar_logp, sentence_posterior)``: ``recognize_grammar``'s best
+        sentence, the natural log of the summed probability of every path the grammar accepts (the rejection score) and the
+        posterior of ``text`` given that a sentence of the grammar was said (``DanSpeechRecognizer.grammar_confidence_batch``)."""
+        return self.danspeech_recognizer.grammar_confidence_batch(audio_list, grammar)
+
+    def grammar_confidence(self, audio_data, grammar):
+        """``grammar_confidence_batch`` of one clip."""
+        return self.danspeech_recognizer.grammar_confidence(audio_data, grammar)
+
     def align_flexible(self, audio_data, grammar_text):
         """``align`` for a transcript that is almost right: ``grammar_text`` is the transcript with alternatives ``(2 | to |
         toogtyve)`` and optional words ``[øh]`` (``danspeech_amd.grammar``).  ``(text, [(word, start_s, end_s, confidence),

@@ -214,6 +214,8 @@ _PROTOS = {
     "dsmi_alternatives": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "dsmi_grammar": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(GrammarPool), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsmi_grammar_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i64p]),
+    "dsmi_grammar_posterior": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(GrammarPool), _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "dsmi_grammar_posterior_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i64p]),
     "dsmi_grammar_net_create": (C.c_int, [_vp, C.POINTER(GrammarPool), C.POINTER(_vp)]),
     "dsmi_grammar_net_destroy": (None, [_vp]),
     "dsmi_grammar_net_last_error": (C.c_char_p, [_vp]),
@@ -1227,6 +1229,30 @@ class NativeDecoder(_Handle):
         del keep
         return lens, nodes, spans, tp, lp, st
 
+    def grammar_posterior(self, probs, sizes, graphs, clip_graph=None, want_visits=True, want_occ=True):
+        """CTC grammar posterior (``dsmi_grammar_posterior``): the summed probability of every path a token graph accepts.
+        Arguments as ``grammar``.  Returns ``(logp, visits, occ, status)``: logp float64 [B] and status int32 [B] (1 = no
+        accepted sentence fits, logp = -inf) are numpy; visits float64 [B, N] numpy (N the most nodes of a graph: each node's
+        expected number of entries, zeros past a graph's nodes) and occ [B, T, C] a CUDA float64 tensor written in full (the
+        per-frame label posteriors given the grammar), or None where ``want_visits`` / ``want_occ`` is false."""
+        import torch
+        B, T = probs.shape[0], probs.shape[1]
+        pool, keep = grammar_pool(graphs)
+        cg = None if clip_graph is None else np.ascontiguousarray(clip_graph, dtype=np.int32).reshape(-1)
+        if cg is not None and len(cg) != B:
+            raise ValueError("grammar: %d graph indices for a batch of %d" % (len(cg), B))
+        N = int(np.diff(keep[0]).max()) if pool.K else 0
+        lp = np.zeros(B, dtype=np.float64)
+        st = np.zeros(B, dtype=np.int32)
+        visits = np.zeros((B, N), dtype=np.float64) if want_visits else None
+        occ = torch.empty((B, T, probs.shape[2]), dtype=torch.float64, device=probs.device) if want_occ else None
+        self._check(lib().dsmi_grammar_posterior(self._h, probs.data_ptr(), _sizes_ptr(sizes), B, T, C.byref(pool),
+                                                 None if cg is None else _np_ptr(cg), N, _np_ptr(lp),
+                                                 _np_ptr(visits) if want_visits and visits.size else None,
+                                                 occ.data_ptr() if want_occ else None, _np_ptr(st), _stream(self.device)))
+        del keep
+        return lp, visits, occ, st
+
     def edit_distance(self, seqs, pairs, seq_lens=None):
         """Batched edit distance (``dsmi_edit_distance``).  seqs: the pool, an int array [M, L_stride] with ``seq_lens`` [M],
         or a list of M id sequences (``seq_lens`` None); tokens are any int32.  pairs: int [N, 2], row n = (a, b) compares
@@ -1341,6 +1367,17 @@ def grammar_plan(B, T_out, n_nodes, n_arcs):
         raise DsmiError(rc, "dsmi_grammar_plan: B and T_out positive, 0 .. %d nodes, 0 .. %d arcs, at most 2^31 bytes of backpointers"
                         % (GRAMMAR_MAX_NODES, GRAMMAR_MAX_ARCS))
     return dict(zip(("node_stride", "lds_bytes", "bp_bytes"), (int(v) for v in info)))
+
+
+def grammar_posterior_plan(B, T_out, n_nodes, n_arcs):
+    """dsmi_grammar_posterior_plan (host only): the geometry of a dsmi_grammar_posterior call of B clips of T_out frames whose
+    largest graph has n_nodes nodes and n_arcs arcs, as a dict; DsmiError with the code the call would refuse these numbers with."""
+    info = np.zeros(3, dtype=np.int64)
+    rc = lib().dsmi_grammar_posterior_plan(int(B), int(T_out), int(n_nodes), int(n_arcs), info.ctypes.data_as(_i64p))
+    if rc < 0:
+        raise DsmiError(rc, "dsmi_grammar_posterior_plan: B and T_out positive, 0 .. %d nodes, 0 .. %d arcs, at most 2^30 bytes of stored trellises"
+                        % (GRAMMAR_MAX_NODES, GRAMMAR_MAX_ARCS))
+    return dict(zip(("node_stride", "lds_bytes", "ws_bytes"), (int(v) for v in info)))
 
 
 def grammar_stream_plan(n_nodes, n_arcs, n_labels, max_frames):

@@ -1,6 +1,6 @@
 // The six tools over the CTC trellis of probabilities that are already on the device: forced alignment of known transcripts
 // (dsmi_align; the kernel: align.hip), of one long recording (dsmi_align_long; align_long.hip), phrase search (dsmi_spot; spot.hip), transcript scoring (dsmi_score; score.hip),
-// token confidence (dsmi_alternatives; alt.hip), occupancy (dsmi_occupancy; occ.hip) and grammar decoding (dsmi_grammar; grammar.hip) -- and, on the same handle and by the
+// token confidence (dsmi_alternatives; alt.hip), occupancy (dsmi_occupancy; occ.hip), grammar decoding (dsmi_grammar; grammar.hip) and the grammar posterior (dsmi_grammar_posterior; grammar_post.hip) -- and, on the same handle and by the
 // same conventions, the batched edit distance of token sequences (dsmi_edit_distance; edit.hip) and the language-model score of
 // known sentences (dsmi_lm_score; lmscore.hip), which need no probabilities.
 // Each entry checks its pointers, hands every number and array to its check (ctc_host.h: a refusal comes before any launch and
@@ -14,6 +14,7 @@
 #include "alt.h"
 #include "occ.h"
 #include "grammar.h"
+#include "grammar_post.h"
 #include "edit.h"
 #include "lmscore.h"
 
@@ -415,6 +416,103 @@ extern "C" int dsmi_grammar(dsmi_decoder* d, const float* probs, const int32_t* 
     std::memcpy(token_probs, out.data() + B + 3 * BT, sizeof(float) * BT);
     std::memcpy(path_logp, out.data() + B + 4 * BT, sizeof(float) * B);
     std::memcpy(status, out.data() + 2 * B + 4 * BT, sizeof(int32_t) * B);
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_grammar_posterior_plan(int B, int To, int n_nodes, int n_arcs, int64_t* info) {
+    if (!info) return DSMI_ERR_INVALID;
+    GrammarPostPlan plan;
+    std::string err;
+    if (int rc = grammar_post_plan(B, To, n_nodes, n_arcs, &plan, err)) return rc;
+    info[0] = plan.node_stride; info[1] = plan.lds_bytes; info[2] = plan.ws_bytes;
+    return DSMI_OK;
+}
+
+extern "C" int dsmi_grammar_posterior(dsmi_decoder* d, const float* probs, const int32_t* sizes, int B, int To, const dsmi_grammar_pool* pool,
+                                      const int32_t* clip_graph, int N_stride, double* logp, double* visits, double* occ, int32_t* status,
+                                      void* stream) {
+    if (!d) return DSMI_ERR_INVALID;
+    const int C = (int)d->labels.size();
+    if (!probs || !pool || !logp || !status) { d->err = "bad grammar posterior arguments"; return DSMI_ERR_INVALID; }
+    const int K = pool->K;
+    if (K > 0 && (!pool->node_off || !pool->labels || !pool->flags || !pool->arc_off || !pool->arc_pred || !pool->empty_ok)) {
+        d->err = "grammar: a NULL array in the pool"; return DSMI_ERR_INVALID;
+    }
+    std::vector<int32_t> sz, cg;
+    int n_nodes = 0, n_arcs = 0;
+    GrammarPostPlan plan;
+    if (int rc = grammar_post_check(sizes, B, To, K, pool->node_off, pool->labels, pool->weights, pool->flags, pool->arc_off, pool->arc_pred,
+                                    pool->empty_ok, clip_graph, C, d->blank, visits != nullptr, N_stride, sz, cg, &n_nodes, &n_arcs, &plan, d->err))
+        return rc;
+    GrammarPostPack pk;
+    grammar_post_pack(K, pool->node_off, pool->labels, pool->flags, pool->arc_off, pool->arc_pred, C, pk);
+    // ---- the upload, int32 words: sizes [B], graphs [B], node_off [K + 1], empty_ok [K], start_off [K + 1], bucket_off [K][C + 1],
+    // node words [nodes], weights [nodes], bucket_nodes [nodes], arc_off [nodes + 1], succ_off [nodes + 1]; then the 16-bit words:
+    // arcs, successors, start nodes
+    const size_t total = (size_t)pool->node_off[K], n_arc_all = (size_t)pool->arc_off[total], n_start = pk.start16.size();
+    const size_t NS = (size_t)plan.node_stride, BT = (size_t)B * To;
+    const size_t o_cg = B, o_no = o_cg + B, o_eo = o_no + K + 1, o_so = o_eo + K, o_bo = o_so + K + 1, o_wd = o_bo + (size_t)K * (C + 1);
+    const size_t o_wt = o_wd + total, o_bn = o_wt + total, o_ao = o_bn + total, o_su = o_ao + total + 1, o_16 = o_su + total + 1;
+    const size_t h_ar = 0, h_su = h_ar + n_arc_all, h_st = h_su + n_arc_all, n_half = h_st + n_start;
+    const size_t in_words = (o_16 + (n_half + 1) / 2 + 1) & ~(size_t)1;      // (the doubles behind it on 8 bytes)
+    std::vector<int32_t> up(in_words, 0);
+    std::memcpy(up.data(), sz.data(), sizeof(int32_t) * B);
+    std::memcpy(up.data() + o_cg, cg.data(), sizeof(int32_t) * B);
+    std::memcpy(up.data() + o_no, pool->node_off, sizeof(int32_t) * (K + 1));
+    std::memcpy(up.data() + o_eo, pool->empty_ok, sizeof(int32_t) * K);
+    std::memcpy(up.data() + o_so, pk.start_off.data(), sizeof(int32_t) * (K + 1));
+    std::memcpy(up.data() + o_bo, pk.bucket_off.data(), sizeof(int32_t) * pk.bucket_off.size());
+    if (total) {
+        std::memcpy(up.data() + o_wd, pk.words.data(), sizeof(int32_t) * total);
+        if (pool->weights) std::memcpy(up.data() + o_wt, pool->weights, sizeof(float) * total);
+        std::memcpy(up.data() + o_bn, pk.bucket_nodes.data(), sizeof(int32_t) * total);
+    }
+    std::memcpy(up.data() + o_ao, pool->arc_off, sizeof(int32_t) * (total + 1));
+    std::memcpy(up.data() + o_su, pk.succ_off.data(), sizeof(int32_t) * (total + 1));
+    uint16_t* half = reinterpret_cast<uint16_t*>(up.data() + o_16);
+    if (n_arc_all) {
+        std::memcpy(half + h_ar, pk.arc16.data(), sizeof(uint16_t) * n_arc_all);
+        std::memcpy(half + h_su, pk.succ16.data(), sizeof(uint16_t) * n_arc_all);
+    }
+    if (n_start) std::memcpy(half + h_st, pk.start16.data(), sizeof(uint16_t) * n_start);
+    DEC_HIP(d, hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspaces: io = the upload, then logp [B] and visits [B][node stride] doubles, then status [B]; ws = the stored
+    // trellises, (tok, blk) pairs [B][T_out][node stride] forward and backward, then lead [B][T_out] forward and backward
+    const size_t out_doubles = (size_t)B + (size_t)B * NS;
+    if (int rc = reserve_all(d, d->gp_io, sizeof(int32_t) * (in_words + (size_t)B) + sizeof(double) * out_doubles, &d->gp_ws, (size_t)plan.ws_bytes)) return rc;
+    int32_t* w = d->gp_io.as<int32_t>();
+    double* w_lp = reinterpret_cast<double*>(w + in_words);
+    int32_t* w_st = reinterpret_cast<int32_t*>(w_lp + out_doubles);
+    DEC_HIP(d, hipMemcpyAsync(w, up.data(), sizeof(int32_t) * in_words, hipMemcpyHostToDevice, s));
+    DEC_HIP(d, hipMemsetAsync(w_lp, 0, sizeof(double) * out_doubles + sizeof(int32_t) * B, s));
+    const uint16_t* dh = reinterpret_cast<const uint16_t*>(w + o_16);
+    GrammarPostArgs a{};
+    a.probs = probs; a.B = B; a.T_out = To; a.C = C; a.blank = d->blank;
+    a.sizes = w; a.clip_graph = w + o_cg; a.node_off = w + o_no; a.empty_ok = w + o_eo; a.start_off = w + o_so; a.bucket_off = w + o_bo;
+    a.words = w + o_wd; a.weights = reinterpret_cast<const float*>(w + o_wt); a.bucket_nodes = w + o_bn; a.arc_off = w + o_ao; a.succ_off = w + o_su;
+    a.arc16 = dh + h_ar; a.succ16 = dh + h_su; a.start16 = dh + h_st;
+    a.node_stride = (int)NS; a.arc_words = (int)grammar_arc_words(n_arcs);
+    a.fwd = d->gp_ws.as<double2>(); a.bwd = a.fwd + BT * NS;
+    a.lead_fwd = reinterpret_cast<double*>(a.bwd + BT * NS); a.lead_bwd = a.lead_fwd + BT;
+    a.logp = w_lp; a.status = w_st; a.visits = visits ? w_lp + B : nullptr; a.N_stride = (int)NS; a.occ = occ;
+    a.both = a.visits || a.occ;
+    DEC_HIP(d, launch_grammar_post(a, s));
+    // the results come back into an image of the call's own and reach the caller's arrays only when everything has succeeded
+    std::vector<double> out(visits ? out_doubles : (size_t)B);
+    std::vector<int32_t> st(B);
+    DEC_HIP(d, hipMemcpyAsync(out.data(), w_lp, sizeof(double) * out.size(), hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipMemcpyAsync(st.data(), w_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    DEC_HIP(d, hipStreamSynchronize(s));
+    std::memcpy(logp, out.data(), sizeof(double) * B);
+    std::memcpy(status, st.data(), sizeof(int32_t) * B);
+    if (visits) {
+        for (int b = 0; b < B; ++b) {
+            double* row = visits + (size_t)b * N_stride;
+            const int N = pool->node_off[cg[b] + 1] - pool->node_off[cg[b]];
+            for (int n = 0; n < N_stride; ++n) row[n] = n < N ? out[(size_t)B + (size_t)b * NS + n] : 0.0;
+        }
+    }
     return DSMI_OK;
 }
 

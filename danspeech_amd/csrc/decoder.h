@@ -72,6 +72,8 @@ struct dsmi_decoder {
     DevBuf occ_io, occ_ws;
     // dsmi_grammar: the upload and the results of the launch (int32 words), the backpointers [B][T_out][node stride] of 16 bits
     DevBuf gr_io, gr_bp;
+    // dsmi_grammar_posterior: the upload and, behind it on 8 bytes, logp, visits and the status; the two stored trellises (doubles)
+    DevBuf gp_io, gp_ws;
     // dsmi_edit_distance: the upload of the launch (int32 words: lens, pool, pairs, waves) and, behind it, the packed results
     DevBuf ed_io;
     // dsmi_lm_score: the upload of the launch (int32 words: lm_score_pack) and, behind it on 8 bytes, the results

@@ -85,7 +85,7 @@ extern "C" void dsmi_decoder_destroy(dsmi_decoder* d) {
     free_lm(d);
     if (d->bs_dev) (void)hipFree(d->bs_dev);
     if (d->bs_pin) (void)hipHostFree(d->bs_pin);
-    for (DevBuf* b : {&d->al_io, &d->al_bp, &d->along_io, &d->along_rows, &d->sp_io, &d->sp_tr, &d->sc_io, &d->alt_io, &d->alt_out, &d->alt_ws, &d->occ_io, &d->occ_ws, &d->gr_io, &d->gr_bp, &d->ed_io, &d->lm_io}) b->release();
+    for (DevBuf* b : {&d->al_io, &d->al_bp, &d->along_io, &d->along_rows, &d->sp_io, &d->sp_tr, &d->sc_io, &d->alt_io, &d->alt_out, &d->alt_ws, &d->occ_io, &d->occ_ws, &d->gr_io, &d->gr_bp, &d->gp_io, &d->gp_ws, &d->ed_io, &d->lm_io}) b->release();
     delete d;
 }
 

@@ -158,6 +158,52 @@ class Decoder(object):
             out.append((text, [(text[k], int(spans[b, k, 0]), int(spans[b, k, 1]), float(tp[b, k])) for k in range(M)], float(lp[b])))
         return out
 
+    # ---- CTC grammar posterior (dsmi_grammar_posterior): the summed probability of every path of a word graph
+    def grammar_posterior(self, probs, grammar_or_list, sizes=None, candidates=None):
+        """Was a sentence of the grammar said, and which?  ``probs`` [B,T,C], ``sizes`` frames per clip, ``grammar_or_list`` as
+        for ``decode_grammar``.  Per clip ``None`` when no accepted sentence fits the clip's frames, else a dict: ``logp``, the
+        natural log (float64) of the summed probability of every path the grammar accepts, its weights included (the
+        posterior that a sentence of the grammar was said, for an unambiguous grammar without weights); ``visits`` float64
+        [nodes], the expected number of entries into each node of the clip's graph; ``occ`` a CUDA float64 [T, C] view, the
+        posterior of each label at each frame given the grammar.  With ``candidates`` (sentences, normalised like
+        transcripts; the same for every clip) also ``posteriors``: per candidate exp(its ``score`` + its weight in the
+        graph, ``Grammar.weight_of`` - logp), 0.0 for a sentence the grammar does not accept or that cannot fit -- one
+        ``dsmi_score`` call for the whole batch."""
+        import torch
+        probs = self._on_gpu(probs)
+        B = probs.shape[0]
+        if isinstance(grammar_or_list, (list, tuple)):
+            if len(grammar_or_list) != B:
+                raise ValueError("grammar_posterior: %d grammars for a batch of %d" % (len(grammar_or_list), B))
+            graphs, clip_graph = [self.grammar(g) for g in grammar_or_list], np.arange(B, dtype=np.int32)
+        else:
+            graphs, clip_graph = [self.grammar(grammar_or_list)], None
+        texts = None if candidates is None else [self.normalise_transcript(t) for t in candidates]
+        cand_ids = None if texts is None else [self.transcript_ids(t) for t in texts]       # every check before any GPU work
+        dec = self._dec(probs.device.index or 0)
+        sz = None if sizes is None else np.asarray(torch.as_tensor(sizes).cpu()).astype(np.int32)
+        logp, visits, occ, status = dec.grammar_posterior(probs, sz, graphs, clip_graph)
+        scored = None
+        if texts is not None:
+            weights = [[g.weight_of(t) for t in texts] for g in graphs]
+            live = [[k for k in range(len(texts)) if not status[b] and weights[0 if clip_graph is None else b][k] is not None] for b in range(B)]
+            scored = self.score_ids(probs, [[cand_ids[k] for k in ks] for ks in live], sz)
+        out = []
+        for b in range(B):
+            if status[b]:
+                out.append(None)
+                continue
+            gi = 0 if clip_graph is None else b
+            res = dict(logp=float(logp[b]), visits=visits[b, :graphs[gi].n_nodes].copy(), occ=occ[b])
+            if texts is not None:
+                post = np.zeros(len(texts), dtype=np.float64)
+                for k, s in zip(live[b], scored[b]):
+                    if s is not None:
+                        post[k] = np.exp(s + weights[gi][k] - res["logp"])
+                res["posteriors"] = post
+            out.append(res)
+        return out
+
     def grammar_net(self, grammar_or_list, device_index=0):
         """Streaming grammar decoding (``dsmi_grammar_net_*``): one grammar or a list of them (``Grammar`` or text), compiled,
         checked, packed and uploaded once -> a ``NativeGrammarNet`` whose ``NativeGrammarStream``s carry one live utterance's

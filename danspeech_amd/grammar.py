@@ -204,6 +204,34 @@ class Grammar:
                 return False
         return any(self.flags[n] & FINAL for n in cur)
 
+    def weight_of(self, text):
+        """The weight the graph gives a sentence, as ``dsmi_grammar_posterior`` counts it: the log-sum-exp, over the node paths
+        that spell the (normalised) text, of the sum of their nodes' weights -- 0.0 for one path without weights, ln 2 for two --
+        or None when the grammar does not accept it."""
+        text = normalise(text)
+        if not text:
+            return 0.0 if self.empty_ok else None
+        w = self.weights.astype(np.float64)
+        cur = None                       # node -> the log-sum over the paths that end in it
+        for c in text:
+            if c not in self._ids:
+                return None
+            nxt = {}
+            for n in np.nonzero(self.labels == self._ids[c])[0]:
+                n = int(n)
+                if cur is None:
+                    if self.flags[n] & START:
+                        nxt[n] = w[n]
+                else:
+                    inn = [cur[int(p)] for p in self.preds(n) if int(p) in cur]
+                    if inn:
+                        nxt[n] = float(np.logaddexp.reduce(inn)) + w[n]
+            if not nxt:
+                return None
+            cur = nxt
+        ends = [v for n, v in cur.items() if self.flags[n] & FINAL]
+        return float(np.logaddexp.reduce(ends)) if ends else None
+
     def sentences(self, max_count=1000):
         """The accepted sentences, shortest first and in label order among equals, at most ``max_count`` of them."""
         out = [""] if self.empty_ok else []

@@ -893,6 +893,80 @@ int dsmi_grammar(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_h
                  int32_t* status_host, void* stream);
 int dsmi_grammar_plan(int B, int T_out, int n_nodes, int n_arcs, int64_t* info);
 
+/* ---- CTC grammar posterior (no reference counterpart): was a sentence of the grammar said at all, how sure is the decoded
+ * sentence given that one was, which label does each frame carry given the grammar, and how much probability flows through each
+ * node?  dsmi_grammar's recurrence in the log-sum-exp semiring: the all-paths half of the word-graph tools, as dsmi_score and
+ * dsmi_occupancy are of the transcript tools.  A CTC model's frame rows each sum to 1, so the probabilities of all labellings
+ * sum to 1 and the summed probability of every path the graph accepts is a posterior that needs no garbage model.
+ * probs_dev, sizes_host, pool and clip_graph_host are dsmi_grammar's, and so are the states: lead, tok(n) and blk(n).
+ * Everything is float64, with lp(t, c) = log((double)fmaxf(p, FLT_MIN)) as in dsmi_score and the float32 weights widened; a
+ * weight is added once, on entry to its node.  LSE is log-sum-exp; one whose arguments are all -inf is -inf, never NaN.
+ *     t = 0:  lead = lp(0, blank);  tok(n) = start[n] ? lp(0, lab[n]) + w[n] : -inf;  blk(n) = -inf
+ *     t >= 1: ent(n)  = LSE{ lead [if start[n]];  per predecessor p: blk(p), and tok(p) only if lab[p] != lab[n] }
+ *             tok'(n) = LSE(tok(n), ent(n) + w[n]) + lp(t, lab[n])
+ *             blk'(n) = LSE(blk(n), tok(n)) + lp(t, blank)
+ *             lead'   = lead + lp(t, blank)
+ *     end:    logp = LSE{ lead [if empty_ok];  per final n: blk(n), tok(n) }
+ * These are alpha_t.  beta_t(state) is the mirror image over the successor lists: the log of the summed probability of every
+ * way to finish from the state at frame t, frame t's emission and the weights of the nodes still to be entered included; at the
+ * last frame beta = lp(T-1, label) for tok and blk of a final node and for lead when empty_ok holds, else -inf.
+ *     gamma_t(state) = exp(alpha_t + beta_t - lp(t, label(state)) - logp), 0 where alpha or beta is -inf, never NaN
+ *     occ[b][t][c]   = the sum of gamma_t over the states carrying label c (the blank's column collects lead and every blk)
+ *     visits[b][n]   = the sum over t of the posterior of ENTERING tok(n) at frame t: gamma_t(tok n) less the share that was in
+ *                      tok(n) at t-1 already; a start node's occupancy at frame 0 counts as an entry
+ * Every path is in exactly one state per frame, so each row of occ with t < frames sums to 1, and d logp / d lp(t, c) =
+ * occ[t][c]: the gradient of the graph loss, as dsmi_occupancy's occ is of the transcript loss.  visits[n] = d logp / d w[n], the
+ * expected number of entries into node n: at most 1 on an acyclic graph, and on a hand-built graph with one node per slot value
+ * the slot's posterior.
+ * Paths, not sentences.  The sum runs over the paths of the graph -- sequences of states -- and not over sentences: a sentence
+ * that two node sequences spell counts twice, and a predecessor listed twice is two arcs.  exp(logp) is the probability of the
+ * grammar's language exactly when the graph is unambiguous (no sentence has two node sequences) and its weights are 0; then
+ * exp(dsmi_score's logp of a sentence - logp) is the sentence's posterior given that a sentence of the grammar was said.
+ * Outputs: logp_host [B] float64; status_host [B] = 0 decoded, 1 when no accepted sentence fits the clip's frames (logp = -inf);
+ * lp is finite, so -inf at the end means unreachable and nothing else: the device decides the status.  visits_host
+ * [B][N_stride] float64, may be NULL; N_stride >= the most nodes of any graph of the pool, columns past a graph's nodes are 0.
+ * occ_dev [B][T_out][n_labels] float64, caller-allocated, stays on the DEVICE, may be NULL.  Everything is written in full: rows
+ * t >= sizes[b] are 0.0 and an infeasible clip is all zeros, so the caller never clears them.  A clip of 0 frames is decoded
+ * only when empty_ok holds (logp = 0, all zeros).
+ * The results are values with a bound, not fixed bits.  With F the largest number of predecessors of one node in the call's
+ * graphs and k(F) = 32 + (F + 1) / 8: logp is within 8 * T * 2^-52 * max(1, |logp|) + (F + 1) * T * 2^-52 of the recurrence
+ * evaluated exactly (dsmi_score's form and the term below), every occ element within
+ *     bound = k(F) * T * 2^-52 * max(1, |logp| + 88)
+ * in absolute terms, and every visits element within T * bound.  The derivation is dsmi_occupancy's with one added term.  One
+ * step is a log-sum-exp of up to 2F + 1 terms where a transcript's has 3: formed as the greatest term m, the sum of exp(x - m)
+ * and one log, the sum of at most 2F + 1 terms in [0, 1] with one of them 1 carries a relative error of at most (2F + 1) 2^-53,
+ * which the log turns into as much absolute error of the step, on top of the few ulp of |alpha| per frame that make up the
+ * 8 T 2^-52 max(1, |value|) of alpha, beta and logp each.  The exponent of gamma has three such values, so the added term is
+ * 3 (2F + 1) T 2^-53 <= ((F + 1) / 8) T 2^-52 * 88, and e^x <= 1 passes it on as it stands; the rest -- |alpha| + |beta| <= |x| +
+ * |logp| + |lp|, sum g |x| <= ln(states) + 1 over the at most 4097 states of one label -- is dsmi_occupancy's and stays inside
+ * 32.  (It takes alpha and beta to be <= 0: weights that are log probabilities.  Positive weights add the greatest sum of them
+ * along one path to |logp| in the bound.)  visits is a sum over T frames of differences of two such terms, each within the
+ * bound: T times it, the cancellation being absolute.  The sums of occ (at most 2049 terms of sum <= 1) add 2049 * 2^-53.
+ * Deterministic and batch-invariant: a clip's logp, visits and occ are the same bits whatever else is in the call and from run
+ * to run.  There is no floating-point atomic, and the order of every sum is fixed by the graph alone: a node's entry over its
+ * predecessor list in order, the backward pass over its successors ascending (a node with more than 24 of either: lane l of a
+ * wave over the arcs l, l + 64, ... in order, then the lanes in a fixed tree), the end and the start nodes in a fixed tree over
+ * ascending nodes, a label's occ over its nodes ascending, a node's visits over the frames in order.  Frames past sizes[b] are
+ * never read.
+ * Refused before any launch with nothing written on host or device: everything dsmi_grammar refuses, with its codes and
+ * messages (the same check); DSMI_ERR_INVALID for a NULL logp_host or status_host, and for N_stride below the pool's largest
+ * graph when visits_host is given; DSMI_ERR_CAPACITY, the limit named in the message, when the stored trellises -- B * T_out *
+ * (32 * node stride + 16) bytes, two float64 (tok, blk) pairs per frame and node and lead, kept on the handle -- exceed 2^30
+ * bytes (32 clips of 501 frames fit at DSMI_GRAMMAR_MAX_NODES: 1002 MiB; a loop over 300 words compiles to about 1000 to 1500 nodes: 510 to 734 MiB).  The
+ * graph limits are dsmi_grammar's: at both, a workgroup's LDS holds two double-buffered 16-byte pairs per node (64 KB), node
+ * words, weights, offsets and start nodes (24 KB), the arcs (16 KB), the float64 image of the probabilities (32 KB), the end's
+ * reduction and the list of wave-reduced nodes (3 KB): 139 KB of 160 KB.  What the numbers alone refuse (B, T_out, and the cap at the least node stride) is refused
+ * before any array is read.  Three kernel launches whatever B (one when visits_host and occ_dev are both NULL: the forward pass
+ * alone).  Synchronises `stream`.
+ * dsmi_grammar_posterior_plan (host only, no handle): for a call of B clips of T_out frames whose largest graph has n_nodes nodes
+ * and n_arcs arcs, info = {node stride (n_nodes rounded up to a multiple of 4, at least 4), LDS bytes per workgroup, workspace
+ * bytes}.  Returns DSMI_OK, or the code with which dsmi_grammar_posterior would refuse these numbers; DSMI_ERR_INVALID for a NULL
+ * info. */
+int dsmi_grammar_posterior(dsmi_decoder* d, const float* probs_dev, const int32_t* sizes_host, int B, int T_out,
+                           const dsmi_grammar_pool* pool, const int32_t* clip_graph_host, int N_stride,
+                           double* logp_host, double* visits_host, double* occ_dev, int32_t* status_host, void* stream);
+int dsmi_grammar_posterior_plan(int B, int T_out, int n_nodes, int n_arcs, int64_t* info);
+
 /* ---- Streaming grammar decoding (no reference counterpart): dsmi_grammar's search carried from one chunk of a live session's
  * probabilities to the next, so that a streaming caller pays for each frame once and neither keeps the rows nor packs the
  * graph again.  A dsmi_grammar_net is a pool of K graphs bound to one dsmi_decoder: dsmi_grammar_net_create applies

@@ -21,6 +21,10 @@
 //   host_fuzz grammarcheck SEED N  the host half of dsmi_grammar (grammar_host.h: grammar_check, grammar_plan) on N random calls whose pool of
 //                             graphs lies in exactly sized heap arrays, each good or with one fault, against the rules written out
 //                             below; one node or arc over each limit; what is refused on the numbers alone is called with null arrays
+//   host_fuzz grammarpostcheck SEED N  the host half of dsmi_grammar_posterior (grammar_post_host.h: grammar_post_check, grammar_post_plan,
+//                             grammar_post_pack) on N random calls whose pool lies in exactly sized heap arrays, each good or with one
+//                             fault: the successor transpose, the start lists and the label buckets against a plain restatement, the
+//                             plan's numbers, the refusals and the cap on the stored trellises
 //   host_fuzz grammarstreamcheck SEED N  the host half of streaming grammar decoding (grammar_stream_host.h: grammar_stream_plan,
 //                             grammar_heavy_list, grammar_stream_check) on N random advance calls held in exactly sized heap arrays, each
 //                             good or with one fault, against the rules written out below; the plan's numbers and refusals
@@ -58,6 +62,7 @@
 #include "ctc_host.h"
 #include "align_long_host.h"
 #include "grammar_host.h"
+#include "grammar_post_host.h"
 #include "grammar_stream_host.h"
 #include "edit_host.h"
 #include "lm_score_host.h"
@@ -902,6 +907,139 @@ static int run_grammarcheck(int argc, char** argv) {
     return good > 0 && refused > 0 ? 0 : 11;
 }
 
+// ---- grammarpostcheck: dsmi_grammar_posterior's check, plan and packing (grammar_post_host.h) -- the transposed arcs, the start
+// lists and the label buckets against a plain restatement -- every array of the pool a heap block of exactly the size the
+// offsets declare
+#define GP_FAIL(what) do { std::fprintf(stderr, "grammarpostcheck: %s (repetition %d, line %d): %s\n", what, rep, __LINE__, err.c_str()); return 11; } while (0)
+
+static int run_grammarpostcheck(int argc, char** argv) {
+    std::mt19937 rng(argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u);
+    const int reps = argc > 3 ? std::atoi(argv[3]) : 200;
+    long good = 0, refused = 0, arcs_seen = 0;
+    for (int rep = 0; rep < reps; ++rep) {
+        const int C = 2 + (int)(rng() % 127), blank = (int)(rng() % (unsigned)C);
+        const int B = 1 + (int)(rng() % 6), To = 1 + (int)(rng() % 40), K = 1 + (int)(rng() % 4);
+        std::string err;
+        std::vector<int32_t> node_off = exact((size_t)K + 1);
+        for (int g = 0; g < K; ++g) node_off[(size_t)g + 1] = node_off[(size_t)g] + (int32_t)(rng() % 4 == 0 ? 0 : 1 + rng() % 9);
+        const int total = node_off[(size_t)K];
+        std::vector<int32_t> labels = exact((size_t)total), flags = exact((size_t)total), arc_off = exact((size_t)total + 1), empty_ok = exact((size_t)K);
+        std::vector<float> weights((size_t)total);
+        weights.shrink_to_fit();
+        std::vector<int32_t> preds;
+        int n_most = 0;
+        for (int g = 0; g < K; ++g) {
+            const int n0 = node_off[(size_t)g], N = node_off[(size_t)g + 1] - n0;
+            n_most = std::max(n_most, N);
+            empty_ok[(size_t)g] = (int32_t)(rng() % 2);
+            for (int n = 0; n < N; ++n) {
+                int lab = (int)(rng() % (unsigned)std::min(C, 4));        // few labels: equal neighbours and full buckets
+                if (lab == blank) lab = (blank + 1) % C;
+                labels[(size_t)(n0 + n)] = lab;
+                flags[(size_t)(n0 + n)] = (int32_t)(rng() % 4);
+                weights[(size_t)(n0 + n)] = (float)((int)(rng() % 2000) - 1000) / 250.f;
+                const int fan = (int)(rng() % 5);
+                for (int j = 0; j < fan; ++j) preds.push_back((int32_t)(rng() % (unsigned)N));      // self-loops, cycles, an arc twice
+                arc_off[(size_t)(n0 + n) + 1] = (int32_t)preds.size();
+            }
+            if (N > 0) { flags[(size_t)n0 + rng() % (unsigned)N] |= DSMI_GRAMMAR_START; flags[(size_t)n0 + rng() % (unsigned)N] |= DSMI_GRAMMAR_FINAL; }
+        }
+        std::vector<int32_t> arc_pred(preds);
+        arc_pred.shrink_to_fit();
+        std::vector<int32_t> sizes = exact((size_t)B), clip_graph = exact((size_t)B);
+        for (auto& v : sizes) v = (int32_t)(rng() % (unsigned)(To + 1));
+        for (auto& v : clip_graph) v = (int32_t)(rng() % (unsigned)K);
+        const bool want_visits = rng() % 3 != 0;
+        int N_stride = n_most + (int)(rng() % 3);
+        // ---- with `fault` one thing is wrong with the call
+        int fault = rng() % 2 ? 0 : 1 + (int)(rng() % 4), code = DSMI_ERR_INVALID;
+        const char* text = "";
+        if (fault == 1) { sizes[rng() % (unsigned)B] = To + 1; text = "size outside 0 .. T_out"; }
+        if (fault == 2) { if (total == 0) fault = 0; else { labels[rng() % (unsigned)total] = blank; text = "is the blank or not a label"; } }
+        if (fault == 3) { if (!want_visits || n_most == 0) fault = 0; else { N_stride = n_most - 1; text = "is below the pool's largest graph"; } }
+        if (fault == 4) { if (total == 0) fault = 0; else { clip_graph[rng() % (unsigned)B] = K; text = "graph outside 0 .. K-1"; } }
+        std::vector<int32_t> sz, cg;
+        int n_nodes = -7, n_arcs = -7;
+        GrammarPostPlan plan{};
+        const int rc = grammar_post_check(sizes.data(), B, To, K, node_off.data(), ptr_or_null(labels), weights.empty() ? nullptr : weights.data(), ptr_or_null(flags),
+                                          arc_off.data(), ptr_or_null(arc_pred), empty_ok.data(), clip_graph.data(), C, blank, want_visits, N_stride, sz, cg,
+                                          &n_nodes, &n_arcs, &plan, err);
+        if (fault) {
+            if (rc != code) GP_FAIL("a bad call passed");
+            if (err.rfind("grammar", 0) != 0 || err.find(text) == std::string::npos) GP_FAIL("wrong message");
+            ++refused;
+        } else {
+            if (rc != DSMI_OK) GP_FAIL("a good call refused");
+            if (n_nodes != n_most) GP_FAIL("the largest graph");
+            // ---- the plan's numbers
+            if (plan.node_stride < n_nodes || plan.node_stride % 4 || plan.node_stride < 4 || plan.node_stride > n_nodes + 4) GP_FAIL("the node stride");
+            if (plan.ws_bytes != (int64_t)B * To * (32 * plan.node_stride + 16)) GP_FAIL("the workspace bytes");
+            if (plan.lds_bytes != 44 * plan.node_stride + 8 + 2 * ((n_arcs + 3) / 4 * 4) + 32768 + 2048 + 2 * (DSMI_GRAMMAR_MAX_ARCS / 25 + 1) + 8 || plan.lds_bytes > 160 * 1024) GP_FAIL("the LDS bytes");
+            // ---- the packing against a plain restatement
+            GrammarPostPack pk;
+            grammar_post_pack(K, node_off.data(), ptr_or_null(labels), ptr_or_null(flags), arc_off.data(), ptr_or_null(arc_pred), C, pk);
+            if (pk.words.size() != (size_t)total || pk.arc16.size() != arc_pred.size() || pk.succ16.size() != arc_pred.size() ||
+                pk.succ_off.size() != (size_t)total + 1 || pk.start_off.size() != (size_t)K + 1 || pk.bucket_off.size() != (size_t)K * (C + 1) ||
+                pk.bucket_nodes.size() != (size_t)total || pk.succ_off[0] != 0 || pk.succ_off[(size_t)total] != (int32_t)arc_pred.size()) GP_FAIL("the sizes of the pack");
+            int fan_most = 0;
+            for (int g = 0; g < K; ++g) {
+                const int n0 = node_off[(size_t)g], N = node_off[(size_t)g + 1] - n0;
+                std::vector<int> starts;
+                for (int n = 0; n < N; ++n) {
+                    const int i = n0 + n;
+                    if (pk.words[(size_t)i] != (labels[(size_t)i] | ((flags[(size_t)i] & 1) << 8) | ((flags[(size_t)i] & 2) << 8))) GP_FAIL("a node word");
+                    if (flags[(size_t)i] & DSMI_GRAMMAR_START) starts.push_back(n);
+                    fan_most = std::max(fan_most, arc_off[(size_t)i + 1] - arc_off[(size_t)i]);
+                    // the successors of n: every arc p -> s with p == n, the successors ascending, an arc listed twice twice
+                    std::vector<int> want;
+                    for (int s2 = 0; s2 < N; ++s2)
+                        for (int j = arc_off[(size_t)(n0 + s2)]; j < arc_off[(size_t)(n0 + s2) + 1]; ++j)
+                            if (arc_pred[(size_t)j] == n) want.push_back(s2 | (labels[(size_t)(n0 + s2)] != labels[(size_t)i] ? 0x8000 : 0));
+                    if (pk.succ_off[(size_t)i + 1] - pk.succ_off[(size_t)i] != (int32_t)want.size()) GP_FAIL("a successor count");
+                    for (size_t k = 0; k < want.size(); ++k)
+                        if (pk.succ16[(size_t)pk.succ_off[(size_t)i] + k] != want[k]) GP_FAIL("a successor");
+                    for (int j = arc_off[(size_t)i]; j < arc_off[(size_t)i + 1]; ++j) {
+                        const int p = arc_pred[(size_t)j];
+                        if (pk.arc16[(size_t)j] != (p | (labels[(size_t)(n0 + p)] != labels[(size_t)i] ? 0x8000 : 0))) GP_FAIL("a predecessor word");
+                    }
+                    arcs_seen += (long)want.size();
+                }
+                if (pk.start_off[(size_t)g + 1] - pk.start_off[(size_t)g] != (int32_t)starts.size()) GP_FAIL("a start count");
+                for (size_t k = 0; k < starts.size(); ++k)
+                    if (pk.start16[(size_t)pk.start_off[(size_t)g] + k] != starts[k]) GP_FAIL("a start node");
+                const int32_t* bo = pk.bucket_off.data() + (size_t)g * (C + 1);
+                if (bo[0] != 0 || bo[C] != N) GP_FAIL("the bucket offsets' ends");
+                for (int c = 0; c < C; ++c) {
+                    std::vector<int> want;
+                    for (int n = 0; n < N; ++n) if (labels[(size_t)(n0 + n)] == c) want.push_back(n);
+                    if (bo[c + 1] - bo[c] != (int32_t)want.size()) GP_FAIL("a bucket's count");
+                    for (size_t k = 0; k < want.size(); ++k)
+                        if (pk.bucket_nodes[(size_t)n0 + bo[c] + k] != want[k]) GP_FAIL("a bucket's node");
+                }
+            }
+            if (pk.max_fan_in != fan_most) GP_FAIL("the largest fan-in");
+            ++good;
+        }
+        // ---- the plan: limits, the cap, and what the numbers alone refuse (no array exists)
+        {
+            const int32_t* none = nullptr;
+            const int big = 1 + (int)(rng() % 1000);
+            if (grammar_post_plan(B, To, DSMI_GRAMMAR_MAX_NODES + 1, 0, &plan, err) != DSMI_ERR_CAPACITY || err.find("DSMI_GRAMMAR_MAX_NODES") == std::string::npos) GP_FAIL("the plan, one node over");
+            if (grammar_post_plan(B, To, 1, DSMI_GRAMMAR_MAX_ARCS + 1, &plan, err) != DSMI_ERR_CAPACITY || err.find("DSMI_GRAMMAR_MAX_ARCS") == std::string::npos) GP_FAIL("the plan, one arc over");
+            if (grammar_post_plan(32, 501, DSMI_GRAMMAR_MAX_NODES, DSMI_GRAMMAR_MAX_ARCS, &plan, err) != DSMI_OK || plan.lds_bytes > 160 * 1024 || plan.ws_bytes > ((int64_t)1 << 30)) GP_FAIL("the plan at both limits");
+            if (grammar_post_plan(33, 501, DSMI_GRAMMAR_MAX_NODES, 0, &plan, err) != DSMI_ERR_CAPACITY || err.find("2^30") == std::string::npos) GP_FAIL("the cap");
+            if (grammar_post_plan(0, To, 1, 1, &plan, err) != DSMI_ERR_INVALID || grammar_post_plan(B, -big, 1, 1, &plan, err) != DSMI_ERR_INVALID ||
+                grammar_post_plan(B, To, -big, 1, &plan, err) != DSMI_ERR_INVALID || grammar_post_plan(B, To, 1, -big, &plan, err) != DSMI_ERR_INVALID) GP_FAIL("the plan's numbers");
+            if (grammar_post_check(none, 0, To, K, none, none, nullptr, none, none, none, none, none, C, blank, true, 0, sz, cg, &n_nodes, &n_arcs, &plan, err) != DSMI_ERR_INVALID) GP_FAIL("B = 0");
+            if (grammar_post_check(none, B, To, 0, none, none, nullptr, none, none, none, none, none, C, blank, true, 0, sz, cg, &n_nodes, &n_arcs, &plan, err) != DSMI_ERR_INVALID) GP_FAIL("K = 0");
+            if (grammar_post_check(none, 1 << 12, (1 << 12) + big, K, none, none, nullptr, none, none, none, none, none, C, blank, true, 0, sz, cg, &n_nodes, &n_arcs, &plan, err) != DSMI_ERR_CAPACITY ||
+                err.find("stored trellises") == std::string::npos) GP_FAIL("the cap on the numbers alone");
+        }
+    }
+    std::printf("%d posterior calls ok, %ld good, %ld refused, %ld arcs transposed\n", reps, good, refused, arcs_seen);
+    return good > 0 && refused > 0 && arcs_seen > 0 ? 0 : 11;
+}
+
 // ---- grammarstreamcheck: the plan of a stream's block, the heavy list and the check of an advance call (grammar_stream_host.h),
 // every array a heap block of exactly n entries
 #define GS_FAIL(what) do { std::fprintf(stderr, "grammarstreamcheck: %s (repetition %d, line %d): %s\n", what, rep, __LINE__, err.c_str()); return 11; } while (0)
@@ -1580,12 +1718,13 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "ctccheck")) return run_ctccheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "occcheck")) return run_occcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "grammarcheck")) return run_grammarcheck(argc, argv);
+    if (argc >= 2 && !std::strcmp(argv[1], "grammarpostcheck")) return run_grammarpostcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "grammarstreamcheck")) return run_grammarstreamcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "alignlong")) return run_alignlong(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "editcheck")) return run_editcheck(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "lmscore")) return run_lmscore(argc, argv);
     if (argc >= 2 && !std::strcmp(argv[1], "spotwatch")) return run_spotwatch(argc, argv);
     if (argc >= 3 && !std::strcmp(argv[1], "streampass")) return run_streampass(argc, argv);
-    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz grammarcheck [SEED [N]] | host_fuzz grammarstreamcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
+    std::fprintf(stderr, "usage: host_fuzz lm FILE... | host_fuzz plan [SEED [N]] | host_fuzz rnnplan FILE|grid | host_fuzz rnnforms | host_fuzz gate [SEED [N]] | host_fuzz scoreplan [SEED [N]] | host_fuzz ctccheck [SEED [N]] | host_fuzz occcheck [SEED [N]] | host_fuzz grammarcheck [SEED [N]] | host_fuzz grammarpostcheck [SEED [N]] | host_fuzz grammarstreamcheck [SEED [N]] | host_fuzz alignlong [SEED [N]] | host_fuzz editcheck [SEED [N]] | host_fuzz lmscore [SEED [N]] | host_fuzz spotwatch [SEED [N]] | host_fuzz streampass FILE\n");
     return 2;
 }
